@@ -22,6 +22,14 @@ rank i mod N, every cloud uploaded, searched, imaged, scored and its candidates 
 Prints ONE JSON line (rank 0).  Extra objects: "roofline" (dominant kernel), "kernels"
 (both stages), "cpu_baseline" (the CPU oracle on a bounded sample, all host cores — and, where oracle/_ref is in the
 tree, the reference's own sources timed on a few samples of the same list, one core, in a child process).
+
+A plain run sets up, warms up, times the steps and prints the line (value, ms_per_step, the per-kernel HIP-event times of the
+timed steps and the roofline made of them).  --full adds everything that takes runs of its own: in replay mode the search stage
+timed alone, `detect_end_to_end`, the batch legs, the score-accuracy leg, `preprocess` and `cpu_baseline` (and --live-pmc).
+
+--dump-outputs DIR: after the timed steps, what the timed path returned in its last step, as DIR/<name>.npy (rank 0; float32 /
+float64, at most 64 MB: a fixed seeded sample of the rows beyond that).  Replay mode: scores.npy (the candidate list's scores, in
+list order).  Batch mode: the scored hand records of the last pass, field by field, and per-cloud counts.
 """
 import argparse
 import hashlib
@@ -169,7 +177,14 @@ def main():
                          "~20 s) instead of reading profiles/r06_traffic.json; default: on for the default line on one GPU, unless this "
                          "process is itself being profiled")
     ap.add_argument("--no-live-pmc", dest="live_pmc", action="store_false")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline (replay mode: search alone, detect_end_to_end, batch legs, score "
+                         "accuracy, preprocess, cpu_baseline); a plain run times the steps and prints the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (rank 0, at most 64 MB)")
     args = ap.parse_args()
+    if args.live_pmc and not args.full:
+        ap.error("--live-pmc runs child benchmarks of its own: it needs --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: one process per GPU under torch.distributed.run (RCCL / gloo rendezvous on
         # 127.0.0.1), same arguments; rank 0 of the children prints the ONE line
@@ -275,6 +290,7 @@ def main():
         numa = {"node": node, "cpus": ncpu} if node >= 0 else {"node": None, "note": "the host exposes no NUMA topology for this device"}
     ctx = api.Context(api.default_params(C), device=device)
     ctx.set_lenet_weights(w)                       # weights copied once per device at init
+    last_pass = []  # (hands, n_sets, n_candidates, stage_ms) per cloud of batch_leg's last timed pass
 
     def batch_leg(cloud_ids, passes, warm):
         """gpd_hip_detect_batch over the listed clouds (seed 1234 + id): `warm` untimed FULL passes (every lane buffer at its
@@ -296,7 +312,8 @@ def main():
             tp = time.perf_counter()
             nc_pass = 0
             per_cloud = []
-            for hands, ns, nc, ms in ctx.run_batch(prepared):
+            last_pass[:] = ctx.run_batch(prepared)  # views into the batch's buffers: the last pass's results until the next run
+            for hands, ns, nc, ms in last_pass:
                 nc_pass += nc
                 stage += ms
                 per_cloud.append([round(float(x), 2) for x in ms])
@@ -353,6 +370,8 @@ def main():
                 "batch_end_to_end": leg, "host_binding_rank0": numa,
                 "roofline": lenet_stage_roofline(C, n0, net_s),
             }
+            if args.dump_outputs:
+                _dump_outputs(args.dump_outputs, _batch_outputs(last_pass))
             sys.stdout.flush()
             os.write(json_fd, (json.dumps(out) + "\n").encode())
         ctx.close()
@@ -370,7 +389,7 @@ def main():
     si = synth.sample_indices(cloud, n_samples)
     hands = ctx.search(si)  # first call: allocations
     search_ms, search_wall = 1e30, 1e30
-    for _ in range(3):     # the stage kernels by HIP events / the unfused call incl. the download of every hand record
+    for _ in range(3 if args.full else 0):  # the stage kernels by HIP events / the unfused call incl. the download of every hand record
         t0 = time.perf_counter()
         hands = ctx.search(si)
         search_wall = min(search_wall, time.perf_counter() - t0)
@@ -385,15 +404,16 @@ def main():
         flat["valid"][vidx[candidates:]] = 0
 
     # end-to-end latency of the fused entry point (search + filter + images + LeNet, host buffers in / out)
-    ctx.detect(si)
-    walls, kms = [], []
-    for _ in range(5):  # median of five calls
-        t0 = time.perf_counter()
-        _, n_detect = ctx.detect(si)
-        walls.append(time.perf_counter() - t0)
-        kms.append([float(x) for x in ctx.stage_ms()])
-    mid = int(np.argsort(walls)[len(walls) // 2])
-    detect_wall, detect_kernel_ms = walls[mid], kms[mid]
+    if args.full:
+        ctx.detect(si)
+        walls, kms = [], []
+        for _ in range(5):  # median of five calls
+            t0 = time.perf_counter()
+            _, n_detect = ctx.detect(si)
+            walls.append(time.perf_counter() - t0)
+            kms.append([float(x) for x in ctx.stage_ms()])
+        mid = int(np.argsort(walls)[len(walls) // 2])
+        detect_wall, detect_kernel_ms = walls[mid], kms[mid]
 
     _, cand = ctx.images(hands_f, download=False)   # the benchmark's candidate list, first pass
     n_cand = len(cand)
@@ -416,19 +436,21 @@ def main():
         dist.barrier()
     elapsed, total_cand = reduce(elapsed, n_cand)
     assert launches == args.steps
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, {"scores": timed_scores})
     pairs_done, pairs_seen = ctx.conv1_stats(reset=True)
     live_frac = pairs_done / pairs_seen if pairs_seen else None
     # (the batch leg runs BEFORE any leg that uses the host's cores: the oracle's OpenMP team and torch's intra-op threads keep
     #  spinning for a while after their last parallel region, and a spinning team beside the HIP runtime's threads showed up as
     #  one 30 ms stall in one of eight batch passes — r04_cold.sh on two boxes; 48 passes without those legs: none)
     batch = None
-    if args.batch_clouds > 0 and C == 15 and not clutter:
+    if args.full and args.batch_clouds > 0 and C == 15 and not clutter:
         batch = batch_leg([rank + world * k for k in range(args.batch_clouds)], args.batch_passes, 1)
     batch_raw = None
-    if args.batch_clouds > 0 and C == 15 and not clutter and args.config is None and args.gpus == 1:
+    if args.full and args.batch_clouds > 0 and C == 15 and not clutter and args.config is None and args.gpus == 1:
         batch_raw = _raw_batch_leg(ctx, api, synth, max(args.batch_clouds // 2, 2), max(args.batch_passes // 2, 3), args.batch_samples)
     trained = None
-    if rank == 0 and args.gpus == 1 and C == 15 and args.cpu_samples > 0:
+    if args.full and rank == 0 and args.gpus == 1 and C == 15 and args.cpu_samples > 0:
         if batch is not None:  # the batch left its last cloud resident: the benchmark's cloud and its search state once more
             ctx.upload_cloud(cloud["xyz"], cloud["normals"], cloud["cam_source"], cloud["view_points"])
             ctx.search(si)
@@ -474,13 +496,14 @@ def main():
         else:
             roofline = {"kernel": "image stage (shadow_set + shadow_image + grasp_image kernels)", "bound": "hbm", "achieved": img_gbs, "peak": HBM_PEAK_GBS,
                         "unit": "GB/s", "frac": img_gbs / HBM_PEAK_GBS, "traffic": traffic.get("image")}
-        # the stage before the timed one, per call of gpd_hip_search (B_search = sum_samples [12 k_f + 24 N_h + 12] + S n_orient 184)
-        sum_kf, sum_nh = _neighbour_counts(cloud, si, ctx.params)
-        b_search = 12.0 * sum_kf + 24.0 * sum_nh + 12.0 * n_samples + float(hands.size) * 184.0
-        kernels["search"] = {"ms": search_ms, "samples": int(n_samples), "algorithmic_bytes": b_search,
-                             "achieved_GBps": b_search / (search_ms / 1e3) / 1e9, "frac_hbm": b_search / (search_ms / 1e3) / 1e9 / HBM_PEAK_GBS,
-                             "pmc_traffic_bytes": traffic.get("search"),
-                             "note": "neighbourhood + height_list + hand_eval + plan (+ centre on a side stream); not part of `value`"}
+        if args.full:
+            # the stage before the timed one, per call of gpd_hip_search (B_search = sum_samples [12 k_f + 24 N_h + 12] + S n_orient 184)
+            sum_kf, sum_nh = _neighbour_counts(cloud, si, ctx.params)
+            b_search = 12.0 * sum_kf + 24.0 * sum_nh + 12.0 * n_samples + float(hands.size) * 184.0
+            kernels["search"] = {"ms": search_ms, "samples": int(n_samples), "algorithmic_bytes": b_search,
+                                 "achieved_GBps": b_search / (search_ms / 1e3) / 1e9, "frac_hbm": b_search / (search_ms / 1e3) / 1e9 / HBM_PEAK_GBS,
+                                 "pmc_traffic_bytes": traffic.get("search"),
+                                 "note": "neighbourhood + height_list + hand_eval + plan (+ centre on a side stream); not part of `value`"}
         out = {
             "metric": "15-ch grasp candidates scored/sec (imagegen+LeNet) at 1/2/4/8 MI355X" if C == 15 else "%d-ch grasp candidates scored/sec (imagegen+LeNet)" % C,
             "value": value, "unit": "candidates/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
@@ -492,15 +515,16 @@ def main():
                        "samples": int(n_samples), "channels": C, "sharding": "one cloud per GPU, no collective"},
             "roofline": roofline, "kernels": kernels, "pmc_traffic": traffic,
             "fallbacks": fallbacks,
-            "search": {"samples": int(n_samples), "hand_sets": int(hands.shape[0]), "kernel_ms": search_ms,
-                       "wall_ms_incl_download": search_wall * 1e3},
-            "detect_end_to_end": {"candidates": int(n_detect), "wall_ms": detect_wall * 1e3,
-                                  "kernel_ms": {"search": detect_kernel_ms[0], "images": detect_kernel_ms[1], "lenet": detect_kernel_ms[2]},
-                                  "kernel_sum_over_wall": sum(detect_kernel_ms) / (detect_wall * 1e3),
-                                  "cand_per_s": n_detect / detect_wall,
-                                  "note": "gpd_hip_detect: all candidates of the sample set, host buffers in, scored hands out; "
-                                          "filter / compaction / score scatter on the device"},
         }
+        if args.full:
+            out["search"] = {"samples": int(n_samples), "hand_sets": int(hands.shape[0]), "kernel_ms": search_ms,
+                             "wall_ms_incl_download": search_wall * 1e3}
+            out["detect_end_to_end"] = {"candidates": int(n_detect), "wall_ms": detect_wall * 1e3,
+                                        "kernel_ms": {"search": detect_kernel_ms[0], "images": detect_kernel_ms[1], "lenet": detect_kernel_ms[2]},
+                                        "kernel_sum_over_wall": sum(detect_kernel_ms) / (detect_wall * 1e3),
+                                        "cand_per_s": n_detect / detect_wall,
+                                        "note": "gpd_hip_detect: all candidates of the sample set, host buffers in, scored hands out; "
+                                                "filter / compaction / score scatter on the device"}
         if numa is not None:
             out["host_binding_rank0"] = numa
         if trained is not None:
@@ -513,9 +537,9 @@ def main():
         if batch_raw is not None:
             out["batch_raw_end_to_end"] = batch_raw
         raw = None
-        if args.config is None and C == 15 and not clutter:  # the widened row before the path, on the default line only
+        if args.full and args.config is None and C == 15 and not clutter:  # the widened row before the path, on the default line only
             raw, out["preprocess"] = _preprocess_leg(ctx)
-        if args.cpu_samples > 0 and args.gpus == 1:  # the CPU leg runs on rank 0 at N=1 only
+        if args.full and args.cpu_samples > 0 and args.gpus == 1:  # the CPU leg runs on rank 0 at N=1 only
             out["cpu_baseline"] = _cpu_baseline(cloud, w, C, si, n_cand, args.cpu_samples)
             if raw is not None:
                 out["cpu_baseline"]["preprocess_ms"] = _cpu_preprocess_ms(raw)
@@ -555,6 +579,40 @@ def _raw_batch_leg(ctx, api, synth, n_clouds, passes, n_samples):
             "kernel_ms_last_cloud": {"search": float(jobs[-1].stage_ms[0]), "images": float(jobs[-1].stage_ms[1]), "lenet": float(jobs[-1].stage_ms[2])},
             "note": "CandidatesGenerator::preprocessPointCloud inside the batch entry: the voxelised cloud never leaves the device, the voxeliser's "
                     "sequential chain of cloud i + 1 runs on the calling host thread beside cloud i's image / LeNet kernels"}
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together
+NPY_HEADER_BYTES = 256               # room kept per file for its .npy header
+HAND_DUMP_FIELDS = ("score", "sample", "frame", "position", "top", "bottom", "center", "grasp_width", "finger_placement_index",
+                    "set_index", "slot", "half_antipodal", "full_antipodal")
+
+
+def _dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy (float32 stays float32, everything else float64)."""
+    out = {k: np.ascontiguousarray(v, np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    assert sum(v.nbytes + NPY_HEADER_BYTES for v in out.values()) <= DUMP_MAX_BYTES, "outputs beyond the dump limit"
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+def _batch_outputs(last_pass):
+    """The scored hand records of batch_leg's last timed pass, all clouds in order, one array per field (hand_<field>), and the
+    per-cloud counts.  Beyond DUMP_MAX_BYTES a fixed seeded sample of the records is kept, its row numbers in hand_rows."""
+    hands = np.concatenate([np.asarray(h) for h, _, _, _ in last_pass])
+    out = {"num_sets": np.array([ns for _, ns, _, _ in last_pass], np.float64),
+           "num_candidates": np.array([nc for _, _, nc, _ in last_pass], np.float64),
+           "num_hands": np.array([len(h) for h, _, _, _ in last_pass], np.float64)}
+    row_bytes = sum((4 if f == "score" else 8) * int(np.prod(hands.dtype[f].shape)) for f in HAND_DUMP_FIELDS)
+    files = len(out) + len(HAND_DUMP_FIELDS) + 1
+    budget = (DUMP_MAX_BYTES - files * NPY_HEADER_BYTES - sum(v.nbytes for v in out.values())) // (row_bytes + 8)
+    if len(hands) > budget:
+        rows = np.sort(np.random.RandomState(0).choice(len(hands), budget, replace=False))
+        hands = hands[rows]
+        out["hand_rows"] = rows.astype(np.float64)
+    for f in HAND_DUMP_FIELDS:
+        out["hand_" + f] = hands[f].astype(np.float32 if f == "score" else np.float64)
+    return out
 
 
 def _host_split(tl):
@@ -745,7 +803,7 @@ def _live_pmc_kernels():
         for counter, key in (("FETCH_SIZE", "fetch_KiB_raw"), ("WRITE_SIZE", "write_KiB")):
             d = os.path.join(tmp, counter)
             cmd = [exe, "--pmc", counter, "-d", d, "-o", "bench", "--", sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1",
-                   "--cpu-samples", "0", "--batch-clouds", "0", "--no-live-pmc"]
+                   "--cpu-samples", "0", "--batch-clouds", "0", "--no-live-pmc", "--full"]
             p = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             try:
                 p.wait(timeout=120)

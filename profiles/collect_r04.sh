@@ -9,10 +9,10 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
-timeout 400 python bench.py > $OUT/bench_config2.json 2> $OUT/bench_config2.err
-timeout 400 python bench.py --config 3a > $OUT/bench_config3a.json 2> $OUT/bench_config3a.err
-timeout 400 python bench.py --config 3b > $OUT/bench_config3b.json 2> $OUT/bench_config3b.err
-timeout 600 python bench.py --config 4 --steps 5 --warmup 1 --cpu-samples 600 > $OUT/bench_config4.json 2> $OUT/bench_config4.err
+timeout 400 python bench.py --full > $OUT/bench_config2.json 2> $OUT/bench_config2.err
+timeout 400 python bench.py --full --config 3a > $OUT/bench_config3a.json 2> $OUT/bench_config3a.err
+timeout 400 python bench.py --full --config 3b > $OUT/bench_config3b.json 2> $OUT/bench_config3b.err
+timeout 600 python bench.py --full --config 4 --steps 5 --warmup 1 --cpu-samples 600 > $OUT/bench_config4.json 2> $OUT/bench_config4.err
 timeout 400 python bench.py --mode batch --clouds 64 --steps 3 --warmup 1 > $OUT/bench_batch64.json 2> $OUT/bench_batch64.err
 cd /tmp && export TMPDIR=/tmp
 P=$OUT/prof

@@ -14,7 +14,7 @@ if [ "${2:-}" != "skip-tests" ]; then
   $G --seconds 900 -- python -m pytest tests -m gpu -x -q > $OUT/gputests.txt 2>&1
   tail -3 $OUT/gputests.txt
 fi
-$G --seconds 400 -- python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+$G --seconds 400 -- python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 cd /tmp && export TMPDIR=/tmp
 P=$OUT/prof
 mkdir -p $P

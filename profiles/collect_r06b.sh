@@ -11,8 +11,8 @@ OUT=$ROOT/gpurun_out/$TAG
 G="python $ROOT/profiles/memguard.py --rss-gb 24"
 mkdir -p $OUT
 cd $ROOT
-$G --seconds 300 -- python bench.py --config 3a --cpu-samples 0 > $OUT/bench_config3a.json 2> $OUT/bench_config3a.err
-$G --seconds 300 -- python bench.py --config 3b --cpu-samples 0 > $OUT/bench_config3b.json 2> $OUT/bench_config3b.err
+$G --seconds 300 -- python bench.py --full --config 3a --cpu-samples 0 > $OUT/bench_config3a.json 2> $OUT/bench_config3a.err
+$G --seconds 300 -- python bench.py --full --config 3b --cpu-samples 0 > $OUT/bench_config3b.json 2> $OUT/bench_config3b.err
 $G --seconds 400 -- python bench.py --mode batch --clouds 64 --steps 3 --warmup 1 > $OUT/bench_batch64.json 2> $OUT/bench_batch64.err
 cd /tmp && export TMPDIR=/tmp
 P=$OUT/prof
@@ -20,7 +20,7 @@ mkdir -p $P
 $G --seconds 300 -- rocprofv3 --kernel-trace --stats -d $P/batch -o batch -- python $ROOT/bench.py --mode batch --clouds 16 --steps 2 --warmup 1 > $P/batch.log 2>&1
 cd $ROOT
 python profiles/timeline.py $(find $P/batch -name "*.db" | head -1) --last-seconds 0.25 > $OUT/batch_timeline.txt 2>&1
-$G --seconds 600 -- python bench.py --config 4 --steps 5 --warmup 1 --cpu-samples 600 > $OUT/bench_config4.json 2> $OUT/bench_config4.err
+$G --seconds 600 -- python bench.py --full --config 4 --steps 5 --warmup 1 --cpu-samples 600 > $OUT/bench_config4.json 2> $OUT/bench_config4.err
 for f in $OUT/bench_*.json; do python - "$f" <<PY
 import json, sys
 try:

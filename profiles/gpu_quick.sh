@@ -11,7 +11,7 @@ cd $ROOT
 timeout 900 python -m pytest $SEL -m gpu -x -q > $OUT/pytest.log 2>&1
 echo "pytest rc=$?"; tail -4 $OUT/pytest.log
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- python $ROOT/bench.py --steps 10 --warmup 2 --cpu-samples 0 --batch-clouds 0 > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- python $ROOT/bench.py --full --steps 10 --warmup 2 --cpu-samples 0 --batch-clouds 0 > $OUT/bench.json 2> $OUT/bench.err
 cd $ROOT
 python - <<PY
 import json

@@ -6,12 +6,12 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_cold.json 2> $OUT/bench_cold.err
+timeout 900 python bench.py --gpus 1 --full --steps 20 --warmup 5 > $OUT/bench_cold.json 2> $OUT/bench_cold.err
 echo "bench cold rc=$?"
 timeout 2400 python -m pytest tests -m gpu -x -q "$@" > $OUT/pytest.log 2>&1
 echo "pytest rc=$?" | tee -a $OUT/pytest.log
 tail -5 $OUT/pytest.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_warm.json 2> $OUT/bench_warm.err
+timeout 900 python bench.py --gpus 1 --full --steps 20 --warmup 5 > $OUT/bench_warm.json 2> $OUT/bench_warm.err
 echo "bench warm rc=$?"
 python - $OUT <<'PY'
 import json, sys

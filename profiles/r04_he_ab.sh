@@ -10,6 +10,6 @@ for v in 2048 1664 1536; do
   cp $T/gpd_amd/libgpd_hip.so ab/libgpd_hip_he$v.so; rm -rf $T
 done
 for rep in 1 2 3; do for v in 2048 1664 1536; do
-  GPD_HIP_LIB=$ROOT/ab/libgpd_hip_he$v.so python bench.py --cpu-samples 0 --batch-clouds 0 --no-live-pmc --steps 5 2>/dev/null | python -c "
+  GPD_HIP_LIB=$ROOT/ab/libgpd_hip_he$v.so python bench.py --full --cpu-samples 0 --batch-clouds 0 --no-live-pmc --steps 5 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('HE_COMPACT $v: search %.4f ms  detect %.3f ms (search %.3f)' % (d['search']['kernel_ms'], d['detect_end_to_end']['wall_ms'], d['detect_end_to_end']['kernel_ms']['search']))"
 done; done | tee $ROOT/gpurun_out/r04he/ab.txt

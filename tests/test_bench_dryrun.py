@@ -28,7 +28,7 @@ def _finite(x):
 
 
 def test_default_line_assembles(oracle_mod):
-    d = _run("--points", "6000", "--candidates", "160", "--steps", "2", "--warmup", "1", "--batch-clouds", "2", "--batch-passes", "2",
+    d = _run("--full", "--points", "6000", "--candidates", "160", "--steps", "2", "--warmup", "1", "--batch-clouds", "2", "--batch-passes", "2",
              "--batch-samples", "30", "--cpu-samples", "24")
     # the driver's contract
     assert d["metric"].startswith("15-ch grasp candidates scored/sec") and d["unit"] == "candidates/s"
@@ -103,7 +103,7 @@ def test_off_lattice_side_config(oracle_mod):
 def test_accuracy_leg_is_bounded_on_a_long_list(oracle_mod):
     """configs[3] times 50 000 candidates; the score-accuracy leg then looks at the first ACCURACY_LEG_MAX of them only (here 100 of
     160): the images it asks for and the timed scores it compares them with are the same candidates, in the same order."""
-    d = _run("--points", "6000", "--candidates", "160", "--steps", "1", "--warmup", "0", "--batch-clouds", "0", "--cpu-samples", "24",
+    d = _run("--full", "--points", "6000", "--candidates", "160", "--steps", "1", "--warmup", "0", "--batch-clouds", "0", "--cpu-samples", "24",
              GPD_DRYRUN_ACCURACY_MAX="100")
     s = d["scores_timed_list"]
     assert d["config"]["candidates_per_gpu"] == 160 and s["images"] == 100
@@ -133,7 +133,7 @@ def test_two_ranks_under_the_drivers_launcher(oracle_mod):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "tests", "bench_dryrun_harness.py"), "--gpus", "2", "--dist-backend", "gloo",
+                        "--master-port", str(port), os.path.join(ROOT, "tests", "bench_dryrun_harness.py"), "--gpus", "2", "--dist-backend", "gloo", "--full",
                         "--points", "6000", "--candidates", "160", "--steps", "2", "--warmup", "1", "--batch-clouds", "2", "--batch-passes", "2",
                         "--batch-samples", "30"], capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -158,8 +158,50 @@ def test_smoke_entry_runs_against_the_stand_in(oracle_mod):
 def test_a_failing_reference_timing_does_not_cost_the_line(oracle_mod):
     """cpu_baseline.reference_sources is timed in a child process: a reference library that cannot even be loaded (here: a file
     that is not one) leaves the line intact, the committed figure in its place and the failure on record."""
-    d = _run("--points", "6000", "--candidates", "120", "--steps", "1", "--warmup", "0", "--batch-clouds", "0", "--cpu-samples", "16",
+    d = _run("--full", "--points", "6000", "--candidates", "120", "--steps", "1", "--warmup", "0", "--batch-clouds", "0", "--cpu-samples", "16",
              GPD_REF_LIB="/bin/true")
     rs = d["cpu_baseline"]["reference_sources"]
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0
     assert "live_attempt_failed" in rs and "NOT measured in this run" in rs["note"] and rs["value"] > 0
+
+
+MOVED_TO_FULL = ("search", "detect_end_to_end", "scores_timed_list", "batch_end_to_end", "batch_raw_end_to_end", "preprocess", "cpu_baseline")
+
+
+def test_plain_line_is_the_headline_and_dumps_its_outputs(oracle_mod, tmp_path):
+    """Without --full the line is the timed steps' own (no leg beside them, whatever --cpu-samples / --batch-clouds say), and
+    --dump-outputs writes the scores of the last timed step: the same from run to run and the same as a --full run's."""
+    import numpy as np
+    args = ("--points", "6000", "--candidates", "160", "--steps", "3", "--warmup", "1", "--batch-clouds", "2", "--batch-samples", "30",
+            "--cpu-samples", "24")
+    d = _run(*args, "--dump-outputs", str(tmp_path / "a"))
+    assert d["metric"].startswith("15-ch grasp candidates scored/sec") and d["unit"] == "candidates/s" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["warmup"] == 1 and _finite(d["ms_per_step"]) and d["ms_per_step"] > 0 and "int8" in d["dtype"]
+    assert abs(d["value"] - 160 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert not [k for k in MOVED_TO_FULL if k in d] and "search" not in d["kernels"]
+    assert d["roofline"]["kernel"] == "conv2_bf16_kernel" and d["kernels"]["conv2_bf16_kernel"]["ms"] > 0
+    a = np.load(tmp_path / "a" / "scores.npy")
+    assert sorted(os.listdir(tmp_path / "a")) == ["scores.npy"] and a.dtype == np.float32 and a.shape == (160,) and np.isfinite(a).all()
+    _run(*args, "--dump-outputs", str(tmp_path / "b"))
+    full = _run(*args, "--full", "--dump-outputs", str(tmp_path / "c"))
+    assert all(k in full for k in MOVED_TO_FULL)
+    for other in ("b", "c"):
+        assert np.array_equal(np.load(tmp_path / other / "scores.npy"), a), other
+
+
+def test_batch_mode_dumps_its_last_pass(oracle_mod, tmp_path):
+    """--mode batch --dump-outputs: the scored hand records of the last timed pass, every cloud of the rank in order."""
+    import numpy as np
+    d = _run("--mode", "batch", "--clouds", "3", "--steps", "2", "--warmup", "1", "--batch-samples", "30", "--dump-outputs", str(tmp_path))
+    o = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert len(o["num_hands"]) == 3 and "hand_rows" not in o
+    n = int(o["num_hands"].sum())
+    assert n > 0 and 2 * int(o["num_candidates"].sum()) == d["batch_end_to_end"]["candidates"]
+    assert o["hand_score"].dtype == np.float32 and o["hand_score"].shape == (n,) and np.isfinite(o["hand_score"]).all()
+    assert o["hand_position"].shape == (n, 3) and o["hand_frame"].shape == (n, 9) and o["hand_position"].dtype == np.float64
+    assert sum(v.nbytes for v in o.values()) <= 64 * 1000 * 1000
+
+
+def test_live_pmc_needs_full():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--live-pmc"], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert p.returncode != 0 and "--full" in p.stderr

@@ -173,3 +173,23 @@ def test_roofline_object_reproduces_the_committed_line():
     e = bench.lenet_kernel_entry(25e-6, 2000.0, n, None)
     assert "pipe" not in e and e["achieved_TFLOPs"] == pytest.approx(2000.0 * n / 25e-6 / 1e12)
     json.dumps(got)
+
+
+def test_batch_outputs_keep_a_fixed_sample_within_the_limit(monkeypatch):
+    """--dump-outputs of a batch beyond the limit: the same seeded rows every time, their numbers beside them, the files within it."""
+    from gpd_amd.api import HAND_DTYPE
+    rng = np.random.RandomState(5)
+    passes = []
+    for n in (700, 0, 500):
+        h = np.zeros(n, HAND_DTYPE)
+        h["score"] = rng.normal(0, 3, n)
+        h["position"] = rng.normal(0, 1, (n, 3))
+        passes.append((h, 40, n, [0.0, 0.0, 0.0]))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100000)
+    a, b = bench._batch_outputs(passes), bench._batch_outputs(passes)
+    rows = a["hand_rows"].astype(np.int64)
+    assert 0 < len(rows) < 1200 and np.all(np.diff(rows) > 0) and rows[-1] < 1200
+    assert all(np.array_equal(a[k], b[k]) for k in a) and sum(v.nbytes + bench.NPY_HEADER_BYTES for v in a.values()) <= 100000
+    allh = np.concatenate([p[0] for p in passes])
+    assert np.array_equal(a["hand_score"], allh["score"][rows]) and np.array_equal(a["hand_position"], allh["position"][rows])
+    assert list(a["num_hands"]) == [700, 0, 500]
