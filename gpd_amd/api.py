@@ -71,7 +71,8 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_images", "gpd_hip_detect", "gpd_hip_last_stage_ms", "gpd_hip_replay", "gpd_hip_replay_times", "gpd_hip_last_images_stats", "gpd_hip_estimate_normals",
            "gpd_hip_search_samples", "gpd_hip_detect_samples", "gpd_hip_reevaluate", "gpd_hip_replay_kernel_ms", "gpd_hip_last_centre_chains",
            "gpd_hip_detect_select", "gpd_hip_detect_batch", "gpd_hip_detect_batch_multi", "gpd_hip_conv1_stats", "gpd_hip_last_fallbacks", "gpd_hip_preprocess_cloud", "gpd_hip_find_clusters", "gpd_hip_reserve", "gpd_hip_bind_host_thread",
-           "gpd_hip_set_lenet_mode", "gpd_hip_lenet_debug", "gpd_hip_lenet_fast_tables", "gpd_hip_detect_sharded"]
+           "gpd_hip_set_lenet_mode", "gpd_hip_lenet_debug", "gpd_hip_lenet_fast_tables", "gpd_hip_detect_sharded",
+           "gpd_hip_sample_above_plane"]
 
 
 def build(prof=True):
@@ -112,6 +113,8 @@ def lib():
         L.gpd_hip_last_stage_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.gpd_hip_replay.argtypes = [C.c_void_p, C.c_int]
         L.gpd_hip_estimate_normals.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        L.gpd_hip_sample_above_plane.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_int),
+                                                 C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.gpd_hip_find_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_int)]
         L.gpd_hip_preprocess_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
@@ -437,3 +440,14 @@ class Context:
         out = np.zeros((P, 3), np.float32)
         self._check(lib().gpd_hip_estimate_normals(self._h, float(radius), _ptr(out)))
         return out
+
+    def sample_above_plane(self, threshold=0.01, max_iterations=50, probability=0.99, optimize=True):
+        """Cloud::sampleAbovePlane on the uploaded cloud (RANSAC support plane, DESIGN §7) ->
+        (indices off the plane i32 ascending — empty: the fit failed —, plane coefficients f32 [4], inliers, iterations)."""
+        P = self._num_points
+        idx = np.zeros(max(P, 1), np.int32)
+        coeffs = np.zeros(4, np.float32)
+        n, inl, its = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(lib().gpd_hip_sample_above_plane(self._h, float(threshold), int(max_iterations), float(probability), int(bool(optimize)),
+                                                     _ptr(idx), C.byref(n), _ptr(coeffs), C.byref(inl), C.byref(its)))
+        return idx[: n.value].copy(), coeffs, int(inl.value), int(its.value)

@@ -133,6 +133,7 @@ struct gpd_hip_ctx {
   Lane lane[kLanes];
   PreState pre;
   ClusterState cluster;
+  PlaneState plane;  // gpd_hip_sample_above_plane
   std::vector<hipEvent_t> replay_events;  // 6 per gpd_hip_replay call: start, images done, conv1, conv2, fc1, end
   float replay_kernel_ms[4] = {0, 0, 0, 0};  // conv1, conv2, fc1, fc2 sums of the replays of the last gpd_hip_replay_times
   size_t replay_used = 0;
@@ -639,6 +640,7 @@ void gpd_hip_destroy(gpd_hip_ctx *ctx) {
   for (int l = kLanes - 1; l >= 0; l--) lane_free(ctx->lane[l]);
   preprocess_free(ctx->pre);
   cluster_free(ctx->cluster);
+  plane_free(ctx->plane);
   for (auto &e : ctx->pre.ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->pre.ev_keys) (void)hipEventDestroy(ctx->pre.ev_keys);
@@ -916,6 +918,26 @@ int gpd_hip_estimate_normals(gpd_hip_ctx *ctx, double radius, float *normals) {
   }
   HIP_TRY(hipSetDevice(ctx->device));
   return normals_run(L.cloud, radius, normals, L.stream);
+}
+
+int gpd_hip_sample_above_plane(gpd_hip_ctx *ctx, double threshold, int max_iterations, double probability, int optimize,
+                                int32_t *indices_out, int *num_out, float coeffs[4], int *num_inliers, int *iterations) {
+  if (!ctx || !indices_out || !num_out || !coeffs || !num_inliers || !iterations || max_iterations < 0) {
+    set_error("gpd_hip_sample_above_plane: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  if (max_iterations >= kPlaneMaxHyp) {
+    set_error("gpd_hip_sample_above_plane: max_iterations = %d, the capacity is %d", max_iterations, kPlaneMaxHyp - 1);
+    return GPD_ERR_CAPACITY;
+  }
+  Lane &L = ctx->lane[0];
+  if (!L.cloud.num_points) {
+    set_error("gpd_hip_sample_above_plane: no cloud uploaded");
+    return GPD_ERR_STATE;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  return plane_fit_run(ctx->plane, L.cloud, threshold, max_iterations, probability, optimize, indices_out, num_out, coeffs, num_inliers,
+                       iterations, L.stream);
 }
 
 // samples by index (sample_xyz == nullptr) or by coordinates (sample_indices == nullptr)

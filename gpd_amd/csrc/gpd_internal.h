@@ -416,4 +416,24 @@ struct HostConsts {
 };
 void host_consts(const gpd_params &p, HostConsts &h);
 
+// ---- Cloud::sampleAbovePlane on the device (plane.hip; the definition: plane_model.h) ------------------------
+constexpr int kPlaneMaxHyp = 1024;   // hypotheses per call: max_iterations <= 1023
+constexpr int kPlaneSwapCap = 7680;  // positions >= 3 of shuffled_indices the draws of one call may touch (LDS table)
+struct PlaneState {
+  int capacity = 0;                  // points of the compaction buffers
+  void *d_meta = nullptr;            // hypotheses drawn, swap-table overflow, points the last compaction wrote
+  float4 *d_coef = nullptr;          // [kPlaneMaxHyp] plane of every hypothesis
+  int32_t *d_counts = nullptr;       // [kPlaneMaxHyp] its inliers
+  float *d_accu = nullptr;           // [9] the refinement's sums (one-wave variant)
+  int32_t *d_block_count = nullptr, *d_block_off = nullptr;
+  float *d_xyz = nullptr;            // [capacity][3] the best model's inliers in index order
+  int32_t *d_idx = nullptr;          // [capacity] the points off the final plane, ascending
+  char *h_pin = nullptr;             // pinned: meta, planes, counts, sums
+  std::vector<float> h_xyz;          // the inliers' xyz for the host's refinement
+};
+void plane_free(PlaneState &s);
+// on the uploaded cloud c; indices_out holds c.num_points entries.  *num_out = 0: no plane, or no point off it
+int plane_fit_run(PlaneState &s, const Cloud &c, double threshold, int max_iterations, double probability, int optimize, int32_t *indices_out,
+                  int *num_out, float coeffs[4], int *num_inliers, int *iterations, hipStream_t stream);
+
 }  // namespace gpd

@@ -56,6 +56,12 @@ class GraspDetector {
   // Cloud::calculateNormals (cloud.cpp:451-476) on the device: radius PCA, flipped to the view points,
   // reverseNormals; replaces the cloud's normals.  False when the device call fails.
   bool calculateNormals(util::Cloud &cloud, double radius);
+  // Cloud::sampleAbovePlane (cloud.cpp:407-436) on the device (gpd_hip_sample_above_plane, after uploading the cloud):
+  // the sample indices become the points off the fitted support plane, as util::Cloud::sampleAbovePlane sets them.  The
+  // equivalent of cfg sample_above_plane = 1 (ur5.cfg): preprocessPointCloud with num_samples = 0, this, then
+  // cloud.subsample(num_samples).  False when the device call fails.
+  bool sampleAbovePlane(util::Cloud &cloud, double threshold = 0.01, int max_iterations = 50, double probability = 0.99,
+                        bool optimize = true);
   std::vector<std::unique_ptr<candidate::HandSet>> generateGraspCandidates(const util::Cloud &cloud);
   std::vector<std::unique_ptr<candidate::HandSet>> filterGraspsWorkspace(
       std::vector<std::unique_ptr<candidate::HandSet>> &hand_set_list, const std::vector<double> &workspace) const;

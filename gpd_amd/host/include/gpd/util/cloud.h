@@ -51,6 +51,18 @@ class Cloud {
   // Cloud::subsample (cloud.cpp:350-405) draws with pcl::RandomSample (time-seeded); here a
   // seeded Fisher-Yates permutation so runs are reproducible.
   void subsample(int num_samples, unsigned seed = 0);
+  // Cloud::sampleAbovePlane (cloud.cpp:407-436): PCL 1.9's RANSAC plane fit (SACMODEL_PLANE, distance threshold,
+  // refined when `optimize`) and the sample indices set to the points off the plane, ascending — the definition is
+  // DESIGN §7.  When no plane is found or no point lies off it ("plane fit failed") the sample indices stay as they
+  // are.  This is the single-core host model; GraspDetector::sampleAbovePlane runs the same fit on the device.
+  struct PlaneFit {
+    std::vector<int> above;  // the points off the plane (empty: the fit failed)
+    float coeffs[4] = {0, 0, 0, 0};
+    int num_inliers = 0, iterations = 0;
+  };
+  PlaneFit sampleAbovePlane(double threshold = 0.01, int max_iterations = 50, double probability = 0.99, bool optimize = true);
+  // what sampleAbovePlane does with a fit: the reference's messages, the sample indices replaced when it succeeded
+  void applyPlaneFit(const PlaneFit &fit, double seconds);
 
  private:
   std::vector<float> xyz_, normals_;

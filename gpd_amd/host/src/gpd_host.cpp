@@ -17,6 +17,7 @@
 #include "gpd/grasp_detector.h"
 #include "gpd/sequential_importance_sampling.h"
 #include "gpd/util/config_file.h"
+#include "../../csrc/plane_model.h"
 
 namespace gpd {
 
@@ -415,6 +416,29 @@ void Cloud::voxelizeCloud(float cell_size) {
 // repetition (subsampleSamples), sample indices are redrawn num_samples times WITH repetition
 // (subsampleSampleIndices: sample_indices_[rand() % size]), otherwise num_samples points are drawn uniformly
 // (subsampleUniformly).  The reference's generators are time-seeded; here one seeded xorshift.
+Cloud::PlaneFit Cloud::sampleAbovePlane(double threshold, int max_iterations, double probability, bool optimize) {
+  const auto t0 = std::chrono::steady_clock::now();
+  printf("Sampling above plane ...\n");
+  const plane::Result r = plane::fit(xyz_.data(), (int)size(), threshold, max_iterations, probability, optimize);
+  PlaneFit fit;
+  fit.above = r.above;
+  for (int a = 0; a < 4; a++) fit.coeffs[a] = r.coeffs[a];
+  fit.num_inliers = r.num_inliers;
+  fit.iterations = r.iterations;
+  applyPlaneFit(fit, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  return fit;
+}
+
+void Cloud::applyPlaneFit(const PlaneFit &fit, double seconds) {
+  if (!fit.above.empty()) {
+    sample_indices_ = fit.above;
+    printf(" Plane fit succeeded. %zu samples above plane.\n", sample_indices_.size());
+  } else {
+    printf(" Plane fit failed. Using entire point cloud ...\n");
+  }
+  std::cout << " runtime (plane fit): " << seconds << "\n";
+}
+
 void Cloud::subsample(int num_samples, unsigned seed) {
   if (num_samples <= 0) return;
   uint64_t s = 0x9E3779B97F4A7C15ull ^ seed;
@@ -637,9 +661,10 @@ GraspDetector::GraspDetector(const std::string &config_filename) {
   num_selected_ = config_file.getValueOfKey<int>("num_selected", 100);
   use_file_normals_ = config_file.getValueOfKey<int>("use_file_normals", 0) != 0;
   // Preprocessing steps of CandidatesGenerator::preprocessPointCloud that are PCL algorithms of their own and are not
-  // restated here (candidates_generator.cpp:28-34, grasp_detector.cpp:52-63; all off in the shipped cfg files): a cloud
-  // that needs them has to go through them before it gets here.  Refused, not skipped: a silently different cloud would
-  // give silently different grasps.
+  // restated here (candidates_generator.cpp:28-34, grasp_detector.cpp:52-63): a cloud that needs them has to go through
+  // them before it gets here.  Refused, not skipped: a silently different cloud would give silently different grasps.
+  // Not all off in the shipped cfg files: ur5.cfg and cem_vino_params.cfg set sample_above_plane = 1; the fit itself is
+  // GraspDetector::sampleAbovePlane (call it between preprocessPointCloud with num_samples = 0 and subsample).
   const struct {
     const char *key, *what;
   } unsupported[] = {{"remove_outliers", "pcl::StatisticalOutlierRemoval (cloud.cpp:166-174)"},
@@ -819,6 +844,27 @@ void GraspDetector::preprocessPointCloud(util::Cloud &cloud) {
   }
   if (!keep_normals && cloud.size() > 0 && !calculateNormals(cloud, normals_radius_)) return;
   cloud.subsample(num_samples_);
+}
+
+bool GraspDetector::sampleAbovePlane(util::Cloud &cloud, double threshold, int max_iterations, double probability, bool optimize) {
+  const auto t0 = std::chrono::steady_clock::now();
+  printf("Sampling above plane ...\n");
+  if (!ctx_ || cloud.size() == 0) return false;
+  const std::vector<float> zeros(cloud.hasNormals() ? 0 : cloud.size() * 3, 0.f);
+  util::Cloud::PlaneFit fit;
+  fit.above.resize(cloud.size());
+  int num = 0;
+  if (gpd_hip_upload_cloud(ctx_, cloud.getCloudProcessed().data(), cloud.hasNormals() ? cloud.getNormals().data() : zeros.data(),
+                           (int)cloud.size(), cloud.getCameraSource().data(), cloud.numCameras(), cloud.getViewPoints().data()) != GPD_OK ||
+      gpd_hip_sample_above_plane(ctx_, threshold, max_iterations, probability, optimize ? 1 : 0, fit.above.data(), &num, fit.coeffs,
+                                 &fit.num_inliers, &fit.iterations) != GPD_OK) {
+    printf("ERROR: %s\n", gpd_hip_last_error());
+    return false;
+  }
+  last_num_sets_ = 0;
+  fit.above.resize(num);
+  cloud.applyPlaneFit(fit, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  return true;
 }
 
 bool GraspDetector::upload(const util::Cloud &cloud) {
@@ -1474,6 +1520,18 @@ extern "C" int gpd_host_find_clusters(const gpd_hand *hands, const double *score
     out_scores[k] = res[k]->getScore();
   }
   return (int)res.size();
+}
+
+// Flat entry for tests / ctypes: util::Cloud::sampleAbovePlane's fit on xyz [n][3]; above holds n entries.  Returns the
+// number of points off the plane (0: the fit failed).
+extern "C" int gpd_host_sample_above_plane(const float *xyz, int n, double threshold, int max_iterations, double probability, int optimize,
+                                           int *above, float *coeffs, int *num_inliers, int *iterations) {
+  const gpd::plane::Result r = gpd::plane::fit(xyz, n, threshold, max_iterations, probability, optimize != 0);
+  std::copy(r.above.begin(), r.above.end(), above);
+  for (int a = 0; a < 4; a++) coeffs[a] = r.coeffs[a];
+  *num_inliers = r.num_inliers;
+  *iterations = r.iterations;
+  return (int)r.above.size();
 }
 
 // Flat entry for tests / ctypes: loads a PCD like util::Cloud does; returns the number of points

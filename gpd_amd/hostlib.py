@@ -39,6 +39,23 @@ def find_clusters(hands, scores, min_inliers=1, remove_inliers=False):
     return out[:k].copy(), osc[:k].copy(), src[:k].copy()
 
 
+def sample_above_plane(xyz, threshold=0.01, max_iterations=50, probability=0.99, optimize=True):
+    """util::Cloud::sampleAbovePlane's fit on one core (the host model, DESIGN §7) ->
+    (indices off the plane i32 ascending — empty: the fit failed —, plane coefficients f32 [4], inliers, iterations)."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    n = len(xyz)
+    above = np.zeros(max(n, 1), np.int32)
+    coeffs = np.zeros(4, np.float32)
+    inl, its = C.c_int(0), C.c_int(0)
+    L = lib()
+    L.gpd_host_sample_above_plane.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    k = L.gpd_host_sample_above_plane(xyz.ctypes.data_as(C.c_void_p), n, float(threshold), int(max_iterations), float(probability),
+                                      int(bool(optimize)), above.ctypes.data_as(C.c_void_p), coeffs.ctypes.data_as(C.c_void_p), C.byref(inl),
+                                      C.byref(its))
+    return above[:k].copy(), coeffs, int(inl.value), int(its.value)
+
+
 def load_pcd(path, cap=1 << 22):
     """util::Cloud(filename): ASCII or uncompressed binary PCD -> (xyz f32 [n,3], normals f32 [n,3] or None)."""
     xyz = np.zeros((cap, 3), np.float32)

@@ -182,6 +182,19 @@ int gpd_hip_preprocess_cloud(gpd_hip_ctx *ctx, const float *xyz, const int32_t *
  * be zeros).  normals receives num_points*3 floats and also replaces the device copy. */
 int gpd_hip_estimate_normals(gpd_hip_ctx *ctx, double radius, float *normals);
 
+/* Replaces Cloud::sampleAbovePlane (util/cloud.cpp:407-436; CandidatesGenerator::preprocessPointCloud calls it between
+ * the normals and subsample, candidates_generator.cpp:32-34): PCL 1.9's SACSegmentation with SACMODEL_PLANE, SAC_RANSAC,
+ * setDistanceThreshold(threshold) and setOptimizeCoefficients(optimize), then ExtractIndices(negative) — the definition
+ * is DESIGN §7.  The reference's values: threshold 0.01, max_iterations 50, probability 0.99, optimize 1.
+ * On the cloud uploaded last (its normals are not read).  indices_out must hold num_points entries: the points farther
+ * than the threshold from the final plane, ascending, *num_out of them.  *num_out = 0 is the reference's "plane fit
+ * failed" (no model, or every point on the plane): the caller keeps its sample indices then.  coeffs: the final plane
+ * (a, b, c, d), zero without a model; *num_inliers: points within the threshold of it; *iterations: the hypotheses RANSAC
+ * evaluated.  Capacities (GPD_ERR_CAPACITY beyond them): max_iterations <= 1023, and the draws of one call may touch at
+ * most 7680 positions of PCL's shuffled index list (3 per try: only clouds with many degenerate draws come near it). */
+int gpd_hip_sample_above_plane(gpd_hip_ctx *ctx, double threshold, int max_iterations, double probability, int optimize,
+                               int32_t *indices_out, int *num_out, float coeffs[4], int *num_inliers, int *iterations);
+
 /* Replaces CandidatesGenerator::generateGraspCandidateSets ->
  * HandSearch::searchHands (candidates_generator.cpp:62-69, hand_search.cpp:24-64)
  * for samples given by index (Cloud::getSampleIndices).  Writes
