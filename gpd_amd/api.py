@@ -72,7 +72,7 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_search_samples", "gpd_hip_detect_samples", "gpd_hip_reevaluate", "gpd_hip_replay_kernel_ms", "gpd_hip_last_centre_chains",
            "gpd_hip_detect_select", "gpd_hip_detect_batch", "gpd_hip_detect_batch_multi", "gpd_hip_conv1_stats", "gpd_hip_last_fallbacks", "gpd_hip_preprocess_cloud", "gpd_hip_find_clusters", "gpd_hip_reserve", "gpd_hip_bind_host_thread",
            "gpd_hip_set_lenet_mode", "gpd_hip_lenet_debug", "gpd_hip_lenet_fast_tables", "gpd_hip_detect_sharded",
-           "gpd_hip_sample_above_plane"]
+           "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes"]
 
 
 def build(prof=True):
@@ -109,6 +109,7 @@ def lib():
         L.gpd_hip_detect_batch_multi.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(DetectJob), C.c_int]
         L.gpd_hip_detect_sharded.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(DetectJob)]
         L.gpd_hip_last_fallbacks.argtypes = [C.c_void_p, C.c_void_p]
+        L.gpd_hip_last_image_routes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.gpd_hip_last_centre_chains.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
         L.gpd_hip_last_stage_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.gpd_hip_replay.argtypes = [C.c_void_p, C.c_int]
@@ -394,6 +395,19 @@ class Context:
         self._check(lib().gpd_hip_last_fallbacks(self._h, _ptr(out)))
         return dict(neighbourhood_list_capacity=int(out[0]), large_shadow_kernel_candidates=int(out[1]),
                     large_points_kernel_candidates=int(out[2]), lenet_passes=int(out[3]))
+
+    def image_routes(self):
+        """Which image kernels the last image launch sent each candidate through (tests only) -> (route int32 [n], info):
+        route bit 1 = queued for the large shadow instantiation, 2 = queued again for the general shadow kernel, 4 = queued
+        for the large points kernel; info: candidates, window_class (0 default, 1 wide, 2 huge), set_mode
+        (shadow_set_kernel's, -1: none), status (capacity flags), and the caps pt_cap, pt_cap_big, sh_cap, sh_cap_big."""
+        n = self.images_stats()["candidates"]
+        route = np.zeros(max(n, 1), np.int32)
+        info = np.zeros(8, np.int64)
+        self._check(lib().gpd_hip_last_image_routes(self._h, _ptr(route), len(route), _ptr(info)))
+        keys = ("candidates", "window_class", "set_mode", "status", "pt_cap", "pt_cap_big", "sh_cap", "sh_cap_big")
+        info = {k: int(v) for k, v in zip(keys, info)}
+        return route[: info["candidates"]].copy(), info
 
     def centre_chains(self):
         """(sample, coordinate) pairs of the last search whose neighbourhood centre took the serial fp64 chain (the order-free sum

@@ -1737,6 +1737,21 @@ int gpd_hip_last_fallbacks(gpd_hip_ctx *ctx, long long out[4]) {
   return GPD_OK;
 }
 
+int gpd_hip_last_image_routes(gpd_hip_ctx *ctx, int32_t *route, int n, long long info[8]) {
+  if (!ctx || !route || !info || n < 0) {
+    set_error("gpd_hip_last_image_routes: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  Lane &L = ctx->lane[0];
+  if (n < L.images.num_candidates) {
+    set_error("gpd_hip_last_image_routes: room for %d candidates, the last launch had %d", n, L.images.num_candidates);
+    return GPD_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(L.stream));
+  return images_routes(L.images, route, info);
+}
+
 int gpd_hip_last_centre_chains(gpd_hip_ctx *ctx, long long *out) {
   if (!ctx || !out) return GPD_ERR_INVALID;
   HIP_TRY(hipSetDevice(ctx->device));

@@ -398,6 +398,8 @@ int images_run(const gpd_params &p, const Cloud &c, const SearchState &s, const 
 // Re-launches them on the resident list.  Nothing waits for the device: capacity flags accumulate in im.d_status.
 int images_launch(const SearchState &s, const Plan &pl, ImageState &im, hipStream_t stream, bool counters_clean = false);
 void images_status_text(int status, char *buf, size_t len);
+// gpd_hip_last_image_routes on a lane whose stream has been waited for (route: im.num_candidates entries)
+int images_routes(const ImageState &im, int32_t *route, long long info[8]);
 hipError_t planar_to_hwc(const uint8_t *src, uint8_t *dst, int n, int C, hipStream_t stream);
 hipError_t hwc_to_planar(const uint8_t *src, uint8_t *dst, int n, int C, hipStream_t stream);
 void image_cell_thresholds(double len, double *out);  // 61 doubles

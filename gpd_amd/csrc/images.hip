@@ -2256,4 +2256,44 @@ void images_status_text(int status, char *buf, size_t len) {
            "4 shadow voxels in a box > %d)", status, HUGE_WIN, PT_CAP_BIG, HUGE_CAP);
 }
 
+// The routes of the last launch from the three queues images_launch hands the kernels (d_overflow / d_status[1],
+// d_overflow2 / [2], d_pts_overflow / [3]); the caller has waited for the lane's stream.
+int images_routes(const ImageState &im, int32_t *route, long long info[8]) {
+  const int n = im.num_candidates;
+  info[0] = n;
+  info[1] = im.huge ? 2 : (im.wide ? 1 : 0);
+  info[2] = (n > 0 && im.num_shadow_sets > 0) ? (int)info[1] : -1;  // images_launch's condition for shadow_set_kernel
+  info[3] = 0;
+  info[4] = PT_CAP;
+  info[5] = PT_CAP_BIG;
+  info[6] = SH_CAP;
+  info[7] = SH_CAP_BIG;
+  if (n <= 0 || !im.d_status) return GPD_OK;
+  std::memset(route, 0, (size_t)n * sizeof(int32_t));
+  int32_t st[4];
+  HIP_RET(hipMemcpy(st, im.d_status, sizeof(st), hipMemcpyDeviceToHost));
+  info[3] = st[0];
+  const int32_t *lists[3] = {im.d_overflow, im.d_overflow2, im.d_pts_overflow};
+  const int bits[3] = {1, 2, 4};
+  std::vector<int32_t> h;
+  for (int l = 0; l < 3; l++) {
+    const int cnt = st[1 + l];
+    if (cnt == 0) continue;
+    if (cnt < 0 || cnt > n || !lists[l]) {
+      set_error("gpd_hip_last_image_routes: queue %d holds %d entries for %d candidates", l + 1, cnt, n);
+      return GPD_ERR_STATE;
+    }
+    h.resize((size_t)cnt);
+    HIP_RET(hipMemcpy(h.data(), lists[l], (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int i = 0; i < cnt; i++) {
+      if (h[i] < 0 || h[i] >= n || (route[h[i]] & bits[l])) {
+        set_error("gpd_hip_last_image_routes: queue %d entry %d is %d (candidates: %d, or queued twice)", l + 1, i, h[i], n);
+        return GPD_ERR_STATE;
+      }
+      route[h[i]] |= bits[l];
+    }
+  }
+  return GPD_OK;
+}
+
 }  // namespace gpd

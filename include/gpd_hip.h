@@ -370,6 +370,20 @@ int gpd_hip_last_images_stats(gpd_hip_ctx *ctx, long long out[4]);
  * each).  Waits for the context's stream. */
 int gpd_hip_last_fallbacks(gpd_hip_ctx *ctx, long long out[4]);
 
+/* Which image kernels the last image launch of the single-cloud entries (gpd_hip_images, gpd_hip_detect*, gpd_hip_replay)
+ * sent each candidate through, read back from the device lists the kernels fill (none of it changes a result).
+ * Tests only: the timed path never calls it.  Waits for the context's stream.
+ * route (n entries, n >= info[0]): per candidate of the launch, in candidate order, a bit mask —
+ *   1: the two-per-CU shadow kernel could not list its box and queued it for the large instantiation,
+ *   2: the large one (wide windows) could not list it either and queued it for the general shadow kernel,
+ *   4: the two-per-CU normals / depth kernel queued it for the global-scratch instantiation;
+ *   0: its images came from the first kernel of each kind alone (window class 2: the general shadow kernel takes all).
+ * info: [0] candidates of the launch, [1] window class of the geometry (0 default, 1 wide, 2 huge), [2] the
+ * shadow_set_kernel mode that ran (0, 1, 2; -1: none), [3] the capacity flags of the launch (1 window, 2 in-box points,
+ * 4 in-box shadow voxels: what GPD_ERR_CAPACITY reports), [4] PT_CAP, [5] PT_CAP_BIG, [6] SH_CAP, [7] SH_CAP_BIG.
+ * GPD_ERR_INVALID for a null argument or n < info[0]; GPD_ERR_STATE if a list holds an entry that is no candidate. */
+int gpd_hip_last_image_routes(gpd_hip_ctx *ctx, int32_t *route, int n, long long info[8]);
+
 /* Of the last search's 3 x num_samples centre coordinates (the mean of a sample's image neighbourhood, hand_set.cpp:131-133):
  * how many took the serial fp64 chain in neighbour order because the order-free sum taken inside the neighbourhood kernel could
  * not be certified exact (a point within micrometres of a coordinate plane among points decimetres away).  Wherever the

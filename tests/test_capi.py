@@ -90,3 +90,18 @@ def test_shipped_sources_carry_no_experiment_switches():
             if m:
                 names = set(re.findall(r"[A-Za-z_][A-Za-z_0-9]*", m.group(2))) - {"defined"}
                 assert names <= allowed, "%s:%d: %s" % (f, i, line.strip())
+
+
+def test_image_routes_refuses_null_arguments():
+    """gpd_hip_last_image_routes checks its arguments before it touches a context or the device: a null context, route
+    buffer or info block, or a negative size, is GPD_ERR_INVALID (no GPU needed)."""
+    from gpd_amd import api
+    L = api.lib()
+    route = (ctypes.c_int32 * 4)()
+    info = (ctypes.c_longlong * 8)()
+    not_a_context = ctypes.create_string_buffer(64)  # never dereferenced: the null buffer next to it is refused first
+    assert L.gpd_hip_last_image_routes(None, route, 4, info) == -1
+    assert L.gpd_hip_last_image_routes(not_a_context, None, 4, info) == -1
+    assert L.gpd_hip_last_image_routes(not_a_context, route, 4, None) == -1
+    assert L.gpd_hip_last_image_routes(not_a_context, route, -1, info) == -1
+    assert b"bad argument" in L.gpd_hip_last_error()

@@ -368,6 +368,10 @@ def test_dense_cloud_overflow_fallbacks(oracle_mod):
         img, cand = ctx.images(fw)
         oimg, ocand = oracle_mod.images(p, xyz, nrm, cam, cl["view_points"], fw)
         assert np.array_equal(cand, ocand) and np.array_equal(img, oimg)
+        # the device queue says so too: candidates redone by the global-scratch points kernel, no capacity flag
+        route, info = ctx.image_routes()
+        assert info["candidates"] == len(cand) and info["status"] == 0 and info["window_class"] == 0
+        assert (route & 4).any()
         # some box really holds more than 2048 points: count them for the valid hands (hand-frame box test)
         worst = 0
         flat = fw.reshape(-1)
@@ -637,6 +641,10 @@ def test_neighbourhoods_beyond_65535_points(oracle_mod):
         img, cand = ctx.images(fw)
         oimg, ocand = oracle_mod.images(p, xyz, nrm, cam, cl["view_points"], fw)
         assert np.array_equal(cand, ocand) and np.array_equal(img, oimg)
+        # boxes of ten to twenty thousand points (and neighbourhoods beyond 16-bit ranks): the large points kernel ran
+        route, info = ctx.image_routes()
+        assert info["candidates"] == len(cand) and info["status"] == 0
+        assert (route & 4).any()
     finally:
         ctx.close()
 

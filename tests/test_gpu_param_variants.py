@@ -70,6 +70,13 @@ def test_detect_matches_oracle_under_parameter_variant(oracle_mod, name):
         oimg, ocand = oracle_mod.images(op, cl["xyz"], cl["normals"], cl["cam_source"], cl["view_points"],
                                         oracle_mod.filter_workspace(op, ohands.copy()))
         assert np.array_equal(cand, ocand) and np.array_equal(img, oimg)
+        # the window class the volume selects, and the shadow kernels that ran for it (gpd_hip_last_image_routes)
+        route, info = ctx.image_routes()
+        assert info["candidates"] == len(cand) and info["status"] == 0
+        if name == "wide_image_volume":
+            assert info["window_class"] == 1 and info["set_mode"] == 1
+        elif name == "huge_image_volume":
+            assert info["window_class"] == 2 and info["set_mode"] == 2 and not (route & 3).any()
     finally:
         ctx.close()
 
