@@ -331,7 +331,11 @@ static int job_wait_plan(gpd_hip_ctx *ctx, Lane &L, Job &J) {
       set_error("search: a neighbourhood holds %d points, more than the list capacity %d", L.plan.h_summary->worst_found, kNnCapMax);
       return GPD_ERR_CAPACITY;
     }
-    int rc = search_force_capacity(L.search, cap);
+    // the side stream's centre_kernel of the first run is ordered before the plan, so it is done; the main stream still waits for
+    // it explicitly before neighbourhood_kernel rebuilds the lists
+    int rc = search_join(L.search, L.stream);
+    if (rc) return rc;
+    rc = search_force_capacity(L.search, cap);
     if (rc) return rc;
     rc = job_begin(ctx, L, J);
     if (rc) return rc;

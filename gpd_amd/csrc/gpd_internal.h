@@ -233,6 +233,7 @@ struct SearchState {
   float4 *d_hl = nullptr;             // [S][cap] points that can be in-height for some orientation: x, y, z, rank bits (height_list_kernel)
   uint8_t *d_fvalid = nullptr;        // [S][slots] is_valid after filterGraspsWorkspace (hand_eval_kernel writes it; the
                                       // unfused gpd_hip_images overwrites it with the caller's flags)
+  int32_t *d_labels = nullptr;        // [S] reeval_kernel's labels (one hand per sample slot)
   // centre_kernel (serial fp64 chains: a hundred-odd waves, latency-bound) runs on a side stream beside
   // hand_eval_kernel and is joined before anything reads d_centers
   hipStream_t aux = nullptr;
@@ -249,6 +250,8 @@ int search_run(const gpd_params &p, const Cloud &c, SearchState &s, const int32_
 // list capacity the next search_run would use after a neighbourhood of `worst` entries; 0: beyond every capacity
 int search_reserve_samples(SearchState &s, int S, int slots);  // buffers for S samples at the current list capacity
 int search_next_capacity(const SearchState &s, int worst);
+// the main stream waits for the centre sums (side stream) of the last run_neighbourhoods
+int search_join(SearchState &s, hipStream_t stream);
 int search_force_capacity(SearchState &s, int cap);
 // HandSearch::reevaluateHypotheses on the uploaded cloud; invalidates the search state
 int reevaluate_run(const gpd_params &p, const Cloud &c, SearchState &s, gpd_hand *hands, int n, int32_t *labels, hipStream_t stream);

@@ -2085,7 +2085,7 @@ struct HandParams {
   float4 *hl;       // [S][cap] neighbourhood_kernel's gather -> hand_eval_kernel; its length per sample in counts[8 s + 6]
   double radius;    // of the hand-search neighbourhood (bounds |p - sample|)
   int num_samples;
-  int32_t *labels;  // reeval_kernel only: [n][8] rows of the counts table, column 5
+  int32_t *labels;  // reeval_kernel only: [n] labels (SearchState::d_labels; counts[8 s + 5] is centre_kernel's, on the side stream)
   unsigned long long *dbg;  // profiling aid (GPD_HE_TIMING=1): per-phase cycle sums of thread 0, [8] = sum of N, [9] = sum of k
 };
 
@@ -2323,7 +2323,8 @@ __device__ bool closing_region_label(const ListCtx &L, int N, double top, double
 // HandSearch::reevaluateHypotheses (hand_search.cpp:66-134, 190-228): one
 // workgroup per hand checks it again against the uploaded (ground-truth) cloud with the hand's own
 // frame, depth and finger placement: evaluateFingers(points, top, idx), evaluateHand(idx), closing
-// region, antipodal label.  counts[8*i+5] receives the label (1 = full antipodal grasp).
+// region, antipodal label.  labels[i] receives the label (1 = full antipodal grasp): a buffer of its
+// own, since centre_kernel may still be reading counts[8 s + 5] on the side stream.
 __global__ __launch_bounds__(256) void reeval_kernel(HandParams P) {
   __shared__ unsigned s_u[4];
   __shared__ double s_d[4];
@@ -2379,7 +2380,7 @@ __global__ __launch_bounds__(256) void reeval_kernel(HandParams P) {
   if (tid == 0) {
     H->half_antipodal = label == 1;
     H->full_antipodal = label == 2;
-    P.labels[8 * s + 5] = label == 2 ? 1 : 0;
+    P.labels[s] = label == 2 ? 1 : 0;
   }
 }
 
@@ -2656,7 +2657,8 @@ __global__ __launch_bounds__(256) void hand_eval_kernel(HandParams P) {
 // Host side
 // ---------------------------------------------------------------------------
 void search_free(SearchState &s) {
-  void *ptrs[] = {s.d_sample_idx, s.d_sample_xyz, s.d_counts, s.d_nn_idx, s.d_nn, s.d_frames, s.d_centers, s.d_hands, s.d_fvalid, s.d_hl};
+  void *ptrs[] = {s.d_sample_idx, s.d_sample_xyz, s.d_counts, s.d_nn_idx, s.d_nn, s.d_frames, s.d_centers, s.d_hands, s.d_fvalid, s.d_hl,
+                  s.d_labels};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);  // hipFree waits for the device: the side stream is idle as well
   if (s.ev_fork) (void)hipEventDestroy(s.ev_fork);
@@ -2697,12 +2699,19 @@ static int search_reserve(SearchState &s, int S, int cap, int slots) {
   HIP_RET(hipMalloc(&s.d_hands, (size_t)newS * slots * sizeof(gpd_hand)));
   HIP_RET(hipMalloc(&s.d_fvalid, (size_t)newS * slots));
   HIP_RET(hipMalloc(&s.d_hl, (size_t)newS * cap * sizeof(float4)));
+  HIP_RET(hipMalloc(&s.d_labels, (size_t)newS * sizeof(int32_t)));
   s.capacity_samples = newS;
   s.nn_cap = cap;
   return GPD_OK;
 }
 
 int search_reserve_samples(SearchState &s, int S, int slots) { return search_reserve(s, S, s.nn_cap ? s.nn_cap : 8192, slots); }
+
+// the main stream waits for the centre sums of the last run_neighbourhoods
+int search_join(SearchState &s, hipStream_t stream) {
+  if (s.ev_join) HIP_RET(hipStreamWaitEvent(stream, s.ev_join, 0));
+  return GPD_OK;
+}
 
 static int run_neighbourhoods(const gpd_params &p, const Cloud &c, SearchState &s, const HostConsts &hc, int S, int cap, bool by_xyz,
                               int slots, bool want_height_list, hipStream_t stream, bool sync_counts) {
@@ -2789,12 +2798,6 @@ static int run_neighbourhoods(const gpd_params &p, const Cloud &c, SearchState &
   return GPD_OK;
 }
 
-// the main stream waits for the centre sums of the last run_neighbourhoods
-static int search_join(SearchState &s, hipStream_t stream) {
-  if (s.ev_join) HIP_RET(hipStreamWaitEvent(stream, s.ev_join, 0));
-  return GPD_OK;
-}
-
 // neighbourhoods of S samples (by index or by coordinates), list capacity grown once if needed
 static int neighbourhoods(const gpd_params &p, const Cloud &c, SearchState &s, const HostConsts &hc, const int32_t *sample_idx,
                           const double *sample_xyz, int S, int slots, int *cap_out, hipStream_t stream, bool sync_counts = true,
@@ -2822,6 +2825,10 @@ static int neighbourhoods(const gpd_params &p, const Cloud &c, SearchState &s, c
     int worst = 0;
     for (int i = 0; i < S; i++) worst = s.h_counts[8 * i + 3] > worst ? s.h_counts[8 * i + 3] : worst;
     if (worst <= cap) break;
+    // the first run's centre_kernel may still read d_nn / d_counts and write d_centers on the side stream: the lists are
+    // rebuilt (and reallocated) only after it
+    rc = search_join(s, stream);
+    if (rc) return rc;
     cap = search_next_capacity(s, worst);
     if (!cap) {
       set_error("search: a neighbourhood holds %d points, more than the list capacity %d", worst, kNnCapMax);
@@ -2984,7 +2991,7 @@ int reevaluate_run(const gpd_params &p, const Cloud &c, SearchState &s, gpd_hand
   hp.cap = cap;
   hp.hands = s.d_hands;
   hp.fvalid = nullptr;
-  hp.labels = s.d_counts;
+  hp.labels = s.d_labels;
   hp.dbg = nullptr;
   hp.hl = nullptr;
   hp.radius = 0.0;
@@ -2994,9 +3001,8 @@ int reevaluate_run(const gpd_params &p, const Cloud &c, SearchState &s, gpd_hand
   rc = search_join(s, stream);
   if (rc) return rc;
   HIP_RET(hipMemcpyAsync(hands, s.d_hands, (size_t)n * sizeof(gpd_hand), hipMemcpyDeviceToHost, stream));
-  HIP_RET(hipMemcpyAsync(s.h_counts.data(), s.d_counts, (size_t)n * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  HIP_RET(hipMemcpyAsync(labels, s.d_labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   HIP_RET(hipStreamSynchronize(stream));
-  for (int i = 0; i < n; i++) labels[i] = s.h_counts[8 * (size_t)i + 5];
   return GPD_OK;
 }
 

@@ -146,3 +146,70 @@ def eval_hand_set(P, xyz, normals, nbr_idx, frame12, angle_axis):
                     h["half"], h["full"] = lab >= 1, lab == 2
             out.append(h)
     return out
+
+
+def reevaluate(P, xyz, normals, hands):
+    """HandSearch::reevaluateHypotheses (candidate/hand_search.cpp:66-134), reevaluateHypothesis and labelHypothesis
+    (:190-228) -> (labels int32 [n], half bool [n], full bool [n]).
+
+    Neighbourhoods come from scipy's cKDTree, then FLANN's test: the float32 query (eigenVectorToPcl), the float32 squared
+    distance summed over x, y, z, strict < against (float)(radius * radius), ordered by (distance, index).  The padded list
+    of cropByHandHeight is materialised: the in-height points, then copies of column 0.  A hand without a finger placement
+    in range is labelled 0 (the reference would index out of bounds)."""
+    from scipy.spatial import cKDTree
+
+    f32 = np.float32
+    xyz = np.ascontiguousarray(xyz, f32)
+    normals = np.ascontiguousarray(normals, f32)
+    radius = max(P.hand_outer_diameter - P.finger_width, P.hand_depth, P.hand_height / 2.0)
+    r2 = f32(radius * radius)
+    tree = cKDTree(xyz.astype(np.float64))
+    n = len(hands)
+    labels = np.zeros(n, np.int32)
+    half = np.zeros(n, bool)
+    full = np.zeros(n, bool)
+    for i in range(n):
+        h = hands[i]
+        idx = int(h["finger_placement_index"])
+        if idx < 0 or idx >= P.num_finger_placements:
+            continue
+        sample = np.asarray(h["sample"], np.float64)
+        q = sample.astype(f32)
+        cand = np.asarray(tree.query_ball_point(q.astype(np.float64), radius * 1.0001 + 1e-6), np.int64)
+        if len(cand) == 0:
+            continue
+        d = q[None, :] - xyz[cand]
+        d2 = f32(0) + d[:, 0] * d[:, 0]
+        d2 = d2 + d[:, 1] * d[:, 1]
+        d2 = d2 + d[:, 2] * d[:, 2]
+        keep = d2 < r2
+        cand, d2 = cand[keep], d2[keep]
+        if len(cand) == 0:
+            continue
+        nbr = cand[np.lexsort((cand, d2))]
+        # transformToHandFrame(sample, frame^T): rotation * (p - sample), rows of the rotation = columns of the frame
+        F = np.asarray(h["frame"], np.float64).reshape(3, 3)
+        c = xyz[nbr].astype(np.float64) - sample
+        nd = normals[nbr].astype(np.float64)
+        pf = np.stack([F[0, r] * c[:, 0] + F[1, r] * c[:, 1] + F[2, r] * c[:, 2] for r in range(3)])
+        nf = np.stack([F[0, r] * nd[:, 0] + F[1, r] * nd[:, 1] + F[2, r] * nd[:, 2] for r in range(3)])
+        N = pf.shape[1]
+        inh = np.flatnonzero((pf[2] > -1.0 * P.hand_height) & (pf[2] < P.hand_height))
+        col = np.zeros(N, int)
+        col[: len(inh)] = inh
+        pts, nrm = pf[:, col], nf[:, col]
+        fh = FingerHand(P.finger_width, P.hand_outer_diameter, P.hand_depth, P.num_finger_placements)
+        fh.evaluate_fingers(pts, float(h["top"]), idx)
+        fh.hand[:] = False  # evaluateHand(idx)
+        fh.hand[idx] = fh.fingers[idx] and fh.fingers[fh.n + idx]
+        if not fh.hand.any():
+            continue
+        closing = fh.closing_region(pts, int(np.flatnonzero(fh.hand)[0]))
+        if len(closing) == 0:
+            continue
+        lab = antipodal(pts[:, closing], nrm[:, closing], P.friction_coeff, P.min_viable)
+        if lab == 2:
+            labels[i], full[i] = 1, True
+        elif lab == 1:
+            half[i] = True
+    return labels, half, full

@@ -156,3 +156,12 @@ def assert_scores(ctx, img, want, tol=1e-4, rel=0.0):
         bound = max(tol, rel * float(np.abs(want).max()))
         assert np.abs(got - want).max() <= bound, (float(np.abs(got - want).max()), bound)
     return got
+
+
+def ground_truth(xyz, normals, seed, keep=0.85, jitter=0.0004):
+    """A "ground truth" cloud made from a case's cloud: a seeded subsample (`keep` of the points, in cloud order), every point
+    moved by up to `jitter` metres per axis -> (xyz f32, the kept normals, the kept indices)."""
+    rng = np.random.RandomState(seed)
+    sel = np.sort(rng.choice(len(xyz), int(keep * len(xyz)), replace=False))
+    gt = (xyz[sel].astype(np.float64) + rng.uniform(-jitter, jitter, (len(sel), 3))).astype(np.float32)
+    return gt, normals[sel].copy(), sel

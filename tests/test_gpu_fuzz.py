@@ -70,6 +70,17 @@ def test_fuzz_detect_matches_oracle(oracle_mod, seed):
         got = ctx.search_samples(sm)
         want = oracle_mod.search_xyz(op, c["xyz"], c["normals"], sm)
         assert got.shape == want.shape and got.tobytes() == want.tobytes()
+        # HandSearch::reevaluateHypotheses of the detected hands against a jittered subsample of the cloud, the case's parameters
+        rng = np.random.RandomState(3000 + seed)
+        sel = np.sort(rng.choice(len(c["xyz"]), int(0.85 * len(c["xyz"])), replace=False))
+        gt = (c["xyz"][sel].astype(np.float64) + rng.uniform(-0.0004, 0.0004, (len(sel), 3))).astype(np.float32)
+        gn = c["normals"][sel].copy()
+        ctx.upload_cloud(gt, gn, c["cam"][:, sel].copy(), c["vp"])
+        recs = hands.reshape(-1)
+        labels, out = ctx.reevaluate(recs)
+        wl, wout = oracle_mod.reevaluate(op, gt, gn, recs)
+        assert np.array_equal(labels, wl) and out.tobytes() == wout.tobytes()
+        assert np.array_equal(out["half_antipodal"], wout["half_antipodal"]) and np.array_equal(out["full_antipodal"], wout["full_antipodal"])
     finally:
         ctx.close()
 
