@@ -72,7 +72,7 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_search_samples", "gpd_hip_detect_samples", "gpd_hip_reevaluate", "gpd_hip_replay_kernel_ms", "gpd_hip_last_centre_chains",
            "gpd_hip_detect_select", "gpd_hip_detect_batch", "gpd_hip_detect_batch_multi", "gpd_hip_conv1_stats", "gpd_hip_last_fallbacks", "gpd_hip_preprocess_cloud", "gpd_hip_find_clusters", "gpd_hip_reserve", "gpd_hip_bind_host_thread",
            "gpd_hip_set_lenet_mode", "gpd_hip_lenet_debug", "gpd_hip_lenet_fast_tables", "gpd_hip_detect_sharded",
-           "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes"]
+           "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals"]
 
 
 def build(prof=True):
@@ -116,6 +116,8 @@ def lib():
         L.gpd_hip_estimate_normals.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         L.gpd_hip_sample_above_plane.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_int),
                                                  C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.gpd_hip_refine_normals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
+                                             C.POINTER(C.c_int), C.c_void_p]
         L.gpd_hip_find_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_int)]
         L.gpd_hip_preprocess_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
@@ -465,3 +467,18 @@ class Context:
         self._check(lib().gpd_hip_sample_above_plane(self._h, float(threshold), int(max_iterations), float(probability), int(bool(optimize)),
                                                      _ptr(idx), C.byref(n), _ptr(coeffs), C.byref(inl), C.byref(its)))
         return idx[: n.value].copy(), coeffs, int(inl.value), int(its.value)
+
+    def refine_normals(self, k, max_iterations=15, convergence_threshold=1e-5):
+        """Cloud::refineNormals(k) on the normals of the uploaded (or last estimated) cloud (kNN + NormalRefinement, DESIGN §7);
+        the result replaces the device copy, so a detect that follows uses it -> (normals f32 [P,3] (NaN: a singularity),
+        passes run, the stop rule's mean dot product of every pass f32 [passes], normals with a non-finite component).
+        self.last_refine_ms: kNN kernel, refinement passes launched, the whole call (ms)."""
+        P = self._num_points
+        out = np.zeros((P, 3), np.float32)
+        ddots = np.zeros(max(int(max_iterations), 1), np.float32)
+        ms = np.zeros(3, np.float32)
+        its, nan = C.c_int(0), C.c_int(0)
+        self._check(lib().gpd_hip_refine_normals(self._h, int(k), int(max_iterations), float(convergence_threshold), _ptr(out), C.byref(its),
+                                                 _ptr(ddots), C.byref(nan), _ptr(ms)))
+        self.last_refine_ms = tuple(float(v) for v in ms)
+        return out, int(its.value), ddots[: its.value].copy(), int(nan.value)

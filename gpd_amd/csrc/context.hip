@@ -134,6 +134,7 @@ struct gpd_hip_ctx {
   PreState pre;
   ClusterState cluster;
   PlaneState plane;  // gpd_hip_sample_above_plane
+  RefineState refine;  // gpd_hip_refine_normals
   std::vector<hipEvent_t> replay_events;  // 6 per gpd_hip_replay call: start, images done, conv1, conv2, fc1, end
   float replay_kernel_ms[4] = {0, 0, 0, 0};  // conv1, conv2, fc1, fc2 sums of the replays of the last gpd_hip_replay_times
   size_t replay_used = 0;
@@ -645,6 +646,7 @@ void gpd_hip_destroy(gpd_hip_ctx *ctx) {
   preprocess_free(ctx->pre);
   cluster_free(ctx->cluster);
   plane_free(ctx->plane);
+  refine_free(ctx->refine);
   for (auto &e : ctx->pre.ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->pre.ev_keys) (void)hipEventDestroy(ctx->pre.ev_keys);
@@ -942,6 +944,27 @@ int gpd_hip_sample_above_plane(gpd_hip_ctx *ctx, double threshold, int max_itera
   HIP_TRY(hipSetDevice(ctx->device));
   return plane_fit_run(ctx->plane, L.cloud, threshold, max_iterations, probability, optimize, indices_out, num_out, coeffs, num_inliers,
                        iterations, L.stream);
+}
+
+int gpd_hip_refine_normals(gpd_hip_ctx *ctx, int k, int max_iterations, float convergence_threshold, float *normals_out, int *iterations_out,
+                           float *ddot_out, int *num_nan_out, float kernel_ms[3]) {
+  if (!ctx || !normals_out || !iterations_out || !num_nan_out || k < 1 || max_iterations < 0 || !std::isfinite(convergence_threshold) ||
+      convergence_threshold < 0.f) {
+    set_error("gpd_hip_refine_normals: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  if (k > kRefineKCap) {
+    set_error("gpd_hip_refine_normals: k = %d, the capacity is %d", k, kRefineKCap);
+    return GPD_ERR_CAPACITY;
+  }
+  Lane &L = ctx->lane[0];
+  if (!L.cloud.num_points) {
+    set_error("gpd_hip_refine_normals: bad argument: no cloud uploaded");
+    return GPD_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  return refine_run(ctx->refine, L.cloud, k, max_iterations, convergence_threshold, normals_out, iterations_out, ddot_out, num_nan_out, kernel_ms,
+                    L.stream);
 }
 
 // samples by index (sample_xyz == nullptr) or by coordinates (sample_indices == nullptr)

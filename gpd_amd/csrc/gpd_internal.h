@@ -441,4 +441,23 @@ void plane_free(PlaneState &s);
 int plane_fit_run(PlaneState &s, const Cloud &c, double threshold, int max_iterations, double probability, int optimize, int32_t *indices_out,
                   int *num_out, float coeffs[4], int *num_inliers, int *iterations, hipStream_t stream);
 
+// ---- Cloud::refineNormals on the device (refine.hip; the definition: refine_model.h) --------------------------
+constexpr int kRefineKCap = 256;     // neighbours per point: k <= 256
+struct RefineState {
+  int cap_points = 0;
+  size_t cap_lists = 0;              // int32 entries of d_lists
+  int32_t *d_lists = nullptr;        // [ceil(P / 64)][k][64] the sorted neighbour indices by cell-order position
+  float4 *d_buf[2] = {nullptr, nullptr};  // [P] the normals between passes (ping-pong), by original index
+  float *d_dots = nullptr;           // [P] the stop rule's dot of every point (NaN: not counted)
+  float *d_aos = nullptr;            // [P][3] the result for the caller
+  float *h_dots = nullptr;           // pinned [2][cap_points]
+  hipEvent_t ev_dots[2] = {nullptr, nullptr};  // a pass's dots are on the host
+  std::vector<hipEvent_t> ev;        // kNN start / end, then start / end of every pass
+};
+void refine_free(RefineState &s);
+// on the uploaded cloud c, k <= kRefineKCap (clamped to the cloud's size); replaces c's normals and bumps its generation.
+// ddot_out (may be null) receives one mean per pass; kernel_ms (may be null): kNN, the passes launched, the whole call.
+int refine_run(RefineState &s, Cloud &c, int k, int max_iterations, float threshold, float *normals_out, int *iterations_out, float *ddot_out,
+               int *num_nan_out, float *kernel_ms, hipStream_t stream);
+
 }  // namespace gpd

@@ -1,0 +1,347 @@
+// Cloud::refineNormals(k) on the device (util/cloud.cpp:176-204): the k nearest neighbours of every point, then
+// pcl::NormalRefinement's Jacobi passes — the definition is DESIGN §7 ("refineNormals") and refine_model.h, the host model
+// this path equals bit for bit.  On the cloud uploaded last (Cloud::g_p, pnrm), which never leaves the device:
+//   1. knn_kernel, a WAVE per point in cell order (neighbouring waves share grid cells in L1): the cloud's uniform grid is
+//      visited in square shells of cells around the point's cell.  Every visited point's (d2 bits, index) key that beats the
+//      current k-th key goes to the wave's LDS row; the row is sorted in registers by the normals path's bitonic network
+//      (grid_sort.h) and cut to k whenever it fills and after every shell.  The search stops when the k-th key's d2 is below
+//      refine::ring_bound of the shell — a lower bound of the float d2 of every point not visited yet — or the shells have
+//      covered the grid.  The sorted indices leave as [P / 64][k][64]: lane p of a block reads one contiguous row per rank.
+//   2. refine_pass_kernel, a LANE per point: the k normals of its list gathered, the finite ones summed in list order (k
+//      sequential float adds), sqrtf and three divisions — the correctly rounded sequences (-ffp-contract=off, Makefile;
+//      hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt) — and the dot product with the point's old normal.
+//   3. on the host, between passes: the stop rule's sequential float sum of the dots in ascending index order
+//      (refine::StopRule).  It overlaps the next pass, launched speculatively on the other buffer of a ping-pong pair: a
+//      stop discards it.
+//   4. the result replaces the cloud's normals (planes nx, ny, nz and pnrm); the cloud's generation moves on.
+#include "gpd_internal.h"
+#include "grid_sort.h"
+#include "refine_model.h"
+
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#define HIP_RET(expr)                                                                       \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if (e_ != hipSuccess) {                                                                 \
+      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+      return GPD_ERR_HIP;                                                                   \
+    }                                                                                       \
+  } while (0)
+
+namespace gpd {
+
+namespace {
+
+constexpr int KN_WAVES = 4;     // points per workgroup of knn_kernel
+constexpr int KN_BUF = 1024;    // keys a wave's LDS row holds (cut back to k <= kRefineKCap whenever it fills)
+constexpr int KN_SHELLS = 257;  // ring_bound of shells 0 .. 256 (a grid has at most 256 cells per axis)
+static_assert(KN_BUF - kRefineKCap >= 64, "a cut row must take the next 64 candidates");
+
+struct KnnParams {
+  GridView grid;
+  int num_points;
+  int k;
+  int32_t *lists;           // [ceil(P / 64)][k][64] by cell-order position
+  float bound[KN_SHELLS];   // refine::ring_bound(R, cell)
+};
+
+// sort the n keys of the row through registers and keep the first `keep` (n <= 64 K)
+template <int K>
+__device__ __forceinline__ void knn_cut(unsigned long long *keys, int n, int keep, int lane) {
+  double key[K];
+#pragma unroll
+  for (int r = 0; r < K; r++) key[r] = __longlong_as_double((long long)(lane * K + r < n ? keys[lane * K + r] : NL_PAD_KEY));
+  wave_sort_regs<K>(key, lane);
+#pragma unroll
+  for (int r = 0; r < K; r++)
+    if (lane * K + r < keep) keys[lane * K + r] = (unsigned long long)__double_as_longlong(key[r]);
+}
+
+__global__ __launch_bounds__(64 * KN_WAVES) void knn_kernel(KnnParams P) {
+  __shared__ unsigned long long s_keys[KN_WAVES][KN_BUF];
+  __shared__ int s_beg[KN_WAVES][128], s_off[KN_WAVES][128];  // the point ranges of a batch of 64 cell columns, two per column
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int w = blockIdx.x * KN_WAVES + wv;
+  if (w >= P.num_points) return;
+  unsigned long long *keys = s_keys[wv];
+  int *beg = s_beg[wv], *off = s_off[wv];
+  const GridView &g = P.grid;
+  const float4 q4 = g.p[w];
+  const float qx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q4.x))),
+              qy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q4.y))),
+              qz = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q4.z)));
+  const int cx = grid_coord(g, 0, qx), cy = grid_coord(g, 1, qy), cz = grid_coord(g, 2, qz);
+  const int k = P.k;
+  int n = 0;                           // wave-uniform: keys in the row
+  bool sorted = true;                  // the row is sorted and holds at most k keys
+  unsigned long long kth = ~0ull;      // the k-th key once k are known: a candidate must beat it
+  auto sync_row = [&]() {
+    __threadfence_block();  // the row was written by other lanes of this wave
+    __builtin_amdgcn_wave_barrier();
+  };
+  auto cut = [&]() {
+    sync_row();
+    const int keep = n < k ? n : k;
+    if (n <= 256)
+      knn_cut<4>(keys, n, keep, lane);
+    else if (n <= 512)
+      knn_cut<8>(keys, n, keep, lane);
+    else
+      knn_cut<16>(keys, n, keep, lane);
+    sync_row();
+    n = keep;
+    sorted = true;
+    if (n == k) kth = keys[k - 1];
+  };
+  for (int R = 0;; R++) {
+    const int xa = max(0, cx - R), xb = min(g.dim[0] - 1, cx + R);
+    const int ya = max(0, cy - R), yb = min(g.dim[1] - 1, cy + R);
+    const int za = max(0, cz - R), zb = min(g.dim[2] - 1, cz + R);
+    const int nyc = yb - ya + 1, ncol = (xb - xa + 1) * nyc;
+    // the shell: border columns whole (za .. zb), inner columns their bottom and top cells; a lane per column, 64 at a time
+    for (int col0 = 0; col0 < ncol; col0 += 64) {
+      const int col = col0 + lane;
+      int b0 = 0, l0 = 0, b1 = 0, l1 = 0;
+      if (col < ncol) {
+        const int x = xa + col / nyc, y = ya + col % nyc;
+        const int base = (x * g.dim[1] + y) * g.dim[2];
+        if (abs(x - cx) == R || abs(y - cy) == R) {
+          b0 = g.start[base + za];
+          l0 = g.start[base + zb + 1] - b0;
+        } else {
+          if (cz - R >= 0) {
+            b0 = g.start[base + cz - R];
+            l0 = g.start[base + cz - R + 1] - b0;
+          }
+          if (cz + R <= g.dim[2] - 1) {
+            b1 = g.start[base + cz + R];
+            l1 = g.start[base + cz + R + 1] - b1;
+          }
+        }
+      }
+      int incl = l0 + l1;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int x = __shfl_up(incl, o);
+        if (lane >= o) incl += x;
+      }
+      const int excl = incl - (l0 + l1);
+      const int T = __builtin_amdgcn_readlane(incl, 63);
+      sync_row();  // the previous batch's lanes are done with the range table
+      beg[2 * lane] = b0;
+      beg[2 * lane + 1] = b1;
+      off[2 * lane] = excl;
+      off[2 * lane + 1] = excl + l0;
+      sync_row();
+      for (int t0 = 0; t0 < T; t0 += 64) {
+        if (n + 64 > KN_BUF) cut();
+        const int t = t0 + lane;
+        const bool in = t < T;
+        int r = 0;  // the last range that starts at or before t (it is not empty)
+#pragma unroll
+        for (int step = 64; step > 0; step >>= 1)
+          if (off[r + step] <= t) r += step;
+        const float4 p = g.p[in ? beg[r] + (t - off[r]) : 0];
+        float d = qx - p.x;  // FLANN L2_Simple<float>: d2 accumulated over x, y, z
+        float d2 = 0.f;
+        d2 += d * d;
+        d = qy - p.y;
+        d2 += d * d;
+        d = qz - p.z;
+        d2 += d * d;
+        const unsigned long long kv = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)__float_as_int(p.w);
+        const bool hit = in && kv < kth;
+        const unsigned long long ballot = __ballot(hit);
+        if (hit) keys[n + __popcll(ballot & ((1ull << lane) - 1ull))] = kv;
+        const int add = __popcll(ballot);
+        n += add;
+        sorted = sorted && add == 0;
+      }
+    }
+    if (!sorted) cut();
+    const bool all = cx - R <= 0 && cx + R >= g.dim[0] - 1 && cy - R <= 0 && cy + R >= g.dim[1] - 1 && cz - R <= 0 && cz + R >= g.dim[2] - 1;
+    if (all || (n == k && __uint_as_float((unsigned)(kth >> 32)) < P.bound[R < KN_SHELLS ? R : KN_SHELLS - 1])) break;
+  }
+  int32_t *row = P.lists + (size_t)(w >> 6) * k * 64 + (w & 63);
+  for (int r = lane; r < n; r += 64) row[(size_t)r * 64] = (int32_t)(unsigned)keys[r];
+}
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+// one Jacobi pass: in / out by original index, a lane per cell-order position w (its list is a contiguous row per rank)
+__global__ __launch_bounds__(256) void refine_pass_kernel(const float4 *__restrict__ gp, const int32_t *__restrict__ lists, int num_points, int k,
+                                                          const float4 *__restrict__ in, float4 *__restrict__ out, float *__restrict__ dots) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= num_points) return;
+  const int j = __float_as_int(gp[w].w);
+  const int32_t *row = lists + (size_t)(w >> 6) * k * 64 + (w & 63);
+  float nx = 0.f, ny = 0.f, nz = 0.f;
+#pragma unroll 8
+  for (int r = 0; r < k; r++) {
+    const float4 v = in[row[(size_t)r * 64]];
+    if (finite3(v.x, v.y, v.z)) {
+      nx += 1.0f * v.x;
+      ny += 1.0f * v.y;
+      nz += 1.0f * v.z;
+    }
+  }
+  const float norm = sqrtf(nx * nx + ny * ny + nz * nz);
+  const float nan = __int_as_float(0x7fc00000);
+  float4 t = make_float4(nan, nan, nan, 0.f);
+  if (isfinite(norm) && norm > FLT_EPSILON) t = make_float4(nx / norm, ny / norm, nz / norm, 0.f);
+  out[j] = t;
+  const float4 o = in[j];
+  dots[j] = finite3(t.x, t.y, t.z) ? t.x * o.x + t.y * o.y + t.z * o.z : nan;
+}
+
+// the result into the cloud's normal planes and an AoS copy for the caller
+__global__ void refine_store_kernel(const float4 *__restrict__ res, int num_points, float *nx, float *ny, float *nz, float4 *pnrm, float *aos) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= num_points) return;
+  const float4 v = res[i];
+  nx[i] = v.x;
+  ny[i] = v.y;
+  nz[i] = v.z;
+  pnrm[i] = make_float4(v.x, v.y, v.z, 0.f);
+  aos[3 * (size_t)i] = v.x;
+  aos[3 * (size_t)i + 1] = v.y;
+  aos[3 * (size_t)i + 2] = v.z;
+}
+
+int refine_reserve(RefineState &s, int n, int k) {
+  const size_t lists = ((size_t)n + 63) / 64 * 64 * (size_t)k;
+  if (n > s.cap_points) {
+    note_alloc(__func__);
+    for (float4 *&b : s.d_buf) {
+      (void)hipFree(b);
+      b = nullptr;
+    }
+    (void)hipFree(s.d_dots);
+    (void)hipFree(s.d_aos);
+    if (s.h_dots) (void)hipHostFree(s.h_dots);
+    s.d_dots = s.d_aos = s.h_dots = nullptr;
+    s.cap_points = 0;
+    const int cap = n + n / 4;
+    for (float4 *&b : s.d_buf) HIP_RET(hipMalloc(&b, (size_t)cap * sizeof(float4)));
+    HIP_RET(hipMalloc(&s.d_dots, (size_t)cap * sizeof(float)));
+    HIP_RET(hipMalloc(&s.d_aos, (size_t)cap * 3 * sizeof(float)));
+    HIP_RET(hipHostMalloc(reinterpret_cast<void **>(&s.h_dots), (size_t)cap * 2 * sizeof(float), 0));
+    s.cap_points = cap;
+  }
+  if (lists > s.cap_lists) {
+    note_alloc(__func__);
+    (void)hipFree(s.d_lists);
+    s.d_lists = nullptr;
+    s.cap_lists = 0;
+    HIP_RET(hipMalloc(&s.d_lists, (lists + lists / 4) * sizeof(int32_t)));
+    s.cap_lists = lists + lists / 4;
+  }
+  if (!s.ev_dots[0])
+    for (hipEvent_t &e : s.ev_dots) HIP_RET(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return GPD_OK;
+}
+
+}  // namespace
+
+void refine_free(RefineState &s) {
+  (void)hipFree(s.d_lists);
+  for (float4 *b : s.d_buf) (void)hipFree(b);
+  (void)hipFree(s.d_dots);
+  (void)hipFree(s.d_aos);
+  if (s.h_dots) (void)hipHostFree(s.h_dots);
+  for (hipEvent_t e : s.ev_dots)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : s.ev)
+    if (e) (void)hipEventDestroy(e);
+  s = RefineState();
+}
+
+int refine_run(RefineState &s, Cloud &c, int k, int max_iterations, float threshold, float *normals_out, int *iterations_out, float *ddot_out,
+               int *num_nan_out, float *kernel_ms, hipStream_t stream) {
+  StageRange range_("gpd:refine_normals");
+  const auto t_start = std::chrono::steady_clock::now();
+  const int n = c.num_points;
+  const int kk = k < n ? k : n;  // KdTreeFLANN::nearestKSearch clamps k to the cloud's size
+  int rc = refine_reserve(s, n, kk);
+  if (rc) return rc;
+  const size_t need_ev = 2 + 2 * (size_t)max_iterations;
+  while (s.ev.size() < need_ev) {
+    hipEvent_t e;
+    HIP_RET(hipEventCreate(&e));
+    s.ev.push_back(e);
+  }
+
+  // 1: the lists
+  KnnParams kp;
+  kp.grid = grid_view(c);
+  kp.num_points = n;
+  kp.k = kk;
+  kp.lists = s.d_lists;
+  for (int R = 0; R < KN_SHELLS; R++) kp.bound[R] = refine::ring_bound(R, c.g_cell);
+  HIP_RET(hipEventRecord(s.ev[0], stream));
+  knn_kernel<<<(n + KN_WAVES - 1) / KN_WAVES, 64 * KN_WAVES, 0, stream>>>(kp);
+  HIP_RET(hipGetLastError());
+  HIP_RET(hipEventRecord(s.ev[1], stream));
+
+  // 2-3: the passes, ping-pong between d_buf[0] (a copy of the cloud's normals: an error leaves those as they were) and d_buf[1]
+  HIP_RET(hipMemcpyAsync(s.d_buf[0], c.pnrm, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+  const bool need_dots = threshold > 0.f || ddot_out;
+  int launched = 0;
+  auto launch = [&](int t) -> int {
+    HIP_RET(hipEventRecord(s.ev[2 + 2 * (size_t)t], stream));
+    refine_pass_kernel<<<(n + 255) / 256, 256, 0, stream>>>(c.g_p, s.d_lists, n, kk, s.d_buf[t & 1], s.d_buf[(t + 1) & 1], s.d_dots);
+    HIP_RET(hipGetLastError());
+    HIP_RET(hipEventRecord(s.ev[3 + 2 * (size_t)t], stream));
+    if (need_dots) {
+      HIP_RET(hipMemcpyAsync(s.h_dots + (size_t)(t & 1) * s.cap_points, s.d_dots, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, stream));
+      HIP_RET(hipEventRecord(s.ev_dots[t & 1], stream));
+    }
+    launched = t + 1;
+    return GPD_OK;
+  };
+  int done = 0;
+  if (max_iterations > 0 && (rc = launch(0))) return rc;
+  for (int t = 0; t < max_iterations; t++) {
+    if (t + 1 < max_iterations && (rc = launch(t + 1))) return rc;  // speculative: runs while the host sums pass t
+    done = t + 1;
+    if (need_dots) {
+      HIP_RET(hipEventSynchronize(s.ev_dots[t & 1]));
+      refine::StopRule st;
+      st.add(s.h_dots + (size_t)(t & 1) * s.cap_points, n);
+      const float mean = st.mean();
+      if (ddot_out) ddot_out[t] = mean;
+      if (refine::StopRule::stop(mean, threshold)) break;
+    }
+  }
+
+  // 4: pass `done` wrote d_buf[done & 1]
+  refine_store_kernel<<<(n + 255) / 256, 256, 0, stream>>>(s.d_buf[done & 1], n, c.nx, c.ny, c.nz, c.pnrm, s.d_aos);
+  HIP_RET(hipGetLastError());
+  HIP_RET(hipMemcpyAsync(normals_out, s.d_aos, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HIP_RET(hipStreamSynchronize(stream));
+  c.generation++;
+  int nan = 0;
+  for (int i = 0; i < n; i++) nan += !refine::finite3(normals_out[3 * (size_t)i], normals_out[3 * (size_t)i + 1], normals_out[3 * (size_t)i + 2]);
+  *iterations_out = done;
+  *num_nan_out = nan;
+  if (kernel_ms) {
+    float ms = 0.f, passes = 0.f;
+    HIP_RET(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
+    for (int t = 0; t < launched; t++) {
+      float m = 0.f;
+      HIP_RET(hipEventElapsedTime(&m, s.ev[2 + 2 * (size_t)t], s.ev[3 + 2 * (size_t)t]));
+      passes += m;
+    }
+    kernel_ms[0] = ms;
+    kernel_ms[1] = passes;
+    kernel_ms[2] = (float)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
+  }
+  return GPD_OK;
+}
+
+}  // namespace gpd

@@ -62,6 +62,12 @@ class GraspDetector {
   // cloud.subsample(num_samples).  False when the device call fails.
   bool sampleAbovePlane(util::Cloud &cloud, double threshold = 0.01, int max_iterations = 50, double probability = 0.99,
                         bool optimize = true);
+  // Cloud::refineNormals (cloud.cpp:176-204) on the device (gpd_hip_refine_normals, after uploading the cloud with its
+  // normals): the k-nearest-neighbour lists and pcl::NormalRefinement with its defaults (15 passes, threshold 1e-5); the
+  // cloud's normals become the refined ones, as util::Cloud::refineNormals sets them.  The equivalent of cfg
+  // refine_normals_k = k: preprocessPointCloud with num_samples = 0, this, then cloud.subsample(num_samples).  False when
+  // the device call fails or the cloud has no normals.
+  bool refineNormals(util::Cloud &cloud, int k, int max_iterations = 15, float convergence_threshold = 1e-5f);
   std::vector<std::unique_ptr<candidate::HandSet>> generateGraspCandidates(const util::Cloud &cloud);
   std::vector<std::unique_ptr<candidate::HandSet>> filterGraspsWorkspace(
       std::vector<std::unique_ptr<candidate::HandSet>> &hand_set_list, const std::vector<double> &workspace) const;

@@ -63,6 +63,19 @@ class Cloud {
   PlaneFit sampleAbovePlane(double threshold = 0.01, int max_iterations = 50, double probability = 0.99, bool optimize = true);
   // what sampleAbovePlane does with a fit: the reference's messages, the sample indices replaced when it succeeded
   void applyPlaneFit(const PlaneFit &fit, double seconds);
+  // Cloud::refineNormals (cloud.cpp:176-204): the k nearest neighbours of every point (pcl::search::KdTree, sorted by
+  // (d2, index), k clamped to the cloud's size), then pcl::NormalRefinement with max_iterations passes and the
+  // convergence threshold (the reference's defaults 15 and 1e-5) — the definition is DESIGN §7.  The normals become the
+  // refined ones (NaN where the refinement met a singularity).  This is the single-core host model;
+  // GraspDetector::refineNormals runs the same refinement on the device.  A cloud without normals is left as it is.
+  struct NormalRefinement {
+    int iterations = 0;        // passes run
+    std::vector<float> ddots;  // the stop rule's mean dot product of every pass
+    int num_nan = 0;           // refined normals with a non-finite component
+  };
+  NormalRefinement refineNormals(int k, int max_iterations = 15, float convergence_threshold = 1e-5f);
+  // what refineNormals does with refined normals: the reference's messages, then the normals replaced
+  void applyRefinedNormals(const std::vector<float> &refined);
 
  private:
   std::vector<float> xyz_, normals_;

@@ -18,6 +18,7 @@
 #include "gpd/sequential_importance_sampling.h"
 #include "gpd/util/config_file.h"
 #include "../../csrc/plane_model.h"
+#include "../../csrc/refine_model.h"
 
 namespace gpd {
 
@@ -437,6 +438,35 @@ void Cloud::applyPlaneFit(const PlaneFit &fit, double seconds) {
     printf(" Plane fit failed. Using entire point cloud ...\n");
   }
   std::cout << " runtime (plane fit): " << seconds << "\n";
+}
+
+Cloud::NormalRefinement Cloud::refineNormals(int k, int max_iterations, float convergence_threshold) {
+  NormalRefinement out;
+  if (!hasNormals() || k < 1) return out;
+  std::vector<int32_t> lists;
+  const int kk = refine::knn(xyz_.data(), (int)size(), k, lists);
+  refine::Result r = refine::refine(normals_.data(), (int)size(), lists.data(), kk, max_iterations, convergence_threshold);
+  out.iterations = r.iterations;
+  out.ddots = r.ddots;
+  out.num_nan = r.num_nan;
+  applyRefinedNormals(r.normals);
+  return out;
+}
+
+// The reference prints the statistics of (refined - input) over pcl::Normal's 8-float map, whose padding and curvature rows
+// are zero in both (the four extra rows add nothing to the sum and max, and dilute the mean by 8 / 3); here they are taken
+// over the three normal rows alone.
+void Cloud::applyRefinedNormals(const std::vector<float> &refined) {
+  float mx = -std::numeric_limits<float>::infinity(), sum = 0.f;
+  for (size_t i = 0; i < refined.size(); i++) {
+    const float d = refined[i] - normals_[i];
+    sum += d;
+    mx = std::isnan(d) || d > mx ? d : mx;
+  }
+  const float mean = sum / (float)refined.size();
+  printf("Refining surface normals ...\n");
+  printf(" mean: %.3f, max: %.3f, sum: %.3f\n", mean, mx, sum);
+  normals_ = refined;
 }
 
 void Cloud::subsample(int num_samples, unsigned seed) {
@@ -864,6 +894,21 @@ bool GraspDetector::sampleAbovePlane(util::Cloud &cloud, double threshold, int m
   last_num_sets_ = 0;
   fit.above.resize(num);
   cloud.applyPlaneFit(fit, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  return true;
+}
+
+bool GraspDetector::refineNormals(util::Cloud &cloud, int k, int max_iterations, float convergence_threshold) {
+  if (!ctx_ || cloud.size() == 0 || !cloud.hasNormals()) return false;
+  std::vector<float> refined(cloud.size() * 3, 0.f);
+  int iterations = 0, num_nan = 0;
+  if (gpd_hip_upload_cloud(ctx_, cloud.getCloudProcessed().data(), cloud.getNormals().data(), (int)cloud.size(), cloud.getCameraSource().data(),
+                           cloud.numCameras(), cloud.getViewPoints().data()) != GPD_OK ||
+      gpd_hip_refine_normals(ctx_, k, max_iterations, convergence_threshold, refined.data(), &iterations, nullptr, &num_nan, nullptr) != GPD_OK) {
+    printf("ERROR: %s\n", gpd_hip_last_error());
+    return false;
+  }
+  last_num_sets_ = 0;
+  cloud.applyRefinedNormals(refined);
   return true;
 }
 
@@ -1532,6 +1577,52 @@ extern "C" int gpd_host_sample_above_plane(const float *xyz, int n, double thres
   *num_inliers = r.num_inliers;
   *iterations = r.iterations;
   return (int)r.above.size();
+}
+
+// Flat entry for tests / ctypes: util::Cloud::refineNormals on xyz / normals [n][3] (the host model); normals_out [n][3],
+// ddots holds max_iterations floats.  Returns the passes run; *num_nan: refined normals with a non-finite component.
+extern "C" int gpd_host_refine_normals(const float *xyz, const float *normals, int n, int k, int max_iterations, float convergence_threshold,
+                                       float *normals_out, float *ddots, int *num_nan) {
+  std::vector<int32_t> lists;
+  const int kk = gpd::refine::knn(xyz, n, k, lists);
+  const gpd::refine::Result r = gpd::refine::refine(normals, n, lists.data(), kk, max_iterations, convergence_threshold);
+  std::copy(r.normals.begin(), r.normals.end(), normals_out);
+  std::copy(r.ddots.begin(), r.ddots.end(), ddots);
+  *num_nan = r.num_nan;
+  return r.iterations;
+}
+
+// Flat entry for tests / ctypes: the host model's kNN lists [n][min(k, n)] (the (d2, index) order); returns min(k, n)
+extern "C" int gpd_host_knn(const float *xyz, int n, int k, int32_t *lists) {
+  std::vector<int32_t> out;
+  const int kk = gpd::refine::knn(xyz, n, k, out);
+  std::copy(out.begin(), out.end(), lists);
+  return kk;
+}
+
+// Flat entry for tests / ctypes: GraspDetector::refineNormals on a cloud of one camera at the origin, through a detector
+// of the reference's default geometry on device 0.  normals_out [n][3]; returns 0, or -1 when the device call failed.
+extern "C" int gpd_host_detector_refine_normals(const float *xyz, const float *normals, int n, int k, float *normals_out) {
+  gpd_params p;
+  gpd_hip_default_params(&p);
+  gpd::candidate::HandSearch::Parameters hs;
+  hs.nn_radius_frames_ = p.nn_radius_frames;
+  hs.num_threads_ = 1;
+  hs.num_samples_ = 0;
+  hs.num_orientations_ = p.num_orientations;
+  hs.num_finger_placements_ = p.num_finger_placements;
+  hs.hand_axes_.assign(p.hand_axes, p.hand_axes + p.num_hand_axes);
+  hs.deepen_hand_ = p.deepen_hand != 0;
+  hs.friction_coeff_ = p.friction_coeff;
+  hs.min_viable_ = p.min_viable;
+  hs.hand_geometry_ = {p.finger_width, p.hand_outer_diameter, p.hand_depth, p.hand_height, p.init_bite};
+  const gpd::descriptor::ImageGeometry ig = {p.volume_width, p.volume_depth, p.volume_height, p.image_size, p.image_num_channels};
+  gpd::GraspDetector detector(hs, ig, 0);
+  gpd::util::Cloud cloud(std::vector<float>(xyz, xyz + 3 * (size_t)n), std::vector<float>(normals, normals + 3 * (size_t)n),
+                         std::vector<int>((size_t)n, 1), std::vector<double>(3, 0.0));
+  if (!detector.refineNormals(cloud, k)) return -1;
+  std::copy(cloud.getNormals().begin(), cloud.getNormals().end(), normals_out);
+  return 0;
 }
 
 // Flat entry for tests / ctypes: loads a PCD like util::Cloud does; returns the number of points

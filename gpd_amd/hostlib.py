@@ -56,6 +56,48 @@ def sample_above_plane(xyz, threshold=0.01, max_iterations=50, probability=0.99,
     return above[:k].copy(), coeffs, int(inl.value), int(its.value)
 
 
+def refine_normals(xyz, normals, k, max_iterations=15, convergence_threshold=1e-5):
+    """util::Cloud::refineNormals on one core (the host model, DESIGN §7) ->
+    (normals f32 [n,3] (NaN: a singularity), passes run, the stop rule's mean dot product of every pass f32, non-finite normals)."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    n = len(xyz)
+    out = np.zeros((max(n, 1), 3), np.float32)
+    ddots = np.zeros(max(int(max_iterations), 1), np.float32)
+    nan = C.c_int(0)
+    L = lib()
+    L.gpd_host_refine_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    its = L.gpd_host_refine_normals(xyz.ctypes.data_as(C.c_void_p), normals.ctypes.data_as(C.c_void_p), n, int(k), int(max_iterations),
+                                    float(convergence_threshold), out.ctypes.data_as(C.c_void_p), ddots.ctypes.data_as(C.c_void_p), C.byref(nan))
+    return out[:n].copy(), int(its), ddots[:its].copy(), int(nan.value)
+
+
+def knn(xyz, k):
+    """the host model's k-nearest-neighbour lists -> i32 [n, min(k, n)], ascending by (float d2, index)."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    n = len(xyz)
+    kk = min(int(k), n)
+    out = np.zeros((max(n, 1), max(kk, 1)), np.int32)
+    L = lib()
+    L.gpd_host_knn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.gpd_host_knn(xyz.ctypes.data_as(C.c_void_p), n, int(k), out.ctypes.data_as(C.c_void_p))
+    return out[:n, :kk].copy()
+
+
+def detector_refine_normals(xyz, normals, k):
+    """GraspDetector::refineNormals (the device path through the C++ mirror) on a one-camera cloud -> normals f32 [n,3]."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    out = np.zeros_like(xyz)
+    L = lib()
+    L.gpd_host_detector_refine_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    rc = L.gpd_host_detector_refine_normals(xyz.ctypes.data_as(C.c_void_p), normals.ctypes.data_as(C.c_void_p), len(xyz), int(k),
+                                            out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise RuntimeError("GraspDetector::refineNormals failed")
+    return out
+
+
 def load_pcd(path, cap=1 << 22):
     """util::Cloud(filename): ASCII or uncompressed binary PCD -> (xyz f32 [n,3], normals f32 [n,3] or None)."""
     xyz = np.zeros((cap, 3), np.float32)

@@ -195,6 +195,20 @@ int gpd_hip_estimate_normals(gpd_hip_ctx *ctx, double radius, float *normals);
 int gpd_hip_sample_above_plane(gpd_hip_ctx *ctx, double threshold, int max_iterations, double probability, int optimize,
                                int32_t *indices_out, int *num_out, float coeffs[4], int *num_inliers, int *iterations);
 
+/* Replaces Cloud::refineNormals(k) (util/cloud.cpp:176-204; CandidatesGenerator::preprocessPointCloud calls it after the
+ * normals when cfg refine_normals_k > 0, candidates_generator.cpp:28-30): pcl::search::KdTree::nearestKSearch of every
+ * point (itself included, FLANN's float d2, ascending by (d2, index), k clamped to the cloud's size), then
+ * pcl::NormalRefinement — the definition is DESIGN §7.  The reference's values: max_iterations 15, convergence_threshold
+ * 1e-5; threshold 0 runs exactly max_iterations passes.  On the normals of the cloud uploaded last, or last estimated
+ * (gpd_hip_estimate_normals); the result replaces the device copy, so a following gpd_hip_detect uses it without an upload.
+ * normals_out receives num_points*3 floats (NaN: a singularity, as in the reference); *iterations_out: the passes run;
+ * ddot_out (may be NULL, else max_iterations floats): the mean dot product of every pass, the value the stop rule tests;
+ * *num_nan_out: normals with a non-finite component; kernel_ms (may be NULL): the kNN kernel, the refinement passes launched
+ * (one past a stop is launched speculatively), the whole call, in ms.  GPD_ERR_INVALID: a NULL argument, k < 1,
+ * max_iterations < 0, a negative or non-finite threshold, or no cloud.  Capacity (GPD_ERR_CAPACITY beyond it): k <= 256. */
+int gpd_hip_refine_normals(gpd_hip_ctx *ctx, int k, int max_iterations, float convergence_threshold, float *normals_out, int *iterations_out,
+                           float *ddot_out, int *num_nan_out, float kernel_ms[3]);
+
 /* Replaces CandidatesGenerator::generateGraspCandidateSets ->
  * HandSearch::searchHands (candidates_generator.cpp:62-69, hand_search.cpp:24-64)
  * for samples given by index (Cloud::getSampleIndices).  Writes
