@@ -79,7 +79,8 @@ def test_config3_other_image_geometries(oracle_mod, cloud30k, C):
 
 def test_config4_dense_clutter_300k(oracle_mod):
     """configs[3] at its stated size: 300k-point clutter cloud, at least 50000 candidates through the fused
-    device path (the 16384-image LeNet chunk loop, large neighbourhoods), every one compared with the oracle."""
+    device path (one LeNet pass: the passes hold 65536 images, test_gpu_lenet_limits.py crosses them; large neighbourhoods),
+    every one compared with the oracle."""
     cl = synth.make_cloud(1234, 300000, clutter=True)
     si = synth.sample_indices(cl, 19000)
     n, err = _full_compare(oracle_mod, cl, si, 15)

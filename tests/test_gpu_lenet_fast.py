@@ -11,6 +11,7 @@ three-piece operands) through the C-ABI, stage by stage and end to end.
 import numpy as np
 import pytest
 
+import lenet_ref
 import ref_cases as rcs
 from gpd_amd import synth
 
@@ -26,37 +27,7 @@ def _ctx(C, mode=None, weights=None):
     return ctx
 
 
-def _bf16_to_f64(u16):
-    return (u16.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
-
-
-def _conv_valid(x, w):
-    F = w.shape[0]
-    H, W = x.shape[1] - 4, x.shape[2] - 4
-    out = np.zeros((F, H, W), np.int64 if x.dtype == np.int64 else np.float64)
-    for ky in range(5):
-        for kx in range(5):
-            out += np.einsum("fc,chw->fhw", w[:, :, ky, kx], x[:, ky:ky + H, kx:kx + W])
-    return out
-
-
-def _pool(h):
-    F, H, W = h.shape
-    return h.reshape(F, H // 2, 2, W // 2, 2).max(axis=(2, 4))
-
-
-def _pool1_exact(img_hwc, w, C):
-    """conv1 + pool1 as the split path defines it: integer dot products with round(w 2^s), one rounding, + bias"""
-    c1w = w["c1w"].reshape(20, C, 5, 5)
-    x = np.transpose(img_hwc, (2, 0, 1)).astype(np.int64)
-    out = np.zeros((20, 28, 28), np.float32)
-    for f in range(20):
-        mx = float(np.abs(c1w[f]).max())
-        s = 30 - int(np.frexp(mx)[1]) if mx > 0 else 0
-        Wi = np.rint(c1w[f].astype(np.float64) * 2.0 ** s).astype(np.int64)[None]
-        h = _pool(_conv_valid(x, Wi))[0]
-        out[f] = np.ldexp(h.astype(np.float32), -s).astype(np.float32) + w["c1b"][f]
-    return np.transpose(out, (1, 2, 0))  # [row][column][filter]
+_bf16_to_f64, _conv_valid, _pool, _pool1_exact = lenet_ref.bf16_to_f64, lenet_ref.conv_valid, lenet_ref.pool, lenet_ref.pool1_exact
 
 
 @pytest.mark.parametrize("C", [15, 12, 3, 1])
