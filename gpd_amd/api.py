@@ -48,6 +48,10 @@ class DetectJob(C.Structure):
         ("reserved_", C.c_int32), ("lcg_base", C.c_uint64), ("lcg_draws", C.c_uint64),
         ("raw", C.c_int32), ("voxel_size", C.c_float), ("workspace", C.c_void_p), ("normals_radius", C.c_double), ("sample_xyz", C.c_void_p),
         ("num_points_processed", C.c_int32), ("num_samples_processed", C.c_int32),
+        ("refine_normals_k", C.c_int32), ("sample_above_plane", C.c_int32), ("num_draws", C.c_int32), ("sample_seed", C.c_uint32),
+        ("samples_out", C.c_void_p),
+        ("refine_passes", C.c_int32), ("refine_num_nan", C.c_int32), ("plane_num_above", C.c_int32), ("plane_iterations", C.c_int32),
+        ("preprocess_ms", C.c_float * 4),
     ]
 
 
@@ -57,6 +61,16 @@ class GpdHipError(RuntimeError):
 
 # gpd_hip_set_lenet_mode (include/gpd_hip.h)
 LENET_SPLIT, LENET_F32_CHAIN = 0, 1
+
+
+def sample_positions(n, num_draws, seed=0, with_repetition=False):
+    """gpd_hip_sample_positions: the positions Cloud::subsample(num_draws) draws from a list of n entries (host only) -> i32."""
+    out = np.zeros(max(min(int(num_draws), int(n)), 1), np.int32)
+    k = C.c_int(0)
+    rc = lib().gpd_hip_sample_positions(int(n), int(num_draws), int(seed) & 0xFFFFFFFF, int(bool(with_repetition)), _ptr(out), C.byref(k))
+    if rc != 0:
+        raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
+    return out[: k.value].copy()
 
 
 def bind_host_thread(device):
@@ -72,7 +86,7 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_search_samples", "gpd_hip_detect_samples", "gpd_hip_reevaluate", "gpd_hip_replay_kernel_ms", "gpd_hip_last_centre_chains",
            "gpd_hip_detect_select", "gpd_hip_detect_batch", "gpd_hip_detect_batch_multi", "gpd_hip_conv1_stats", "gpd_hip_last_fallbacks", "gpd_hip_preprocess_cloud", "gpd_hip_find_clusters", "gpd_hip_reserve", "gpd_hip_bind_host_thread",
            "gpd_hip_set_lenet_mode", "gpd_hip_lenet_debug", "gpd_hip_lenet_fast_tables", "gpd_hip_detect_sharded",
-           "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals"]
+           "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals", "gpd_hip_sample_positions"]
 
 
 def build(prof=True):
@@ -118,6 +132,7 @@ def lib():
                                                  C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.gpd_hip_refine_normals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
                                              C.POINTER(C.c_int), C.c_void_p]
+        L.gpd_hip_sample_positions.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
         L.gpd_hip_find_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_int)]
         L.gpd_hip_preprocess_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
@@ -284,26 +299,42 @@ class Context:
             j.num_selected, j.hands_capacity = int(num_selected), cap
         return jobs, keep
 
-    def raw_batch(self, scans, samples_xyz, workspace=None, voxel_size=0.003, normals_radius=0.03, num_selected=0):
+    def raw_batch(self, scans, samples_xyz, workspace=None, voxel_size=0.003, normals_radius=0.03, num_selected=0,
+                  refine_normals_k=0, sample_above_plane=False, num_draws=0, sample_seed=0):
         """The job array of gpd_hip_detect_batch for RAW scans (dicts with xyz, cam_source, view_points): preprocessPointCloud
-        (workspace cut, voxeliser, normals) on the device, search at the given sample coordinates (one f64 [S, 3] array per scan)."""
+        (workspace cut, voxeliser, normals, refineNormals when refine_normals_k > 0) on the device, search at the given sample
+        coordinates (one f64 [S, 3] array per scan).  samples_xyz[i] is None: the index route — sampleAbovePlane when asked for,
+        then Cloud::subsample(num_draws) on the stream seeded with sample_seed; the sample indices searched arrive in keep[i][7].
+        refine_normals_k, sample_above_plane, num_draws and sample_seed take one value for all scans or a sequence with one per scan."""
         jobs = (DetectJob * len(scans))()
         keep = []
         ws = None if workspace is None else np.ascontiguousarray(workspace, np.float64)
-        for j, cl, sm in zip(jobs, scans, samples_xyz):
+
+        def per_scan(v, i):
+            return v[i] if isinstance(v, (list, tuple, np.ndarray)) else v
+
+        for i, (j, cl, sm) in enumerate(zip(jobs, scans, samples_xyz)):
             xyz = np.ascontiguousarray(cl["xyz"], np.float32)
             P = len(xyz)
             cam = np.ascontiguousarray(cl["cam_source"], np.int32).reshape(-1, P)
             vp = np.ascontiguousarray(cl["view_points"], np.float64).reshape(-1, 3)
-            sm = np.ascontiguousarray(sm, np.float64).reshape(-1, 3)
-            cap = len(sm) * self.n_slots if num_selected == 0 else min(num_selected, len(sm) * self.n_slots)
+            draws = int(per_scan(num_draws, i))
+            if sm is None:
+                S, drawn = max(draws, 0), np.zeros(max(draws, 1), np.int32)
+            else:
+                sm = np.ascontiguousarray(sm, np.float64).reshape(-1, 3)
+                S, drawn = len(sm), None
+            cap = S * self.n_slots if num_selected == 0 else min(num_selected, S * self.n_slots)
             hands = np.empty(max(cap, 1), HAND_DTYPE)
-            keep.append((xyz, None, cam, vp, sm, hands, ws))
+            keep.append((xyz, None, cam, vp, sm, hands, ws, drawn))
             j.xyz, j.cam_source, j.view_points, j.hands = _ptr(xyz), _ptr(cam), _ptr(vp), _ptr(hands)
             j.sample_xyz, j.workspace = _ptr(sm), _ptr(ws)
-            j.num_points, j.num_cams, j.num_samples = P, cam.shape[0], len(sm)
+            j.num_points, j.num_cams, j.num_samples = P, cam.shape[0], 0 if sm is None else len(sm)
             j.num_selected, j.hands_capacity = int(num_selected), cap
             j.raw, j.voxel_size, j.normals_radius = 1, float(voxel_size), float(normals_radius)
+            j.refine_normals_k, j.sample_above_plane = int(per_scan(refine_normals_k, i)), int(bool(per_scan(sample_above_plane, i)))
+            j.num_draws, j.sample_seed = draws, int(per_scan(sample_seed, i)) & 0xFFFFFFFF
+            j.samples_out = _ptr(drawn)
         return jobs, keep
 
     def batch(self, clouds, samples, num_selected=0):

@@ -32,6 +32,7 @@
 #include <sched.h>
 
 #include "gpd_internal.h"
+#include "sample_model.h"
 
 namespace gpd {
 
@@ -102,6 +103,13 @@ struct Lane {
   uint8_t *d_img_in = nullptr;      // HWC images handed to gpd_hip_score
   uint8_t *d_img_planar = nullptr;  // their planar copy
   size_t d_img_in_bytes = 0;
+  // raw scans of gpd_hip_detect_batch that carry on past the normals: a state per LANE — the next cloud's fit runs on the other
+  // lane's stream while this lane's search still gathers from plane.d_idx
+  PlaneState plane;
+  RefineState refine;
+  int32_t *d_pos = nullptr;  // [draw_cap] the draw positions of Cloud::subsample (sample_model.h), computed on the host
+  int32_t *h_pos = nullptr;  // pinned: [draw_cap] their way up, then [2][draw_cap] the sample indices searched on their way
+  int draw_cap = 0;          //   down (samples_out), one half per job of the lane in flight
 };
 
 // one fused detect in flight on a lane
@@ -121,6 +129,8 @@ struct Job {
   int chunks = 0;          // > 0: the records leave the device in this many copies, an event behind each
   unsigned long long lcg_base = 0;   // in: shadow draws of the cloud's sample ranges before this one (gpd_hip_detect_sharded)
   unsigned long long lcg_draws = 0;  // out: shadow draws of this job's hand sets
+  bool resident = false;             // the sample indices are gathered on the device from `gather` (neither host pointer is read)
+  SampleGather gather;
 };
 
 }  // namespace
@@ -176,7 +186,10 @@ static void lane_free(Lane &L) {
   search_free(L.search);
   plan_free(L.plan);
   images_free(L.images);
-  void *dev[] = {L.d_scores, L.d_out, L.d_sel, L.d_all, L.d_img_in, L.d_img_planar};
+  plane_free(L.plane);
+  refine_free(L.refine);
+  if (L.h_pos) (void)hipHostFree(L.h_pos);
+  void *dev[] = {L.d_scores, L.d_out, L.d_sel, L.d_all, L.d_img_in, L.d_img_planar, L.d_pos};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (L.h_out) (void)hipHostFree(L.h_out);
@@ -223,6 +236,21 @@ static int reserve_out(Lane &L, size_t records, size_t extra_bytes) {
     HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&L.h_out), cap, 0));
     L.h_out_bytes = cap;
   }
+  return GPD_OK;
+}
+
+// the draw positions of up to n samples and the sample indices that come back
+static int reserve_draws(Lane &L, int n) {
+  if (n <= L.draw_cap) return GPD_OK;
+  note_alloc(__func__);
+  if (L.d_pos) (void)hipFree(L.d_pos);
+  if (L.h_pos) (void)hipHostFree(L.h_pos);
+  L.d_pos = L.h_pos = nullptr;
+  L.draw_cap = 0;
+  const int cap = n + n / 4;
+  HIP_TRY(hipMalloc(&L.d_pos, (size_t)cap * sizeof(int32_t)));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&L.h_pos), (size_t)cap * 3 * sizeof(int32_t), 0));
+  L.draw_cap = cap;
   return GPD_OK;
 }
 
@@ -304,7 +332,8 @@ static int job_begin(gpd_hip_ctx *ctx, Lane &L, Job &J) {
   int rc;
   {
     StageRange r("gpd:search (neighbourhoods, frames, hand evaluation, workspace filter)");
-    rc = search_run(ctx->params, L.cloud, L.search, J.sample_idx, J.sample_xyz, J.S, L.stream, /*sync_counts=*/false);
+    rc = search_run(ctx->params, L.cloud, L.search, J.sample_idx, J.sample_xyz, J.S, L.stream, /*sync_counts=*/false,
+                    J.resident ? &J.gather : nullptr);
   }
   if (rc) return rc;
   HIP_TRY(hipEventRecord(L.ev[1], L.stream));
@@ -946,6 +975,21 @@ int gpd_hip_sample_above_plane(gpd_hip_ctx *ctx, double threshold, int max_itera
                        iterations, L.stream);
 }
 
+int gpd_hip_sample_positions(int n, int num_draws, uint32_t seed, int with_repetition, int32_t *out, int *num_out) {
+  if (n < 0 || !num_out || (!out && n > 0 && num_draws > 0)) {
+    set_error("gpd_hip_sample_positions: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  std::vector<int32_t> pos;
+  if (with_repetition)
+    sample::with_repetition(n, num_draws, seed, pos);
+  else
+    sample::distinct(n, num_draws, seed, pos);
+  if (!pos.empty()) std::memcpy(out, pos.data(), pos.size() * sizeof(int32_t));
+  *num_out = (int)pos.size();
+  return GPD_OK;
+}
+
 int gpd_hip_refine_normals(gpd_hip_ctx *ctx, int k, int max_iterations, float convergence_threshold, float *normals_out, int *iterations_out,
                            float *ddot_out, int *num_nan_out, float kernel_ms[3]) {
   if (!ctx || !normals_out || !iterations_out || !num_nan_out || k < 1 || max_iterations < 0 || !std::isfinite(convergence_threshold) ||
@@ -1221,12 +1265,23 @@ int gpd_hip_detect_batch(gpd_hip_ctx *ctx, gpd_detect_job *jobs, int num_jobs) {
     // middle of the batch is a hipFree + hipMalloc, which waits for the whole device (both lanes).  Points, cameras and
     // samples are known; the candidate-sized buffers (images, LeNet scratch, records) take the upper bound
     // samples x slots, cut to kReserveBudget per lane — a cloud beyond that still grows its lane, and says so in `allocs`.
-    int maxP = 0, maxC = 0, maxS = 0, maxSel = 0;
+    int maxP = 0, maxC = 0, maxS = 0, maxSel = 0, maxDraws = 0;
+    int planeP = 0, refineP = 0, refineK = 0;  // raw jobs that carry on past the normals: their largest cloud (before the cut) and k
     bool all_selected = num_jobs > 0;
     for (int i = 0; i < num_jobs; i++) {
       maxP = std::max(maxP, jobs[i].num_points);
       maxC = std::max(maxC, jobs[i].num_cams);
       maxS = std::max(maxS, jobs[i].num_samples);
+      // the index route of a raw scan searches at most num_draws samples, and no more than the cloud has points
+      if (jobs[i].raw && !jobs[i].sample_xyz && jobs[i].num_draws > 0) {
+        maxS = std::max(maxS, std::min(jobs[i].num_draws, jobs[i].num_points));
+        maxDraws = std::max(maxDraws, std::min(jobs[i].num_draws, jobs[i].num_points));
+        if (jobs[i].sample_above_plane) planeP = std::max(planeP, jobs[i].num_points);
+      }
+      if (jobs[i].raw && jobs[i].refine_normals_k > 0 && jobs[i].refine_normals_k <= kRefineKCap) {
+        refineP = std::max(refineP, jobs[i].num_points);
+        refineK = std::max(refineK, jobs[i].refine_normals_k);
+      }
       maxSel = std::max(maxSel, jobs[i].num_selected);
       all_selected = all_selected && jobs[i].num_selected > 0;
     }
@@ -1245,6 +1300,12 @@ int gpd_hip_detect_batch(gpd_hip_ctx *ctx, gpd_detect_job *jobs, int num_jobs) {
       free_b = 2 * kReserveBudget;
     }
     const int lanes_used = std::min(kLanes, num_jobs);
+    // the draw buffers first and for every lane, not best effort: a few KB, and they must not grow inside the batch — a
+    // lane's previous job still has its sample indices in them when the next one draws
+    for (int l = 0; l < lanes_used && maxDraws > 0; l++) {
+      const int rc = reserve_draws(ctx->lane[l], maxDraws);
+      if (rc) return rc;
+    }
     const size_t budget = std::min(kReserveBudget, free_b / 2 / (size_t)std::max(lanes_used, 1));
     for (int l = 0; l < lanes_used; l++) {
       Lane &L = ctx->lane[l];
@@ -1256,6 +1317,9 @@ int gpd_hip_detect_batch(gpd_hip_ctx *ctx, gpd_detect_job *jobs, int num_jobs) {
       int rc = GPD_OK;
       if (!all_selected) rc = lane_reserve(ctx, L, maxP, maxC, maxS, cand, 0);
       if (!rc && maxSel > 0) rc = lane_reserve(ctx, L, maxP, maxC, maxS, cand, maxSel);
+      // the lane's fit / refinement states for the raw scans as they come in (the voxeliser only makes them smaller)
+      if (!rc && planeP > 0) rc = plane_reserve(L.plane, planeP);
+      if (!rc && refineP > 0) rc = refine_reserve(L.refine, refineP, std::min(refineK, refineP));
       if (rc == GPD_ERR_HIP) {
         (void)hipGetLastError();  // out of memory: clear it, the jobs size their buffers themselves
         break;
@@ -1289,7 +1353,21 @@ int gpd_hip_detect_batch(gpd_hip_ctx *ctx, gpd_detect_job *jobs, int num_jobs) {
     const int allocs0 = g_allocs;
     j.num_points_processed = 0;
     j.num_samples_processed = 0;
+    j.refine_passes = j.refine_num_nan = j.plane_num_above = j.plane_iterations = 0;
+    for (float &t : j.preprocess_ms) t = 0.f;
+    const double t_begin = now_ms();
     int rc = check_samples(ctx, L, "gpd_hip_detect_batch", nullptr, j.sample_xyz, j.num_samples, j.num_points);
+    if (!rc && (j.refine_normals_k < 0 || j.num_draws < 0 || (j.num_draws != 0 && j.sample_xyz))) {
+      set_error("gpd_hip_detect_batch: cloud %d: %s", i,
+                j.refine_normals_k < 0 ? "refine_normals_k is negative"
+                : j.num_draws < 0     ? "num_draws is negative"
+                                      : "num_draws and sample_xyz are both given (draw sample indices or pass coordinates)");
+      rc = GPD_ERR_INVALID;
+    }
+    if (!rc && j.refine_normals_k > kRefineKCap) {
+      set_error("gpd_hip_detect_batch: cloud %d: refine_normals_k = %d, the capacity is %d", i, j.refine_normals_k, kRefineKCap);
+      rc = GPD_ERR_CAPACITY;
+    }
     if (!rc && j.workspace) {
       // strict double comparisons on both sides, sample by sample, order kept (cloud.cpp:229-233): a sample outside the cut would
       // still find neighbours, produce hand sets and shift every later set's shadow LCG offset away from the reference's
@@ -1304,6 +1382,7 @@ int gpd_hip_detect_batch(gpd_hip_ctx *ctx, gpd_detect_job *jobs, int num_jobs) {
     // Cloud::removeNans (candidates_generator.cpp:17) is part of preprocessPointCloud: non-finite points are dropped here
     if (!rc) rc = preprocess_begin(L.pre, j.xyz, j.cam_source, j.num_points, j.num_cams, j.workspace, j.voxel_size, L.stream, /*drop_nonfinite=*/true);
     j.allocs += g_allocs - allocs0;
+    j.preprocess_ms[0] = (float)(now_ms() - t_begin);
     if (rc) return fail(i, rc);
     raw_pending[(size_t)i] = 1;
   };
@@ -1315,18 +1394,74 @@ int gpd_hip_detect_batch(gpd_hip_ctx *ctx, gpd_detect_job *jobs, int num_jobs) {
     gpd_detect_job &j = jobs[i];
     Lane &L = ctx->lane[i % kLanes];
     const int allocs0 = g_allocs;
+    double t0 = now_ms();
     int rc = preprocess_finish(L.pre, L.stream);
     if (!rc && L.pre.M < 1) {
       set_error("gpd_hip_detect_batch: cloud %d: no point is left after the workspace cut", i);
       rc = GPD_ERR_INVALID;
     }
     if (!rc) rc = cloud_from_device(L.cloud, L.pre.d_out_xyz, L.pre.d_out_cam, L.pre.M, j.num_cams, j.view_points, L.stream);
+    j.preprocess_ms[0] += (float)(now_ms() - t0);
+    t0 = now_ms();
     if (!rc) rc = normals_run(L.cloud, j.normals_radius, nullptr, L.stream);
-    if (rc) return fail(i, rc);
+    j.preprocess_ms[1] = (float)(now_ms() - t0);
+    // the rest of preprocessPointCloud (candidates_generator.cpp:28-36), resident: nothing cloud-sized comes back.
+    // refineNormals replaces the lane cloud's normals and bumps its generation before the search below takes it
+    if (!rc && j.refine_normals_k > 0) {
+      t0 = now_ms();
+      rc = refine_run(L.refine, L.cloud, j.refine_normals_k, 15, 1e-5f, nullptr, &j.refine_passes, nullptr, &j.refine_num_nan, nullptr, L.stream);
+      j.preprocess_ms[2] = (float)(now_ms() - t0);
+    }
+    const bool index_route = !j.sample_xyz && j.num_draws > 0;
+    if (!rc && index_route) {
+      const int M = L.pre.M;
+      int above = 0;
+      if (j.sample_above_plane) {
+        t0 = now_ms();
+        float coeffs[4];
+        int inliers = 0;
+        rc = plane_fit_run(L.plane, L.cloud, 0.01, 50, 0.99, 1, nullptr, &above, coeffs, &inliers, &j.plane_iterations, L.stream);
+        j.preprocess_ms[3] = (float)(now_ms() - t0);
+        if (rc) above = 0;
+        j.plane_num_above = above;
+      }
+      // Cloud::subsample: the positions come from a count alone (the list's, or the cloud's when there is none — no fit
+      // asked for, or "plane fit failed": the reference then uses the entire point cloud), the indices never leave the device
+      std::vector<int32_t> pos;
+      if (!rc) {
+        if (above > 0)
+          sample::with_repetition(above, j.num_draws, j.sample_seed, pos);
+        else
+          sample::distinct(M, j.num_draws, j.sample_seed, pos);
+        if ((int)pos.size() > L.draw_cap) {  // cannot happen: pos.size() <= min(num_draws, num_points), which sized the lanes
+          set_error("gpd_hip_detect_batch: cloud %d: %d draws, the lane holds %d", i, (int)pos.size(), L.draw_cap);
+          rc = GPD_ERR_STATE;
+        }
+      }
+      if (!rc) {
+        std::memcpy(L.h_pos, pos.data(), pos.size() * sizeof(int32_t));
+        const hipError_t e = hipMemcpyAsync(L.d_pos, L.h_pos, pos.size() * sizeof(int32_t), hipMemcpyHostToDevice, L.stream);
+        if (e != hipSuccess) {
+          set_error("gpd_hip_detect_batch: cloud %d: the draw positions could not be uploaded: %s", i, hipGetErrorString(e));
+          rc = GPD_ERR_HIP;
+        }
+      }
+      J[i].resident = true;
+      J[i].gather.d_list = above > 0 ? L.plane.d_idx : nullptr;
+      J[i].gather.list_size = above;
+      J[i].gather.d_pos = L.d_pos;
+      J[i].sample_xyz = nullptr;
+      J[i].S = (int)pos.size();
+    } else {
+      J[i].sample_xyz = j.workspace ? raw_samples[(size_t)i].data() : j.sample_xyz;
+      J[i].S = j.workspace ? (int)(raw_samples[(size_t)i].size() / 3) : j.num_samples;
+    }
+    if (rc) {
+      j.allocs += g_allocs - allocs0;
+      return fail(i, rc);
+    }
     j.num_points_processed = L.pre.M;
     J[i].sample_idx = nullptr;
-    J[i].sample_xyz = j.workspace ? raw_samples[(size_t)i].data() : j.sample_xyz;
-    J[i].S = j.workspace ? (int)(raw_samples[(size_t)i].size() / 3) : j.num_samples;
     j.num_samples_processed = J[i].S;
     J[i].mode = 1;
     J[i].num_selected = j.num_selected;
@@ -1334,6 +1469,16 @@ int gpd_hip_detect_batch(gpd_hip_ctx *ctx, gpd_detect_job *jobs, int num_jobs) {
     J[i].capacity = j.hands_capacity;
     J[i].lcg_base = j.lcg_base;
     rc = job_begin(ctx, L, J[i]);
+    if (!rc && J[i].resident && j.samples_out && J[i].S > 0) {
+      // the sample indices searched, behind the search in stream order; end(i) hands them over.  A half of the pinned
+      // buffer per job of the lane in flight: this lane's previous job is collected only after this point
+      int32_t *h = L.h_pos + (size_t)L.draw_cap * (1 + ((i / kLanes) & 1));
+      const hipError_t e = hipMemcpyAsync(h, L.search.d_sample_idx, (size_t)J[i].S * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream);
+      if (e != hipSuccess) {
+        set_error("gpd_hip_detect_batch: cloud %d: the sample indices could not be copied back: %s", i, hipGetErrorString(e));
+        rc = GPD_ERR_HIP;
+      }
+    }
     j.allocs += g_allocs - allocs0;
     j.host_ms[0] = (float)(now_ms() - t_entry);
     if (rc) fail(i, rc);
@@ -1368,6 +1513,8 @@ int gpd_hip_detect_batch(gpd_hip_ctx *ctx, gpd_detect_job *jobs, int num_jobs) {
     jobs[i].num_candidates = J[i].num_candidates;
     jobs[i].num_hands = J[i].num_hands;
     jobs[i].lcg_draws = J[i].lcg_draws;
+    if (jobs[i].status == GPD_OK && J[i].resident && jobs[i].samples_out && J[i].S > 0)
+      std::memcpy(jobs[i].samples_out, L.h_pos + (size_t)L.draw_cap * (1 + ((i / kLanes) & 1)), (size_t)J[i].S * sizeof(int32_t));
     for (int k = 0; k < 3; k++) jobs[i].stage_ms[k] = L.stage_ms[k];
   };
   // cloud i+1's upload + search are enqueued (other lane's buffers) before the host waits for cloud i's plan;

@@ -245,8 +245,16 @@ struct SearchState {
 // samples by index (sample_xyz == nullptr) or by coordinates (sample_idx == nullptr).  sync_counts: download the
 // neighbourhood sizes and grow the list capacity when one overflows (the unfused entry points); without it nothing
 // waits for the device and the caller checks `worst found` in the plan summary (search_retry_needed).
+// resident (may be null; then neither host pointer is read): the sample indices are gathered on the device,
+// d_sample_idx[i] = d_list ? d_list[d_pos[i]] : d_pos[i].  Both arrays must stay as they are until the job's plan summary has
+// arrived: a list-capacity retry gathers again.
+struct SampleGather {
+  const int32_t *d_list = nullptr;  // nullptr: the positions are the indices
+  int list_size = 0;
+  const int32_t *d_pos = nullptr;   // [S]
+};
 int search_run(const gpd_params &p, const Cloud &c, SearchState &s, const int32_t *sample_idx, const double *sample_xyz, int S,
-               hipStream_t stream, bool sync_counts = true);
+               hipStream_t stream, bool sync_counts = true, const SampleGather *resident = nullptr);
 // list capacity the next search_run would use after a neighbourhood of `worst` entries; 0: beyond every capacity
 int search_reserve_samples(SearchState &s, int S, int slots);  // buffers for S samples at the current list capacity
 int search_next_capacity(const SearchState &s, int worst);
@@ -437,7 +445,10 @@ struct PlaneState {
   std::vector<float> h_xyz;          // the inliers' xyz for the host's refinement
 };
 void plane_free(PlaneState &s);
-// on the uploaded cloud c; indices_out holds c.num_points entries.  *num_out = 0: no plane, or no point off it
+int plane_reserve(PlaneState &s, int n);  // the buffers for clouds of up to n points (gpd_hip_detect_batch sizes its lanes ahead)
+// on the uploaded cloud c; indices_out holds c.num_points entries.  *num_out = 0: no plane, or no point off it.
+// indices_out == nullptr (the resident form, raw scans of gpd_hip_detect_batch): the list stays in s.d_idx, *num_out of them;
+// only the hypotheses' counts, the refinement's inliers and the 4-byte total cross PCIe
 int plane_fit_run(PlaneState &s, const Cloud &c, double threshold, int max_iterations, double probability, int optimize, int32_t *indices_out,
                   int *num_out, float coeffs[4], int *num_inliers, int *iterations, hipStream_t stream);
 
@@ -453,10 +464,15 @@ struct RefineState {
   float *h_dots = nullptr;           // pinned [2][cap_points]
   hipEvent_t ev_dots[2] = {nullptr, nullptr};  // a pass's dots are on the host
   std::vector<hipEvent_t> ev;        // kNN start / end, then start / end of every pass
+  int32_t *d_nan = nullptr;          // the resident form's count of non-finite normals ...
+  int32_t *h_nan = nullptr;          // ... and its pinned host side
 };
 void refine_free(RefineState &s);
+int refine_reserve(RefineState &s, int n, int k);  // the buffers for clouds of up to n points with k neighbours each
 // on the uploaded cloud c, k <= kRefineKCap (clamped to the cloud's size); replaces c's normals and bumps its generation.
 // ddot_out (may be null) receives one mean per pass; kernel_ms (may be null): kNN, the passes launched, the whole call.
+// normals_out == nullptr (the resident form, raw scans of gpd_hip_detect_batch): the normals are not downloaded, the
+// non-finite ones are counted on the device; only the per-pass dots of the stop rule and that count cross PCIe
 int refine_run(RefineState &s, Cloud &c, int k, int max_iterations, float threshold, float *normals_out, int *iterations_out, float *ddot_out,
                int *num_nan_out, float *kernel_ms, hipStream_t stream);
 

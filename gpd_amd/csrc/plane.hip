@@ -314,6 +314,17 @@ __global__ __launch_bounds__(64) void accu_kernel(const float *__restrict__ xyz,
   }
 }
 
+// flag / scan / write over the cloud for the points whose test against c equals `want`
+hipError_t compact(PlaneState &s, const Cloud &c, float4 plane, float thr, int want, float *xyz_out, int32_t *idx_out, hipStream_t stream) {
+  const int n = c.num_points, nb = (n + kFlagThreads - 1) / kFlagThreads;
+  flag_count_kernel<<<nb, kFlagThreads, 0, stream>>>(c.px, c.py, c.pz, n, plane, thr, want, s.d_block_count);
+  scan_kernel<<<1, 1024, 0, stream>>>(s.d_block_count, nb, s.d_block_off, reinterpret_cast<PlaneMeta *>(s.d_meta));
+  flag_write_kernel<<<nb, kFlagThreads, 0, stream>>>(c.px, c.py, c.pz, n, plane, thr, want, s.d_block_off, xyz_out, idx_out);
+  return hipGetLastError();
+}
+
+}  // namespace
+
 int plane_reserve(PlaneState &s, int n) {
   if (!s.d_meta) {
     HIP_RET(hipMalloc(&s.d_meta, sizeof(PlaneMeta)));
@@ -342,17 +353,6 @@ int plane_reserve(PlaneState &s, int n) {
   }
   return GPD_OK;
 }
-
-// flag / scan / write over the cloud for the points whose test against c equals `want`
-hipError_t compact(PlaneState &s, const Cloud &c, float4 plane, float thr, int want, float *xyz_out, int32_t *idx_out, hipStream_t stream) {
-  const int n = c.num_points, nb = (n + kFlagThreads - 1) / kFlagThreads;
-  flag_count_kernel<<<nb, kFlagThreads, 0, stream>>>(c.px, c.py, c.pz, n, plane, thr, want, s.d_block_count);
-  scan_kernel<<<1, 1024, 0, stream>>>(s.d_block_count, nb, s.d_block_off, reinterpret_cast<PlaneMeta *>(s.d_meta));
-  flag_write_kernel<<<nb, kFlagThreads, 0, stream>>>(c.px, c.py, c.pz, n, plane, thr, want, s.d_block_off, xyz_out, idx_out);
-  return hipGetLastError();
-}
-
-}  // namespace
 
 void plane_free(PlaneState &s) {
   (void)hipFree(s.d_meta);
@@ -448,7 +448,7 @@ int plane_fit_run(PlaneState &s, const Cloud &c, double threshold, int max_itera
     set_error("gpd_hip_sample_above_plane: compaction wrote %d of %d points", m, n);
     return GPD_ERR_HIP;
   }
-  if (m > 0) {
+  if (m > 0 && indices_out) {
     HIP_RET(hipMemcpyAsync(indices_out, s.d_idx, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     HIP_RET(hipStreamSynchronize(stream));
   }

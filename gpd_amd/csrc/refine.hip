@@ -213,6 +213,20 @@ __global__ void refine_store_kernel(const float4 *__restrict__ res, int num_poin
   aos[3 * (size_t)i + 2] = v.z;
 }
 
+// the resident form's only scalar: normals with a non-finite component (a ballot per wave, one atomic per wave that has any)
+__global__ __launch_bounds__(256) void refine_count_nan_kernel(const float4 *__restrict__ res, int num_points, int32_t *count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  if (i < num_points) {
+    const float4 v = res[i];
+    bad = !finite3(v.x, v.y, v.z);
+  }
+  const unsigned long long m = __ballot(bad);
+  if (m && (threadIdx.x & 63) == 0) atomicAdd(count, (int32_t)__popcll(m));
+}
+
+}  // namespace
+
 int refine_reserve(RefineState &s, int n, int k) {
   const size_t lists = ((size_t)n + 63) / 64 * 64 * (size_t)k;
   if (n > s.cap_points) {
@@ -243,10 +257,12 @@ int refine_reserve(RefineState &s, int n, int k) {
   }
   if (!s.ev_dots[0])
     for (hipEvent_t &e : s.ev_dots) HIP_RET(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (!s.d_nan) {
+    HIP_RET(hipMalloc(&s.d_nan, sizeof(int32_t)));
+    HIP_RET(hipHostMalloc(reinterpret_cast<void **>(&s.h_nan), sizeof(int32_t), 0));
+  }
   return GPD_OK;
 }
-
-}  // namespace
 
 void refine_free(RefineState &s) {
   (void)hipFree(s.d_lists);
@@ -254,6 +270,8 @@ void refine_free(RefineState &s) {
   (void)hipFree(s.d_dots);
   (void)hipFree(s.d_aos);
   if (s.h_dots) (void)hipHostFree(s.h_dots);
+  (void)hipFree(s.d_nan);
+  if (s.h_nan) (void)hipHostFree(s.h_nan);
   for (hipEvent_t e : s.ev_dots)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : s.ev)
@@ -322,11 +340,20 @@ int refine_run(RefineState &s, Cloud &c, int k, int max_iterations, float thresh
   // 4: pass `done` wrote d_buf[done & 1]
   refine_store_kernel<<<(n + 255) / 256, 256, 0, stream>>>(s.d_buf[done & 1], n, c.nx, c.ny, c.nz, c.pnrm, s.d_aos);
   HIP_RET(hipGetLastError());
-  HIP_RET(hipMemcpyAsync(normals_out, s.d_aos, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-  HIP_RET(hipStreamSynchronize(stream));
-  c.generation++;
   int nan = 0;
-  for (int i = 0; i < n; i++) nan += !refine::finite3(normals_out[3 * (size_t)i], normals_out[3 * (size_t)i + 1], normals_out[3 * (size_t)i + 2]);
+  if (normals_out) {
+    HIP_RET(hipMemcpyAsync(normals_out, s.d_aos, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    HIP_RET(hipStreamSynchronize(stream));
+    for (int i = 0; i < n; i++) nan += !refine::finite3(normals_out[3 * (size_t)i], normals_out[3 * (size_t)i + 1], normals_out[3 * (size_t)i + 2]);
+  } else {
+    HIP_RET(hipMemsetAsync(s.d_nan, 0, sizeof(int32_t), stream));
+    refine_count_nan_kernel<<<(n + 255) / 256, 256, 0, stream>>>(s.d_buf[done & 1], n, s.d_nan);
+    HIP_RET(hipGetLastError());
+    HIP_RET(hipMemcpyAsync(s.h_nan, s.d_nan, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_RET(hipStreamSynchronize(stream));
+    nan = *s.h_nan;
+  }
+  c.generation++;
   *iterations_out = done;
   *num_nan_out = nan;
   if (kernel_ms) {

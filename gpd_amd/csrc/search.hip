@@ -2581,6 +2581,20 @@ __global__ __launch_bounds__(256) void hand_eval_kernel(HandParams P) {
 #undef HTICK
 }
 
+// Sample indices that never were on the host (raw scans of gpd_hip_detect_batch): out[i] = list ? list[pos[i]] : pos[i] —
+// `pos` the draw positions of Cloud::subsample (sample_model.h, computed on the host from a count), `list` the points above
+// the support plane as the fit left them on the device.  A position outside the list gives -1, which the neighbourhood
+// kernel never sees: the host draws positions below the list's size only.
+__global__ __launch_bounds__(256) void sample_gather_kernel(const int32_t *__restrict__ list, int list_size, const int32_t *__restrict__ pos, int n,
+                                                            int32_t *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int q = pos[i];
+  int32_t v = q;
+  if (list) v = (q >= 0 && q < list_size) ? list[q] : -1;
+  out[i] = v;
+}
+
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
@@ -2729,7 +2743,7 @@ static int run_neighbourhoods(const gpd_params &p, const Cloud &c, SearchState &
 // neighbourhoods of S samples (by index or by coordinates), list capacity grown once if needed
 static int neighbourhoods(const gpd_params &p, const Cloud &c, SearchState &s, const HostConsts &hc, const int32_t *sample_idx,
                           const double *sample_xyz, int S, int slots, int *cap_out, hipStream_t stream, bool sync_counts = true,
-                          bool want_height_list = true) {
+                          bool want_height_list = true, const SampleGather *resident = nullptr) {
   // a new cloud starts from the LDS-sorted list size again: the large lists one dense cloud needed are not carried into the
   // next one (they come back through the retry below if it needs them too)
   if (s.seen_generation != c.generation) {
@@ -2743,10 +2757,14 @@ static int neighbourhoods(const gpd_params &p, const Cloud &c, SearchState &s, c
   int rc = search_reserve(s, S, cap, slots);
   if (rc) return rc;
   for (;;) {
-    if (sample_xyz)
+    if (resident) {  // the indices are on the device already (and stay where they were: a retry gathers them again)
+      sample_gather_kernel<<<(S + 255) / 256, 256, 0, stream>>>(resident->d_list, resident->list_size, resident->d_pos, S, s.d_sample_idx);
+      HIP_RET(hipGetLastError());
+    } else if (sample_xyz) {
       HIP_RET(hipMemcpyAsync(s.d_sample_xyz, sample_xyz, (size_t)S * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-    else
+    } else {
       HIP_RET(hipMemcpyAsync(s.d_sample_idx, sample_idx, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    }
     rc = run_neighbourhoods(p, c, s, hc, S, cap, sample_xyz != nullptr, slots, want_height_list, stream, sync_counts);
     if (rc) return rc;
     if (!sync_counts) break;  // the caller reads `worst found` from the plan summary and retries (search_next_capacity)
@@ -2849,12 +2867,12 @@ int search_force_capacity(SearchState &s, int cap) {
 }
 
 int search_run(const gpd_params &p, const Cloud &c, SearchState &s, const int32_t *sample_idx, const double *sample_xyz, int S,
-               hipStream_t stream, bool sync_counts) {
+               hipStream_t stream, bool sync_counts, const SampleGather *resident) {
   const int slots = p.num_hand_axes * p.num_orientations;
   HostConsts hc;
   host_consts(p, hc);
   int cap = 0;
-  int rc = neighbourhoods(p, c, s, hc, sample_idx, sample_xyz, S, slots, &cap, stream, sync_counts);
+  int rc = neighbourhoods(p, c, s, hc, sample_idx, resident ? nullptr : sample_xyz, S, slots, &cap, stream, sync_counts, true, resident);
   if (rc) return rc;
   std::unique_lock<std::mutex> consts_lock;  // held until the kernels that read c_hand are enqueued
   rc = upload_hand_consts(p, hc, slots, stream, consts_lock);

@@ -19,6 +19,7 @@
 #include "gpd/util/config_file.h"
 #include "../../csrc/plane_model.h"
 #include "../../csrc/refine_model.h"
+#include "../../csrc/sample_model.h"
 
 namespace gpd {
 
@@ -471,41 +472,30 @@ void Cloud::applyRefinedNormals(const std::vector<float> &refined) {
 
 void Cloud::subsample(int num_samples, unsigned seed) {
   if (num_samples <= 0) return;
-  uint64_t s = 0x9E3779B97F4A7C15ull ^ seed;
-  auto next = [&s]() {
-    s ^= s << 13;
-    s ^= s >> 7;
-    s ^= s << 17;
-    return s;
-  };
+  std::vector<int32_t> pos;  // the draws: ../../csrc/sample_model.h, shared with libgpd_hip.so
   if (samples_.size() >= 3) {
     const int have = (int)(samples_.size() / 3);
     if (num_samples >= have) return;
     printf("Using %d out of %d available samples.\n", num_samples, have);
-    std::vector<int> seq(have);
-    std::iota(seq.begin(), seq.end(), 0);
-    for (int i = 0; i < num_samples; i++) std::swap(seq[i], seq[i + (int)(next() % (uint64_t)(have - i))]);
+    gpd::sample::distinct(have, num_samples, seed, pos);
     std::vector<double> sub((size_t)num_samples * 3);
     for (int i = 0; i < num_samples; i++)
-      for (int r = 0; r < 3; r++) sub[3 * (size_t)i + r] = samples_[3 * (size_t)seq[i] + r];
+      for (int r = 0; r < 3; r++) sub[3 * (size_t)i + r] = samples_[3 * (size_t)pos[(size_t)i] + r];
     samples_ = sub;
     return;
   }
   if (!sample_indices_.empty()) {
     if (num_samples >= (int)sample_indices_.size()) return;
+    gpd::sample::with_repetition((int)sample_indices_.size(), num_samples, seed, pos);
     std::vector<int> indices(num_samples);
-    for (int i = 0; i < num_samples; i++) indices[i] = sample_indices_[next() % sample_indices_.size()];
+    for (int i = 0; i < num_samples; i++) indices[i] = sample_indices_[(size_t)pos[(size_t)i]];
     sample_indices_ = indices;
     return;
   }
   const int n = (int)size();
   if (n == 0) return;
-  std::vector<int> idx(n);
-  std::iota(idx.begin(), idx.end(), 0);
-  const int m = std::min(num_samples, n);
-  for (int i = 0; i < m; i++) std::swap(idx[i], idx[i + (int)(next() % (uint64_t)(n - i))]);
-  idx.resize(m);
-  sample_indices_ = idx;
+  gpd::sample::distinct(n, num_samples, seed, pos);
+  sample_indices_.assign(pos.begin(), pos.end());
 }
 
 }  // namespace util
@@ -1590,6 +1580,19 @@ extern "C" int gpd_host_refine_normals(const float *xyz, const float *normals, i
   std::copy(r.ddots.begin(), r.ddots.end(), ddots);
   *num_nan = r.num_nan;
   return r.iterations;
+}
+
+// Flat entry for tests / ctypes: util::Cloud::subsample on a cloud of num_points points that carries the sample indices
+// `list` (num_list of them; 0: none).  out holds max(num_list, num_samples, 0) entries; returns how many sample indices
+// the cloud carries afterwards.
+extern "C" int gpd_host_subsample_indices(int num_points, const int *list, int num_list, int num_samples, unsigned seed, int *out) {
+  const std::vector<float> xyz((size_t)(num_points > 0 ? num_points : 0) * 3, 0.f);
+  gpd::util::Cloud cloud(xyz, std::vector<float>(), std::vector<int>(xyz.size() / 3, 1), {0.0, 0.0, 0.0});
+  if (num_list > 0) cloud.setSampleIndices(std::vector<int>(list, list + num_list));
+  cloud.subsample(num_samples, seed);
+  const std::vector<int> &idx = cloud.getSampleIndices();
+  std::copy(idx.begin(), idx.end(), out);
+  return (int)idx.size();
 }
 
 // Flat entry for tests / ctypes: the host model's kNN lists [n][min(k, n)] (the (d2, index) order); returns min(k, n)

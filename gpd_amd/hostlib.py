@@ -72,6 +72,18 @@ def refine_normals(xyz, normals, k, max_iterations=15, convergence_threshold=1e-
     return out[:n].copy(), int(its), ddots[:its].copy(), int(nan.value)
 
 
+def subsample_indices(num_points, num_samples, seed=0, sample_indices=None):
+    """util::Cloud::subsample on a cloud of num_points points that carries `sample_indices` (None: none) ->
+    the sample indices it carries afterwards, i32."""
+    lst = np.zeros(0, np.int32) if sample_indices is None else np.ascontiguousarray(sample_indices, np.int32).reshape(-1)
+    out = np.zeros(max(len(lst), int(num_samples), 1), np.int32)
+    L = lib()
+    L.gpd_host_subsample_indices.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_void_p]
+    k = L.gpd_host_subsample_indices(int(num_points), lst.ctypes.data_as(C.c_void_p), len(lst), int(num_samples), int(seed) & 0xFFFFFFFF,
+                                     out.ctypes.data_as(C.c_void_p))
+    return out[:k].copy()
+
+
 def knn(xyz, k):
     """the host model's k-nearest-neighbour lists -> i32 [n, min(k, n)], ascending by (float d2, index)."""
     xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)

@@ -134,6 +134,25 @@ def sample_indices(cloud, num_samples, seed=None):
     return np.ascontiguousarray(rng.permutation(obj)[:num_samples].astype(np.int32))
 
 
+def raw_scan(seed, n, base=30000):
+    """A raw two-camera scan, the voxeliser's input: every lattice point of a table-plus-objects cloud (make_cloud(seed, base))
+    several times, moved by up to 1 mm, shuffled, n points in all.
+    -> (dict(xyz f32 [n,3], cam_source i32 [2,n], view_points f64 [2,3]), up to 150 sample coordinates on the objects f64 [S,3])"""
+    rng = np.random.RandomState(seed)
+    cl = make_cloud(seed, base)
+    parts = [(cl["xyz"] + rng.uniform(-1e-3, 1e-3, cl["xyz"].shape)).astype(np.float32) for _ in range(max(1, -(-n // base)))]
+    xyz = np.concatenate(parts)[:n]
+    xyz = np.ascontiguousarray(xyz[rng.permutation(len(xyz))])
+    cam = np.ones((2, len(xyz)), np.int32)
+    cam[1] = rng.rand(len(xyz)) < 0.5
+    cam[0, cam[1] == 1] = rng.rand(int(cam[1].sum())) < 0.5
+    cam[0, (cam[0] == 0) & (cam[1] == 0)] = 1
+    vp = np.array([[0.0, 0.0, 0.0], [0.25, -0.1, 0.05]])
+    obj = np.flatnonzero(cl["is_object"])
+    sm = cl["xyz"][rng.choice(obj, min(150, len(obj)), replace=False)].astype(np.float64)
+    return dict(xyz=xyz, cam_source=cam, view_points=vp), sm
+
+
 TRAINED_IP1_DIVISOR = 128.0  # ip1 / 128: logits of the size a trained LeNet produces (|score| < 20) on real grasp images
 
 

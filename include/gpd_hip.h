@@ -280,8 +280,9 @@ int gpd_hip_reserve(gpd_hip_ctx *ctx, int max_points, int max_cams, int max_samp
 
 /* One independent cloud of a batch: the arguments of gpd_hip_upload_cloud + gpd_hip_detect_select.
  * ZERO the struct (memset / `gpd_detect_job j = {0}`) before filling it: fields added in later rounds (lcg_base, raw, voxel_size,
- * workspace, normals_radius, sample_xyz) are INPUTS, and an uninitialised `raw` or `lcg_base` selects the raw-scan route or
- * offsets the cloud's shadow stream — wrong images, not an error. */
+ * workspace, normals_radius, sample_xyz, refine_normals_k, sample_above_plane, num_draws, sample_seed, samples_out) are INPUTS,
+ * and an uninitialised `raw` or `lcg_base` selects the raw-scan route or offsets the cloud's shadow stream — wrong images, not an
+ * error; an uninitialised `num_draws` or `samples_out` of a raw job draws samples nobody asked for or writes through a wild pointer. */
 typedef struct gpd_detect_job {
   const float *xyz;            /* in */
   const float *normals;
@@ -326,7 +327,49 @@ typedef struct gpd_detect_job {
   const double *sample_xyz;
   int32_t num_points_processed;
   int32_t num_samples_processed;
+  /* The rest of preprocessPointCloud for a RAW scan (candidates_generator.cpp:28-36); read only when raw != 0, all zero: as above.
+   * refine_normals_k (in) > 0: Cloud::refineNormals(k) after the normals (cloud.cpp:176-204) with the reference's fixed settings —
+   *   15 passes at most, convergence threshold 1e-5f — as gpd_hip_refine_normals; the search reads the refined normals.
+   *   k > 256: GPD_ERR_CAPACITY, k < 0: GPD_ERR_INVALID, for this job alone.
+   * The INDEX route — sample_xyz == NULL, num_samples == 0, num_draws > 0 — is detect_grasps on a PCD file without samples:
+   *   sample_above_plane (in) != 0: Cloud::sampleAbovePlane() (cloud.cpp:407-436) with the reference's values (0.01, 50, 0.99,
+   *     optimize) as gpd_hip_sample_above_plane: the candidate list is the points off the support plane, ascending; a failed fit
+   *     (plane_num_above == 0) leaves none, and as in the reference the whole cloud is used then.
+   *   num_draws, sample_seed (in): Cloud::subsample(num_draws) (cloud.cpp:350-405) on the project's seeded stream (xorshift64 from
+   *     0x9E3779B97F4A7C15 ^ sample_seed, steps << 13, >> 7, << 17 — the reference's generators are time-seeded).  With a list of n
+   *     entries: num_draws >= n keeps the whole list in order, otherwise num_draws draws WITH repetition, list[next() % n].  Without
+   *     a list: a partial Fisher-Yates over the M preprocessed points, min(num_draws, M) distinct indices.
+   *     gpd_hip_sample_positions gives the positions on the host.
+   *   samples_out (in; may be NULL, else room for num_draws entries): receives the sample indices into the preprocessed cloud the
+   *     search ran at, num_samples_processed of them.  The list, the draw and the search stay on the device: a few KB of positions
+   *     go up, this copy comes down.
+   *   num_samples_processed, num_sets, num_candidates, lcg_draws follow as on any index search; the lanes are sized with num_draws
+   *   as the sample count (the number searched never exceeds it).
+   * The COORDINATES route (sample_xyz given) is the one above plus the refinement when asked for.  sample_above_plane is accepted
+   *   there and changes nothing: HandSearch::searchHands reads the samples before the sample indices (hand_search.cpp:37-39) and
+   *   sampleAbovePlane only rewrites the latter, so the fit is not run and the plane_* outputs stay 0; samples_out is not written.
+   *   num_draws != 0 together with sample_xyz is GPD_ERR_INVALID for this job (the two sampling modes are not mixed), so is
+   *   num_draws < 0.  With num_draws == 0 and no samples nothing is searched and the fit is not run.
+   * A job that fails here carries its own status; the batch goes on. */
+  int32_t refine_normals_k;
+  int32_t sample_above_plane;
+  int32_t num_draws;
+  uint32_t sample_seed;
+  int32_t *samples_out;
+  int32_t refine_passes;     /* out: passes the refinement ran (0: not asked for) */
+  int32_t refine_num_nan;    /* out: refined normals with a non-finite component */
+  int32_t plane_num_above;   /* out: points off the support plane; 0: the fit failed or was not run */
+  int32_t plane_iterations;  /* out: hypotheses RANSAC evaluated */
+  float preprocess_ms[4];    /* out: host wall time of this job's cut + voxeliser, normals, refinement, plane fit */
 } gpd_detect_job;
+
+/* The positions Cloud::subsample draws from a candidate list of n entries on the seeded stream described at
+ * gpd_detect_job::num_draws — host only, no context.  with_repetition != 0: the list is a cloud's sample indices
+ * (num_draws >= n: 0 .. n-1 in order, else num_draws draws next() % n); 0: the list is the cloud's n points (the first
+ * min(num_draws, n) entries of a Fisher-Yates shuffle, distinct; computed with a sparse swap map, so n may be large).
+ * out holds max(min(num_draws, n), 0) entries; *num_out receives how many were written (num_draws <= 0: none).
+ * GPD_ERR_INVALID: n < 0 or a NULL num_out / out. */
+int gpd_hip_sample_positions(int n, int num_draws, uint32_t seed, int with_repetition, int32_t *out, int *num_out);
 
 /* detect_grasps over a batch of independent clouds (src/detect_grasps.cpp:20-86 called once per
  * cloud; BASELINE configs[4]).  The context keeps two clouds in flight on two streams: upload, grid
