@@ -73,6 +73,50 @@ def sample_positions(n, num_draws, seed=0, with_repetition=False):
     return out[: k.value].copy()
 
 
+TORCH_KEYS = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
+
+
+def torch_state_arrays(state):
+    """The eight tensors of pytorch/network.py::Net out of a state_dict-like mapping -> {key: contiguous f32 array} in torch
+    layout.  Values are numpy arrays or anything with .detach().cpu().numpy() (torch is not imported here); a `module.` prefix
+    on the keys (a model wrapped in nn.DataParallel, as pytorch/train_net3.py may save it) is stripped."""
+    plain = {}
+    for k, v in state.items():
+        k = str(k)
+        plain[k[len("module."):] if k.startswith("module.") else k] = v
+    out = {}
+    for k in TORCH_KEYS:
+        if k not in plain:
+            raise KeyError("state dict has no %r (keys: %s)" % (k, sorted(plain)))
+        v = plain[k]
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        out[k] = np.ascontiguousarray(v, np.float32)
+    return out
+
+
+def lenet_from_torch(state, channels, input_scale=1.0 / 256):
+    """gpd_hip_lenet_from_torch: a state dict of the reference's PyTorch network (pytorch/network.py::Net, trained on
+    image * input_scale, hdf5_dataset.py:17) -> the c1w .. f2b dict set_lenet_weights takes.  Host only.  The network also
+    needs Context.set_lenet_conv_relu(True); Context.set_lenet_torch does both."""
+    t = torch_state_arrays(state)
+    channels = int(channels)
+    sizes = {"conv1.weight": 20 * channels * 25, "conv1.bias": 20, "conv2.weight": 50 * 500, "conv2.bias": 50,
+             "fc1.weight": 500 * 7200, "fc1.bias": 500, "fc2.weight": 2 * 500, "fc2.bias": 2}
+    for k, n in sizes.items():
+        if t[k].size != n:
+            raise ValueError("%s has %d elements, %d expected for %d channels" % (k, t[k].size, n, channels))
+    c1w, f1w, f2w = np.zeros(20 * channels * 25, np.float32), np.zeros(7200 * 500, np.float32), np.zeros(1000, np.float32)
+    L = lib()
+    rc = L.gpd_hip_lenet_from_torch(channels, float(input_scale), _ptr(t["conv1.weight"]), _ptr(t["fc1.weight"]), _ptr(t["fc2.weight"]),
+                                    _ptr(c1w), _ptr(f1w), _ptr(f2w))
+    if rc != 0:
+        raise GpdHipError("libgpd_hip error %d: %s" % (rc, L.gpd_hip_last_error().decode()))
+    # conv2 [50][20][5][5] is the reference's [50][500] already, and the biases are biases
+    return dict(c1w=c1w, c1b=t["conv1.bias"].ravel().copy(), c2w=t["conv2.weight"].ravel().copy(), c2b=t["conv2.bias"].ravel().copy(),
+                f1w=f1w, f1b=t["fc1.bias"].ravel().copy(), f2w=f2w, f2b=t["fc2.bias"].ravel().copy())
+
+
 def bind_host_thread(device):
     """gpd_hip_bind_host_thread: the calling thread onto the CPUs of the device's NUMA node -> (node or -1, cpus)."""
     n = C.c_int(0)
@@ -86,7 +130,8 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_search_samples", "gpd_hip_detect_samples", "gpd_hip_reevaluate", "gpd_hip_replay_kernel_ms", "gpd_hip_last_centre_chains",
            "gpd_hip_detect_select", "gpd_hip_detect_batch", "gpd_hip_detect_batch_multi", "gpd_hip_conv1_stats", "gpd_hip_last_fallbacks", "gpd_hip_preprocess_cloud", "gpd_hip_find_clusters", "gpd_hip_reserve", "gpd_hip_bind_host_thread",
            "gpd_hip_set_lenet_mode", "gpd_hip_lenet_debug", "gpd_hip_lenet_fast_tables", "gpd_hip_detect_sharded",
-           "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals", "gpd_hip_sample_positions"]
+           "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals", "gpd_hip_sample_positions",
+           "gpd_hip_set_lenet_conv_relu", "gpd_hip_lenet_from_torch"]
 
 
 def build(prof=True):
@@ -143,6 +188,8 @@ def lib():
         L.gpd_hip_reserve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         L.gpd_hip_bind_host_thread.argtypes = [C.c_int, C.POINTER(C.c_int)]
         L.gpd_hip_set_lenet_mode.argtypes = [C.c_void_p, C.c_int]
+        L.gpd_hip_set_lenet_conv_relu.argtypes = [C.c_void_p, C.c_int]
+        L.gpd_hip_lenet_from_torch.argtypes = [C.c_int, C.c_double] + [C.c_void_p] * 6
         L.gpd_hip_lenet_debug.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.gpd_hip_replay_times.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
         _LIB = L
@@ -194,6 +241,16 @@ class Context:
         """LENET_SPLIT (default: int8 / bf16 matrix pipes on exactly split operands) or LENET_F32_CHAIN (the oracle's
         k-ascending fmaf chains, bit-identical, 1/16 of the matrix rate)."""
         self._check(lib().gpd_hip_set_lenet_mode(self._h, int(mode)))
+
+    def set_lenet_conv_relu(self, on):
+        """gpd_hip_set_lenet_conv_relu: a ReLU after conv1 and conv2 (the reference's PyTorch network) for every later scoring
+        call of the context; off (default): the reference's Eigen / Caffe network.  Kept across set_lenet_weights."""
+        self._check(lib().gpd_hip_set_lenet_conv_relu(self._h, int(bool(on))))
+
+    def set_lenet_torch(self, state, input_scale=1.0 / 256):
+        """A state dict of pytorch/network.py::Net (see lenet_from_torch) as the context's scoring network: weights + conv ReLUs."""
+        self.set_lenet_weights(lenet_from_torch(state, self.params.image_num_channels, input_scale))
+        self.set_lenet_conv_relu(True)
 
     def lenet_debug(self, which, n):
         """Test hook: pool1 (0), the flattened pool2 as bf16 planes (1) or ip1 transposed (2) of the last score() pass."""

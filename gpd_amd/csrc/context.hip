@@ -806,6 +806,52 @@ int gpd_hip_set_lenet_mode(gpd_hip_ctx *ctx, int mode) {
   return GPD_OK;
 }
 
+// The ReLU after conv1 and conv2 of the reference's PyTorch network (pytorch/network.py: F.relu(conv), then the pool; the Eigen /
+// Caffe / OpenVINO network has none).  Context state like the mode: every scoring entry goes through lenet_forward with
+// ctx->lenet, which picks the kernels' RELU instantiations at enqueue time; gpd_hip_set_lenet_weights leaves it alone.
+int gpd_hip_set_lenet_conv_relu(gpd_hip_ctx *ctx, int on) {
+  if (!ctx || (on != 0 && on != 1)) {
+    set_error("gpd_hip_set_lenet_conv_relu: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  ctx->lenet.conv_relu = on != 0;
+  return GPD_OK;
+}
+
+// pytorch/network.py::Net's tensors -> the layouts gpd_hip_set_lenet_weights takes (host only).  conv2 and all biases need no
+// conversion: [50][20][5][5] row-major is the reference's [50][500], and a bias is a bias.
+//   conv1  [20][C][5][5] is the reference's row-major [20][C*25]; the input scale of the training data (hdf5_dataset.py:17:
+//          image * 1/256) is folded in: w * scale, rounded once from double (exact for a power of two)
+//   ip1    Net flattens pool2 channel-major (x.view(-1, 50*12*12): k = c * 144 + p) and nn.Linear stores [out][in]; the reference
+//          flattens pixel-major (j = p * 50 + c) and stores [in][out] (column-major 500 x 7200)
+//   ip2    [2][500] -> [500][2]
+int gpd_hip_lenet_from_torch(int channels, double input_scale, const float *conv1_weight, const float *fc1_weight, const float *fc2_weight,
+                             float *conv1_w_out, float *ip1_w_out, float *ip2_w_out) {
+  if (!conv1_weight || !fc1_weight || !fc2_weight || !conv1_w_out || !ip1_w_out || !ip2_w_out) {
+    set_error("gpd_hip_lenet_from_torch: null argument");
+    return GPD_ERR_INVALID;
+  }
+  if (channels != 1 && channels != 3 && channels != 12 && channels != 15) {
+    set_error("gpd_hip_lenet_from_torch: channels = %d (1, 3, 12 or 15)", channels);
+    return GPD_ERR_INVALID;
+  }
+  if (!std::isfinite(input_scale) || !(input_scale > 0.0)) {
+    set_error("gpd_hip_lenet_from_torch: input_scale must be finite and positive");
+    return GPD_ERR_INVALID;
+  }
+  const size_t n1 = (size_t)20 * channels * 25;
+  for (size_t i = 0; i < n1; i++) conv1_w_out[i] = (float)((double)conv1_weight[i] * input_scale);
+  for (int p = 0; p < 144; p++)
+    for (int c = 0; c < 50; c++) {
+      float *dst = ip1_w_out + (size_t)(p * 50 + c) * kFc1Out;
+      const float *src = fc1_weight + (size_t)c * 144 + p;
+      for (int u = 0; u < kFc1Out; u++) dst[u] = src[(size_t)u * kFc1In];
+    }
+  for (int j = 0; j < kFc1Out; j++)
+    for (int u = 0; u < 2; u++) ip2_w_out[j * 2 + u] = fc2_weight[(size_t)u * kFc1Out + j];
+  return GPD_OK;
+}
+
 // test hook: the intermediate tensors of lane 0's last LeNet pass (which = 0: pool1 as f32 [n][15680], 1: the three bf16
 // planes of the flattened pool2 [3][n][7200] (split path), 2: fc1 transposed f32 [500][n])
 int gpd_hip_lenet_debug(gpd_hip_ctx *ctx, int which, int n, void *out) {

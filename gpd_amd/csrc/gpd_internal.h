@@ -41,6 +41,7 @@ hipError_t lenet_fast_prepare(LeNetFast &f, int channels, const float *c1w, cons
 struct LeNetWeights {
   int channels = 0;
   int mode = GPD_LENET_SPLIT;  // gpd_hip_set_lenet_mode
+  bool conv_relu = false;      // gpd_hip_set_lenet_conv_relu: ReLU on pool1 and pool2 (the network of the reference's PyTorch scripts)
   LeNetFast fast;
   float *c1w = nullptr, *c1b = nullptr, *c2w = nullptr, *c2b = nullptr;
   float *c1wp = nullptr;  // conv1 weights padded to [20][C][28] (25 taps + 3 zeros): 16-byte rows for the LDS table

@@ -76,10 +76,14 @@ __host__ __device__ inline void c1_pixel_of(int pc, int &py, int &px) {
 // images are numbered through and cut into chunks of 64; the chunk that holds an image's last pixels always exists
 __device__ inline int c1_chunks_of_image(int j) { return (C1_PIX * j + C1_PIX - 1) / 64 - (C1_PIX * j) / 64 + 1; }
 
-template <int C>
-__global__ __launch_bounds__(C1_THREADS) void conv1_mfma_kernel(const uint8_t *__restrict__ images, const float *__restrict__ wp,
-                                                               const float *__restrict__ bias, float *__restrict__ out, int n,
-                                                               unsigned long long *__restrict__ stats, int fault, int *__restrict__ queue) {
+// The kernel's body.  RELU (gpd_hip_set_lenet_conv_relu): a ReLU on every pooled value, after the bias and before the store — the
+// network of the reference's PyTorch scripts (pytorch/network.py: F.relu(conv) before the pool, which commutes with a max-pool).
+// Two kernels instantiate it, inlined: conv1_mfma_kernel<C> (RELU = false, the reference's Eigen / Caffe network) and
+// conv1_mfma_relu_kernel<C>.
+template <int C, bool RELU>
+__device__ __forceinline__ void conv1_mfma_body(const uint8_t *__restrict__ images, const float *__restrict__ wp,
+                                                const float *__restrict__ bias, float *__restrict__ out, int n,
+                                                unsigned long long *__restrict__ stats, int fault, int *__restrict__ queue) {
   __shared__ __attribute__((aligned(16))) uint8_t s_img[2][C * kPix];
   __shared__ __attribute__((aligned(16))) float s_wa[16 * C * 28];  // filters 0..15: [f][c][25 taps + 3 pad]
   __shared__ __attribute__((aligned(16))) float s_wb[4 * C * 28];   // filters 16..19
@@ -274,14 +278,19 @@ __global__ __launch_bounds__(C1_THREADS) void conv1_mfma_kernel(const uint8_t *_
 #pragma unroll
           for (int r = 0; r < 4; r++) {
             const int reg = 4 * b + r, f = 4 * (lane >> 4) + r;
-            o[f * P1_PLANE + po] = fmaxf(fmaxf(acc16[0][reg], acc16[1][reg]), fmaxf(acc16[2][reg], acc16[3][reg])) + bias[f];
+            float v = fmaxf(fmaxf(acc16[0][reg], acc16[1][reg]), fmaxf(acc16[2][reg], acc16[3][reg])) + bias[f];
+            if constexpr (RELU) v = fmaxf(v, 0.f);
+            o[f * P1_PLANE + po] = v;
           }
         }
       }
       if (ooff >= 0) {
 #pragma unroll
-        for (int f = 0; f < 4; f++)
-          o[(16 + f) * P1_PLANE + ooff] = fmaxf(fmaxf(acc4[0][f], acc4[1][f]), fmaxf(acc4[2][f], acc4[3][f])) + bias[16 + f];
+        for (int f = 0; f < 4; f++) {
+          float v = fmaxf(fmaxf(acc4[0][f], acc4[1][f]), fmaxf(acc4[2][f], acc4[3][f])) + bias[16 + f];
+          if constexpr (RELU) v = fmaxf(v, 0.f);
+          o[(16 + f) * P1_PLANE + ooff] = v;
+        }
       }
     }
     // release the chunk's image(s); the wave that releases an image last refills its slot with the image two ahead
@@ -351,6 +360,23 @@ __global__ __launch_bounds__(C1_THREADS) void conv1_mfma_kernel(const uint8_t *_
   }
 }
 
+template <int C>
+__global__ __launch_bounds__(C1_THREADS) void conv1_mfma_kernel(const uint8_t *__restrict__ images,
+                                                                const float *__restrict__ wp, const float *__restrict__ bias,
+                                                                float *__restrict__ out, int n,
+                                                                unsigned long long *__restrict__ stats, int fault,
+                                                                int *__restrict__ queue) {
+  conv1_mfma_body<C, false>(images, wp, bias, out, n, stats, fault, queue);
+}
+template <int C>
+__global__ __launch_bounds__(C1_THREADS) void conv1_mfma_relu_kernel(const uint8_t *__restrict__ images,
+                                                                     const float *__restrict__ wp,
+                                                                     const float *__restrict__ bias, float *__restrict__ out,
+                                                                     int n, unsigned long long *__restrict__ stats, int fault,
+                                                                     int *__restrict__ queue) {
+  conv1_mfma_body<C, true>(images, wp, bias, out, n, stats, fault, queue);
+}
+
 // ---------------------------------------------------------------------------
 // conv2 is an implicit GEMM D[f][pix] = sum_k W[f][k] X[k][pix] on v_mfma_f32_16x16x4_f32,
 // k = c*25 + kh*5 + kw ascending — the MFMA accumulates k..k+3 in order, so each output is
@@ -378,9 +404,11 @@ constexpr int C2_MFMA_WAVES = 12, C2_THREADS = 64 * C2_MFMA_WAVES;
 // tap offset inside a 4-channel period: k in [0, 100) -> c * 784 + kh * 28 + kw
 __host__ __device__ constexpr int c2_tap_off(int k) { return (k / 25) * 784 + ((k % 25) / 5) * 28 + (k % 5); }
 
-__global__ __launch_bounds__(C2_THREADS) void conv2_mfma_kernel(const float *__restrict__ pool1, const float *__restrict__ wt,
-                                                                const float *__restrict__ w, const float *__restrict__ bias,
-                                                                float *__restrict__ flat, int n, int *__restrict__ queue) {
+// The kernel's body; RELU as in conv1_mfma_body.
+template <bool RELU>
+__device__ __forceinline__ void conv2_mfma_body(const float *__restrict__ pool1, const float *__restrict__ wt,
+                                                const float *__restrict__ w, const float *__restrict__ bias,
+                                                float *__restrict__ flat, int n, int *__restrict__ queue) {
   // one array: reads one step past the image / the weights (operand prefetch of the last step)
   // land in the next region, never outside the allocation
   __shared__ __attribute__((aligned(16))) float s_all[20 * 784 + 500 * 48 + 4 * 48];
@@ -525,7 +553,9 @@ __global__ __launch_bounds__(C2_THREADS) void conv2_mfma_kernel(const float *__r
         const int col = lane & 31;
         if (lane < 32 && col < 24 && !(col & 1)) {
           float *o = flat + (size_t)img * kFc1In + (rp * 12 + (col >> 1)) * 50 + 48;
-          *reinterpret_cast<float2 *>(o) = make_float2(m48 + bias[48], m49 + bias[49]);
+          float2 v = make_float2(m48 + bias[48], m49 + bias[49]);
+          if constexpr (RELU) v = make_float2(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f));
+          *reinterpret_cast<float2 *>(o) = v;
         }
       }
 #pragma unroll
@@ -548,6 +578,7 @@ __global__ __launch_bounds__(C2_THREADS) void conv2_mfma_kernel(const float *__r
             const int f0 = 16 * ft + 4 * kq;
             float4 v = make_float4(acc[t][ft][0] + bias[f0], acc[t][ft][1] + bias[f0 + 1], acc[t][ft][2] + bias[f0 + 2],
                                    acc[t][ft][3] + bias[f0 + 3]);
+            if constexpr (RELU) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
             *reinterpret_cast<float2 *>(o + f0) = make_float2(v.x, v.y);
             *reinterpret_cast<float2 *>(o + f0 + 2) = make_float2(v.z, v.w);
           }
@@ -556,6 +587,18 @@ __global__ __launch_bounds__(C2_THREADS) void conv2_mfma_kernel(const float *__r
     }
     img = nxt;
   }
+}
+
+__global__ __launch_bounds__(C2_THREADS) void conv2_mfma_kernel(const float *__restrict__ pool1, const float *__restrict__ wt,
+                                                                const float *__restrict__ w, const float *__restrict__ bias,
+                                                                float *__restrict__ flat, int n, int *__restrict__ queue) {
+  conv2_mfma_body<false>(pool1, wt, w, bias, flat, n, queue);
+}
+__global__ __launch_bounds__(C2_THREADS) void conv2_mfma_relu_kernel(const float *__restrict__ pool1,
+                                                                     const float *__restrict__ wt, const float *__restrict__ w,
+                                                                     const float *__restrict__ bias, float *__restrict__ flat,
+                                                                     int n, int *__restrict__ queue) {
+  conv2_mfma_body<true>(pool1, wt, w, bias, flat, n, queue);
 }
 
 #undef C2_FETCH
@@ -853,16 +896,32 @@ hipError_t lenet_forward(const LeNetWeights &w, LeNetScratch &s, const uint8_t *
     // persistent conv1: one workgroup per CU, at least two images each
     const int fault = prof_env("GPD_C1_FAULT") != nullptr;  // test hook of the slot watchdog (tests/test_gpu_lenet_stress.py)
     const int c1_grid = m / 2 < 1 ? 1 : (m / 2 < num_cus ? m / 2 : num_cus);
-    switch (w.channels) {
-      case 15: conv1_mfma_kernel<15><<<c1_grid, C1_THREADS, 0, stream>>>(img, w.c1wp, w.c1b, s.pool1, m, s.c1_stats, fault, queue); break;
-      case 12: conv1_mfma_kernel<12><<<c1_grid, C1_THREADS, 0, stream>>>(img, w.c1wp, w.c1b, s.pool1, m, s.c1_stats, fault, queue); break;
-      case 3: conv1_mfma_kernel<3><<<c1_grid, C1_THREADS, 0, stream>>>(img, w.c1wp, w.c1b, s.pool1, m, s.c1_stats, fault, queue); break;
-      case 1: conv1_mfma_kernel<1><<<c1_grid, C1_THREADS, 0, stream>>>(img, w.c1wp, w.c1b, s.pool1, m, s.c1_stats, fault, queue); break;
-      default: return hipErrorInvalidValue;
+    // conv_relu (gpd_hip_set_lenet_conv_relu) picks the instantiations whose epilogues clamp the pooled values at zero
+#define C1_LAUNCH(KERNEL, CH) KERNEL<CH><<<c1_grid, C1_THREADS, 0, stream>>>(img, w.c1wp, w.c1b, s.pool1, m, s.c1_stats, fault, queue)
+    if (w.conv_relu) {
+      switch (w.channels) {
+        case 15: C1_LAUNCH(conv1_mfma_relu_kernel, 15); break;
+        case 12: C1_LAUNCH(conv1_mfma_relu_kernel, 12); break;
+        case 3: C1_LAUNCH(conv1_mfma_relu_kernel, 3); break;
+        case 1: C1_LAUNCH(conv1_mfma_relu_kernel, 1); break;
+        default: return hipErrorInvalidValue;
+      }
+    } else {
+      switch (w.channels) {
+        case 15: C1_LAUNCH(conv1_mfma_kernel, 15); break;
+        case 12: C1_LAUNCH(conv1_mfma_kernel, 12); break;
+        case 3: C1_LAUNCH(conv1_mfma_kernel, 3); break;
+        case 1: C1_LAUNCH(conv1_mfma_kernel, 1); break;
+        default: return hipErrorInvalidValue;
+      }
     }
+#undef C1_LAUNCH
     if (kernel_events && off == 0) (void)hipEventRecord(kernel_events[0], stream);
     // conv2 draws its images from the second counter (zero since the memset above)
-    conv2_mfma_kernel<<<(m < num_cus ? m : num_cus), C2_THREADS, 0, stream>>>(s.pool1, w.c2wt, w.c2w, w.c2b, s.flat, m, queue + 1);
+    if (w.conv_relu)
+      conv2_mfma_relu_kernel<<<(m < num_cus ? m : num_cus), C2_THREADS, 0, stream>>>(s.pool1, w.c2wt, w.c2w, w.c2b, s.flat, m, queue + 1);
+    else
+      conv2_mfma_kernel<<<(m < num_cus ? m : num_cus), C2_THREADS, 0, stream>>>(s.pool1, w.c2wt, w.c2w, w.c2b, s.flat, m, queue + 1);
     if (kernel_events && off == 0) (void)hipEventRecord(kernel_events[1], stream);
     switch (fc1_pick_nt(m)) {
       case 1: fc1_launch<1>(w.f1w, w.f1b, s.flat, s.fc1t, m, s.capacity, stream); break;

@@ -100,11 +100,15 @@ __device__ inline double dpp_quad_max(double v) {
   return max_f64(v, o);
 }
 
-template <int C>
-__global__ __launch_bounds__(F1_THREADS) void conv1_i8_kernel(const uint8_t *__restrict__ images, const uint4 *__restrict__ atab,
-                                                              const double *__restrict__ corr, const int *__restrict__ shift,
-                                                              const float *__restrict__ bias, float *__restrict__ pool1, int n,
-                                                              int *__restrict__ queue) {
+// The kernel's body.  RELU (gpd_hip_set_lenet_conv_relu): a ReLU on every pooled value, after the bias and before the store — the
+// network of the reference's PyTorch scripts (pytorch/network.py: F.relu(conv) before the pool, which commutes with a max-pool).
+// Two kernels instantiate it, inlined: conv1_i8_kernel<C> (RELU = false, the reference's Eigen / Caffe network) and
+// conv1_i8_relu_kernel<C>.
+template <int C, bool RELU>
+__device__ __forceinline__ void conv1_i8_body(const uint8_t *__restrict__ images, const uint4 *__restrict__ atab,
+                                              const double *__restrict__ corr, const int *__restrict__ shift,
+                                              const float *__restrict__ bias, float *__restrict__ pool1, int n,
+                                              int *__restrict__ queue) {
   constexpr int RAW = C * kPix, NV = RAW / 16;
   static_assert(RAW % 16 == 0 && C <= 16, "image bytes");
   constexpr bool NARROW = C <= 4;                       // four-byte pixels, four shifted copies (see f1n_slot)
@@ -314,8 +318,12 @@ __global__ __launch_bounds__(F1_THREADS) void conv1_i8_kernel(const uint8_t *__r
         sm[mt] = dpp_quad_max(__builtin_fma((double)hi, 65536.0, (double)lo));
       }
       const double s_own = p == 0 ? sm[0] : p == 1 ? sm[1] : p == 2 ? sm[2] : sm[3];
-      const float v_own = ldexpf((float)(s_own + k_corr_own), -k_shift_own) + k_bias_own;
-      const float v_4 = ldexpf((float)(sm[4] + k_corr_4), -k_shift_4) + k_bias_4;
+      float v_own = ldexpf((float)(s_own + k_corr_own), -k_shift_own) + k_bias_own;
+      float v_4 = ldexpf((float)(sm[4] + k_corr_4), -k_shift_4) + k_bias_4;
+      if constexpr (RELU) {
+        v_own = fmaxf(v_own, 0.f);
+        v_4 = fmaxf(v_4, 0.f);
+      }
       const int trow = t / 7, tcol = t - 7 * trow;
       float *dst = pool1 + ((size_t)img * 784 + trow * 28 + 4 * tcol + w) * 20;
       dst[4 * p + q] = v_own;
@@ -327,6 +335,23 @@ __global__ __launch_bounds__(F1_THREADS) void conv1_i8_kernel(const uint8_t *__r
     transpose();
     img = nxt;
   }
+}
+
+template <int C>
+__global__ __launch_bounds__(F1_THREADS) void conv1_i8_kernel(const uint8_t *__restrict__ images,
+                                                              const uint4 *__restrict__ atab, const double *__restrict__ corr,
+                                                              const int *__restrict__ shift, const float *__restrict__ bias,
+                                                              float *__restrict__ pool1, int n, int *__restrict__ queue) {
+  conv1_i8_body<C, false>(images, atab, corr, shift, bias, pool1, n, queue);
+}
+template <int C>
+__global__ __launch_bounds__(F1_THREADS) void conv1_i8_relu_kernel(const uint8_t *__restrict__ images,
+                                                                   const uint4 *__restrict__ atab,
+                                                                   const double *__restrict__ corr,
+                                                                   const int *__restrict__ shift,
+                                                                   const float *__restrict__ bias, float *__restrict__ pool1,
+                                                                   int n, int *__restrict__ queue) {
+  conv1_i8_body<C, true>(images, atab, corr, shift, bias, pool1, n, queue);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -420,9 +445,11 @@ __host__ __device__ constexpr int f2_slot_tap(int e, int g) {
 }
 __host__ __device__ constexpr int f2_slot_cg(int e, int g) { return e < 25 ? e % 5 : e < 30 ? e - 25 : e == 30 ? g : 4; }
 
-__global__ __launch_bounds__(F2_THREADS) void conv2_bf16_kernel(const float *__restrict__ pool1, const uint4 *__restrict__ btab,
-                                                                const float *__restrict__ bias, unsigned short *__restrict__ xs,
-                                                                int n, int *__restrict__ queue) {
+// The kernel's body; RELU as in conv1_i8_body: both roles clamp their pooled values (+ bias) before store_x.
+template <bool RELU>
+__device__ __forceinline__ void conv2_bf16_body(const float *__restrict__ pool1, const uint4 *__restrict__ btab,
+                                                const float *__restrict__ bias, unsigned short *__restrict__ xs, int n,
+                                                int *__restrict__ queue) {
   __shared__ __attribute__((aligned(16))) uint8_t s_img[F2_IMG];
   __shared__ __attribute__((aligned(16))) uint8_t s_raw[F2_RAW];
   __shared__ int s_nxt;
@@ -563,6 +590,7 @@ __global__ __launch_bounds__(F2_THREADS) void conv2_bf16_kernel(const float *__r
       }
       float pv = fmaxf(conv_row[0], conv_row[1]);
       pv = fmaxf(pv, shl(pv, std::integral_constant<int, 1>())) + k_bias;
+      if constexpr (RELU) pv = fmaxf(pv, 0.f);
       if (q < 2 && (j & 1) == 0 && j < 12) store_x(img, (tt >> 1) * 12 + 6 * (tt & 1) + (j >> 1), f_own, pv);
     });
     return;
@@ -634,8 +662,24 @@ __global__ __launch_bounds__(F2_THREADS) void conv2_bf16_kernel(const float *__r
     }
     // pool over the lane's four registers, bias, split for ip1, store
     const f32x4 t = acc[0] + acc[1];
-    store_x(img, rp * 12 + 4 * xt + q, f_own, fmaxf(fmaxf(t[0], t[1]), fmaxf(t[2], t[3])) + k_bias);
+    float pv = fmaxf(fmaxf(t[0], t[1]), fmaxf(t[2], t[3])) + k_bias;
+    if constexpr (RELU) pv = fmaxf(pv, 0.f);
+    store_x(img, rp * 12 + 4 * xt + q, f_own, pv);
   });
+}
+
+__global__ __launch_bounds__(F2_THREADS) void conv2_bf16_kernel(const float *__restrict__ pool1,
+                                                                const uint4 *__restrict__ btab, const float *__restrict__ bias,
+                                                                unsigned short *__restrict__ xs, int n,
+                                                                int *__restrict__ queue) {
+  conv2_bf16_body<false>(pool1, btab, bias, xs, n, queue);
+}
+__global__ __launch_bounds__(F2_THREADS) void conv2_bf16_relu_kernel(const float *__restrict__ pool1,
+                                                                     const uint4 *__restrict__ btab,
+                                                                     const float *__restrict__ bias,
+                                                                     unsigned short *__restrict__ xs, int n,
+                                                                     int *__restrict__ queue) {
+  conv2_bf16_body<true>(pool1, btab, bias, xs, n, queue);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -979,15 +1023,31 @@ hipError_t lenet_forward_fast(const LeNetWeights &w, LeNetScratch &s, const uint
                               hipEvent_t *kernel_events, int *queue) {
   const int num_cus = s.num_cus;
   const int grid = m < num_cus ? m : num_cus;
-  switch (w.channels) {
-    case 15: conv1_i8_kernel<15><<<grid, F1_THREADS, 0, stream>>>(img, w.fast.c1a, w.fast.c1corr, w.fast.c1shift, w.c1b, s.pool1, m, queue); break;
-    case 12: conv1_i8_kernel<12><<<grid, F1_THREADS, 0, stream>>>(img, w.fast.c1a, w.fast.c1corr, w.fast.c1shift, w.c1b, s.pool1, m, queue); break;
-    case 3: conv1_i8_kernel<3><<<grid, F1_THREADS, 0, stream>>>(img, w.fast.c1a, w.fast.c1corr, w.fast.c1shift, w.c1b, s.pool1, m, queue); break;
-    case 1: conv1_i8_kernel<1><<<grid, F1_THREADS, 0, stream>>>(img, w.fast.c1a, w.fast.c1corr, w.fast.c1shift, w.c1b, s.pool1, m, queue); break;
-    default: return hipErrorInvalidValue;
+  // conv_relu (gpd_hip_set_lenet_conv_relu) picks the instantiations whose epilogues clamp the pooled values at zero
+#define F1_LAUNCH(KERNEL, CH) KERNEL<CH><<<grid, F1_THREADS, 0, stream>>>(img, w.fast.c1a, w.fast.c1corr, w.fast.c1shift, w.c1b, s.pool1, m, queue)
+  if (w.conv_relu) {
+    switch (w.channels) {
+      case 15: F1_LAUNCH(conv1_i8_relu_kernel, 15); break;
+      case 12: F1_LAUNCH(conv1_i8_relu_kernel, 12); break;
+      case 3: F1_LAUNCH(conv1_i8_relu_kernel, 3); break;
+      case 1: F1_LAUNCH(conv1_i8_relu_kernel, 1); break;
+      default: return hipErrorInvalidValue;
+    }
+  } else {
+    switch (w.channels) {
+      case 15: F1_LAUNCH(conv1_i8_kernel, 15); break;
+      case 12: F1_LAUNCH(conv1_i8_kernel, 12); break;
+      case 3: F1_LAUNCH(conv1_i8_kernel, 3); break;
+      case 1: F1_LAUNCH(conv1_i8_kernel, 1); break;
+      default: return hipErrorInvalidValue;
+    }
   }
+#undef F1_LAUNCH
   if (kernel_events) (void)hipEventRecord(kernel_events[0], stream);
-  conv2_bf16_kernel<<<grid, F2_THREADS, 0, stream>>>(s.pool1, w.fast.c2b, w.c2b, s.xs, m, queue + 1);
+  if (w.conv_relu)
+    conv2_bf16_relu_kernel<<<grid, F2_THREADS, 0, stream>>>(s.pool1, w.fast.c2b, w.c2b, s.xs, m, queue + 1);
+  else
+    conv2_bf16_kernel<<<grid, F2_THREADS, 0, stream>>>(s.pool1, w.fast.c2b, w.c2b, s.xs, m, queue + 1);
   if (kernel_events) (void)hipEventRecord(kernel_events[1], stream);
   switch (fc1f_pick_nt(m)) {
     case 1: fc1f_launch<1>(w, s, m, stream); break;

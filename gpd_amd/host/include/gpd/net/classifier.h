@@ -56,12 +56,19 @@ class HipClassifier : public Classifier {
   // The parameters as read from the files (conv1 w, b, conv2 w, b, ip1 w, b, ip2 w, b): GraspDetector loads the
   // same arrays into the context of its fused search -> image -> score path.
   int channels() const { return channels_; }
+  // The parameter directory may hold a network.cfg (python -m gpd_amd.torch_export writes one): layout = torch — the files
+  // are conv1.weight.bin ... fc2.bias.bin of the reference's PyTorch network (pytorch/network.py::Net) in torch layout,
+  // converted on load by gpd_hip_lenet_from_torch with input_scale folded into conv1, so parameter(i) below is in the Eigen
+  // layouts either way; conv_relu = 1 — a ReLU after conv1 and conv2 (gpd_hip_set_lenet_conv_relu), which GraspDetector sets
+  // on the fused path's context as well.  Without the file: the reference's Eigen network, as ever.
+  bool convRelu() const { return conv_relu_; }
   const std::vector<float> &parameter(int i) const { return params_[i]; }
 
  private:
   gpd_hip_ctx *ctx_ = nullptr;
   bool loaded_ = false;
   int channels_ = 0;
+  bool conv_relu_ = false;
   int batch_size_ = 1;
   std::vector<float> params_[8];
 };

@@ -541,12 +541,52 @@ HipClassifier::HipClassifier(const std::string &, const std::string &weights_fil
   const std::string &dir = weights_file;
   static const char *files[8] = {"conv1_weights.bin", "conv1_biases.bin", "conv2_weights.bin", "conv2_biases.bin",
                                  "ip1_weights.bin",   "ip1_biases.bin",   "ip2_weights.bin",   "ip2_biases.bin"};
-  for (int i = 0; i < 8; i++) params_[i] = readBinaryFileIntoVector(dir + files[i]);
+  // A parameter directory describes its own network: network.cfg (written by `python -m gpd_amd.torch_export`) with
+  // layout = torch means the eight tensors of the reference's PyTorch network (pytorch/network.py::Net) as torch stores them;
+  // they are converted here, once, into the Eigen layouts everything else works with.  No network.cfg: the reference's files.
+  static const char *torch_files[8] = {"conv1.weight.bin", "conv1.bias.bin", "conv2.weight.bin", "conv2.bias.bin",
+                                       "fc1.weight.bin",   "fc1.bias.bin",   "fc2.weight.bin",   "fc2.bias.bin"};
+  bool torch_layout = false;
+  double input_scale = 1.0;
+  if (std::ifstream((dir + "network.cfg").c_str()).good()) {
+    util::ConfigFile net_cfg(dir + "network.cfg");
+    net_cfg.ExtractKeys();
+    const std::string layout = net_cfg.getValueOfKeyAsString("layout", "eigen");
+    if (layout != "torch" && layout != "eigen") {
+      printf("ERROR: %snetwork.cfg: unknown layout '%s' (torch or eigen)\n", dir.c_str(), layout.c_str());
+      return;
+    }
+    torch_layout = layout == "torch";
+    const int relu = net_cfg.getValueOfKey<int>("conv_relu", torch_layout ? 1 : 0);
+    if (relu != 0 && relu != 1) {
+      printf("ERROR: %snetwork.cfg: conv_relu = %d (0 or 1)\n", dir.c_str(), relu);
+      return;
+    }
+    conv_relu_ = relu != 0;
+    input_scale = net_cfg.getValueOfKey<double>("input_scale", torch_layout ? 1.0 / 256 : 1.0);
+    if (!torch_layout && input_scale != 1.0) {
+      printf("ERROR: %snetwork.cfg: input_scale needs layout = torch\n", dir.c_str());
+      return;
+    }
+  }
+  for (int i = 0; i < 8; i++) params_[i] = readBinaryFileIntoVector(dir + (torch_layout ? torch_files[i] : files[i]));
   const auto &c1w = params_[0];
   if (c1w.size() % 500 != 0 || c1w.empty() || params_[1].size() != 20 || params_[2].size() != 25000 || params_[3].size() != 50 ||
       params_[4].size() != 3600000 || params_[5].size() != 500 || params_[6].size() != 1000 || params_[7].size() != 2) {
     printf("ERROR: LeNet parameter files in %s are missing or have unexpected sizes\n", dir.c_str());
     return;
+  }
+  if (torch_layout) {
+    // conv2 and the biases are the same in both layouts (gpd_hip.h, gpd_hip_lenet_from_torch)
+    std::vector<float> c1(params_[0].size()), f1(params_[4].size()), f2(params_[6].size());
+    if (gpd_hip_lenet_from_torch((int)(c1w.size() / 500), input_scale, params_[0].data(), params_[4].data(), params_[6].data(), c1.data(),
+                                 f1.data(), f2.data()) != GPD_OK) {
+      printf("ERROR: %snetwork.cfg: %s\n", dir.c_str(), gpd_hip_last_error());
+      return;
+    }
+    params_[0].swap(c1);
+    params_[4].swap(f1);
+    params_[6].swap(f2);
   }
   channels_ = (int)(c1w.size() / 500);
   gpd_params p;
@@ -559,6 +599,10 @@ HipClassifier::HipClassifier(const std::string &, const std::string &weights_fil
   }
   if (gpd_hip_set_lenet_weights(ctx_, channels_, params_[0].data(), params_[1].data(), params_[2].data(), params_[3].data(),
                                 params_[4].data(), params_[5].data(), params_[6].data(), params_[7].data()) != GPD_OK) {
+    printf("ERROR: %s\n", gpd_hip_last_error());
+    return;
+  }
+  if (conv_relu_ && gpd_hip_set_lenet_conv_relu(ctx_, 1) != GPD_OK) {
     printf("ERROR: %s\n", gpd_hip_last_error());
     return;
   }
@@ -733,7 +777,8 @@ GraspDetector::GraspDetector(const std::string &config_filename) {
       classifier_.reset();
     } else if (gpd_hip_set_lenet_weights(ctx_, hc->channels(), hc->parameter(0).data(), hc->parameter(1).data(),
                                          hc->parameter(2).data(), hc->parameter(3).data(), hc->parameter(4).data(),
-                                         hc->parameter(5).data(), hc->parameter(6).data(), hc->parameter(7).data()) == GPD_OK) {
+                                         hc->parameter(5).data(), hc->parameter(6).data(), hc->parameter(7).data()) == GPD_OK &&
+               gpd_hip_set_lenet_conv_relu(ctx_, hc->convRelu() ? 1 : 0) == GPD_OK) {  // (the directory's network.cfg, if any)
       has_classifier_ = true;
       fused_classifier_ = true;
       // hip_lenet_mode (not a reference key): 0 = split operands on the int8 / bf16 matrix pipes (default), 1 = the f32

@@ -1,0 +1,54 @@
+"""python -m gpd_amd.torch_export MODEL.pwf OUT_DIR [--input-scale S]
+
+A state dict saved by the reference's PyTorch training scripts (pytorch/train_net3.py: torch.save(model.state_dict(), ...) of
+pytorch/network.py::Net, possibly wrapped in nn.DataParallel) -> a parameter directory for the host layer (HipClassifier,
+detect_grasps): the eight tensors raw little-endian float32 IN TORCH LAYOUT — conv1.weight.bin ... fc2.bias.bin — and a
+network.cfg that says so (layout = torch), that the network has a ReLU after each convolution (conv_relu = 1) and what its
+inputs were multiplied with in training (input_scale, hdf5_dataset.py:17: 1/256).  Nothing is converted here: the re-layout
+into what gpd_hip_set_lenet_weights takes lives in one place, gpd_hip_lenet_from_torch of the C library, which the host layer
+calls when it finds network.cfg.  From Python: Context.set_lenet_torch(state).
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+from gpd_amd import api
+
+FILES = {k: k + ".bin" for k in api.TORCH_KEYS}
+
+
+def export(state, out_dir, input_scale=1.0 / 256):
+    """Write the eight tensors of `state` (see api.torch_state_arrays) and network.cfg into out_dir -> the file names."""
+    t = api.torch_state_arrays(state)
+    if not (np.isfinite(input_scale) and input_scale > 0):
+        raise ValueError("input_scale must be finite and positive")
+    if t["conv1.weight"].size % 500 != 0 or t["conv1.weight"].size == 0:
+        raise ValueError("conv1.weight is not [20][C][5][5]")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, name in FILES.items():
+        t[k].astype("<f4").tofile(os.path.join(out_dir, name))
+    with open(os.path.join(out_dir, "network.cfg"), "w") as f:
+        f.write("# written by gpd_amd.torch_export: pytorch/network.py::Net, tensors as torch stores them\n"
+                "layout = torch\nconv_relu = 1\ninput_scale = %s\n" % repr(float(input_scale)))
+    return sorted(FILES.values()) + ["network.cfg"]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m gpd_amd.torch_export", description="state dict of the reference's PyTorch network -> parameter directory for the host layer")
+    ap.add_argument("model", help="state dict saved by torch.save (model.pwf)")
+    ap.add_argument("out_dir")
+    ap.add_argument("--input-scale", type=float, default=1.0 / 256, help="what the training data was multiplied with (default 1/256)")
+    a = ap.parse_args(argv)
+    import torch
+    state = torch.load(a.model, map_location="cpu")
+    if hasattr(state, "state_dict"):  # a whole module was saved
+        state = state.state_dict()
+    names = export(state, a.out_dir, a.input_scale)
+    print("wrote %s: %s" % (a.out_dir, " ".join(names)))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -132,6 +132,28 @@ int gpd_hip_set_lenet_weights(gpd_hip_ctx *ctx, int channels,
 /* GPD_LENET_SPLIT or GPD_LENET_F32_CHAIN (above) for every later scoring call of the context. */
 int gpd_hip_set_lenet_mode(gpd_hip_ctx *ctx, int mode);
 
+/* The network of the reference's PyTorch scripts (pytorch/network.py::Net, trained by pytorch/train_net3.py) applies a
+ * ReLU after conv1 and after conv2; EigenClassifier, the Caffe prototxts and the shipped OpenVINO IR have none.  on = 1:
+ * every later scoring call of the context (gpd_hip_score, gpd_hip_detect*, gpd_hip_detect_batch[_multi], gpd_hip_replay;
+ * gpd_hip_detect_sharded reads each context's own flag) clamps the pooled values of both convolutions at zero — ReLU and a
+ * 2x2 max-pool commute — in either scoring mode; on = 0 (default): the reference's Eigen network.  Anything else is
+ * GPD_ERR_INVALID.  Context state like the mode: legal before or after the weights, and gpd_hip_set_lenet_weights does not
+ * reset it.  gpd_hip_lenet_debug(which = 0 / 1) returns the tensors after the ReLU when it is on. */
+int gpd_hip_set_lenet_conv_relu(gpd_hip_ctx *ctx, int on);
+
+/* Net's tensors (a state_dict of pytorch/train_net3.py) -> the layouts gpd_hip_set_lenet_weights takes.  Host only, no
+ * context.  conv1_weight [20][C][5][5], fc1_weight [500][7200] over the channel-major flatten (k = channel * 144 + pixel),
+ * fc2_weight [2][500], all row-major as torch stores them.
+ *   conv1_w_out [20][C*25]  = (float)((double)w * input_scale): the scale the training data was fed with (hdf5_dataset.py:17:
+ *                             1/256; exact for a power of two) folded into the weights, so that raw 0..255 images score the same
+ *   ip1_w_out   [7200][500] : ip1[(p * 50 + c) * 500 + u] = fc1[u][c * 144 + p]
+ *   ip2_w_out   [500][2]    : ip2[j * 2 + u] = fc2[u][j]
+ * conv2.weight ([50][20][5][5] = the reference's [50][500]) and the four biases pass through unchanged: hand them to
+ * gpd_hip_set_lenet_weights as they are.  Together with gpd_hip_set_lenet_conv_relu(ctx, 1) the context computes Net.
+ * GPD_ERR_INVALID: a null pointer, channels not in {1, 3, 12, 15}, a non-finite or non-positive input_scale. */
+int gpd_hip_lenet_from_torch(int channels, double input_scale, const float *conv1_weight, const float *fc1_weight,
+                             const float *fc2_weight, float *conv1_w_out, float *ip1_w_out, float *ip2_w_out);
+
 /* Replaces Classifier::classifyImages (net/classifier.h:70-71,
  * eigen_classifier.cpp:59-79).  images: n contiguous 60x60xC u8 HWC images
  * (cv::Mat CV_8UC(C) layout); scores[i] = logit1 - logit0.
@@ -471,7 +493,8 @@ int gpd_hip_replay_kernel_ms(gpd_hip_ctx *ctx, float ms[4]);
  * GPD_LENET_F32_CHAIN only — the split conv1 executes every tile and counts nothing (both numbers stay 0).
  * Measurement only: no reference counterpart. */
 int gpd_hip_conv1_stats(gpd_hip_ctx *ctx, unsigned long long pairs[2], int reset);
-/* test hook: intermediate tensors of the last gpd_hip_score pass (n images) — which = 0: pool1 f32 [n][15680] (layout of the
+/* test hook: intermediate tensors of the last gpd_hip_score pass (n images; after the conv ReLU when gpd_hip_set_lenet_conv_relu is
+ * on) — which = 0: pool1 f32 [n][15680] (layout of the
  * mode), 1: the three bf16 planes of the flattened pool2 [3][n][7200] (GPD_LENET_SPLIT; un-blocked on the host), 2: ip1 after ReLU, transposed f32 [500][n]
  * (GPD_LENET_SPLIT: the four K-quarter partial sums added on the host as ip2's kernel adds them) */
 int gpd_hip_lenet_debug(gpd_hip_ctx *ctx, int which, int n, void *out);
