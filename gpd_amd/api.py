@@ -55,6 +55,18 @@ class DetectJob(C.Structure):
     ]
 
 
+class LabelViewJob(C.Structure):
+    """Mirror of `gpd_label_view_job` (include/gpd_hip.h)."""
+    _fields_ = [
+        ("sample_indices", C.c_void_p), ("samples_per_round", C.c_int32), ("max_rounds", C.c_int32),
+        ("min_positives", C.c_int32), ("max_grasps_per_view", C.c_int32),
+        ("images", C.c_void_p), ("labels", C.c_void_p), ("hands", C.c_void_p), ("src_index", C.c_void_p), ("capacity", C.c_int32),
+        ("all_labels", C.c_void_p), ("all_labels_capacity", C.c_int32), ("round_counts", C.c_void_p),
+        ("rounds_run", C.c_int32), ("num_candidates", C.c_int32), ("num_positives", C.c_int32), ("num_out", C.c_int32),
+        ("num_positives_out", C.c_int32), ("gt_neighbourhoods", C.c_int32), ("d2h_bytes", C.c_int64), ("stage_ms", C.c_float * 4),
+    ]
+
+
 class GpdHipError(RuntimeError):
     pass
 
@@ -71,6 +83,31 @@ def sample_positions(n, num_draws, seed=0, with_repetition=False):
     if rc != 0:
         raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
     return out[: k.value].copy()
+
+
+def balance_view(labels, max_grasps_per_view):
+    """gpd_hip_balance_view: DataGenerator::balanceInstances over a view's accumulated labels (host only) -> the indices of the
+    kept candidates, i32: the first `end` positives, then the first `end` negatives, end = min(P, N, max_grasps_per_view // 2)."""
+    lab = np.ascontiguousarray(labels, np.uint8).reshape(-1)
+    out = np.zeros(max(2 * (max(int(max_grasps_per_view), 0) // 2), 1), np.int32)
+    n, npos = C.c_int(0), C.c_int(0)
+    rc = lib().gpd_hip_balance_view(_ptr(lab), len(lab), int(max_grasps_per_view), _ptr(out), C.byref(n), C.byref(npos))
+    if rc != 0:
+        raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
+    assert n.value == 2 * npos.value
+    return out[: n.value].copy()
+
+
+def shuffle_orders(seed, sizes):
+    """gpd_hip_shuffle_orders: the orders in which generate_data stores instance sets of the given sizes, one seeded stream
+    running through them in order (host only) -> list of i32 arrays; order[k] = the instance that ends up at position k."""
+    sizes = np.ascontiguousarray(sizes, np.int32).reshape(-1)
+    out = np.zeros(max(int(sizes.sum()), 1), np.int32)
+    rc = lib().gpd_hip_shuffle_orders(int(seed) & 0xFFFFFFFF, _ptr(sizes), len(sizes), _ptr(out))
+    if rc != 0:
+        raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
+    edges = np.concatenate([[0], np.cumsum(sizes)])
+    return [out[a:b].copy() for a, b in zip(edges[:-1], edges[1:])]
 
 
 TORCH_KEYS = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
@@ -131,7 +168,9 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_detect_select", "gpd_hip_detect_batch", "gpd_hip_detect_batch_multi", "gpd_hip_conv1_stats", "gpd_hip_last_fallbacks", "gpd_hip_preprocess_cloud", "gpd_hip_find_clusters", "gpd_hip_reserve", "gpd_hip_bind_host_thread",
            "gpd_hip_set_lenet_mode", "gpd_hip_lenet_debug", "gpd_hip_lenet_fast_tables", "gpd_hip_detect_sharded",
            "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals", "gpd_hip_sample_positions",
-           "gpd_hip_set_lenet_conv_relu", "gpd_hip_lenet_from_torch"]
+           "gpd_hip_set_lenet_conv_relu", "gpd_hip_lenet_from_torch",
+           "gpd_hip_upload_ground_truth", "gpd_hip_label_view", "gpd_hip_balance_view", "gpd_hip_sizeof_label_view_job",
+           "gpd_hip_shuffle_orders"]
 
 
 def build(prof=True):
@@ -192,6 +231,11 @@ def lib():
         L.gpd_hip_lenet_from_torch.argtypes = [C.c_int, C.c_double] + [C.c_void_p] * 6
         L.gpd_hip_lenet_debug.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.gpd_hip_replay_times.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+        L.gpd_hip_upload_ground_truth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.gpd_hip_label_view.argtypes = [C.c_void_p, C.POINTER(LabelViewJob)]
+        L.gpd_hip_balance_view.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.gpd_hip_shuffle_orders.argtypes = [C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+        assert L.gpd_hip_sizeof_label_view_job() == C.sizeof(LabelViewJob)
         _LIB = L
     return _LIB
 
@@ -275,6 +319,48 @@ class Context:
         vp = np.zeros((1, 3)) if view_points is None else np.ascontiguousarray(view_points, np.float64).reshape(-1, 3)
         self._check(lib().gpd_hip_upload_cloud(self._h, _ptr(xyz), _ptr(normals), P, _ptr(cam), cam.shape[0], _ptr(vp)))
         self._num_points = P
+
+    def upload_ground_truth(self, xyz, normals):
+        """gpd_hip_upload_ground_truth: the ground-truth cloud of label_view, a second slot that stays across upload_cloud and
+        every other call; an empty xyz clears it."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        assert xyz.shape == normals.shape
+        self._check(lib().gpd_hip_upload_ground_truth(self._h, _ptr(xyz) if len(xyz) else None, _ptr(normals) if len(xyz) else None,
+                                                      len(xyz)))
+
+    def label_view(self, sample_rounds, min_positives, max_grasps_per_view, want_all_labels=False, capacity=None):
+        """gpd_hip_label_view: one view of DataGenerator::generateData on the uploaded cloud against the uploaded ground truth.
+        sample_rounds: i32 [max_rounds, samples_per_round], the sample indices of every round that may run.
+        -> dict: images u8 [n,60,60,C], labels u8 [n], hands [n], src_index i32 [n] (positives first), rounds_run, num_candidates,
+        num_positives, num_out, num_positives_out, gt_neighbourhoods, d2h_bytes, stage_ms [4], round_counts i32 [max_rounds, 2],
+        and all_labels u8 [num_candidates] when asked for."""
+        sr = np.ascontiguousarray(sample_rounds, np.int32)
+        sr = sr.reshape(sr.shape[0] if sr.ndim > 1 else (1 if sr.size else 0), -1)
+        rounds, per = sr.shape
+        cap = 2 * (max(int(max_grasps_per_view), 0) // 2) if capacity is None else int(capacity)
+        Cn = self.params.image_num_channels
+        img = np.zeros((max(cap, 1), 60, 60, Cn), np.uint8)
+        lab = np.zeros(max(cap, 1), np.uint8)
+        hands = np.zeros(max(cap, 1), HAND_DTYPE)
+        src = np.zeros(max(cap, 1), np.int32)
+        counts = np.zeros((max(rounds, 1), 2), np.int32)
+        all_cap = rounds * per * self.n_slots if want_all_labels else 0
+        all_lab = np.zeros(max(all_cap, 1), np.uint8) if want_all_labels else None
+        j = LabelViewJob()
+        j.sample_indices, j.samples_per_round, j.max_rounds = _ptr(sr), per, rounds
+        j.min_positives, j.max_grasps_per_view = int(min_positives), int(max_grasps_per_view)
+        j.images, j.labels, j.hands, j.src_index, j.capacity = _ptr(img), _ptr(lab), _ptr(hands), _ptr(src), cap
+        j.all_labels, j.all_labels_capacity, j.round_counts = _ptr(all_lab), all_cap, _ptr(counts)
+        self._check(lib().gpd_hip_label_view(self._h, C.byref(j)))
+        n = j.num_out
+        out = dict(images=img[:n].copy(), labels=lab[:n].copy(), hands=hands[:n].copy(), src_index=src[:n].copy(),
+                   rounds_run=int(j.rounds_run), num_candidates=int(j.num_candidates), num_positives=int(j.num_positives),
+                   num_out=int(n), num_positives_out=int(j.num_positives_out), gt_neighbourhoods=int(j.gt_neighbourhoods),
+                   d2h_bytes=int(j.d2h_bytes), stage_ms=[float(x) for x in j.stage_ms], round_counts=counts[:rounds].copy())
+        if want_all_labels:
+            out["all_labels"] = all_lab[: j.num_candidates].copy()
+        return out
 
     def search(self, sample_indices):
         """generateGraspCandidateSets -> hands[n_sets, n_slots]."""

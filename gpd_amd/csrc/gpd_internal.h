@@ -266,6 +266,43 @@ int search_force_capacity(SearchState &s, int cap);
 int reevaluate_run(const gpd_params &p, const Cloud &c, SearchState &s, gpd_hand *hands, int n, int32_t *labels, hipStream_t stream);
 int search_download(const gpd_params &p, SearchState &s, gpd_hand *hands, int *num_sets, hipStream_t stream);
 void search_free(SearchState &s);
+// gpd_hip_label_view, one round: reevaluateHypotheses of n candidate records on the device (set-major, `lists` hand sets among
+// them) against the ground-truth cloud gt, one neighbourhood list per hand set (search.hip)
+int label_round(const gpd_params &p, const Cloud &gt, SearchState &gs, gpd_hand *d_recs, uint8_t *d_labels8, int n, int lists,
+                int32_t *d_cand_list, int32_t *d_meta, int32_t *h_meta, const int32_t *d_img_status, int *img_status, int *positives,
+                long long *d2h_bytes, hipStream_t stream);
+
+// ---- gpd_hip_label_view: the ground-truth slot, a view's accumulator, selection and gather (label.hip) --------------------
+struct LabelState {
+  Cloud gt;                        // the ground-truth cloud (gpd_hip_upload_ground_truth) ...
+  SearchState gt_search;           // ... and its neighbourhood lists, one per hand set with a candidate
+  size_t cap = 0;                  // candidates the accumulator holds
+  size_t image_bytes = 0;          // 3600 * C of the accumulator's images
+  uint8_t *d_images = nullptr;     // [cap][60][60][C] HWC
+  gpd_hand *d_hands = nullptr;     // [cap] candidate records, flags rewritten by the ground-truth check
+  uint8_t *d_labels = nullptr;     // [cap]
+  int32_t *d_cand_list = nullptr;  // [cap_round] candidate of the round in flight -> neighbourhood list of its hand set
+  size_t cap_round = 0;
+  int32_t *d_meta = nullptr;       // [4] largest ground-truth neighbourhood, positives of the round, lists built
+  int32_t *h_meta = nullptr;       // pinned
+  int32_t *d_sel = nullptr;        // [cap_sel] accumulator indices of the kept instances, positives first
+  size_t cap_sel = 0;
+  char *d_out = nullptr;           // the kept instances, contiguous: images | records | src_index | labels (16-byte aligned parts)
+  char *h_out = nullptr;           // pinned: the same, then the labels of every candidate when asked for
+  size_t d_out_bytes = 0, h_out_bytes = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // labels start / end, select + gather start / end
+  int grows = 0;                   // accumulator growths of the last call
+};
+constexpr size_t kLabelAccBudget = 16ull << 30;
+void label_free(LabelState &ls);
+int label_init(LabelState &ls);
+// room for `need` accumulated candidates of image_bytes each, the first `used` kept across a growth; GPD_ERR_CAPACITY beyond 16 GB
+int label_reserve(LabelState &ls, size_t need, size_t used, size_t image_bytes, size_t round_candidates, hipStream_t stream);
+// offsets of the four parts of the contiguous output for k kept instances; returns the total
+size_t label_out_layout(size_t k, size_t image_bytes, size_t off[4]);
+// balanceInstances over the n accumulated labels on the device (balance_model.h is the definition) and the gather of the `end`
+// kept positives and negatives into ls.d_out; nothing waits for the device
+int label_select_gather(LabelState &ls, int n, int end, hipStream_t stream);
 
 // GraspDetector::filterGraspsWorkspace (grasp_detector.cpp:334-398) [+ filterGraspsDirection, :423-456] for one valid
 // hand: aperture and the workspace box around the hand's outline [, then the approach direction].  The reference computes right_top from left_bottom

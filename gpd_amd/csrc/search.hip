@@ -2253,15 +2253,11 @@ __device__ bool closing_region_label(const ListCtx &L, int N, double top, double
 // frame, depth and finger placement: evaluateFingers(points, top, idx), evaluateHand(idx), closing
 // region, antipodal label.  labels[i] receives the label (1 = full antipodal grasp): a buffer of its
 // own, since centre_kernel may still be reading counts[8 s + 5] on the side stream.
-__global__ __launch_bounds__(256) void reeval_kernel(HandParams P) {
-  __shared__ unsigned s_u[4];
-  __shared__ double s_d[4];
-  __shared__ long long s_l[4];
+// the check of hand H against neighbourhood list s of P (the whole workgroup calls it) -> 0 none, 1 half, 2 full antipodal
+__device__ inline int reeval_hand(const HandParams &P, int s, const gpd_hand *H, unsigned *s_u, double *s_d, long long *s_l) {
   const HandConsts &K = c_hand;
-  const int s = blockIdx.x;
   const int tid = threadIdx.x;
   const int N = P.counts[8 * s + 0];
-  gpd_hand *H = P.hands + s;
   const int idx = H->finger_placement_index;
   int label = 0;
   if (N > 0 && idx >= 0 && idx < K.nfp) {
@@ -2305,10 +2301,87 @@ __global__ __launch_bounds__(256) void reeval_kernel(HandParams P) {
       closing_region_label(L, N, top, bottom, sl + K.fw, sr, K, width, label, s_u, s_d, s_l);
     }
   }
-  if (tid == 0) {
+  return label;
+}
+
+__global__ __launch_bounds__(256) void reeval_kernel(HandParams P) {
+  __shared__ unsigned s_u[4];
+  __shared__ double s_d[4];
+  __shared__ long long s_l[4];
+  const int s = blockIdx.x;
+  gpd_hand *H = P.hands + s;
+  const int label = reeval_hand(P, s, H, s_u, s_d, s_l);
+  if (threadIdx.x == 0) {
     H->half_antipodal = label == 1;
     H->full_antipodal = label == 2;
     P.labels[s] = label == 2 ? 1 : 0;
+  }
+}
+
+// gpd_hip_label_view: the same check for the candidates of a round, whose records are on the device already and whose
+// neighbourhood lists exist once per hand SET (the hands of a set share their sample): candidate c reads list cand_list[c].
+// labels8[c] = 1 for a full antipodal grasp, one byte per accumulated candidate.
+__global__ __launch_bounds__(256) void label_kernel(HandParams P, const int32_t *__restrict__ cand_list, uint8_t *__restrict__ labels8) {
+  __shared__ unsigned s_u[4];
+  __shared__ double s_d[4];
+  __shared__ long long s_l[4];
+  const int c = blockIdx.x;
+  gpd_hand *H = P.hands + c;
+  const int label = reeval_hand(P, cand_list[c], H, s_u, s_d, s_l);
+  if (threadIdx.x == 0) {
+    H->half_antipodal = label == 1;
+    H->full_antipodal = label == 2;
+    labels8[c] = label == 2 ? 1 : 0;
+  }
+}
+
+// The hand sets of a round's candidate records (set-major: the candidates of a set are neighbours): candidate c -> the ordinal of
+// its set among the sets that have a candidate (cand_list), that set's sample -> sample_xyz[ordinal] (the query of its ground-truth
+// neighbourhood), the number of such sets -> meta[2].  One workgroup: a round has a few thousand candidates.
+__global__ __launch_bounds__(1024) void label_sets_kernel(const gpd_hand *__restrict__ recs, int n, int32_t *__restrict__ cand_list,
+                                                          double *__restrict__ sample_xyz, int32_t *__restrict__ meta) {
+  __shared__ int s_w[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int running = 0;
+  for (int base = 0; base < n; base += 1024) {
+    const int i = base + tid;
+    const bool head = i < n && (i == 0 || recs[i].set_index != recs[i - 1].set_index);
+    const unsigned long long mask = __ballot(head);
+    if (lane == 0) s_w[wave] = __popcll(mask);
+    __syncthreads();
+    int before = running, total = 0;
+    for (int w = 0; w < 16; w++) {
+      before += w < wave ? s_w[w] : 0;
+      total += s_w[w];
+    }
+    const int ord = before + __popcll(mask & ((1ull << lane) - 1ull)) + (head ? 1 : 0) - 1;  // the set of candidate 0 is a head
+    if (i < n) cand_list[i] = ord;
+    if (head)
+      for (int r = 0; r < 3; r++) sample_xyz[3 * (size_t)ord + r] = recs[i].sample[r];
+    running += total;
+    __syncthreads();
+  }
+  if (tid == 0) meta[2] = running;
+}
+
+// what the host needs of a round: meta[0] = the largest ground-truth neighbourhood found (list capacity check), or -1: the lists
+// are not the `lists` the plan counted, or -2 - f: the round's image kernels left the capacity flags f; meta[1] = positives among
+// the round's n labels
+__global__ __launch_bounds__(256) void label_meta_kernel(const int32_t *__restrict__ counts, int lists, const uint8_t *__restrict__ labels8, int n,
+                                                         const int32_t *__restrict__ img_status, int32_t *__restrict__ meta) {
+  __shared__ int s_worst, s_pos;
+  if (threadIdx.x == 0) s_worst = s_pos = 0;
+  __syncthreads();
+  int worst = 0, pos = 0;
+  for (int i = threadIdx.x; i < lists; i += 256) worst = max(worst, counts[8 * i + 3]);
+  for (int i = threadIdx.x; i < n; i += 256) pos += labels8[i] != 0;
+  atomicMax(&s_worst, worst);
+  atomicAdd(&s_pos, pos);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int flags = img_status[0];
+    meta[0] = flags ? -2 - flags : meta[2] == lists ? s_worst : -1;
+    meta[1] = s_pos;
   }
 }
 
@@ -2949,6 +3022,80 @@ int reevaluate_run(const gpd_params &p, const Cloud &c, SearchState &s, gpd_hand
   HIP_RET(hipMemcpyAsync(hands, s.d_hands, (size_t)n * sizeof(gpd_hand), hipMemcpyDeviceToHost, stream));
   HIP_RET(hipMemcpyAsync(labels, s.d_labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   HIP_RET(hipStreamSynchronize(stream));
+  return GPD_OK;
+}
+
+// gpd_hip_label_view, one round: reevaluateHypotheses of the n candidate records d_recs (device, set-major) against the ground
+// truth `gt`, one neighbourhood list per hand set with a candidate (`lists` of them: the plan's live sets).  Rewrites the records'
+// flags, writes d_labels8 [n]; only 8 bytes (largest neighbourhood — or the capacity flags d_img_status[0] of the round's image kernels,
+// *img_status —, positives) come back per attempt — an attempt is repeated
+// with the next list capacity when a neighbourhood overflowed, as the search does.
+int label_round(const gpd_params &p, const Cloud &gt, SearchState &gs, gpd_hand *d_recs, uint8_t *d_labels8, int n, int lists,
+                int32_t *d_cand_list, int32_t *d_meta, int32_t *h_meta, const int32_t *d_img_status, int *img_status, int *positives,
+                long long *d2h_bytes, hipStream_t stream) {
+  *img_status = 0;
+  const int slots = p.num_hand_axes * p.num_orientations;
+  HostConsts hc;
+  host_consts(p, hc);
+  gs.num_samples = 0;
+  if (gs.seen_generation != gt.generation) {  // a new ground truth starts from the LDS-sorted list size again
+    gs.seen_generation = gt.generation;
+    if (gs.nn_cap > 16384) {
+      const int rcf = search_force_capacity(gs, 8192);
+      if (rcf) return rcf;
+    }
+  }
+  int cap = gs.nn_cap ? gs.nn_cap : 8192;
+  for (;;) {
+    int rc = search_reserve(gs, lists, cap, slots);
+    if (rc) return rc;
+    label_sets_kernel<<<1, 1024, 0, stream>>>(d_recs, n, d_cand_list, gs.d_sample_xyz, d_meta);
+    HIP_RET(hipGetLastError());
+    rc = run_neighbourhoods(p, gt, gs, hc, lists, cap, /*by_xyz=*/true, slots, /*want_height_list=*/false, stream, /*sync_counts=*/false);
+    if (rc) return rc;
+    {
+      std::unique_lock<std::mutex> consts_lock;  // held until the kernel that reads c_hand is enqueued
+      rc = upload_hand_consts(p, hc, slots, stream, consts_lock);
+      if (rc) return rc;
+      HandParams hp;
+      hp.counts = gs.d_counts;
+      hp.nn = gs.d_nn;
+      hp.frames = gs.d_frames;
+      hp.cap = cap;
+      hp.hands = d_recs;
+      hp.fvalid = nullptr;
+      hp.labels = nullptr;
+      hp.dbg = nullptr;
+      hp.hl = nullptr;
+      hp.radius = 0.0;
+      hp.num_samples = lists;
+      label_kernel<<<n, 256, 0, stream>>>(hp, d_cand_list, d_labels8);
+      HIP_RET(hipGetLastError());
+    }
+    label_meta_kernel<<<1, 256, 0, stream>>>(gs.d_counts, lists, d_labels8, n, d_img_status, d_meta);
+    HIP_RET(hipGetLastError());
+    rc = search_join(gs, stream);
+    if (rc) return rc;
+    HIP_RET(hipMemcpyAsync(h_meta, d_meta, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_RET(hipStreamSynchronize(stream));
+    *d2h_bytes += 2 * sizeof(int32_t);
+    const int worst = h_meta[0];
+    if (worst <= -2) {  // the caller words the image stage's capacity error
+      *img_status = -2 - worst;
+      return GPD_ERR_CAPACITY;
+    }
+    if (worst < 0) {
+      set_error("label_view: the candidate records do not form the %d hand sets the plan counted", lists);
+      return GPD_ERR_STATE;
+    }
+    if (worst <= cap) break;
+    cap = search_next_capacity(gs, worst);
+    if (!cap) {
+      set_error("label_view: a ground-truth neighbourhood holds %d points, more than the list capacity %d", worst, kNnCapMax);
+      return GPD_ERR_CAPACITY;
+    }
+  }
+  *positives = h_meta[1];
   return GPD_OK;
 }
 

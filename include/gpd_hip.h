@@ -256,6 +256,67 @@ int gpd_hip_search_samples(gpd_hip_ctx *ctx, const double *samples_xyz, int num_
  * gpd_hip_search can no longer be passed to gpd_hip_images afterwards. */
 int gpd_hip_reevaluate(gpd_hip_ctx *ctx, gpd_hand *hands, int num_hands, int32_t *labels);
 
+/* The ground-truth cloud of DataGenerator (data_generator.cpp:98-131: the object's mesh) as a SECOND cloud slot of the
+ * context, with its own grid and search scratch: xyz / normals as gpd_hip_upload_cloud takes them, no cameras
+ * (reevaluateHypotheses reads none).  It stays until it is replaced, or cleared with num_points == 0 (the pointers are not
+ * read then); gpd_hip_upload_cloud and the detect, batch, reevaluate, normals and preprocess entries do not touch it.
+ * Read by gpd_hip_label_view only. */
+int gpd_hip_upload_ground_truth(gpd_hip_ctx *ctx, const float *xyz, const float *normals, int num_points);
+
+/* BalanceInstances of DataGenerator (data_generator.cpp:406-430) + the order addInstances writes (:432-458) over the labels
+ * of a view's n accumulated candidates — host only, no context; the definition gpd_hip_label_view's device selection equals
+ * (gpd_amd/csrc/balance_model.h).  With P labels != 0 and N labels == 0: end = min(min(P, N), max_grasps_per_view / 2); out_index
+ * receives the first `end` positives, then the first `end` negatives, each in accumulated order; *num_out = 2 * end,
+ * *num_positives_out = end.  out_index holds 2 * floor(max_grasps_per_view / 2) entries (or n, if that is less).
+ * GPD_ERR_INVALID: n < 0, a NULL labels with n > 0, a NULL count pointer, or a NULL out_index when something is kept. */
+int gpd_hip_balance_view(const uint8_t *labels, int n, int max_grasps_per_view, int32_t *out_index, int *num_out, int *num_positives_out);
+
+/* The orders in which DataGenerator stores its shuffled instance sets (data_generator.cpp:219-220) — host only, no context.
+ * The reference's std::random_shuffle draws from rand(); here a Fisher-Yates from the back (entry i with entry next() % (i + 1))
+ * on the seeded xorshift64 stream described at gpd_detect_job::num_draws, ONE stream from `seed` that runs on through the
+ * num_sets sets of sizes[] in order (per object: the training set, then the test set).  out receives the orders back to back
+ * (sum of sizes entries): out[k] of a set = the instance that ends up at position k.  GPD_ERR_INVALID: a negative size or a
+ * NULL argument. */
+int gpd_hip_shuffle_orders(uint32_t seed, const int32_t *sizes, int num_sets, int32_t *out);
+
+/* One view of DataGenerator::generateData (data_generator.cpp:140-213): rounds of createGraspImages (grasp_detector.cpp:458-521)
+ * + evalGroundTruth (:522-526) on the cloud uploaded last, against the ground truth of gpd_hip_upload_ground_truth, until
+ * min_positives positives have accumulated; then balanceInstances.  Everything stays on the device between the upload of the
+ * sample indices and ONE copy of the kept instances: per round only the 56-byte plan summary and 8 bytes of counts come back.
+ *  - round r (while positives < min_positives and r < max_rounds; min_positives <= 0: no round) runs what gpd_hip_detect builds
+ *    before the LeNet on sample_indices[r * samples_per_round ...] — index search, filterGraspsWorkspace, the direction filter
+ *    when set, one image per valid hand, set-major / slot-minor; each round's shadow stream starts at 0; no weights are needed.
+ *    The reference's loop has no bound on r and never ends on a view without positives: max_rounds is ours.
+ *  - its candidates are checked by reevaluateHypotheses against the ground truth: one neighbourhood list per hand SET with a
+ *    candidate (the hands of a set share their sample), labels and flags byte for byte those of gpd_hip_reevaluate.
+ *  - images, records and labels are appended to the view's accumulator; EVERY round's indices are shifted by the accumulated
+ *    count (the reference shifts only when earlier rounds found positives, :171-180, and then moves the wrong images).
+ *  - the kept instances are those of gpd_hip_balance_view over the accumulated labels, positives first.
+ * hands[i] is the record gpd_hip_detect_select(num_selected = 0) returns for its round, with score = 0 and the flags of the
+ * ground-truth check; labels[i] == hands[i].full_antipodal; src_index[i]: its index in the accumulated candidate list.
+ * GPD_ERR_INVALID (before any work): a capacity below 2 * floor(max_grasps_per_view / 2), a sample index out of range.
+ * GPD_ERR_STATE: no view cloud or no ground truth.  GPD_ERR_CAPACITY: an accumulator beyond 16 GB. */
+typedef struct gpd_label_view_job {          /* zero it first */
+  const int32_t *sample_indices;             /* in: max_rounds x samples_per_round, round-major, into the cloud uploaded last */
+  int32_t samples_per_round, max_rounds;
+  int32_t min_positives;                     /* cfg min_grasps_per_view */
+  int32_t max_grasps_per_view;
+  uint8_t *images;                           /* out: capacity x 60*60*C, HWC */
+  uint8_t *labels;                           /* out: capacity */
+  gpd_hand *hands;                           /* out: capacity records (may be NULL) */
+  int32_t *src_index;                        /* out: capacity, index into the view's accumulated candidate list (may be NULL) */
+  int32_t capacity;                          /* >= 2 * floor(max_grasps_per_view / 2), else GPD_ERR_INVALID before any work */
+  uint8_t *all_labels; int32_t all_labels_capacity;  /* out, may be NULL: the label of EVERY accumulated candidate (1 byte each);
+                                                        the first all_labels_capacity of them when there are more */
+  int32_t *round_counts;                     /* out, may be NULL: max_rounds x {candidates, positives} */
+  int32_t rounds_run, num_candidates, num_positives, num_out, num_positives_out;  /* out */
+  int32_t gt_neighbourhoods;                 /* out: ground-truth neighbourhood lists built */
+  int64_t d2h_bytes;                         /* out: bytes this call copied device -> host */
+  float stage_ms[4];                         /* out: search, images, labels, select + gather (HIP events) */
+} gpd_label_view_job;
+int gpd_hip_label_view(gpd_hip_ctx *ctx, gpd_label_view_job *job);
+int gpd_hip_sizeof_label_view_job(void);
+
 /* Replaces ImageGenerator::createImages (image_generator.cpp:17-99) for hand
  * sets produced by the last gpd_hip_search / gpd_hip_detect on this context (optionally after
  * the host filters, grasp_detector.cpp:334-398 / :422-453, which clear `valid`: only the `valid`
