@@ -67,6 +67,12 @@ class LabelViewJob(C.Structure):
     ]
 
 
+class TrainParams(C.Structure):
+    """Mirror of `gpd_train_params` (include/gpd_hip.h)."""
+    _fields_ = [("channels", C.c_int32), ("max_batch", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("weight_decay", C.c_double), ("input_scale", C.c_double)]
+
+
 class GpdHipError(RuntimeError):
     pass
 
@@ -170,7 +176,11 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals", "gpd_hip_sample_positions",
            "gpd_hip_set_lenet_conv_relu", "gpd_hip_lenet_from_torch",
            "gpd_hip_upload_ground_truth", "gpd_hip_label_view", "gpd_hip_balance_view", "gpd_hip_sizeof_label_view_job",
-           "gpd_hip_shuffle_orders"]
+           "gpd_hip_shuffle_orders",
+           "gpd_hip_train_default_params", "gpd_hip_train_create", "gpd_hip_train_destroy", "gpd_hip_train_init_state",
+           "gpd_hip_train_set_state", "gpd_hip_train_get_state", "gpd_hip_train_set_data", "gpd_hip_train_steps",
+           "gpd_hip_train_gradients", "gpd_hip_train_apply", "gpd_hip_train_eval", "gpd_hip_train_step_timed",
+           "gpd_hip_train_kernel_name"]
 
 
 def build(prof=True):
@@ -235,6 +245,22 @@ def lib():
         L.gpd_hip_label_view.argtypes = [C.c_void_p, C.POINTER(LabelViewJob)]
         L.gpd_hip_balance_view.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.gpd_hip_shuffle_orders.argtypes = [C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+        L.gpd_hip_train_default_params.argtypes = [C.POINTER(TrainParams)]
+        L.gpd_hip_train_default_params.restype = None
+        L.gpd_hip_train_create.argtypes = [C.c_void_p, C.POINTER(TrainParams), C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_destroy.argtypes = [C.c_void_p]
+        L.gpd_hip_train_destroy.restype = None
+        L.gpd_hip_train_init_state.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_set_state.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_get_state.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_set_data.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.gpd_hip_train_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.gpd_hip_train_gradients.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_float)]
+        L.gpd_hip_train_apply.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_eval.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+        L.gpd_hip_train_step_timed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.gpd_hip_train_kernel_name.argtypes = [C.c_int]
+        L.gpd_hip_train_kernel_name.restype = C.c_char_p
         assert L.gpd_hip_sizeof_label_view_job() == C.sizeof(LabelViewJob)
         _LIB = L
     return _LIB
@@ -656,3 +682,135 @@ class Context:
                                                  _ptr(ddots), C.byref(nan), _ptr(ms)))
         self.last_refine_ms = tuple(float(v) for v in ms)
         return out, int(its.value), ddots[: its.value].copy(), int(nan.value)
+
+
+def torch_state_shapes(channels):
+    """The shapes of Net's eight tensors, in TORCH_KEYS order."""
+    return ((20, int(channels), 5, 5), (20,), (50, 20, 5, 5), (50,), (500, 7200), (500,), (2, 500), (2,))
+
+
+def _state_buffers(channels):
+    arrs = [np.zeros(s, np.float32) for s in torch_state_shapes(channels)]
+    return arrs, (C.c_void_p * 8)(*[a.ctypes.data for a in arrs])
+
+
+def _state_pointers(state, channels):
+    t = torch_state_arrays(state)
+    arrs = [t[k] for k in TORCH_KEYS]
+    for k, a, s in zip(TORCH_KEYS, arrs, torch_state_shapes(channels)):
+        if a.size != int(np.prod(s)):
+            raise ValueError("%s has %d elements, %d expected for %d channels" % (k, a.size, int(np.prod(s)), channels))
+    return arrs, (C.c_void_p * 8)(*[a.ctypes.data for a in arrs])
+
+
+def train_default_params(channels=15, max_batch=64):
+    p = TrainParams()
+    lib().gpd_hip_train_default_params(C.byref(p))
+    p.channels, p.max_batch = int(channels), int(max_batch)
+    return p
+
+
+def init_state(channels, seed=0):
+    """gpd_hip_train_init_state: a seeded initial state of Net, every tensor U(-1/sqrt(fan_in), 1/sqrt(fan_in)) (host only)
+    -> {key: f32 array in torch layout}."""
+    if int(channels) not in (1, 3, 12, 15):
+        raise GpdHipError("libgpd_hip error -1: init_state: %d channels (1, 3, 12 or 15)" % int(channels))
+    arrs, ptrs = _state_buffers(channels)
+    rc = lib().gpd_hip_train_init_state(int(channels), int(seed) & 0xFFFFFFFF, ptrs)
+    if rc != 0:
+        raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
+    return dict(zip(TORCH_KEYS, arrs))
+
+
+class Trainer:
+    """One gpd_hip_trainer on a Context's device and stream: Net (pytorch/network.py) under softmax cross-entropy and Adam, as
+    pytorch/train_net3.py trains it.  The state travels as a dict of numpy arrays in torch layout, both ways.  Close it before
+    its context."""
+
+    def __init__(self, ctx, params=None, **kw):
+        self.params = params if params is not None else train_default_params(ctx.params.image_num_channels)
+        for k, v in kw.items():
+            if k not in dict(TrainParams._fields_):
+                raise TypeError("gpd_train_params has no field %r" % k)
+            setattr(self.params, k, v)
+        self.channels = int(self.params.channels)
+        self._ctx = ctx  # keeps the context (the stream) alive
+        self._h = C.c_void_p()
+        self._check(lib().gpd_hip_train_create(ctx._h, C.byref(self.params), C.byref(self._h)))
+
+    _check = Context._check
+
+    def close(self):
+        if self._h:
+            lib().gpd_hip_train_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_state(self, state):
+        """The eight tensors; Adam's moments and the step count start again."""
+        arrs, ptrs = _state_pointers(state, self.channels)
+        self._check(lib().gpd_hip_train_set_state(self._h, ptrs))
+
+    def get_state(self):
+        arrs, ptrs = _state_buffers(self.channels)
+        self._check(lib().gpd_hip_train_get_state(self._h, ptrs))
+        return dict(zip(TORCH_KEYS, arrs))
+
+    def set_data(self, images, labels, which=0):
+        """The resident set `which` (0: training, 1: test): images u8 [n,60,60,C], labels u8 [n] of 0 / 1."""
+        images = np.ascontiguousarray(images, np.uint8)
+        labels = np.ascontiguousarray(labels, np.uint8).reshape(-1)
+        if images.shape != (len(labels), 60, 60, self.channels):
+            raise ValueError("images %s do not match %d labels of %d channels" % (images.shape, len(labels), self.channels))
+        self._check(lib().gpd_hip_train_set_data(self._h, int(which), _ptr(images), _ptr(labels), len(labels)))
+
+    def steps(self, indices, batch=None):
+        """Adam steps on the training set: indices i32 [num_steps, batch] (or flat with `batch` given) -> each step's loss f32."""
+        idx = np.ascontiguousarray(indices, np.int32)
+        if batch is None:
+            idx = idx.reshape(1, -1) if idx.ndim < 2 else idx
+            batch = idx.shape[1]
+        idx = idx.reshape(-1, int(batch))
+        losses = np.zeros(len(idx), np.float32)
+        self._check(lib().gpd_hip_train_steps(self._h, _ptr(idx), len(idx), int(batch), _ptr(losses)))
+        return losses
+
+    def gradients(self, indices):
+        """Forward and backward of one batch, no update -> ({key: gradient}, loss)."""
+        idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        arrs, ptrs = _state_buffers(self.channels)
+        loss = C.c_float(0)
+        self._check(lib().gpd_hip_train_gradients(self._h, _ptr(idx), len(idx), ptrs, C.byref(loss)))
+        return dict(zip(TORCH_KEYS, arrs)), float(loss.value)
+
+    def apply(self, grads):
+        """One Adam step from the host's gradients (a dict like gradients() returns)."""
+        arrs, ptrs = _state_pointers(grads, self.channels)
+        self._check(lib().gpd_hip_train_apply(self._h, ptrs))
+
+    def eval(self, indices=None, n=None, which=0):
+        """Forward only over set `which`: the images `indices`, or the first n (default: all given by n) -> (logits f32 [n,2], num_correct)."""
+        idx = None if indices is None else np.ascontiguousarray(indices, np.int32).reshape(-1)
+        n = len(idx) if idx is not None else int(n)
+        logits = np.zeros((max(n, 1), 2), np.float32)
+        k = C.c_int(0)
+        self._check(lib().gpd_hip_train_eval(self._h, int(which), _ptr(idx), n, _ptr(logits), C.byref(k)))
+        return logits[:n], int(k.value)
+
+    def step_timed(self, indices):
+        """Measurement only: one step with an event behind every kernel -> [(kernel name, ms)]."""
+        idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        ms = np.zeros(32, np.float32)
+        k = C.c_int(0)
+        self._check(lib().gpd_hip_train_step_timed(self._h, _ptr(idx), len(idx), _ptr(ms), len(ms), C.byref(k)))
+        return [(lib().gpd_hip_train_kernel_name(i).decode(), float(ms[i])) for i in range(k.value)]
+
+    def install(self, ctx=None, input_scale=None):
+        """get_state followed by Context.set_lenet_torch: the trained network becomes `ctx`'s (default: the trainer's own) scoring network."""
+        ctx = self._ctx if ctx is None else ctx
+        ctx.set_lenet_torch(self.get_state(), float(self.params.input_scale) if input_scale is None else input_scale)

@@ -160,6 +160,13 @@ struct gpd_hip_ctx {
   unsigned pipe_k = 0;
 };
 
+namespace gpd {
+void ctx_device_stream(gpd_hip_ctx *ctx, int *device, hipStream_t *stream) {
+  *device = ctx->device;
+  *stream = ctx->lane[0].stream;
+}
+}  // namespace gpd
+
 static int lane_init(Lane &L, hipStream_t shared = nullptr) {
   if (L.stream) return GPD_OK;
   if (shared) {

@@ -75,6 +75,8 @@ int lenet_check(LeNetScratch &s);
 void lenet_scratch_free(LeNetScratch &s);
 
 void set_error(const char *fmt, ...);
+// the device and the first lane's stream of a context (context.hip): what a trainer (train.hip) runs on
+void ctx_device_stream(gpd_hip_ctx *ctx, int *device, hipStream_t *stream);
 // every growth of a device / pinned buffer (hipFree + hipMalloc: a device stall) is counted per host thread; the batch
 // entry reports the count per cloud (gpd_detect_job::allocs) so that a pass that was supposed to run on pre-sized lanes
 // can be seen to have done so

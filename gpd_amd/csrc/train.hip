@@ -1,0 +1,867 @@
+// Training of pytorch/network.py::Net on the device: forward with pooling argmax, backward, Adam.
+//
+// Every GEMM-shaped pass is one instantiation of gemm32: a wave owns a 32 x 32 tile of the result and walks its K range with
+// v_mfma_f32_32x32x2_f32, whose result is a k-ascending f32 fmaf chain.  The operands are never materialised: an operand type
+// turns (row or column, k) into an address — a convolution patch, a transposed-convolution patch, the pooled gradient expanded
+// to the one window position its argmax names, or a plain strided matrix — and an epilogue type turns the accumulators into
+// what the pass leaves behind (pooled value + argmax byte, a raw partial, a masked gradient).  Long K ranges are split over
+// grid.y into partials that sum_partials adds in a fixed tree: no floating-point atomics anywhere, so a step is a pure
+// function of state, data and index list.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "gpd_internal.h"
+#include "sample_model.h"
+
+using namespace gpd;
+
+#define HIP_TRY(expr)                                                                   \
+  do {                                                                                  \
+    hipError_t e_ = (expr);                                                             \
+    if (e_ != hipSuccess) {                                                             \
+      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+      return GPD_ERR_HIP;                                                               \
+    }                                                                                   \
+  } while (0)
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kF1 = 20, kF2 = 50, kTaps = 25;
+constexpr int kP1 = 784, kP1W = 28;    // pool1: 28 x 28
+constexpr int kP2 = 144, kP2W = 12;    // pool2: 12 x 12
+constexpr int kO1 = 3136, kO1W = 56;   // conv1 output: 56 x 56
+constexpr int kO2 = 576, kO2W = 24;    // conv2 output: 24 x 24
+constexpr int kMasked = 4;             // argmax byte of a pooled value the ReLU clamped (value <= 0)
+constexpr int kFc1Splits = 16;         // fc1 forward: K = 7200 in 16 ranges of 450
+constexpr int kIdxCap = 1 << 20;       // indices of one enqueue
+constexpr int kMaxBatch = 1024;
+constexpr int kMaxKernels = 24;
+
+// ---- operands: ctx(i) once per lane, at(ctx, k) once per k step --------------------------------------------------------------
+
+// a [batch][channel][y][x] tensor with arbitrary strides; idx != null: image b is idx[b] of a resident set
+template <class T>
+struct Input {
+  const T *p;
+  const int *idx;
+  long long sb;
+  int sc, sy, sx;
+  float scale;
+  __device__ long long image(int b) const { return (long long)(idx ? idx[b] : b) * sb; }
+  __device__ float load(long long off) const { return (float)p[off] * scale; }
+};
+
+// element (i, k) = p[i * si + k * sk], i < n
+struct Plain {
+  const float *p;
+  long long si, sk;
+  int n;
+  struct Ctx {
+    const float *q;
+  };
+  __device__ Ctx ctx(int i) const { return {i < n ? p + (long long)i * si : nullptr}; }
+  __device__ float at(const Ctx &c, int k) const { return c.q ? c.q[(long long)k * sk] : 0.f; }
+};
+
+// forward A: i = (pooled position of the batch) * 4 + window position, k = (channel, ky, kx)
+template <class T>
+struct PatchByPos {
+  Input<T> in;
+  int pw, pp, m;  // pooled width, pooled positions per image, rows
+  struct Ctx {
+    long long off;
+  };
+  __device__ Ctx ctx(int i) const {
+    if (i >= m) return {-1};
+    const int pm = i >> 2, w = i & 3, b = pm / pp, q = pm % pp;
+    const int y = 2 * (q / pw) + (w >> 1), x = 2 * (q % pw) + (w & 1);
+    return {in.image(b) + (long long)y * in.sy + (long long)x * in.sx};
+  }
+  __device__ float at(const Ctx &c, int k) const {
+    if (c.off < 0) return 0.f;
+    const int ch = k / kTaps, t = k % kTaps;
+    return in.load(c.off + (long long)ch * in.sc + (t / 5) * in.sy + (t % 5) * in.sx);
+  }
+};
+
+// weight-gradient B: i = (channel, ky, kx), k = (image, y, x) over the convolution's output positions
+template <class T, int OW, int OP>  // output width, output positions per image: constants, so that the k decode is multiplies
+struct PatchByTap {
+  Input<T> in;
+  int n;  // taps
+  struct Ctx {
+    long long off;
+  };
+  __device__ Ctx ctx(int i) const {
+    if (i >= n) return {-1};
+    const int ch = i / kTaps, t = i % kTaps;
+    return {(long long)ch * in.sc + (t / 5) * in.sy + (t % 5) * in.sx};
+  }
+  __device__ float at(const Ctx &c, int k) const {
+    if (c.off < 0) return 0.f;
+    const int b = k / OP, q = k % OP;
+    return in.load(in.image(b) + c.off + (long long)(q / OW) * in.sy + (long long)(q % OW) * in.sx);
+  }
+};
+
+// the gradient in front of a 2 x 2 max-pool, never stored: the pooled gradient sits at the window position its argmax byte names
+struct PoolGrad {
+  const float *g;        // [batch][F][pp]
+  const uint8_t *arg;    // 0 .. 3: row-major window position of the first maximum; kMasked: clamped by the ReLU
+  int F, pw, pp;
+  __device__ float at(int b, int f, int y, int x) const {
+    const long long o = ((long long)b * F + f) * pp + (y >> 1) * pw + (x >> 1);
+    return arg[o] == ((y & 1) * 2 + (x & 1)) ? g[o] : 0.f;
+  }
+};
+
+// weight-gradient A: i = filter, k = (image, y, x)
+template <int OW, int OP>
+struct GradByFilter {
+  PoolGrad pg;
+  struct Ctx {
+    int f;
+  };
+  __device__ Ctx ctx(int i) const { return {i < pg.F ? i : -1}; }
+  __device__ float at(const Ctx &c, int k) const {
+    if (c.f < 0) return 0.f;
+    const int b = k / OP, q = k % OP;
+    return pg.at(b, c.f, q / OW, q % OW);
+  }
+};
+
+// input-gradient A (transposed convolution): i = (image, y, x) of the layer's input, k = (filter, ky, kx)
+struct GradByPos {
+  PoolGrad pg;
+  int iw, ip, ow, m;  // input width, input positions per image, output width, rows
+  struct Ctx {
+    int b, y, x;
+  };
+  __device__ Ctx ctx(int i) const {
+    if (i >= m) return {-1, 0, 0};
+    const int q = i % ip;
+    return {i / ip, q / iw, q % iw};
+  }
+  __device__ float at(const Ctx &c, int k) const {
+    if (c.b < 0) return 0.f;
+    const int f = k / kTaps, t = k % kTaps;
+    const int y = c.y - t / 5, x = c.x - t % 5;
+    if (y < 0 || y >= ow || x < 0 || x >= ow) return 0.f;
+    return pg.at(c.b, f, y, x);
+  }
+};
+
+// input-gradient B: weights [F][cin][25] read as (k = (filter, tap), i = input channel)
+struct WeightByChannel {
+  const float *w;
+  int cin;
+  struct Ctx {
+    int c;
+  };
+  __device__ Ctx ctx(int i) const { return {i < cin ? i : -1}; }
+  __device__ float at(const Ctx &c, int k) const {
+    if (c.c < 0) return 0.f;
+    return w[((long long)(k / kTaps) * cin + c.c) * kTaps + k % kTaps];
+  }
+};
+
+// ---- epilogues: lane (r = lane & 31, h = lane >> 5) holds column n0 + r, rows m0 + 8 (reg >> 2) + 4 h + (reg & 3) -----------
+
+// bias, 2 x 2 max-pool over the four consecutive rows of a register quad (first maximum in row-major window order), ReLU
+struct PoolStore {
+  const float *bias;
+  float *out;
+  uint8_t *arg;
+  int F, pp, mp;  // filters, pooled positions per image, pooled rows
+  __device__ void store(const f32x16 &acc, int m0, int n0, int lane, int) const {
+    const int f = n0 + (lane & 31);
+    if (f >= F) return;
+    const float bv = bias[f];
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+      const int pm = (m0 >> 2) + 2 * g + (lane >> 5);
+      if (pm >= mp) continue;
+      float best = acc[4 * g] + bv;
+      int w = 0;
+#pragma unroll
+      for (int j = 1; j < 4; j++) {
+        const float v = acc[4 * g + j] + bv;
+        if (v > best) best = v, w = j;
+      }
+      const long long o = ((long long)(pm / pp) * F + f) * pp + pm % pp;
+      out[o] = best > 0.f ? best : 0.f;
+      arg[o] = (uint8_t)(best > 0.f ? w : kMasked);
+    }
+  }
+};
+
+// out[(split * M + m) * N + n]
+struct RawStore {
+  float *out;
+  int M, N;
+  __device__ void store(const f32x16 &acc, int m0, int n0, int lane, int split) const {
+    const int n = n0 + (lane & 31);
+    if (n >= N) return;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      const int m = m0 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+      if (m < M) out[((long long)split * M + m) * N + n] = acc[r];
+    }
+  }
+};
+
+// the gradient of a pooled, clamped tensor [m / ip][N][ip]: zero where the ReLU clamped
+struct MaskStore {
+  float *out;
+  const uint8_t *arg;
+  int M, N, ip;
+  __device__ void store(const f32x16 &acc, int m0, int n0, int lane, int) const {
+    const int n = n0 + (lane & 31);
+    if (n >= N) return;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      const int m = m0 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+      if (m >= M) continue;
+      const long long o = ((long long)(m / ip) * N + n) * ip + m % ip;
+      out[o] = arg[o] != kMasked ? acc[r] : 0.f;
+    }
+  }
+};
+
+template <class A, class B, class E>
+__global__ void __launch_bounds__(256) gemm32(A a, B b, E e, int tiles_m, int tiles_n, int K, int k_chunk) {
+  const int lane = threadIdx.x & 63;
+  const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (tile >= tiles_m * tiles_n) return;
+  const int m0 = (tile / tiles_n) * 32, n0 = (tile % tiles_n) * 32;
+  const int k0 = blockIdx.y * k_chunk;
+  const int k1 = min(K, k0 + k_chunk);
+  const auto ca = a.ctx(m0 + (lane & 31));
+  const auto cb = b.ctx(n0 + (lane & 31));
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc[r] = 0.f;
+  for (int k = k0; k < k1; k += 2) {
+    const int kk = k + (lane >> 5);
+    const float av = kk < k1 ? a.at(ca, kk) : 0.f;
+    const float bv = kk < k1 ? b.at(cb, kk) : 0.f;
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+  }
+  e.store(acc, m0, n0, lane, blockIdx.y);
+}
+
+template <class A, class B, class E>
+void launch_gemm(hipStream_t st, const A &a, const B &b, const E &e, int M, int N, int K, int k_chunk) {
+  const int tm = (M + 31) / 32, tn = (N + 31) / 32;
+  hipLaunchKernelGGL((gemm32<A, B, E>), dim3((tm * tn + 3) / 4, (K + k_chunk - 1) / k_chunk), dim3(256), 0, st, a, b, e, tm, tn, K,
+                     k_chunk);
+}
+
+// ---- the small kernels -----------------------------------------------------------------------------------------------------
+
+// out[e] = sum over s of part[s][e], the partials in eight interleaved chains (s mod 8) joined pairwise; RELU: + bias[e % nb], clamped
+template <bool RELU>
+__global__ void sum_partials(const float *part, int S, int E, const float *bias, int nb, float *out) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  float c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < S; s++) c[s & 7] += part[(size_t)s * E + e];
+  float v = ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7]));
+  if (RELU) {
+    v += bias[e % nb];
+    v = v > 0.f ? v : 0.f;
+  }
+  out[e] = v;
+}
+
+// fc2, softmax cross-entropy and its gradient, one image per thread
+__global__ void head_kernel(const float *a1, const float *w, const float *bias, const uint8_t *labels, const int *idx, int B, float *logits,
+                            float *loss_b, float *dl) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float z0 = bias[0], z1 = bias[1];
+  for (int u = 0; u < kFc1Out; u++) {
+    const float a = a1[(size_t)b * kFc1Out + u];
+    z0 = fmaf(a, w[u], z0);
+    z1 = fmaf(a, w[kFc1Out + u], z1);
+  }
+  logits[2 * b] = z0;
+  logits[2 * b + 1] = z1;
+  if (!dl) return;
+  const int lab = labels[idx[b]];
+  // two classes: everything hangs on d = z1 - z0.  loss = softplus(-+d); p1 = 1 / (1 + e^-d) as 1/2 + tanh(d / 2) / 2 near
+  // d = 0 (one rounding of a value near 1/2) and as e^-|d| / (1 + e^-|d|) beyond (the small probability keeps its relative
+  // precision); the wrong class gets p_false / B, the true class (p_true - 1) / B = -p_false / B
+  const float d = z1 - z0, s = lab ? d : -d;  // s: the margin of the true class
+  const float e = expf(-fabsf(d));
+  loss_b[b] = fmaxf(-s, 0.f) + log1pf(e);
+  float p_false;  // the probability of the wrong class
+  if (fabsf(d) < 1.f)
+    p_false = fmaf(-0.5f, tanhf(0.5f * s), 0.5f);
+  else
+    p_false = (s > 0.f ? e : 1.f) / (1.f + e);
+  const float g_false = p_false / (float)B;
+  dl[2 * b] = lab ? g_false : -g_false;
+  dl[2 * b + 1] = lab ? -g_false : g_false;
+}
+
+// a block's sum of v[0 .. n): 256 strided chains, then a tree
+__device__ float block_sum(const float *v, long long n) {
+  __shared__ float sh[256];
+  float s = 0.f;
+  for (long long i = threadIdx.x; i < n; i += 256) s += v[i];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+__global__ void __launch_bounds__(256) loss_kernel(const float *loss_b, int B, float *out) {
+  const float s = block_sum(loss_b, B);
+  if (threadIdx.x == 0) *out = s / (float)B;
+}
+
+// dZ1 = (dlogits W2) where fc1's ReLU passed
+__global__ void fc2_back_kernel(const float *dl, const float *w, const float *a1, int B, float *dz1) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= B * kFc1Out) return;
+  const int b = e / kFc1Out, u = e % kFc1Out;
+  dz1[e] = a1[e] > 0.f ? fmaf(dl[2 * b + 1], w[kFc1Out + u], dl[2 * b] * w[u]) : 0.f;
+}
+
+// fc2.weight [2][500], fc2.bias [2], fc1.bias [500]: sums over the batch in image order
+__global__ void head_grads_kernel(const float *dl, const float *a1, const float *dz1, int B, float *g_f2w, float *g_f2b, float *g_f1b) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  float s = 0.f;
+  if (t < 2 * kFc1Out) {
+    const int j = t / kFc1Out, u = t % kFc1Out;
+    for (int b = 0; b < B; b++) s = fmaf(dl[2 * b + j], a1[(size_t)b * kFc1Out + u], s);
+    g_f2w[t] = s;
+  } else if (t < 2 * kFc1Out + 2) {
+    for (int b = 0; b < B; b++) s += dl[2 * b + (t - 2 * kFc1Out)];
+    g_f2b[t - 2 * kFc1Out] = s;
+  } else if (t < 3 * kFc1Out + 2) {
+    const int u = t - 2 * kFc1Out - 2;
+    for (int b = 0; b < B; b++) s += dz1[(size_t)b * kFc1Out + u];
+    g_f1b[u] = s;
+  }
+}
+
+// a convolution's bias gradient: block f sums g[b][f][0 .. pp) image by image, the images' sums joined in image order
+__global__ void __launch_bounds__(256) bias_grad_kernel(const float *g, int B, int F, int pp, float *out) {
+  const int f = blockIdx.x;
+  float total = 0.f;
+  for (int b = 0; b < B; b++) {
+    const float s = block_sum(g + ((size_t)b * F + f) * pp, pp);
+    __syncthreads();
+    total += s;
+  }
+  if (threadIdx.x == 0) out[f] = total;
+}
+
+// torch.optim.Adam (single-tensor form, weight_decay as L2) over the eight tensors, which are one buffer
+__global__ void adam_kernel(float *p, const float *g, float *m, float *v, int n, float wd, float w1, float b2, float w2, float step_size,
+                            float bc2_sqrt, float eps) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float pi = p[i];
+  const float gi = fmaf(wd, pi, g[i]);
+  const float mi = fmaf(w1, gi - m[i], m[i]);           // exp_avg.lerp_(grad, 1 - beta1)
+  const float vi = fmaf(w2 * gi, gi, v[i] * b2);        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+  m[i] = mi;
+  v[i] = vi;
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p[i] = pi - step_size * (mi / denom);
+}
+
+const char *const kKernelNames[] = {"conv1_forward", "conv2_forward", "fc1_forward", "fc1_sum_relu", "head", "loss", "fc2_backward",
+                                    "head_grads", "fc1_dw", "fc1_dx", "conv2_db", "conv2_dw", "conv2_dw_sum", "conv2_dx", "conv1_db",
+                                    "conv1_dw", "conv1_dw_sum", "adam"};
+constexpr int kNumKernels = sizeof(kKernelNames) / sizeof(kKernelNames[0]);
+static_assert(kNumKernels + 1 <= kMaxKernels, "events");
+
+bool channels_ok(int c) { return c == 1 || c == 3 || c == 12 || c == 15; }
+
+void tensor_sizes(int C, size_t n[8]) {
+  n[0] = (size_t)kF1 * C * kTaps, n[1] = kF1, n[2] = (size_t)kF2 * kF1 * kTaps, n[3] = kF2;
+  n[4] = (size_t)kFc1Out * kFc1In, n[5] = kFc1Out, n[6] = 2 * kFc1Out, n[7] = 2;
+}
+
+}  // namespace
+
+struct gpd_hip_trainer {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  gpd_train_params p;
+  int C = 0, maxb = 0;
+  size_t off[9] = {0};                                                // the eight tensors inside the four parameter-sized buffers
+  float *d_p = nullptr, *d_g = nullptr, *d_m = nullptr, *d_v = nullptr;
+  long long step = 0;
+  uint8_t *d_img[2] = {nullptr, nullptr}, *d_lab[2] = {nullptr, nullptr};
+  int n[2] = {0, 0};
+  int *d_idx = nullptr;        // [kIdxCap]
+  float *d_loss = nullptr;     // [kIdxCap] one per step of an enqueue
+  float *d_pool1 = nullptr, *d_pool2 = nullptr, *d_dpool1 = nullptr, *d_dpool2 = nullptr;  // [maxb][20][784], [maxb][7200]
+  uint8_t *d_arg1 = nullptr, *d_arg2 = nullptr;
+  float *d_a1 = nullptr, *d_dz1 = nullptr;  // [maxb][500]
+  float *d_logits = nullptr, *d_dl = nullptr, *d_loss_b = nullptr;
+  float *d_part = nullptr;     // split-K partials of fc1 forward, conv2 dW, conv1 dW
+  hipEvent_t ev[kMaxKernels] = {nullptr};
+  std::vector<float> h_all;    // host staging of a parameter-sized buffer
+};
+
+namespace {
+
+void mark(gpd_hip_trainer *t, bool timed, int &k) {
+  if (timed) (void)hipEventRecord(t->ev[k], t->stream);
+  k++;
+}
+
+// forward over batch B of set `which` on the indices at d_idx; train: the loss of the batch into *d_loss_out and dlogits
+void enqueue_forward(gpd_hip_trainer *t, int which, const int *d_idx, int B, bool train, float *d_loss_out, bool timed, int &k) {
+  hipStream_t st = t->stream;
+  const int C = t->C;
+  const float *p = t->d_p;
+  const Input<uint8_t> img{t->d_img[which], d_idx, (long long)kPix * C, 1, kImg * C, C, (float)t->p.input_scale};
+  launch_gemm(st, PatchByPos<uint8_t>{img, kP1W, kP1, B * kO1}, Plain{p + t->off[0], (long long)C * kTaps, 1, kF1},
+              PoolStore{p + t->off[1], t->d_pool1, t->d_arg1, kF1, kP1, B * kP1}, B * kO1, kF1, C * kTaps, (C * kTaps + 1) & ~1);
+  mark(t, timed, k);
+  const Input<float> p1{t->d_pool1, nullptr, (long long)kF1 * kP1, kP1, kP1W, 1, 1.f};
+  launch_gemm(st, PatchByPos<float>{p1, kP2W, kP2, B * kO2}, Plain{p + t->off[2], (long long)kF1 * kTaps, 1, kF2},
+              PoolStore{p + t->off[3], t->d_pool2, t->d_arg2, kF2, kP2, B * kP2}, B * kO2, kF2, kF1 * kTaps, kF1 * kTaps);
+  mark(t, timed, k);
+  launch_gemm(st, Plain{t->d_pool2, kFc1In, 1, B}, Plain{p + t->off[4], kFc1In, 1, kFc1Out}, RawStore{t->d_part, B, kFc1Out}, B, kFc1Out,
+              kFc1In, kFc1In / kFc1Splits);
+  mark(t, timed, k);
+  hipLaunchKernelGGL(sum_partials<true>, dim3((B * kFc1Out + 255) / 256), dim3(256), 0, st, t->d_part, kFc1Splits, B * kFc1Out,
+                     p + t->off[5], kFc1Out, t->d_a1);
+  mark(t, timed, k);
+  hipLaunchKernelGGL(head_kernel, dim3((B + 63) / 64), dim3(64), 0, st, t->d_a1, p + t->off[6], p + t->off[7], t->d_lab[which], d_idx, B,
+                     t->d_logits, t->d_loss_b, train ? t->d_dl : nullptr);
+  mark(t, timed, k);
+  if (!train) return;
+  hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(256), 0, st, t->d_loss_b, B, d_loss_out);
+  mark(t, timed, k);
+}
+
+void enqueue_backward(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, int &k) {
+  hipStream_t st = t->stream;
+  const int C = t->C;
+  const float *p = t->d_p;
+  float *g = t->d_g;
+  hipLaunchKernelGGL(fc2_back_kernel, dim3((B * kFc1Out + 255) / 256), dim3(256), 0, st, t->d_dl, p + t->off[6], t->d_a1, B, t->d_dz1);
+  mark(t, timed, k);
+  hipLaunchKernelGGL(head_grads_kernel, dim3((3 * kFc1Out + 2 + 255) / 256), dim3(256), 0, st, t->d_dl, t->d_a1, t->d_dz1, B, g + t->off[6],
+                     g + t->off[7], g + t->off[5]);
+  mark(t, timed, k);
+  // fc1.weight [500][7200] = dZ1^T P2, K = B
+  launch_gemm(st, Plain{t->d_dz1, 1, kFc1Out, kFc1Out}, Plain{t->d_pool2, 1, kFc1In, kFc1In}, RawStore{g + t->off[4], kFc1Out, kFc1In},
+              kFc1Out, kFc1In, B, (B + 1) & ~1);
+  mark(t, timed, k);
+  // dPool2 [B][7200] = dZ1 W1, K = 500, zero where conv2's ReLU clamped
+  launch_gemm(st, Plain{t->d_dz1, kFc1Out, 1, B}, Plain{p + t->off[4], 1, kFc1In, kFc1In}, MaskStore{t->d_dpool2, t->d_arg2, B, kFc1In, 1},
+              B, kFc1In, kFc1Out, kFc1Out);
+  mark(t, timed, k);
+  hipLaunchKernelGGL(bias_grad_kernel, dim3(kF2), dim3(256), 0, st, t->d_dpool2, B, kF2, kP2, g + t->off[3]);
+  mark(t, timed, k);
+  // conv2.weight [50][500], K = B * 576: one partial per image
+  const PoolGrad pg2{t->d_dpool2, t->d_arg2, kF2, kP2W, kP2};
+  const Input<float> p1{t->d_pool1, nullptr, (long long)kF1 * kP1, kP1, kP1W, 1, 1.f};
+  launch_gemm(st, GradByFilter<kO2W, kO2>{pg2}, PatchByTap<float, kO2W, kO2>{p1, kF1 * kTaps}, RawStore{t->d_part, kF2, kF1 * kTaps}, kF2,
+              kF1 * kTaps, B * kO2, kO2);
+  mark(t, timed, k);
+  hipLaunchKernelGGL(sum_partials<false>, dim3((kF2 * kF1 * kTaps + 255) / 256), dim3(256), 0, st, t->d_part, B, kF2 * kF1 * kTaps, nullptr, 1,
+                     g + t->off[2]);
+  mark(t, timed, k);
+  // dPool1 [B][20][784] = transposed convolution of the expanded dPool2, K = 1250, zero where conv1's ReLU clamped
+  launch_gemm(st, GradByPos{pg2, kP1W, kP1, kO2W, B * kP1}, WeightByChannel{p + t->off[2], kF1}, MaskStore{t->d_dpool1, t->d_arg1, B * kP1, kF1, kP1},
+              B * kP1, kF1, kF2 * kTaps, kF2 * kTaps);
+  mark(t, timed, k);
+  hipLaunchKernelGGL(bias_grad_kernel, dim3(kF1), dim3(256), 0, st, t->d_dpool1, B, kF1, kP1, g + t->off[1]);
+  mark(t, timed, k);
+  // conv1.weight [20][25 C], K = B * 3136: four partials per image
+  const PoolGrad pg1{t->d_dpool1, t->d_arg1, kF1, kP1W, kP1};
+  const Input<uint8_t> img{t->d_img[0], d_idx, (long long)kPix * C, 1, kImg * C, C, (float)t->p.input_scale};
+  launch_gemm(st, GradByFilter<kO1W, kO1>{pg1}, PatchByTap<uint8_t, kO1W, kO1>{img, C * kTaps}, RawStore{t->d_part, kF1, C * kTaps}, kF1,
+              C * kTaps, B * kO1, kO1 / 4);
+  mark(t, timed, k);
+  hipLaunchKernelGGL(sum_partials<false>, dim3((kF1 * C * kTaps + 255) / 256), dim3(256), 0, st, t->d_part, 4 * B, kF1 * C * kTaps, nullptr, 1,
+                     g + t->off[0]);
+  mark(t, timed, k);
+}
+
+void enqueue_adam(gpd_hip_trainer *t, bool timed, int &k) {
+  t->step++;
+  const gpd_train_params &q = t->p;
+  const double bc1 = 1.0 - std::pow(q.beta1, (double)t->step), bc2 = 1.0 - std::pow(q.beta2, (double)t->step);
+  const int n = (int)t->off[8];
+  hipLaunchKernelGGL(adam_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, t->d_p, t->d_g, t->d_m, t->d_v, n, (float)q.weight_decay,
+                     (float)(1.0 - q.beta1), (float)q.beta2, (float)(1.0 - q.beta2), (float)(q.lr / bc1), (float)std::sqrt(bc2), (float)q.eps);
+  mark(t, timed, k);
+}
+
+int check_indices(const char *who, const int32_t *indices, long long count, int n) {
+  for (long long i = 0; i < count; i++)
+    if (indices[i] < 0 || indices[i] >= n) {
+      set_error("%s: index %d at position %lld is outside the resident set of %d images", who, indices[i], i, n);
+      return GPD_ERR_INVALID;
+    }
+  return GPD_OK;
+}
+
+int check_batch(const char *who, gpd_hip_trainer *t, const void *indices, int batch) {
+  if (!t || !indices) {
+    set_error("%s: null argument", who);
+    return GPD_ERR_INVALID;
+  }
+  if (batch < 1 || batch > t->maxb) {
+    set_error("%s: batch %d is outside 1 .. max_batch = %d", who, batch, t->maxb);
+    return GPD_ERR_INVALID;
+  }
+  if (t->n[0] < 1) {
+    set_error("%s: no training set (gpd_hip_train_set_data)", who);
+    return GPD_ERR_STATE;
+  }
+  return GPD_OK;
+}
+
+bool all_finite(const float *v, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+template <class T>
+hipError_t dev_alloc(T **p, size_t count) {
+  return hipMalloc(reinterpret_cast<void **>(p), (count ? count : 1) * sizeof(T));
+}
+
+}  // namespace
+
+extern "C" {
+
+void gpd_hip_train_default_params(gpd_train_params *p) {
+  if (!p) return;
+  p->channels = 15;
+  p->max_batch = 64;
+  p->lr = 1e-3, p->beta1 = 0.9, p->beta2 = 0.999, p->eps = 1e-8, p->weight_decay = 5e-4;
+  p->input_scale = 1.0 / 256;
+}
+
+int gpd_hip_train_create(gpd_hip_ctx *ctx, const gpd_train_params *params, gpd_hip_trainer **out) {
+  if (!ctx || !params || !out) {
+    set_error("gpd_hip_train_create: null argument");
+    return GPD_ERR_INVALID;
+  }
+  const gpd_train_params &q = *params;
+  if (!channels_ok(q.channels)) {
+    set_error("gpd_hip_train_create: %d channels (1, 3, 12 or 15)", q.channels);
+    return GPD_ERR_INVALID;
+  }
+  if (q.max_batch < 1 || q.max_batch > kMaxBatch) {
+    set_error("gpd_hip_train_create: max_batch %d is outside 1 .. %d", q.max_batch, kMaxBatch);
+    return GPD_ERR_INVALID;
+  }
+  if (!(q.lr >= 0 && std::isfinite(q.lr)) || !(q.beta1 >= 0 && q.beta1 < 1) || !(q.beta2 >= 0 && q.beta2 < 1) ||
+      !(q.eps >= 0 && std::isfinite(q.eps)) || !(q.weight_decay >= 0 && std::isfinite(q.weight_decay)) ||
+      !(q.input_scale > 0 && std::isfinite(q.input_scale))) {
+    set_error("gpd_hip_train_create: a hyper-parameter is out of range");
+    return GPD_ERR_INVALID;
+  }
+  gpd_hip_trainer *t = new gpd_hip_trainer();
+  ctx_device_stream(ctx, &t->device, &t->stream);
+  t->p = q;
+  t->C = q.channels;
+  t->maxb = q.max_batch;
+  size_t sz[8];
+  tensor_sizes(t->C, sz);
+  for (int i = 0; i < 8; i++) t->off[i + 1] = t->off[i] + sz[i];
+  const size_t total = t->off[8], B = (size_t)t->maxb;
+  const size_t part = B * (size_t)std::max(std::max(kF2 * kF1 * kTaps, 4 * kF1 * kTaps * t->C), kFc1Splits * kFc1Out);
+  hipError_t e = hipSetDevice(t->device);
+  if (e == hipSuccess) e = dev_alloc(&t->d_p, total);
+  if (e == hipSuccess) e = dev_alloc(&t->d_g, total);
+  if (e == hipSuccess) e = dev_alloc(&t->d_m, total);
+  if (e == hipSuccess) e = dev_alloc(&t->d_v, total);
+  if (e == hipSuccess) e = dev_alloc(&t->d_idx, (size_t)kIdxCap);
+  if (e == hipSuccess) e = dev_alloc(&t->d_loss, (size_t)kIdxCap);
+  if (e == hipSuccess) e = dev_alloc(&t->d_pool1, B * kF1 * kP1);
+  if (e == hipSuccess) e = dev_alloc(&t->d_dpool1, B * kF1 * kP1);
+  if (e == hipSuccess) e = dev_alloc(&t->d_arg1, B * kF1 * kP1);
+  if (e == hipSuccess) e = dev_alloc(&t->d_pool2, B * kFc1In);
+  if (e == hipSuccess) e = dev_alloc(&t->d_dpool2, B * kFc1In);
+  if (e == hipSuccess) e = dev_alloc(&t->d_arg2, B * kFc1In);
+  if (e == hipSuccess) e = dev_alloc(&t->d_a1, B * kFc1Out);
+  if (e == hipSuccess) e = dev_alloc(&t->d_dz1, B * kFc1Out);
+  if (e == hipSuccess) e = dev_alloc(&t->d_logits, B * 2);
+  if (e == hipSuccess) e = dev_alloc(&t->d_dl, B * 2);
+  if (e == hipSuccess) e = dev_alloc(&t->d_loss_b, B);
+  if (e == hipSuccess) e = dev_alloc(&t->d_part, part);
+  for (int i = 0; i < kMaxKernels && e == hipSuccess; i++) e = hipEventCreate(&t->ev[i]);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_p, 0, total * sizeof(float), t->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_m, 0, total * sizeof(float), t->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_v, 0, total * sizeof(float), t->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  if (e != hipSuccess) {
+    set_error("gpd_hip_train_create: %s", hipGetErrorString(e));
+    gpd_hip_train_destroy(t);
+    return GPD_ERR_HIP;
+  }
+  t->h_all.resize(total);
+  *out = t;
+  return GPD_OK;
+}
+
+void gpd_hip_train_destroy(gpd_hip_trainer *t) {
+  if (!t) return;
+  (void)hipSetDevice(t->device);
+  if (t->stream) (void)hipStreamSynchronize(t->stream);
+  void *dev[] = {t->d_p,     t->d_g,      t->d_m,      t->d_v,    t->d_img[0], t->d_img[1], t->d_lab[0], t->d_lab[1], t->d_idx, t->d_loss, t->d_pool1,
+                 t->d_pool2, t->d_dpool1, t->d_dpool2, t->d_arg1, t->d_arg2,   t->d_a1,     t->d_dz1,    t->d_logits, t->d_dl,  t->d_loss_b, t->d_part};
+  for (void *p : dev)
+    if (p) (void)hipFree(p);
+  for (hipEvent_t e : t->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete t;
+}
+
+int gpd_hip_train_init_state(int channels, uint32_t seed, float *const tensors[8]) {
+  if (!channels_ok(channels) || !tensors) {
+    set_error("gpd_hip_train_init_state: %d channels (1, 3, 12 or 15) or a null argument", channels);
+    return GPD_ERR_INVALID;
+  }
+  size_t sz[8];
+  tensor_sizes(channels, sz);
+  for (int i = 0; i < 8; i++)
+    if (!tensors[i]) {
+      set_error("gpd_hip_train_init_state: tensor %d is null", i);
+      return GPD_ERR_INVALID;
+    }
+  const int fan_in[4] = {channels * kTaps, kF1 * kTaps, kFc1In, kFc1Out};
+  sample::Stream st(seed);
+  for (int i = 0; i < 8; i++) {
+    const double bound = (double)(float)(1.0 / std::sqrt((double)fan_in[i / 2]));
+    // 24 bits of the draw -> the centres of 2^24 equal cells of (-bound, bound)
+    for (size_t j = 0; j < sz[i]; j++) tensors[i][j] = (float)((2.0 * ((double)(st.next() >> 40) + 0.5) / 16777216.0 - 1.0) * bound);
+  }
+  return GPD_OK;
+}
+
+int gpd_hip_train_set_state(gpd_hip_trainer *t, const float *const tensors[8]) {
+  if (!t || !tensors) {
+    set_error("gpd_hip_train_set_state: null argument");
+    return GPD_ERR_INVALID;
+  }
+  static const char *const names[8] = {"conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"};
+  for (int i = 0; i < 8; i++)
+    if (!tensors[i] || !all_finite(tensors[i], t->off[i + 1] - t->off[i])) {
+      set_error("gpd_hip_train_set_state: %s is null or holds a non-finite value", names[i]);
+      return GPD_ERR_INVALID;
+    }
+  for (int i = 0; i < 8; i++) std::memcpy(t->h_all.data() + t->off[i], tensors[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
+  HIP_TRY(hipSetDevice(t->device));
+  const size_t bytes = t->off[8] * sizeof(float);
+  HIP_TRY(hipMemcpyAsync(t->d_p, t->h_all.data(), bytes, hipMemcpyHostToDevice, t->stream));
+  HIP_TRY(hipMemsetAsync(t->d_m, 0, bytes, t->stream));
+  HIP_TRY(hipMemsetAsync(t->d_v, 0, bytes, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  t->step = 0;
+  return GPD_OK;
+}
+
+int gpd_hip_train_get_state(gpd_hip_trainer *t, float *const tensors[8]) {
+  if (!t || !tensors) {
+    set_error("gpd_hip_train_get_state: null argument");
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < 8; i++)
+    if (!tensors[i]) {
+      set_error("gpd_hip_train_get_state: tensor %d is null", i);
+      return GPD_ERR_INVALID;
+    }
+  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(hipMemcpyAsync(t->h_all.data(), t->d_p, t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  for (int i = 0; i < 8; i++) std::memcpy(tensors[i], t->h_all.data() + t->off[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
+  return GPD_OK;
+}
+
+int gpd_hip_train_set_data(gpd_hip_trainer *t, int which, const uint8_t *images_hwc, const uint8_t *labels, int n) {
+  if (!t || which < 0 || which > 1 || n < 0 || (n > 0 && (!images_hwc || !labels))) {
+    set_error("gpd_hip_train_set_data: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < n; i++)
+    if (labels[i] > 1) {
+      set_error("gpd_hip_train_set_data: label %d of image %d (0 or 1)", (int)labels[i], i);
+      return GPD_ERR_INVALID;
+    }
+  const size_t bytes = (size_t)n * kPix * t->C;
+  if (bytes > ((size_t)4 << 30)) {
+    set_error("gpd_hip_train_set_data: %d images of %d channels are %zu bytes; a resident set holds 4 GiB", n, t->C, bytes);
+    return GPD_ERR_CAPACITY;
+  }
+  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  if (t->d_img[which]) HIP_TRY(hipFree(t->d_img[which]));
+  if (t->d_lab[which]) HIP_TRY(hipFree(t->d_lab[which]));
+  t->d_img[which] = t->d_lab[which] = nullptr;
+  t->n[which] = 0;
+  if (n == 0) return GPD_OK;
+  HIP_TRY(dev_alloc(&t->d_img[which], bytes));
+  HIP_TRY(dev_alloc(&t->d_lab[which], (size_t)n));
+  HIP_TRY(hipMemcpyAsync(t->d_img[which], images_hwc, bytes, hipMemcpyHostToDevice, t->stream));
+  HIP_TRY(hipMemcpyAsync(t->d_lab[which], labels, (size_t)n, hipMemcpyHostToDevice, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  t->n[which] = n;
+  return GPD_OK;
+}
+
+int gpd_hip_train_steps(gpd_hip_trainer *t, const int32_t *indices, int num_steps, int batch, float *losses) {
+  int rc = check_batch("gpd_hip_train_steps", t, indices, batch);
+  if (rc) return rc;
+  if (num_steps < 0 || (num_steps > 0 && !losses)) {
+    set_error("gpd_hip_train_steps: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  rc = check_indices("gpd_hip_train_steps", indices, (long long)num_steps * batch, t->n[0]);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(t->device));
+  const int per = kIdxCap / batch;
+  for (int s0 = 0; s0 < num_steps; s0 += per) {
+    const int ns = std::min(per, num_steps - s0);
+    HIP_TRY(hipMemcpyAsync(t->d_idx, indices + (size_t)s0 * batch, (size_t)ns * batch * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
+    for (int s = 0; s < ns; s++) {
+      int k = 0;
+      const int *idx = t->d_idx + (size_t)s * batch;
+      enqueue_forward(t, 0, idx, batch, true, t->d_loss + s, false, k);
+      enqueue_backward(t, idx, batch, false, k);
+      enqueue_adam(t, false, k);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(losses + s0, t->d_loss, (size_t)ns * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+  }
+  return GPD_OK;
+}
+
+int gpd_hip_train_gradients(gpd_hip_trainer *t, const int32_t *indices, int batch, float *const grads[8], float *loss) {
+  int rc = check_batch("gpd_hip_train_gradients", t, indices, batch);
+  if (rc) return rc;
+  if (!grads || !loss) {
+    set_error("gpd_hip_train_gradients: null argument");
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < 8; i++)
+    if (!grads[i]) {
+      set_error("gpd_hip_train_gradients: tensor %d is null", i);
+      return GPD_ERR_INVALID;
+    }
+  rc = check_indices("gpd_hip_train_gradients", indices, batch, t->n[0]);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(hipMemcpyAsync(t->d_idx, indices, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
+  int k = 0;
+  enqueue_forward(t, 0, t->d_idx, batch, true, t->d_loss, false, k);
+  enqueue_backward(t, t->d_idx, batch, false, k);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(t->h_all.data(), t->d_g, t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipMemcpyAsync(loss, t->d_loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  for (int i = 0; i < 8; i++) std::memcpy(grads[i], t->h_all.data() + t->off[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
+  return GPD_OK;
+}
+
+int gpd_hip_train_apply(gpd_hip_trainer *t, const float *const grads[8]) {
+  if (!t || !grads) {
+    set_error("gpd_hip_train_apply: null argument");
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < 8; i++)
+    if (!grads[i] || !all_finite(grads[i], t->off[i + 1] - t->off[i])) {
+      set_error("gpd_hip_train_apply: tensor %d is null or holds a non-finite value", i);
+      return GPD_ERR_INVALID;
+    }
+  for (int i = 0; i < 8; i++) std::memcpy(t->h_all.data() + t->off[i], grads[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
+  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(hipMemcpyAsync(t->d_g, t->h_all.data(), t->off[8] * sizeof(float), hipMemcpyHostToDevice, t->stream));
+  int k = 0;
+  enqueue_adam(t, false, k);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  return GPD_OK;
+}
+
+int gpd_hip_train_eval(gpd_hip_trainer *t, int which, const int32_t *indices, int n, float *logits, int *num_correct) {
+  if (!t || which < 0 || which > 1 || n < 0 || (n > 0 && !logits) || !num_correct) {
+    set_error("gpd_hip_train_eval: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  if (n > 0 && t->n[which] < 1) {
+    set_error("gpd_hip_train_eval: set %d is empty (gpd_hip_train_set_data)", which);
+    return GPD_ERR_STATE;
+  }
+  if (indices) {
+    const int rc = check_indices("gpd_hip_train_eval", indices, n, t->n[which]);
+    if (rc) return rc;
+  } else if (n > t->n[which]) {
+    set_error("gpd_hip_train_eval: %d images asked for, set %d holds %d", n, which, t->n[which]);
+    return GPD_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(t->device));
+  std::vector<int32_t> idx((size_t)n);
+  std::vector<uint8_t> lab((size_t)n);
+  for (int i = 0; i < n; i++) idx[(size_t)i] = indices ? indices[i] : i;
+  for (int i0 = 0; i0 < n; i0 += t->maxb) {
+    const int B = std::min(t->maxb, n - i0);
+    HIP_TRY(hipMemcpyAsync(t->d_idx, idx.data() + i0, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
+    int k = 0;
+    enqueue_forward(t, which, t->d_idx, B, false, nullptr, false, k);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(logits + 2 * (size_t)i0, t->d_logits, (size_t)B * 2 * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+  }
+  // the labels of the set come back once; argmax as torch.max: the first maximum
+  std::vector<uint8_t> all((size_t)std::max(t->n[which], 1));
+  if (n > 0) HIP_TRY(hipMemcpy(all.data(), t->d_lab[which], (size_t)t->n[which], hipMemcpyDeviceToHost));
+  int correct = 0;
+  for (int i = 0; i < n; i++) correct += (logits[2 * i + 1] > logits[2 * i] ? 1 : 0) == all[(size_t)idx[(size_t)i]];
+  *num_correct = correct;
+  return GPD_OK;
+}
+
+int gpd_hip_train_step_timed(gpd_hip_trainer *t, const int32_t *indices, int batch, float *ms, int capacity, int *num) {
+  int rc = check_batch("gpd_hip_train_step_timed", t, indices, batch);
+  if (rc) return rc;
+  if (!ms || !num || capacity < kNumKernels) {
+    set_error("gpd_hip_train_step_timed: ms must hold %d values", kNumKernels);
+    return GPD_ERR_INVALID;
+  }
+  rc = check_indices("gpd_hip_train_step_timed", indices, batch, t->n[0]);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(hipMemcpyAsync(t->d_idx, indices, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
+  int k = 0;
+  mark(t, true, k);
+  enqueue_forward(t, 0, t->d_idx, batch, true, t->d_loss, true, k);
+  enqueue_backward(t, t->d_idx, batch, true, k);
+  enqueue_adam(t, true, k);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  for (int i = 0; i + 1 < k; i++) HIP_TRY(hipEventElapsedTime(&ms[i], t->ev[i], t->ev[i + 1]));
+  *num = k - 1;
+  return GPD_OK;
+}
+
+const char *gpd_hip_train_kernel_name(int i) { return i >= 0 && i < kNumKernels ? kKernelNames[i] : ""; }
+
+}  // extern "C"

@@ -565,6 +565,51 @@ int gpd_hip_lenet_debug(gpd_hip_ctx *ctx, int which, int n, void *out);
 int gpd_hip_lenet_fast_tables(int channels, const float *conv1_w, const float *conv2_w, uint8_t *atab, double *corr, int *shift,
                               unsigned short *btab);
 
+/* ---- training (train.hip) ----------------------------------------------------------------------------------
+ * A trainer for pytorch/network.py::Net as pytorch/train_net3.py trains it: softmax cross-entropy (mean over the batch) and
+ * torch.optim.Adam with weight_decay as L2 (g + wd * p), all in f32, every sum in a fixed order: two runs from the same state,
+ * data and index lists give the same bytes.  The state is exchanged as the eight tensors of the state dict in torch layout, in
+ * this order: conv1.weight [20][C][5][5], conv1.bias [20], conv2.weight [50][20][5][5], conv2.bias [50], fc1.weight [500][7200],
+ * fc1.bias [500], fc2.weight [2][500], fc2.bias [2] — what gpd_hip_lenet_from_torch takes. */
+typedef struct gpd_train_params {
+  int32_t channels;     /* 1, 3, 12 or 15 */
+  int32_t max_batch;    /* 1 .. 1024: every buffer is sized for it at creation */
+  double lr, beta1, beta2, eps, weight_decay; /* torch.optim.Adam; train_net3.py: 1e-3, 0.9, 0.999, 1e-8, 5e-4 */
+  double input_scale;   /* images enter as u8 * input_scale (hdf5_dataset.py:17: 1/256) */
+} gpd_train_params;
+typedef struct gpd_hip_trainer gpd_hip_trainer;
+
+void gpd_hip_train_default_params(gpd_train_params *p); /* 15 channels, max_batch 64, the values above */
+/* The trainer lives on the context's device and stream and must be destroyed before the context.  GPD_ERR_INVALID: a null
+ * pointer, channels not in {1, 3, 12, 15}, max_batch outside 1 .. 1024, a non-finite or out-of-range hyper-parameter. */
+int gpd_hip_train_create(gpd_hip_ctx *ctx, const gpd_train_params *params, gpd_hip_trainer **out);
+void gpd_hip_train_destroy(gpd_hip_trainer *t);
+/* Host only: every tensor U(-1/sqrt(fan_in), 1/sqrt(fan_in)) (fan_in 25 C, 500, 7200, 500; a bias has its layer's) — the
+ * distribution of torch's default initialisation, drawn from the project's seeded xorshift64 stream (sample_model.h), the eight
+ * tensors in order; NOT torch's bits. */
+int gpd_hip_train_init_state(int channels, uint32_t seed, float *const tensors[8]);
+/* set: also clears Adam's moments and the step count; GPD_ERR_INVALID (nothing changed) for a non-finite value. */
+int gpd_hip_train_set_state(gpd_hip_trainer *t, const float *const tensors[8]);
+int gpd_hip_train_get_state(gpd_hip_trainer *t, float *const tensors[8]);
+/* The resident set `which` (0: training, 1: test): images u8 [n][60][60][C] HWC, labels u8 [n] (0 / 1, GPD_ERR_INVALID
+ * otherwise).  n = 0 clears the slot.  GPD_ERR_CAPACITY: more than 4 GiB of images in one slot. */
+int gpd_hip_train_set_data(gpd_hip_trainer *t, int which, const uint8_t *images_hwc, const uint8_t *labels, int n);
+/* num_steps Adam steps on the training set, step s on the images indices[s * batch .. (s + 1) * batch), 1 <= batch <= max_batch;
+ * losses [num_steps]: each step's loss before its update.  The steps are enqueued back to back and waited for once (calls
+ * with more than 2^20 indices: once per 2^20).  GPD_ERR_INVALID before anything is launched: an index outside [0, n). */
+int gpd_hip_train_steps(gpd_hip_trainer *t, const int32_t *indices, int num_steps, int batch, float *losses);
+/* Forward and backward of one batch with no update: grads as the eight tensors, the loss. */
+int gpd_hip_train_gradients(gpd_hip_trainer *t, const int32_t *indices, int batch, float *const grads[8], float *loss);
+/* One Adam step from gradients of the host's (non-finite values: GPD_ERR_INVALID). */
+int gpd_hip_train_apply(gpd_hip_trainer *t, const float *const grads[8]);
+/* Forward only over set `which`: images indices[0 .. n), or 0 .. n - 1 for indices == NULL -> logits [n][2], the number of rows
+ * whose first maximum (torch.max) is the label. */
+int gpd_hip_train_eval(gpd_hip_trainer *t, int which, const int32_t *indices, int n, float *logits, int *num_correct);
+/* Measurement only: one training step with a HIP event behind every kernel -> ms [*num] in launch order, names
+ * gpd_hip_train_kernel_name(i); capacity: ms holds that many. */
+int gpd_hip_train_step_timed(gpd_hip_trainer *t, const int32_t *indices, int batch, float *ms, int capacity, int *num);
+const char *gpd_hip_train_kernel_name(int i);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,114 @@
+"""References and inputs of the trainer's tests (gpd_hip_train_*), computed once and shared (lru_cache); callers do
+not write into what they get.
+
+  * images(C, n): random bytes with 60 % zeros, the pattern of lenet_torch_ref.images, so that pooling windows tie;
+  * autograd(): pytorch/network.py::Net (conv, ReLU, 2 x 2 max-pool twice, channel-major flatten, fc1, ReLU, fc2 on image *
+    input_scale) under nn.CrossEntropyLoss through torch autograd on the CPU -> the eight gradients and the loss.  float64 is
+    the truth; float32 is the yardstick, taken twice — the batch in order on several threads, the batch reversed on one — and
+    the larger of the two errors counts (yardstick());
+  * learn_set(C): the 256-image task of the "it learns" check — label 1 images have max(pixel, 128) over [20:40, 20:40] of
+    channel 0 — and its 40 index lists of 64.
+"""
+import functools
+
+import numpy as np
+
+from gpd_amd import api
+
+FACTOR = 4  # the allowance: this many times torch's own float32 error against float64
+
+
+@functools.lru_cache(maxsize=None)
+def images(C, n=70, seed=11):
+    rng = np.random.RandomState(seed)
+    img = rng.randint(0, 256, (n, 60, 60, C)).astype(np.uint8)
+    img[rng.rand(n, 60, 60, C) < 0.6] = 0
+    img.setflags(write=False)
+    return img
+
+
+@functools.lru_cache(maxsize=None)
+def labels(n=70, seed=12):
+    lab = np.random.RandomState(seed).randint(0, 2, n).astype(np.uint8)
+    lab.setflags(write=False)
+    return lab
+
+
+def autograd(state, img, lab, dtype, input_scale=1.0 / 256, reverse=False, threads=None):
+    """-> ({key: gradient as numpy of dtype}, loss)"""
+    import torch
+    import torch.nn.functional as F
+    before = torch.get_num_threads()
+    if threads:
+        torch.set_num_threads(threads)
+    try:
+        order = np.arange(len(lab))[::-1].copy() if reverse else np.arange(len(lab))
+        t = {k: torch.from_numpy(np.array(state[k])).to(dtype).requires_grad_(True) for k in api.TORCH_KEYS}
+        x = torch.from_numpy(np.array(np.transpose(np.asarray(img)[order], (0, 3, 1, 2)), order="C")).to(dtype) * input_scale
+        y = torch.from_numpy(np.asarray(lab)[order].astype(np.int64))
+        h = F.max_pool2d(F.relu(F.conv2d(x, t["conv1.weight"], t["conv1.bias"])), 2)
+        h = F.max_pool2d(F.relu(F.conv2d(h, t["conv2.weight"], t["conv2.bias"])), 2)
+        h = F.relu(F.linear(h.reshape(len(lab), 7200), t["fc1.weight"], t["fc1.bias"]))
+        loss = F.cross_entropy(F.linear(h, t["fc2.weight"], t["fc2.bias"]), y)
+        loss.backward()
+        return {k: t[k].grad.numpy().copy() for k in api.TORCH_KEYS}, float(loss.item())
+    finally:
+        torch.set_num_threads(before)
+
+
+def yardstick(state, img, lab, input_scale=1.0 / 256):
+    """-> (g64, loss64, {key: e32}, e32 of the loss): e32 = the larger of the two float32 runs' max-abs errors against float64"""
+    import torch
+    g64, l64 = autograd(state, img, lab, torch.float64, input_scale)
+    a, la = autograd(state, img, lab, torch.float32, input_scale)
+    b, lb = autograd(state, img, lab, torch.float32, input_scale, reverse=True, threads=1)
+    e32 = {k: max(float(np.abs(a[k].astype(np.float64) - g64[k]).max()), float(np.abs(b[k].astype(np.float64) - g64[k]).max())) for k in api.TORCH_KEYS}
+    return g64, l64, e32, max(abs(la - l64), abs(lb - l64))
+
+
+def check_gradients(what, got, loss, g64, l64, e32, el32):
+    """The bound of the gradient check, per tensor in max-abs: FACTOR * e32, with a floor of 2^-22 * max |g64| (where torch's
+    float32 is exact or nearly so: all-tie batches); the loss: max(FACTOR * |L32 - L64|, 2^-21).  Prints every measured ratio
+    before it asserts -> the largest ratio."""
+    worst, bad = 0.0, []
+    for k in api.TORCH_KEYS:
+        err = float(np.abs(got[k].astype(np.float64) - g64[k]).max())
+        allow = max(FACTOR * e32[k], 2.0 ** -22 * float(np.abs(g64[k]).max()))
+        ratio = err / e32[k] if e32[k] > 0 else (0.0 if err == 0 else float("inf"))
+        print("%s %-12s max|g64| = %.3g  e32 = %.3g  device error = %.3g  ratio = %.2f  allowance = %.3g" % (what, k, float(np.abs(g64[k]).max()), e32[k], err, ratio, allow))
+        if err > allow:
+            bad.append((k, err, allow))
+        elif e32[k] > 0 and err > 2.0 ** -22 * float(np.abs(g64[k]).max()):
+            worst = max(worst, ratio)
+    lerr, lallow = abs(loss - l64), max(FACTOR * el32, 2.0 ** -21)
+    print("%s loss: f64 %.9g  device %.9g  error = %.3g  allowance = %.3g" % (what, l64, loss, lerr, lallow))
+    assert not bad, (what, bad)
+    assert lerr <= lallow, (what, loss, l64, lallow)
+    return worst
+
+
+@functools.lru_cache(maxsize=None)
+def learn_set(C):
+    """-> (images u8 [256,60,60,C], labels u8 [256], indices i32 [40,64]): step s takes the images (s * 64 + i) mod 256"""
+    rng = np.random.RandomState(100 + C)
+    img = rng.randint(0, 256, (256, 60, 60, C)).astype(np.uint8)
+    img[rng.rand(256, 60, 60, C) < 0.6] = 0
+    lab = rng.randint(0, 2, 256).astype(np.uint8)
+    img[lab == 1, 20:40, 20:40, 0] = np.maximum(img[lab == 1, 20:40, 20:40, 0], 128)
+    idx = ((np.arange(40)[:, None] * 64 + np.arange(64)[None, :]) % 256).astype(np.int32)
+    for a in (img, lab, idx):
+        a.setflags(write=False)
+    return img, lab, idx
+
+
+def logits64(state, img, input_scale=1.0 / 256):
+    """Net's logits in float64 -> [n, 2]"""
+    import torch
+    import torch.nn.functional as F
+    t = {k: torch.from_numpy(np.array(state[k])).to(torch.float64) for k in api.TORCH_KEYS}
+    x = torch.from_numpy(np.array(np.transpose(img, (0, 3, 1, 2)), order="C")).to(torch.float64) * input_scale
+    with torch.no_grad():
+        h = F.max_pool2d(F.relu(F.conv2d(x, t["conv1.weight"], t["conv1.bias"])), 2)
+        h = F.max_pool2d(F.relu(F.conv2d(h, t["conv2.weight"], t["conv2.bias"])), 2)
+        h = F.relu(F.linear(h.reshape(len(img), 7200), t["fc1.weight"], t["fc1.bias"]))
+        return F.linear(h, t["fc2.weight"], t["fc2.bias"]).numpy()
