@@ -32,6 +32,7 @@
 // interface is produced by planar_to_hwc_kernel when the caller asks for the pixels.
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -151,6 +152,7 @@ struct __attribute__((aligned(16))) SmemPts {
   int red_i[IMG_WAVES];
   int counter;
   int flag;
+  int nnz;  // non-empty pixels of the projection (scan_cells_hist)
 };
 typedef SmemPts<false> Smem;
 // shadow kernel: kept under 80 KB (SHC = 6144) so that two workgroups share a CU
@@ -174,6 +176,7 @@ struct __attribute__((aligned(16))) SmemShadow {
   int red_i[IMG_WAVES];
   int vorg[3];
   int flag;
+  int nnz;  // non-empty pixels of the projection (scan_cells_hist)
 };
 
 // a workgroup-uniform double moved to scalar registers (the candidate's box is the same for
@@ -297,12 +300,17 @@ __device__ inline uint32_t lcg_jump(uint32_t s, unsigned long long n) {
   return A * s + Cc;
 }
 
-// block-wide exclusive scan of one int per thread; returns the exclusive prefix, total in *total
+// block-wide exclusive scan of one int per thread; returns the exclusive prefix, total in *total.
+// ONE barrier.  (There was a second one in front of the red_i stores, against a reader of red_i that is still on its
+// way.  No call site has one: each is entered through a barrier of its own — the row counts / the pixel counts that
+// are summed here were written by other threads — and red_i is not read between that barrier and this call: its
+// last readers, the previous scan's sums below (in the general shadow kernel also the `return S.red_i[0]` of
+// list_nonempty_cells and the mask flags of its walk), lie several barriers back, for the persistent kernels the one
+// at the loop head included.  A new call site has to keep that: a barrier between the last read of red_i and the call.)
 template <class SM>
 __device__ inline int block_excl_scan(SM &S, int v, int *total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int incl = wave_incl_scan_i32(v);
-  __syncthreads();
   if (lane == 63) S.red_i[wave] = incl;
   __syncthreads();
   int base = 0, tot = 0;
@@ -323,7 +331,7 @@ __device__ int scan_cells(SM &S) {
   constexpr int PER = 8;  // consecutive cells per thread: two 16-byte LDS accesses each way (450 threads hold the 3600 cells)
   static_assert(kPix % PER == 0 && kPix / PER <= IMG_THREADS, "scan_cells: cells per thread");
   uint4 *c4 = reinterpret_cast<uint4 *>(S.cells);
-  if (tid < 32) reinterpret_cast<int *>(S.red_f)[tid] = 0;  // the histogram of list_nonempty_cells (three barriers from here)
+  if (tid < 32) reinterpret_cast<int *>(S.red_f)[tid] = 0;  // the histogram of list_nonempty_cells (two barriers from here; its last readers, the scale factors of the final phase, are behind that phase's closing barrier)
   uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
   if (tid < kPix / PER) {
     a = c4[2 * tid];
@@ -389,6 +397,74 @@ __device__ int list_nonempty_cells(SM &S, uint16_t *nz) {
   return S.red_i[0];
 }
 
+// scan_cells and list_nonempty_cells in the phases of ONE scan, for the per-candidate kernels: two barriers and a share of
+// the caller's next phase where the pair above takes six.  A thread holds the counts of its eight pixels anyway, so
+//   - scan_cells_hist: the histogram of the list is filled beside the wave scan (the caller has cleared S.red_f in the
+//     phase of its count: the last readers of red_f are behind the closing barrier of the final phase) | barrier | the
+//     segment starts go to `cells`, and the first wave turns the histogram into bucket offsets and leaves the number of
+//     non-empty pixels in S.nnz | barrier.  The eight buckets stay with the thread, a byte each (0: empty pixel);
+//   - scatter_nonempty: the list itself, in the phase in which the caller fills its segment table — both only read what
+//     the second barrier published, the list is first read behind the barrier that ends that phase, and so is S.nnz.
+// Same list as list_nonempty_cells up to the order inside a bucket, which is the order of LDS atomics there as here.
+template <class SM>
+__device__ inline void scan_cells_hist(SM &S, uint32_t (&pk)[2]) {
+  const int tid = threadIdx.x;
+  constexpr int PER = 8;
+  static_assert(kPix % PER == 0 && kPix / PER <= IMG_THREADS, "scan_cells_hist: cells per thread");
+  uint4 *c4 = reinterpret_cast<uint4 *>(S.cells);
+  int *hist = reinterpret_cast<int *>(S.red_f);
+  uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
+  if (tid < kPix / PER) {
+    a = c4[2 * tid];
+    b = c4[2 * tid + 1];
+  }
+  const int c[PER] = {(int)(a.x & 0xffffu), (int)(a.y & 0xffffu), (int)(a.z & 0xffffu), (int)(a.w & 0xffffu),
+                      (int)(b.x & 0xffffu), (int)(b.y & 0xffffu), (int)(b.z & 0xffffu), (int)(b.w & 0xffffu)};
+  int sum = 0;
+  pk[0] = pk[1] = 0u;
+#pragma unroll
+  for (int k = 0; k < PER; k++) {
+    sum += c[k];
+    if (c[k]) {
+      const int bucket = 31 - (c[k] < 31 ? c[k] : 31);  // 0 .. 30: counter 31 stays zero
+      atomicAdd(&hist[bucket], 1);
+      pk[k >> 2] |= (uint32_t)(bucket + 1) << (8 * (k & 3));
+    }
+  }
+  int total;
+  int run = block_excl_scan(S, sum, &total);
+  uint32_t o[PER];
+#pragma unroll
+  for (int k = 0; k < PER; k++) {
+    o[k] = (uint32_t)(run < 0xffff ? run : 0xffff) << 16;
+    run += c[k];
+  }
+  if (tid < kPix / PER) {
+    c4[2 * tid] = make_uint4(o[0], o[1], o[2], o[3]);
+    c4[2 * tid + 1] = make_uint4(o[4], o[5], o[6], o[7]);
+  }
+  if (tid < 64) {
+    const int v = tid < 32 ? hist[tid] : 0;
+    const int incl = wave_incl_scan_i32(v);
+    if (tid < 32) hist[tid] = incl - v;
+    if (tid == 31) S.nnz = incl;
+  }
+  __syncthreads();
+}
+template <class SM>
+__device__ inline void scatter_nonempty(SM &S, uint16_t *nz, const uint32_t (&pk)[2]) {
+  int *hist = reinterpret_cast<int *>(S.red_f);
+  // (the pixel numbers are made here, from a value the optimiser cannot follow: hoisted out of the callers' projection
+  // loops they were registers held through every phase of kernels that sit on their 128-register cap)
+  int first = threadIdx.x * 8;
+  asm volatile("" : "+v"(first));
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int b = (int)((pk[k >> 2] >> (8 * (k & 3))) & 0xffu);
+    if (b) nz[atomicAdd(&hist[b - 1], 1)] = (uint16_t)(first + k);
+  }
+}
+
 // 3x3 rect max-dilate (border ignored), NORM_MINMAX to [0,1], u8 = round-half-even(v*255)
 // (image_strategy.cpp:144-153, 178-187, 221-230; cv::dilate / cv::normalize / convertTo).
 // Planes are in cell-index order (cell row = 59 - image row; the 3x3 window is symmetric).
@@ -398,8 +474,18 @@ __device__ int list_nonempty_cells(SM &S, uint16_t *nz) {
 // image: a clamped duplicate cannot change a max), one dword store.
 // planes 0..2 (or 0 alone) start at p012 and are kPix apart; plane 3, if present, is p3 and is
 // normalised on its own; output channels are consecutive planes starting at out.
-template <int NPL, class SM>
-__device__ void finalize_planes(SM &S, const float *p012, const float *p3, uint8_t *out) {
+//
+// finalize_planes_ex is the same pass with three hooks for a caller that folds neighbouring phases into it:
+//   fold(x)   applied to every value as it is loaded (a pure function of the stored word: the dilation, the min / max
+//             and the bytes see fold(x) wherever the plain pass sees x);
+//   tail()    run by every thread in the last phase, behind the barrier that ends all reads of the planes — work that
+//             only has to be done before the caller's next phase rides on the closing barrier;
+//   OWN_RED   false (NPL == 1 only): the caller still reads red_f[4 * w + 2] and [4 * w + 3] when it enters, so the pass
+//             writes just the two slots per wave that one norm group needs and does without the barrier in front of them
+//             (nothing reads slots 4 * w + 0 / + 1 between the caller's previous barrier and this pass).
+template <int NPL, bool OWN_RED, class SM, class FOLD, class TAIL>
+__device__ __forceinline__ void finalize_planes_ex(SM &S, const float *p012, const float *p3, uint8_t *out, FOLD fold, TAIL tail) {
+  static_assert(OWN_RED || NPL == 1, "the shared reduction slots hold one norm group");
   const int tid = threadIdx.x;
   constexpr int GROUPS = NPL * 900;
   constexpr int PER = (GROUPS + IMG_THREADS - 1) / IMG_THREADS;
@@ -417,10 +503,10 @@ __device__ void finalize_planes(SM &S, const float *p012, const float *p3, uint8
       const float4 a = *reinterpret_cast<const float4 *>(pl + rm * kImg + c0);
       const float4 b = *reinterpret_cast<const float4 *>(pl + r * kImg + c0);
       const float4 c = *reinterpret_cast<const float4 *>(pl + rp * kImg + c0);
-      const float el = fmaxf(fmaxf(pl[rm * kImg + cl], pl[r * kImg + cl]), pl[rp * kImg + cl]);
-      const float er = fmaxf(fmaxf(pl[rm * kImg + cr], pl[r * kImg + cr]), pl[rp * kImg + cr]);
-      const float m0 = fmaxf(fmaxf(a.x, b.x), c.x), m1 = fmaxf(fmaxf(a.y, b.y), c.y);
-      const float m2 = fmaxf(fmaxf(a.z, b.z), c.z), m3 = fmaxf(fmaxf(a.w, b.w), c.w);
+      const float el = fmaxf(fmaxf(fold(pl[rm * kImg + cl]), fold(pl[r * kImg + cl])), fold(pl[rp * kImg + cl]));
+      const float er = fmaxf(fmaxf(fold(pl[rm * kImg + cr]), fold(pl[r * kImg + cr])), fold(pl[rp * kImg + cr]));
+      const float m0 = fmaxf(fmaxf(fold(a.x), fold(b.x)), fold(c.x)), m1 = fmaxf(fmaxf(fold(a.y), fold(b.y)), fold(c.y));
+      const float m2 = fmaxf(fmaxf(fold(a.z), fold(b.z)), fold(c.z)), m3 = fmaxf(fmaxf(fold(a.w), fold(b.w)), fold(c.w));
       d[k][0] = fmaxf(fmaxf(el, m0), m1);
       d[k][1] = fmaxf(fmaxf(m0, m1), m2);
       d[k][2] = fmaxf(fmaxf(m1, m2), m3);
@@ -441,17 +527,19 @@ __device__ void finalize_planes(SM &S, const float *p012, const float *p3, uint8
     mn[q] = wave_min_f32(mn[q]);
     mx[q] = wave_max_f32(mx[q]);
   }
-  __syncthreads();
+  if constexpr (OWN_RED) __syncthreads();
   if ((tid & 63) == 0) {
     S.red_f[4 * (tid >> 6) + 0] = mn[0];
     S.red_f[4 * (tid >> 6) + 1] = mx[0];
-    S.red_f[4 * (tid >> 6) + 2] = mn[1];
-    S.red_f[4 * (tid >> 6) + 3] = mx[1];
+    if constexpr (OWN_RED) {
+      S.red_f[4 * (tid >> 6) + 2] = mn[1];
+      S.red_f[4 * (tid >> 6) + 3] = mx[1];
+    }
   }
   __syncthreads();
-  float fs[2], fb[2];
+  float fs[2] = {0.f, 0.f}, fb[2] = {0.f, 0.f};
 #pragma unroll
-  for (int q = 0; q < 2; q++) {
+  for (int q = 0; q < (OWN_RED ? 2 : 1); q++) {
     float a = S.red_f[2 * q], b = S.red_f[2 * q + 1];
 #pragma unroll
     for (int w = 1; w < IMG_WAVES; w++) {
@@ -484,7 +572,12 @@ __device__ void finalize_planes(SM &S, const float *p012, const float *p3, uint8
       *reinterpret_cast<uint32_t *>(out + (size_t)ch * kPix + (kImg - 1 - r) * kImg + c0) = packed;
     }
   }
+  tail();
   __syncthreads();
+}
+template <int NPL, class SM>
+__device__ void finalize_planes(SM &S, const float *p012, const float *p3, uint8_t *out) {
+  finalize_planes_ex<NPL, true>(S, p012, p3, out, [](float x) { return x; }, [] {});
 }
 
 // ---- one plane at a time (grasp_image_kernel): the same arithmetic as finalize_planes, with the dilated values
@@ -727,6 +820,10 @@ __device__ __forceinline__ void shadow_image_body(const ImgParams &P, SmemShadow
   load_box(P.hands[P.cand_hand[cand]], B);
   for (int i = tid; i < 3 * (kImg + 1); i += IMG_THREADS) (&S.thr[0][0])[i] = (&K.thr[0][0])[i];
   for (int i = tid; i < 128; i += IMG_THREADS) S.recip[i] = i ? 1.0 / (double)i : 0.0;
+  // the pixel counters of the first projection start from zero (nothing touches `cells` before the projections, and the
+  // barriers of the list phases lie between this and the first count; projections 1 and 2 find them cleared by the last
+  // phase of the projection before)
+  for (int c = tid; c < kPix / 4; c += IMG_THREADS) reinterpret_cast<uint4 *>(S.cells)[c] = make_uint4(0u, 0u, 0u, 0u);
   if (tid == 0) {
     S.flag = 0;
     // voxel AABB of the image box: corners sample + F * (bx, by, bz)
@@ -973,18 +1070,24 @@ __device__ __forceinline__ void shadow_image_body(const ImgParams &P, SmemShadow
     const uint32_t v = S.lin[k];
     return cell_of_key(((v >> LB) & 0xfffu) | ((uint32_t)S.cz[k] << 12), pr);
   };
+  // A pixel of the raster that no voxel falls into holds EMPTY, a bit pattern no running mean takes (a NaN: the means are
+  // sums and products of finite numbers — voxel indices, the box's frame, table reciprocals); the final phase reads it
+  // as the 0 of the reference's zero-initialised image (the hook handed to finalize_planes_ex below).
+  constexpr uint32_t EMPTY = 0xffffffffu;
   for (int pr = 0; pr < 3; pr++) {
-    for (int c = tid; c < kPix / 4; c += IMG_THREADS) reinterpret_cast<uint4 *>(S.cells)[c] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
+    // Seven barriers per projection (sixteen before): count | scan (2) | place and list | walk | final (2).
+    // (the pixel counters are zero: cleared at the kernel's entry, then by the last phase of the previous projection —
+    // that was a pass and a barrier of its own at this place)
+    if (tid < 32) reinterpret_cast<int *>(S.red_f)[tid] = 0;  // the histogram of scan_cells_hist
     for (int k = tid; k < ns; k += IMG_THREADS) atomicAdd(&S.cells[cell_of_entry(k, pr)], 1u);
     __syncthreads();
-    scan_cells(S);
+    uint32_t pk[2];
+    scan_cells_hist(S, pk);
+    scatter_nonempty(S, S.nz, pk);
     for (int k = tid; k < ns; k += IMG_THREADS) {
       const uint32_t old = atomicAdd(&S.cells[cell_of_entry(k, pr)], 1u);
       S.bp.place[(old >> 16) + (old & 0xffffu)] = (uint16_t)k;
     }
-    __syncthreads();
-    TICK(2);
     const int da = depth_axis(pr);
     // column `da` of F and the matching offset, selected without indexing the register-resident box
     const double Fd0 = da == 0 ? B.F[0] : (da == 1 ? B.F[1] : B.F[2]);
@@ -993,9 +1096,16 @@ __device__ __forceinline__ void shadow_image_body(const ImgParams &P, SmemShadow
     const double offd = da == 0 ? B.off[0] : (da == 1 ? B.off[1] : B.off[2]);
     float lmax = -FLT_MAX;
     int lany = 0;
-    const int n_nz = list_nonempty_cells(S, S.nz);
-    for (int c = tid; c < kPix / 4; c += IMG_THREADS) reinterpret_cast<float4 *>(S.raster0)[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    // The raster is reset in the phase of the segment table (it followed the list, with a barrier of its own): its last
+    // readers, the dilation loads of the previous projection, are behind that projection's closing barrier, and the
+    // walk that writes it next starts behind the barrier below.
+    for (int c = tid; c < kPix / 4; c += IMG_THREADS) {
+      const float e = __uint_as_float(EMPTY);
+      reinterpret_cast<float4 *>(S.raster0)[c] = make_float4(e, e, e, e);
+    }
     __syncthreads();
+    TICK(2);
+    const int n_nz = S.nnz;
     TICK(9);
     for (int qn = tid; qn < n_nz; qn += IMG_THREADS) {
       const int c = S.nz[qn];
@@ -1018,38 +1128,41 @@ __device__ __forceinline__ void shadow_image_body(const ImgParams &P, SmemShadow
       lany = 1;
       S.raster0[c] = v;
     }
-    __syncthreads();
-    TICK(10);
+    // The waves leave their maxima BEFORE the barrier that ends the walk (they had a barrier pair of their own behind
+    // it), in slots 4 * w + 2 / + 3 of red_f.  Those 32 words were the histogram of the list until the barrier in front
+    // of the walk; n_nz, read behind that barrier, is in S.nnz, which is not written here.  The final phase below writes slots
+    // 4 * w + 0 / + 1 only, so it needs no barrier against the reads that follow, and the next writer of + 2 / + 3 is
+    // the next projection's count phase (it clears the histogram), behind the two barriers of the final phase.
     lmax = wave_max_f32(lmax);
     lany = __ballot(lany != 0) != 0ull;
-    if (lane == 0) {  // (red_f / red_i were last read before the barrier above)
-      S.red_f[tid >> 6] = lmax;
-      S.red_i[tid >> 6] = lany;
+    if (lane == 0) {
+      S.red_f[4 * (tid >> 6) + 2] = lmax;
+      reinterpret_cast<int *>(S.red_f)[4 * (tid >> 6) + 3] = lany;
     }
     __syncthreads();
+    TICK(10);
     float gmax = -FLT_MAX;
     int gany = 0;
 #pragma unroll
     for (int w = 0; w < IMG_WAVES; w++) {
-      gmax = fmaxf(gmax, S.red_f[w]);
-      gany |= S.red_i[w];
+      gmax = fmaxf(gmax, S.red_f[4 * w + 2]);
+      gany |= reinterpret_cast<const int *>(S.red_f)[4 * w + 3];
     }
     // minMaxLoc with mask -> max (0 if the mask is empty); image = max_img - image
     const double mxd = gany ? (double)gmax : 0.0;
     const float mxf = (float)mxd;
-    // (no barrier: red_f is rewritten behind the first barrier of finalize_planes only)
-    for (int c = tid; c < kPix / 4; c += IMG_THREADS) {
-      const uint4 w = reinterpret_cast<const uint4 *>(S.cells)[c];
-      float4 r = reinterpret_cast<float4 *>(S.raster0)[c];
-      r.x = ((w.x & 0xffffu) ? mxf : 0.0f) - r.x;
-      r.y = ((w.y & 0xffffu) ? mxf : 0.0f) - r.y;
-      r.z = ((w.z & 0xffffu) ? mxf : 0.0f) - r.z;
-      r.w = ((w.w & 0xffffu) ? mxf : 0.0f) - r.w;
-      reinterpret_cast<float4 *>(S.raster0)[c] = r;
-    }
-    __syncthreads();
     TICK(3);
-    finalize_planes<1>(S, &S.raster0[0], nullptr, out + (size_t)(pr * K.per + 4) * kPix);
+    // `max_img - image` is taken as the dilation loads the raster (it was a read-modify-write of all 3600 pixels and a
+    // barrier): a pixel with voxels gives mxf - mean, an empty one 0 - 0, the same float operations on the same
+    // operands.  The last phase clears the pixel counters for the next projection: the walk was their last reader.
+    finalize_planes_ex<1, false>(
+        S, &S.raster0[0], nullptr, out + (size_t)(pr * K.per + 4) * kPix,
+        [mxf](float x) { return __float_as_uint(x) == EMPTY ? 0.0f - 0.0f : mxf - x; },
+        [&S, tid] {
+          int c0 = tid;  // (opaque, so that the store address is made here and not held in a register through the whole loop)
+          asm volatile("" : "+v"(c0));
+          for (int c = c0; c < kPix / 4; c += IMG_THREADS) reinterpret_cast<uint4 *>(S.cells)[c] = make_uint4(0u, 0u, 0u, 0u);
+        });
     TICK(4);
   }
   if (tid == 0 && S.flag) atomicOr(P.status, S.flag);
@@ -1340,10 +1453,12 @@ __device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG
   for (int i = tid; i < 3 * (kImg + 1); i += IMG_THREADS) (&S.thr[0][0])[i] = (&K.thr[0][0])[i];
   for (int i = tid; i < 128; i += IMG_THREADS) S.recip[i] = i ? 1.0 / (double)i : 0.0;
   if (tid == 0) {
-    S.flag = 0;
-    S.counter = 0;
+    S.flag = 0;  // (S.counter is reset in front of every walk)
     S.nzv[0] = make_float4(0.f, 0.f, 0.f, 0.f);  // the empty pixel of the index raster (the walks write slots >= 1)
   }
+  // the cell counters of the first projection start from zero (the ballot counts of the compaction below used to borrow
+  // their storage, so they were cleared behind it, with a barrier of their own; see `cnt`)
+  for (int c = tid; c < kPix / 4; c += IMG_THREADS) reinterpret_cast<uint4 *>(S.cells)[c] = make_uint4(0u, 0u, 0u, 0u);
   __syncthreads();
   // The in-box points are numbered IN NEIGHBOUR ORDER (an ordered compaction: per 512 neighbours one ballot per wave
   // and a prefix over the eight wave counts), so that an entry's number is its rank among the in-box points: the
@@ -1353,7 +1468,10 @@ __device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG
   // every thread derives the entry numbers of its in-box points from those counts and writes them.  (One round per
   // barrier pair exposed the latency of its global loads six times per candidate: 28 of the kernel's 130 kcycles.)
   int n_before = 0;  // in-box points of the earlier blocks (the same in every thread)
-  int *cnt = reinterpret_cast<int *>(S.cells);  // [16 + 3][IMG_WAVES] ballot counts; the cell counters are not in use yet
+  // [16][IMG_WAVES] ballot counts, in the storage of the list of non-empty pixels: the first projection writes that list
+  // three barriers into its own phases, the counts are last read in front of the barrier that closes the last block
+  static_assert(offsetof(SmemPts<BIG>, nzlist) % sizeof(int) == 0 && sizeof(S.nzlist) >= 16 * IMG_WAVES * sizeof(int), "ballot counts in nzlist");
+  int *cnt = reinterpret_cast<int *>(S.nzlist);
   constexpr int RB = 16;
   const int wave = tid >> 6;
   for (int b0 = 0; b0 < N; b0 += RB * IMG_THREADS) {
@@ -1402,7 +1520,9 @@ __device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG
       }
     }
     n_before = run;
-    __syncthreads();  // the counts are rewritten by the next block / the cell counters start here
+    // the counts are rewritten by the next block / the entries below read the index list: for the last block this barrier
+    // is the one in front of the entry phase (there is no other)
+    __syncthreads();
   }
   const int n_box_all = n_before;
   if (n_box_all > CAP || (!BIG && N > 65536)) {
@@ -1457,13 +1577,21 @@ __device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG
     atomicAdd(&P.dbg[31], (unsigned long long)n_box_all);
   }
   TICK(5);
-  for (int c = tid; c < kPix / 4; c += IMG_THREADS) reinterpret_cast<uint4 *>(S.cells)[c] = make_uint4(0u, 0u, 0u, 0u);
-  __syncthreads();
+  // No barrier between the entries and the first count (there was one, behind the clearing of the cell counters that has
+  // moved to the kernel's entry): a thread counts and places exactly the entries it has written itself (e = tid + k *
+  // IMG_THREADS in all three loops), and the index list in `place`, which other threads read above, is rewritten only
+  // behind the barrier of the count.
   for (int pr = 0; pr < K.nproj; pr++) {
-    // (the cell counters are zero: cleared above, then by the copy-out of the previous projection)
+    // Nine barriers per projection (fifteen before): count | scan (2) | place and list | walk | listing of the live
+    // groups | min / max | staging | copy-out.
+    // (the cell counters are zero: cleared at the entry, then by the copy-out of the previous projection)
+    if (tid < 32) reinterpret_cast<int *>(S.red_f)[tid] = 0;  // the histogram of scan_cells_hist
     for (int e = tid; e < nb; e += IMG_THREADS) atomicAdd(&S.cells[cell_of_key(__float_as_uint(AN(e).w), pr)], 1u);
     __syncthreads();
-    scan_cells(S);
+    uint32_t pk[2];
+    scan_cells_hist(S, pk);
+    uint16_t *nz = S.nzlist;
+    scatter_nonempty(S, nz, pk);
     for (int e = tid; e < nb; e += IMG_THREADS) {
       const uint32_t key = __float_as_uint(AN(e).w);
       const uint32_t old = atomicAdd(&S.cells[cell_of_key(key, pr)], 1u);
@@ -1474,9 +1602,11 @@ __device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG
     // the pixel owner walks its segment in neighbour order
     const int da = depth_axis(pr);
     const double offd = da == 0 ? B.off[0] : (da == 1 ? B.off[1] : B.off[2]);
-    uint16_t *nz = S.nzlist;
-    const int n_nz = list_nonempty_cells(S, nz);
+    const int n_nz = S.nnz;
     TICK(11);
+    // the counter of the live-group list below is reset here, in front of the walk's barrier (it had a barrier of its
+    // own behind it): its last reader, `n_live` of the previous projection, is three barriers back
+    if (tid == 0) S.counter = 0;
     for (int qn = tid; qn < n_nz; qn += IMG_THREADS) {
       const int c = nz[qn];
       const uint32_t w = S.cells[c];
@@ -1523,8 +1653,6 @@ __device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG
     //      list, gave the same.)
     const bool with_normals = K.C != 1, with_depth = K.C == 1 || K.C >= 12;
     uint16_t *alist = S.place;  // the segment table is dead after the walks
-    if (tid == 0) S.counter = 0;
-    __syncthreads();
     bool live[GPT];  // this thread's own groups tid + k * IMG_THREADS: does the window hold points?
     auto window = [&](int g, uint32_t(&ix)[3][6]) {
       const int r = g / 15, c0 = (g - r * 15) * 4;
@@ -1644,13 +1772,21 @@ __device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG
     // four-byte ones (the store phase was issue bound: 36 of the 158 us a projection costs, profiles/img_phases.sh).
     uint32_t *stage = S.cells;
     uint4 *stage4 = reinterpret_cast<uint4 *>(S.cells);
-    for (int c = tid; c < 900; c += IMG_THREADS) {  // every pixel background ...
-      const uint32_t w = bg[c < 3 * 225 ? 0 : 1];
-      stage4[c] = make_uint4(w, w, w, w);
-    }
-    __syncthreads();
+    // Every group is staged exactly once, so the staging is ONE phase ("fill everything with background, barrier, the
+    // live groups over it" before): a thread stages the background of its OWN groups tid + k * IMG_THREADS that it found
+    // without points when it listed the live ones ...
 #pragma unroll
-    for (int k = 0; k < GPT; k++) {  // ... the live groups over it
+    for (int k = 0; k < GPT; k++) {
+      const int g = tid + k * IMG_THREADS;
+      if (g < 900 && !live[k]) {
+        const int r = g / 15, cg = g - r * 15;
+        const int m = (kImg - 1 - r) * 15 + cg;
+#pragma unroll
+        for (int pl = 0; pl < 4; pl++) stage[pl * 900 + m] = bg[pl < 3 ? 0 : 1];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < GPT; k++) {  // ... and the live groups of the list that it has dilated
       const int a = tid + k * IMG_THREADS;
       if (a < n_live) {
         const int g = (int)alist[a];
@@ -2236,9 +2372,13 @@ int images_launch(const SearchState &s, const Plan &pl, ImageState &im, hipStrea
     unsigned long long h[32];
     HIP_RET(hipMemcpyAsync(h, d_dbg, sizeof(h), hipMemcpyDeviceToHost, stream));
     HIP_RET(hipStreamSynchronize(stream));
-    static const char *names[14] = {"sh_extract",  "sh_list",         "sh_count_place", "sh_walk_tail", "sh_final",
-                                    "pts_collect", "pts_count_place", "pts_walk_tail",  "pts_final",    "sh_nzlist",
-                                    "sh_walk_loop", "pts_nzlist",     "pts_zero",       "pts_walk_loop"};
+    // sh_sort_list / pts_sort_list: count, scan, segment table AND the list of non-empty pixels (one run of phases since the
+    // list is built inside the scan); sh_nnz_read / pts_nnz_read: the read of its length behind the barrier (slots 9 / 11
+    // held the list's three phases); sh_max_read: the read of the walk's maxima; pts_setup: nothing but address
+    // arithmetic (it held the barrier of the live-group counter)
+    static const char *names[14] = {"sh_extract",  "sh_list",       "sh_sort_list",  "sh_max_read", "sh_final",
+                                    "pts_collect", "pts_sort_list", "pts_walk_tail", "pts_final",   "sh_nnz_read",
+                                    "sh_walk_loop", "pts_nnz_read", "pts_setup",     "pts_walk_loop"};
     unsigned long long tot = 0;
     for (int i = 0; i < 14; i++) tot += h[i];
     for (int i = 0; i < 14; i++)
