@@ -280,17 +280,27 @@ __global__ void sum_partials(const float *part, int S, int E, const float *bias,
   out[e] = v;
 }
 
+// eight interleaved chains joined pairwise (sum_partials' shape): a 500-term or a batch-long sum as ONE chain rounds some
+// sqrt(8) times more than torch's blocked float32 sums do, and it showed in the loss and in fc2.bias at B = 257 (NOTES §L)
+__device__ inline float join8(const float c[8]) { return ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7])); }
+
 // fc2, softmax cross-entropy and its gradient, one image per thread
 __global__ void head_kernel(const float *a1, const float *w, const float *bias, const uint8_t *labels, const int *idx, int B, float *logits,
                             float *loss_b, float *dl) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float z0 = bias[0], z1 = bias[1];
-  for (int u = 0; u < kFc1Out; u++) {
-    const float a = a1[(size_t)b * kFc1Out + u];
-    z0 = fmaf(a, w[u], z0);
-    z1 = fmaf(a, w[kFc1Out + u], z1);
+  float c0[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, c1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int u0 = 0; u0 < kFc1Out; u0 += 8) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      if (u0 + j < kFc1Out) {
+        const float a = a1[(size_t)b * kFc1Out + u0 + j];
+        c0[j] = fmaf(a, w[u0 + j], c0[j]);
+        c1[j] = fmaf(a, w[kFc1Out + u0 + j], c1[j]);
+      }
+    }
   }
+  const float z0 = join8(c0) + bias[0], z1 = join8(c1) + bias[1];
   logits[2 * b] = z0;
   logits[2 * b + 1] = z1;
   if (!dl) return;
@@ -338,22 +348,33 @@ __global__ void fc2_back_kernel(const float *dl, const float *w, const float *a1
   dz1[e] = a1[e] > 0.f ? fmaf(dl[2 * b + 1], w[kFc1Out + u], dl[2 * b] * w[u]) : 0.f;
 }
 
-// fc2.weight [2][500], fc2.bias [2], fc1.bias [500]: sums over the batch in image order
+// fc2.weight [2][500], fc2.bias [2], fc1.bias [500]: sums over the batch, image b on chain b mod 8
 __global__ void head_grads_kernel(const float *dl, const float *a1, const float *dz1, int B, float *g_f2w, float *g_f2b, float *g_f1b) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  float s = 0.f;
-  if (t < 2 * kFc1Out) {
-    const int j = t / kFc1Out, u = t % kFc1Out;
-    for (int b = 0; b < B; b++) s = fmaf(dl[2 * b + j], a1[(size_t)b * kFc1Out + u], s);
-    g_f2w[t] = s;
-  } else if (t < 2 * kFc1Out + 2) {
-    for (int b = 0; b < B; b++) s += dl[2 * b + (t - 2 * kFc1Out)];
-    g_f2b[t - 2 * kFc1Out] = s;
-  } else if (t < 3 * kFc1Out + 2) {
-    const int u = t - 2 * kFc1Out - 2;
-    for (int b = 0; b < B; b++) s += dz1[(size_t)b * kFc1Out + u];
-    g_f1b[u] = s;
+  if (t >= 3 * kFc1Out + 2) return;
+  const int kind = t < 2 * kFc1Out ? 0 : t < 2 * kFc1Out + 2 ? 1 : 2;
+  const int j = kind == 0 ? t / kFc1Out : t - 2 * kFc1Out, u = kind == 0 ? t % kFc1Out : t - 2 * kFc1Out - 2;
+  float c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int b0 = 0; b0 < B; b0 += 8) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const int b = b0 + i;
+      if (b >= B) continue;
+      if (kind == 0)
+        c[i] = fmaf(dl[2 * b + j], a1[(size_t)b * kFc1Out + u], c[i]);
+      else if (kind == 1)
+        c[i] += dl[2 * b + j];
+      else
+        c[i] += dz1[(size_t)b * kFc1Out + u];
+    }
   }
+  const float s = join8(c);
+  if (kind == 0)
+    g_f2w[t] = s;
+  else if (kind == 1)
+    g_f2b[j] = s;
+  else
+    g_f1b[u] = s;
 }
 
 // a convolution's bias gradient: block f sums g[b][f][0 .. pp) image by image, the images' sums joined in image order
@@ -369,13 +390,15 @@ __global__ void __launch_bounds__(256) bias_grad_kernel(const float *g, int B, i
 }
 
 // torch.optim.Adam (single-tensor form, weight_decay as L2) over the eight tensors, which are one buffer
-__global__ void adam_kernel(float *p, const float *g, float *m, float *v, int n, float wd, float w1, float b2, float w2, float step_size,
-                            float bc2_sqrt, float eps) {
+__global__ void adam_kernel(float *p, const float *g, float *m, float *v, int n, float wd, float b1, float w1, float b2, float w2,
+                            float step_size, float bc2_sqrt, float eps) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float pi = p[i];
   const float gi = fmaf(wd, pi, g[i]);
-  const float mi = fmaf(w1, gi - m[i], m[i]);           // exp_avg.lerp_(grad, 1 - beta1)
+  // exp_avg.lerp_(grad, 1 - beta1), both forms of torch's lerp: from the start for a weight below 1/2, from the end otherwise —
+  // at beta1 = 0 the first form is (g - m) + m, which is not g (a gradient of 1e-12 behind a moment of 0.05 came out as 0)
+  const float mi = w1 < 0.5f ? fmaf(w1, gi - m[i], m[i]) : fmaf(-b1, gi - m[i], gi);
   const float vi = fmaf(w2 * gi, gi, v[i] * b2);        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
   m[i] = mi;
   v[i] = vi;
@@ -505,7 +528,7 @@ void enqueue_adam(gpd_hip_trainer *t, bool timed, int &k) {
   const double bc1 = 1.0 - std::pow(q.beta1, (double)t->step), bc2 = 1.0 - std::pow(q.beta2, (double)t->step);
   const int n = (int)t->off[8];
   hipLaunchKernelGGL(adam_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, t->d_p, t->d_g, t->d_m, t->d_v, n, (float)q.weight_decay,
-                     (float)(1.0 - q.beta1), (float)q.beta2, (float)(1.0 - q.beta2), (float)(q.lr / bc1), (float)std::sqrt(bc2), (float)q.eps);
+                     (float)q.beta1, (float)(1.0 - q.beta1), (float)q.beta2, (float)(1.0 - q.beta2), (float)(q.lr / bc1), (float)std::sqrt(bc2), (float)q.eps);
   mark(t, timed, k);
 }
 

@@ -6,6 +6,8 @@ not write into what they get.
     input_scale) under nn.CrossEntropyLoss through torch autograd on the CPU -> the eight gradients and the loss.  float64 is
     the truth; float32 is the yardstick, taken twice — the batch in order on several threads, the batch reversed on one — and
     the larger of the two errors counts (yardstick());
+  * trajectory(): the same network under torch.optim.Adam over a list of index rows -> every step's loss and the final state;
+  * head64(): the two-class head (loss and the probability of the wrong class) in float64 from given logits;
   * learn_set(C): the 256-image task of the "it learns" check — label 1 images have max(pixel, 128) over [20:40, 20:40] of
     channel 0 — and its 40 index lists of 64.
 """
@@ -34,22 +36,28 @@ def labels(n=70, seed=12):
     return lab
 
 
+def _net_loss(t, img, lab, dtype, input_scale):
+    """Net's mean cross-entropy on the batch (img u8 [n,60,60,C], lab [n]) under the tensors t"""
+    import torch
+    import torch.nn.functional as F
+    x = torch.from_numpy(np.array(np.transpose(np.asarray(img), (0, 3, 1, 2)), order="C")).to(dtype) * input_scale
+    y = torch.from_numpy(np.asarray(lab).astype(np.int64))
+    h = F.max_pool2d(F.relu(F.conv2d(x, t["conv1.weight"], t["conv1.bias"])), 2)
+    h = F.max_pool2d(F.relu(F.conv2d(h, t["conv2.weight"], t["conv2.bias"])), 2)
+    h = F.relu(F.linear(h.reshape(len(y), 7200), t["fc1.weight"], t["fc1.bias"]))
+    return F.cross_entropy(F.linear(h, t["fc2.weight"], t["fc2.bias"]), y)
+
+
 def autograd(state, img, lab, dtype, input_scale=1.0 / 256, reverse=False, threads=None):
     """-> ({key: gradient as numpy of dtype}, loss)"""
     import torch
-    import torch.nn.functional as F
     before = torch.get_num_threads()
     if threads:
         torch.set_num_threads(threads)
     try:
         order = np.arange(len(lab))[::-1].copy() if reverse else np.arange(len(lab))
         t = {k: torch.from_numpy(np.array(state[k])).to(dtype).requires_grad_(True) for k in api.TORCH_KEYS}
-        x = torch.from_numpy(np.array(np.transpose(np.asarray(img)[order], (0, 3, 1, 2)), order="C")).to(dtype) * input_scale
-        y = torch.from_numpy(np.asarray(lab)[order].astype(np.int64))
-        h = F.max_pool2d(F.relu(F.conv2d(x, t["conv1.weight"], t["conv1.bias"])), 2)
-        h = F.max_pool2d(F.relu(F.conv2d(h, t["conv2.weight"], t["conv2.bias"])), 2)
-        h = F.relu(F.linear(h.reshape(len(lab), 7200), t["fc1.weight"], t["fc1.bias"]))
-        loss = F.cross_entropy(F.linear(h, t["fc2.weight"], t["fc2.bias"]), y)
+        loss = _net_loss(t, np.asarray(img)[order], np.asarray(lab)[order], dtype, input_scale)
         loss.backward()
         return {k: t[k].grad.numpy().copy() for k in api.TORCH_KEYS}, float(loss.item())
     finally:
@@ -87,6 +95,52 @@ def check_gradients(what, got, loss, g64, l64, e32, el32):
     return worst
 
 
+HYPER = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=5e-4, input_scale=1.0 / 256)  # gpd_hip_train_default_params
+
+
+def trajectory(state, img, lab, rows, dtype, hyper=None, reverse=False, threads=None):
+    """autograd()'s network under torch.optim.Adam(lr, betas, eps, weight_decay): one step per row of `rows` (indices into img /
+    lab; reverse: each row back to front) -> (every step's loss f64 [len(rows)], the final state {key: numpy of dtype})"""
+    import torch
+    h = dict(HYPER, **(hyper or {}))
+    before = torch.get_num_threads()
+    if threads:
+        torch.set_num_threads(threads)
+    try:
+        t = {k: torch.from_numpy(np.array(state[k])).to(dtype).requires_grad_(True) for k in api.TORCH_KEYS}
+        opt = torch.optim.Adam([t[k] for k in api.TORCH_KEYS], lr=h["lr"], betas=(h["beta1"], h["beta2"]), eps=h["eps"], weight_decay=h["weight_decay"])
+        losses = []
+        for row in np.asarray(rows):
+            order = row[::-1].copy() if reverse else row
+            opt.zero_grad()
+            loss = _net_loss(t, np.asarray(img)[order], np.asarray(lab)[order], dtype, h["input_scale"])
+            loss.backward()
+            opt.step()
+            losses.append(float(loss.item()))
+        return np.array(losses, np.float64), {k: t[k].detach().numpy().copy() for k in api.TORCH_KEYS}
+    finally:
+        torch.set_num_threads(before)
+
+
+def trajectory_yardstick(state, img, lab, rows, hyper=None):
+    """-> (losses64, state64, e32 of every step's loss [len(rows)], {key: e32 of the final state}): yardstick()'s two float32 runs"""
+    import torch
+    l64, s64 = trajectory(state, img, lab, rows, torch.float64, hyper)
+    la, sa = trajectory(state, img, lab, rows, torch.float32, hyper)
+    lb, sb = trajectory(state, img, lab, rows, torch.float32, hyper, reverse=True, threads=1)
+    e32 = {k: max(float(np.abs(sa[k].astype(np.float64) - s64[k]).max()), float(np.abs(sb[k].astype(np.float64) - s64[k]).max())) for k in api.TORCH_KEYS}
+    return l64, s64, np.maximum(np.abs(la - l64), np.abs(lb - l64)), e32
+
+
+def head64(logits, lab):
+    """The two-class head in float64 from given logits [n, 2] and labels [n] -> (d = z1 - z0, each image's loss
+    max(-s, 0) + log1p(e^-|d|), the probability of the wrong class 1 / (1 + e^s)), s = the margin of the true class"""
+    z = np.asarray(logits).astype(np.float64).reshape(-1, 2)
+    d = z[:, 1] - z[:, 0]
+    s = np.where(np.asarray(lab).reshape(-1) == 1, d, -d)
+    return d, np.maximum(-s, 0.0) + np.log1p(np.exp(-np.abs(d))), 1.0 / (1.0 + np.exp(s))
+
+
 @functools.lru_cache(maxsize=None)
 def learn_set(C):
     """-> (images u8 [256,60,60,C], labels u8 [256], indices i32 [40,64]): step s takes the images (s * 64 + i) mod 256"""
@@ -104,9 +158,15 @@ def learn_set(C):
 def logits64(state, img, input_scale=1.0 / 256):
     """Net's logits in float64 -> [n, 2]"""
     import torch
+    return logits(state, img, torch.float64, input_scale)
+
+
+def logits(state, img, dtype, input_scale=1.0 / 256):
+    """Net's logits in `dtype` -> [n, 2]"""
+    import torch
     import torch.nn.functional as F
-    t = {k: torch.from_numpy(np.array(state[k])).to(torch.float64) for k in api.TORCH_KEYS}
-    x = torch.from_numpy(np.array(np.transpose(img, (0, 3, 1, 2)), order="C")).to(torch.float64) * input_scale
+    t = {k: torch.from_numpy(np.array(state[k])).to(dtype) for k in api.TORCH_KEYS}
+    x = torch.from_numpy(np.array(np.transpose(img, (0, 3, 1, 2)), order="C")).to(dtype) * input_scale
     with torch.no_grad():
         h = F.max_pool2d(F.relu(F.conv2d(x, t["conv1.weight"], t["conv1.bias"])), 2)
         h = F.max_pool2d(F.relu(F.conv2d(h, t["conv2.weight"], t["conv2.bias"])), 2)
