@@ -1,0 +1,482 @@
+// C-ABI of libgpd_hip.so (include/gpd_hip.h): the fused detect — its three steps, the single-cloud entries built on
+// them, and gpd_hip_label_view, whose round loop is the first step and a half with a tail of its own.
+//
+// A context owns two LANES — each a HIP stream with its own cloud, search buffers, candidate plan,
+// image buffers and LeNet scratch.  Every single-cloud entry point runs on lane 0.
+// gpd_hip_detect_batch alternates the lanes: while the image + LeNet kernels of cloud i run on one
+// lane, the upload + grid + search of cloud i+1 is already enqueued on the other, so host hops and
+// the host-device copies of one cloud hide behind the kernels of its neighbour, and the
+// tail of one cloud's kernel is filled by the other's.  (Measured against ONE stream carrying
+// search(i+1) ahead of images+LeNet(i), i.e. the same pipelining with strictly sequential kernels: two streams
+// 796 k candidates/s, one stream 735 k, same box, same 48 clouds.)
+//
+// A fused detect is three steps per cloud:
+//   begin   enqueue sample upload, neighbourhood / centre / hand_eval kernels (incl. the workspace filter)
+//           and plan_kernel (candidate list, shadow LCG offsets) + the 48-byte summary copy — no waiting
+//   middle  wait for the summary (the only mid-pipeline wait: the launch sizes), enqueue image kernels,
+//           LeNet, the record gather (all sets / candidates / the num_selected best) and ONE device-to-host
+//           copy into pinned memory
+//   end     wait, hand the records to the caller
+// Between the stages nothing crosses PCIe but that summary.
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "context.h"
+#include "balance_model.h"
+
+using namespace gpd;
+
+namespace gpd {
+
+// ---- the three steps of a fused detect -------------------------------------------------------
+int job_begin(gpd_hip_ctx *ctx, Lane &L, Job &J) {
+  J.live = false;
+  J.num_sets = J.num_candidates = J.num_hands = 0;
+  if (J.S == 0) return GPD_OK;
+  HIP_TRY(hipEventRecord(L.ev[0], L.stream));
+  int rc;
+  {
+    StageRange r("gpd:search (neighbourhoods, frames, hand evaluation, workspace filter)");
+    rc = search_run(ctx->params, L.cloud, L.search, J.sample_idx, J.sample_xyz, J.S, L.stream, /*sync_counts=*/false,
+                    J.resident ? &J.gather : nullptr);
+  }
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(L.ev[1], L.stream));
+  {
+    StageRange r("gpd:plan (hand sets, candidate list, shadow LCG offsets)");
+    rc = plan_build(ctx->params, L.cloud, L.search, L.plan, L.stream);
+  }
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(L.ev_plan, L.stream));
+  J.live = true;
+  return GPD_OK;
+}
+
+// the middle step in two halves: wait for the plan summary (the only mid-pipeline wait; a list-capacity retry happens here), then
+// enqueue images + LeNet + gather.  gpd_hip_detect_sharded puts the host-side scan of the shards' draw totals between the two.
+int job_wait_plan(gpd_hip_ctx *ctx, Lane &L, Job &J) {
+  if (!J.live) return GPD_OK;
+  J.live = false;  // set again once everything is enqueued
+  HIP_TRY(hipEventSynchronize(L.ev_plan));  // not the stream: in a batch the next cloud's search is already queued behind
+  J.t_plan_ms = now_ms();
+  if (L.plan.h_summary->worst_found > L.search.nn_cap) {
+    // a neighbourhood overflowed the list capacity of the search kernel: once more with the large lists
+    const int cap = search_next_capacity(L.search, L.plan.h_summary->worst_found);
+    if (!cap) {
+      set_error("search: a neighbourhood holds %d points, more than the list capacity %d", L.plan.h_summary->worst_found, kNnCapMax);
+      return GPD_ERR_CAPACITY;
+    }
+    // the side stream's centre_kernel of the first run is ordered before the plan, so it is done; the main stream still waits for
+    // it explicitly before neighbourhood_kernel rebuilds the lists
+    int rc = search_join(L.search, L.stream);
+    if (rc) return rc;
+    rc = search_force_capacity(L.search, cap);
+    if (rc) return rc;
+    rc = job_begin(ctx, L, J);
+    if (rc) return rc;
+    J.live = false;
+    HIP_TRY(hipStreamSynchronize(L.stream));
+  }
+  J.lcg_draws = L.plan.h_summary->total_draws;
+  J.live = true;
+  return GPD_OK;
+}
+
+int job_enqueue(gpd_hip_ctx *ctx, Lane &L, Job &J) {
+  if (!J.live) return GPD_OK;
+  J.live = false;
+  const PlanSummary sm = *L.plan.h_summary;
+  static const bool plan_timing = prof_env("GPD_PLAN_TIMING") != nullptr;
+  if (plan_timing)
+    fprintf(stderr, "[plan-timing] own sums %.2f us, look-back %.2f, tables + summary %.2f (last workgroup's thread 0, 100 MHz clock)\n",
+            (sm.pad_[0] & 0xffff) * 0.01, ((unsigned)sm.pad_[0] >> 16) * 0.01, (sm.pad_[1] & 0xffff) * 0.01);
+  const int slots = ctx->params.num_hand_axes * ctx->params.num_orientations;
+  J.num_sets = sm.num_sets;
+  J.num_candidates = sm.num_candidates;
+  const int n = sm.num_candidates;
+  int k = 0;
+  if (J.mode == 0)
+    J.out_records = sm.num_sets * slots;
+  else if (J.num_selected > 0)
+    J.out_records = k = std::min(J.num_selected, n);
+  else
+    J.out_records = n;
+  J.num_hands = J.out_records;
+  if ((long long)J.out_records > J.capacity) {
+    set_error("detect: %d hand records to return, the caller's buffer holds %lld", J.out_records, J.capacity);
+    return GPD_ERR_INVALID;
+  }
+  (void)hipEventElapsedTime(&L.stage_ms[0], L.ev[0], L.ev[1]);  // here: the next job on this lane records them again
+  HIP_TRY(hipEventRecord(L.ev[4], L.stream));
+  L.images.side_stream = !ctx->in_batch;
+  L.images.lcg_base = J.lcg_base;
+  int rc;
+  {
+    StageRange r("gpd:images (shadow sets, shadow channels, normals + depth channels)");
+    rc = images_run(ctx->params, L.cloud, L.search, L.plan, L.images, L.stream);
+  }
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(L.ev[2], L.stream));
+  if (n > 0) {
+    rc = reserve_scores(L, n);
+    if (rc) return rc;
+    {
+      StageRange r("gpd:lenet (conv1, conv2, ip1, ip2)");
+      HIP_TRY(lenet_forward(ctx->lenet, L.lenet_scratch, L.images.d_images, n, L.d_scores, L.stream));
+    }
+    HIP_TRY(hipMemcpyAsync(&L.h_flags->lenet, L.lenet_scratch.c1_stats + 2, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+  } else {
+    L.h_flags->lenet = 0;
+  }
+  HIP_TRY(hipEventRecord(L.ev[3], L.stream));
+  rc = reserve_out(L, (size_t)J.out_records, k ? (size_t)n * sizeof(float) : 0);
+  if (rc) return rc;
+  L.h_flags->tie = 0;
+  if (J.mode == 0) {
+    rc = plan_emit_hands(ctx->params, L.search, L.plan, n > 0 ? L.d_scores : nullptr, L.d_out, false, L.stream);
+  } else if (k > 0) {
+    rc = reserve_selection(L, k, n);
+    if (rc) return rc;
+    // every candidate record, scored, in a list of this job's own: the selection gathers from it, and so does the
+    // std::partial_sort rerun of job_end — by then, in a batch, the lane's search / plan buffers already hold the
+    // cloud after next (begin(i + 1) is enqueued before end(i - 1))
+    rc = plan_emit_hands(ctx->params, L.search, L.plan, L.d_scores, L.d_all, true, L.stream);
+    if (rc) return rc;
+    if (k <= select_topk_capacity()) {
+      rc = select_topk(L.d_scores, n, k, L.d_sel, L.d_sel + k, L.stream);
+      if (rc) return rc;
+      rc = gather_records(L.d_all, L.d_sel, k, L.d_out, L.stream);
+      if (rc) return rc;
+      HIP_TRY(hipMemcpyAsync(&L.h_flags->tie, L.d_sel + k, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+    } else {
+      L.h_flags->tie = 2;  // more winners than the device selection sorts: std::partial_sort on the host (job_end), no limit
+    }
+    // the scores (4 bytes per candidate) ride along: equal scores are settled with std::partial_sort on the host
+    HIP_TRY(hipMemcpyAsync(L.h_out + L.d_out_cap * sizeof(gpd_hand), L.d_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost,
+                           L.stream));
+  } else {
+    rc = plan_emit_hands(ctx->params, L.search, L.plan, L.d_scores, L.d_out, true, L.stream);
+  }
+  if (rc) return rc;
+  // A megabyte or more of records (all hand sets of a cloud: 3.6 MB) leaves in four copies with an event behind each, so that
+  // job_end hands chunk c to the caller while chunk c + 1 is still on the bus: the pinned-to-caller memcpy (0.2 ms for 3.6 MB)
+  // used to start only after the last byte had arrived.  Not for selections: their records may be gathered again (ties).
+  J.chunks = ((size_t)J.out_records * sizeof(gpd_hand) >= (1u << 20) && !(J.mode == 1 && J.num_selected > 0)) ? 4 : 0;
+  if (J.chunks) {
+    const size_t per = ((size_t)J.out_records + J.chunks - 1) / J.chunks;
+    for (int c = 0; c < J.chunks; c++) {
+      const size_t r0 = std::min((size_t)c * per, (size_t)J.out_records), r1 = std::min(r0 + per, (size_t)J.out_records);
+      if (r1 > r0)
+        HIP_TRY(hipMemcpyAsync(L.h_out + r0 * sizeof(gpd_hand), L.d_out + r0, (r1 - r0) * sizeof(gpd_hand), hipMemcpyDeviceToHost, L.stream));
+      HIP_TRY(hipEventRecord(L.ev_chunk[c], L.stream));
+    }
+  } else if (J.out_records > 0) {
+    HIP_TRY(hipMemcpyAsync(L.h_out, L.d_out, (size_t)J.out_records * sizeof(gpd_hand), hipMemcpyDeviceToHost, L.stream));
+  }
+  HIP_TRY(hipMemcpyAsync(&L.h_flags->status, L.images.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+  HIP_TRY(hipEventRecord(L.ev_done, L.stream));
+  J.live = true;
+  return GPD_OK;
+}
+
+int job_middle(gpd_hip_ctx *ctx, Lane &L, Job &J) {
+  const int rc = job_wait_plan(ctx, L, J);
+  return rc ? rc : job_enqueue(ctx, L, J);
+}
+
+static bool score_greater(const std::pair<float, int32_t> &a, const std::pair<float, int32_t> &b) { return a.first > b.first; }
+
+int job_end(gpd_hip_ctx *ctx, Lane &L, Job &J) {
+  if (!J.live) return GPD_OK;
+  J.live = false;
+  double early_copy_ms = 0.0;
+  if (J.chunks) {
+    // (should a flag below turn out set, the caller's buffer holds records of a failed call: its content is unspecified then)
+    const size_t per = ((size_t)J.out_records + J.chunks - 1) / J.chunks;
+    for (int c = 0; c < J.chunks; c++) {
+      HIP_TRY(hipEventSynchronize(L.ev_chunk[c]));
+      const auto t0 = std::chrono::steady_clock::now();
+      const size_t r0 = std::min((size_t)c * per, (size_t)J.out_records), r1 = std::min(r0 + per, (size_t)J.out_records);
+      if (r1 > r0) std::memcpy(J.hands + r0, L.h_out + r0 * sizeof(gpd_hand), (r1 - r0) * sizeof(gpd_hand));
+      early_copy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+  }
+  HIP_TRY(hipEventSynchronize(L.ev_done));
+  const auto t_done = std::chrono::steady_clock::now();
+  (void)hipEventElapsedTime(&L.stage_ms[1], L.ev[4], L.ev[2]);
+  (void)hipEventElapsedTime(&L.stage_ms[2], L.ev[2], L.ev[3]);
+  if (L.h_flags->status) {
+    set_images_status_error(L.h_flags->status);
+    return GPD_ERR_CAPACITY;
+  }
+  if (L.h_flags->lenet) {
+    const int rc = lenet_check(L.lenet_scratch);  // clears the device word, sets the error text
+    return rc ? rc : GPD_ERR_HIP;
+  }
+  const int n = J.num_candidates;
+  if (J.mode == 1 && J.num_selected > 0 && J.out_records > 0 && L.h_flags->tie) {
+    // equal scores among the winners: the reference's result is whatever std::partial_sort leaves
+    // (grasp_detector.cpp:409), which depends on the history of its heap — so run exactly that, on
+    // (score, candidate) pairs in candidate order, and gather the winners again
+    const float *sc = reinterpret_cast<const float *>(L.h_out + L.d_out_cap * sizeof(gpd_hand));
+    std::vector<std::pair<float, int32_t>> v((size_t)n);
+    for (int i = 0; i < n; i++) v[i] = {sc[i], i};
+    const int k = J.out_records;
+    std::partial_sort(v.begin(), v.begin() + k, v.end(), score_greater);
+    std::vector<int32_t> sel((size_t)k);
+    for (int i = 0; i < k; i++) sel[i] = v[i].second;
+    HIP_TRY(hipMemcpyAsync(L.d_sel, sel.data(), (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, L.stream));
+    int rc = gather_records(L.d_all, L.d_sel, k, L.d_out, L.stream);  // not from L.search / L.plan: see job_middle
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(L.h_out, L.d_out, (size_t)k * sizeof(gpd_hand), hipMemcpyDeviceToHost, L.stream));
+    HIP_TRY(hipStreamSynchronize(L.stream));
+  }
+  if (J.out_records > 0 && !J.chunks) std::memcpy(J.hands, L.h_out, (size_t)J.out_records * sizeof(gpd_hand));
+  J.copy_ms = early_copy_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_done).count();
+  return GPD_OK;
+}
+
+}  // namespace gpd
+
+extern "C" {
+
+static int detect_any(gpd_hip_ctx *ctx, const char *who, const int32_t *sample_indices, const double *sample_xyz, int num_samples,
+                      int mode, int num_selected, gpd_hand *hands, long long capacity, int *num_sets, int *num_candidates,
+                      int *num_hands) {
+  if (!ctx || !hands || !num_sets || !num_candidates || (!sample_indices && !sample_xyz) || num_samples < 0 || num_selected < 0) {
+    set_error("%s: bad argument", who);
+    return GPD_ERR_INVALID;
+  }
+  if (!ctx->lenet.channels) {
+    set_error("%s: LeNet weights not set", who);
+    return GPD_ERR_STATE;
+  }
+  Lane &L = ctx->lane[0];
+  if (!L.cloud.num_points) {
+    set_error("%s: no cloud uploaded", who);
+    return GPD_ERR_STATE;
+  }
+  *num_sets = 0;
+  *num_candidates = 0;
+  if (num_hands) *num_hands = 0;
+  int rc = check_samples(who, sample_indices, sample_xyz, num_samples, L.cloud.num_points);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  // GPD_DETECT_TIMING=1: wall time of the three steps, to stderr
+  const bool timing = prof_env("GPD_DETECT_TIMING") != nullptr;
+  const double t0 = now_ms();
+  Job J;
+  J.sample_idx = sample_indices;
+  J.sample_xyz = sample_xyz;
+  J.S = num_samples;
+  J.mode = mode;
+  J.num_selected = num_selected;
+  J.hands = hands;
+  J.capacity = capacity;
+  rc = job_begin(ctx, L, J);
+  if (rc) return rc;
+  const double t1 = now_ms();
+  rc = job_middle(ctx, L, J);
+  if (rc) return rc;
+  const double t2 = now_ms();
+  rc = job_end(ctx, L, J);
+  if (rc) return rc;
+  *num_sets = J.num_sets;
+  *num_candidates = J.num_candidates;
+  if (num_hands) *num_hands = J.num_hands;
+  if (timing)
+    fprintf(stderr, "[detect-timing] enqueue search+plan %.3f ms, wait+enqueue images/LeNet/gather %.3f, wait+copy out %.3f; kernels: search %.3f images %.3f LeNet %.3f\n",
+            t1 - t0, t2 - t1, now_ms() - t2, L.stage_ms[0], L.stage_ms[1], L.stage_ms[2]);
+  return GPD_OK;
+}
+
+int gpd_hip_detect(gpd_hip_ctx *ctx, const int32_t *sample_indices, int num_samples, gpd_hand *hands, int *num_sets,
+                   int *num_candidates) {
+  if (!sample_indices) {
+    set_error("gpd_hip_detect: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  const long long cap = ctx ? (long long)num_samples * ctx->params.num_hand_axes * ctx->params.num_orientations : 0;
+  return detect_any(ctx, "gpd_hip_detect", sample_indices, nullptr, num_samples, 0, 0, hands, cap, num_sets, num_candidates, nullptr);
+}
+
+int gpd_hip_detect_samples(gpd_hip_ctx *ctx, const double *samples_xyz, int num_samples, gpd_hand *hands, int *num_sets,
+                           int *num_candidates) {
+  if (!samples_xyz) {
+    set_error("gpd_hip_detect_samples: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  const long long cap = ctx ? (long long)num_samples * ctx->params.num_hand_axes * ctx->params.num_orientations : 0;
+  return detect_any(ctx, "gpd_hip_detect_samples", nullptr, samples_xyz, num_samples, 0, 0, hands, cap, num_sets, num_candidates,
+                    nullptr);
+}
+
+int gpd_hip_detect_select(gpd_hip_ctx *ctx, const int32_t *sample_indices, int num_samples, int num_selected, gpd_hand *hands,
+                          int hands_capacity, int *num_sets, int *num_candidates, int *num_hands) {
+  if (!sample_indices || !num_hands || hands_capacity < 0) {
+    set_error("gpd_hip_detect_select: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  return detect_any(ctx, "gpd_hip_detect_select", sample_indices, nullptr, num_samples, 1, num_selected, hands, hands_capacity, num_sets,
+                    num_candidates, num_hands);
+}
+
+int gpd_hip_label_view(gpd_hip_ctx *ctx, gpd_label_view_job *job) {
+  StageRange range_("gpd:label_view");
+  if (!ctx || !job) {
+    set_error("gpd_hip_label_view: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  gpd_label_view_job &j = *job;
+  j.rounds_run = j.num_candidates = j.num_positives = j.num_out = j.num_positives_out = j.gt_neighbourhoods = 0;
+  j.d2h_bytes = 0;
+  for (float &m : j.stage_ms) m = 0.f;
+  const int half = j.max_grasps_per_view > 0 ? j.max_grasps_per_view / 2 : 0;
+  const long long total_samples = (long long)j.samples_per_round * j.max_rounds;
+  if (j.samples_per_round < 0 || j.max_rounds < 0 || (total_samples > 0 && !j.sample_indices) || total_samples > 0x7fffffffll ||
+      j.capacity < 0 || (j.capacity > 0 && (!j.images || !j.labels)) || (j.all_labels && j.all_labels_capacity < 0)) {
+    set_error("gpd_hip_label_view: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  if ((long long)j.capacity < 2ll * half) {
+    set_error("gpd_hip_label_view: capacity %d, up to %d instances are kept at max_grasps_per_view = %d", j.capacity, 2 * half,
+              j.max_grasps_per_view);
+    return GPD_ERR_INVALID;
+  }
+  Lane &L = ctx->lane[0];
+  LabelState &ls = ctx->label;
+  if (!L.cloud.num_points) {
+    set_error("gpd_hip_label_view: no cloud uploaded");
+    return GPD_ERR_STATE;
+  }
+  if (!ls.gt.num_points) {
+    set_error("gpd_hip_label_view: no ground truth uploaded (gpd_hip_upload_ground_truth)");
+    return GPD_ERR_STATE;
+  }
+  int rc = check_samples("gpd_hip_label_view", j.sample_indices, nullptr, (int)total_samples, L.cloud.num_points);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  rc = label_init(ls);
+  if (rc) return rc;
+  if (j.round_counts) std::memset(j.round_counts, 0, (size_t)j.max_rounds * 2 * sizeof(int32_t));
+  const gpd_params &p = ctx->params;
+  const int C = p.image_num_channels;
+  const size_t image_bytes = (size_t)kPix * C;
+  ls.grows = 0;
+  long long d2h = 0;
+  size_t acc = 0;  // candidates accumulated
+  int positives = 0, lists = 0, r = 0;
+  for (; r < j.max_rounds && positives < j.min_positives; r++) {
+    // createGraspImages (grasp_detector.cpp:458-521): what a fused detect builds before the LeNet
+    Job J;
+    J.sample_idx = j.sample_indices + (size_t)r * j.samples_per_round;
+    J.S = j.samples_per_round;
+    J.mode = 1;
+    rc = job_begin(ctx, L, J);
+    if (rc) return rc;
+    if (!J.live) continue;  // a round without samples
+    const int cap_before = L.search.nn_cap;
+    rc = job_wait_plan(ctx, L, J);
+    if (rc) return rc;
+    d2h += (long long)sizeof(PlanSummary) * (L.search.nn_cap != cap_before ? 2 : 1);
+    const PlanSummary sm = *L.plan.h_summary;
+    const int n = sm.num_candidates;
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, L.ev[0], L.ev[1]);
+    j.stage_ms[0] += ms;
+    int round_pos = 0;
+    if (n > 0) {
+      HIP_TRY(hipEventRecord(L.ev[4], L.stream));
+      L.images.side_stream = true;
+      L.images.lcg_base = 0;  // every round is an ordinary call: its shadow stream starts at 0
+      {
+        StageRange r_("gpd:images (label_view round)");
+        rc = images_run(p, L.cloud, L.search, L.plan, L.images, L.stream);
+      }
+      if (rc) return rc;
+      HIP_TRY(hipEventRecord(L.ev[2], L.stream));
+      // the round joins the view's accumulator: images in the caller's layout, records as detect_select(0) returns them
+      HIP_TRY(hipEventRecord(ls.ev[0], L.stream));
+      rc = label_reserve(ls, acc + (size_t)n, acc, image_bytes, (size_t)n, L.stream);
+      if (rc) return rc;
+      HIP_TRY(planar_to_hwc(L.images.d_images, ls.d_images + acc * image_bytes, n, C, L.stream));
+      rc = plan_emit_hands(p, L.search, L.plan, nullptr, ls.d_hands + acc, true, L.stream);
+      if (rc) return rc;
+      // evalGroundTruth (grasp_detector.cpp:522-526) on the records where they are
+      int img_status = 0;
+      {
+        StageRange r_("gpd:labels (ground-truth neighbourhoods per hand set, reevaluateHypotheses)");
+        rc = label_round(p, ls.gt, ls.gt_search, ls.d_hands + acc, ls.d_labels + acc, n, sm.live_sets, ls.d_cand_list, ls.d_meta, ls.h_meta,
+                         L.images.d_status, &img_status, &round_pos, &d2h, L.stream);
+      }
+      if (img_status) set_images_status_error(img_status);
+      if (rc) return rc;
+      HIP_TRY(hipEventRecord(ls.ev[1], L.stream));
+      HIP_TRY(hipEventSynchronize(ls.ev[1]));
+      (void)hipEventElapsedTime(&ms, L.ev[4], L.ev[2]);
+      j.stage_ms[1] += ms;
+      (void)hipEventElapsedTime(&ms, ls.ev[0], ls.ev[1]);
+      j.stage_ms[2] += ms;
+      lists += sm.live_sets;
+    } else {
+      L.images.num_candidates = 0;  // no candidate list of this round is resident
+    }
+    if (j.round_counts) {
+      j.round_counts[2 * r] = n;
+      j.round_counts[2 * r + 1] = round_pos;
+    }
+    acc += (size_t)n;
+    positives += round_pos;
+    if (acc > 0x7fffffffull) {
+      set_error("gpd_hip_label_view: more than 2^31 accumulated candidates");
+      return GPD_ERR_CAPACITY;
+    }
+  }
+  j.rounds_run = r;
+  j.num_candidates = (int)acc;
+  j.num_positives = positives;
+  j.gt_neighbourhoods = lists;
+  // balanceInstances (data_generator.cpp:406-430): P and N are known here, the indices are the device's business
+  const int end = balance::kept_per_class(positives, (long long)acc - positives, j.max_grasps_per_view);
+  const size_t k = (size_t)2 * end;
+  const size_t all = j.all_labels ? std::min(acc, (size_t)j.all_labels_capacity) : 0;
+  size_t off[4];
+  const size_t out_bytes = label_out_layout(k, image_bytes, off);
+  if (out_bytes + all > 0) {
+    if (out_bytes + all > ls.h_out_bytes) {
+      note_alloc(__func__);
+      if (ls.h_out) (void)hipHostFree(ls.h_out);
+      ls.h_out = nullptr;
+      ls.h_out_bytes = 0;
+      const size_t cap = out_bytes + all + (out_bytes + all) / 8;
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ls.h_out), cap, 0));
+      ls.h_out_bytes = cap;
+    }
+    HIP_TRY(hipEventRecord(ls.ev[2], L.stream));
+    rc = label_select_gather(ls, (int)acc, end, L.stream);
+    if (rc) return rc;
+    if (k > 0) HIP_TRY(hipMemcpyAsync(ls.h_out, ls.d_out, out_bytes, hipMemcpyDeviceToHost, L.stream));  // the kept set: one copy
+    if (all > 0) HIP_TRY(hipMemcpyAsync(ls.h_out + out_bytes, ls.d_labels, all, hipMemcpyDeviceToHost, L.stream));
+    HIP_TRY(hipEventRecord(ls.ev[3], L.stream));
+    HIP_TRY(hipEventSynchronize(ls.ev[3]));
+    (void)hipEventElapsedTime(&j.stage_ms[3], ls.ev[2], ls.ev[3]);
+    d2h += (long long)(k > 0 ? out_bytes : 0) + (long long)all;
+    if (k > 0) {
+      std::memcpy(j.images, ls.h_out + off[0], k * image_bytes);
+      if (j.hands) std::memcpy(j.hands, ls.h_out + off[1], k * sizeof(gpd_hand));
+      if (j.src_index) std::memcpy(j.src_index, ls.h_out + off[2], k * sizeof(int32_t));
+      std::memcpy(j.labels, ls.h_out + off[3], k);
+    }
+    if (all > 0) std::memcpy(j.all_labels, ls.h_out + out_bytes, all);
+  }
+  j.num_out = (int)k;
+  j.num_positives_out = end;
+  j.d2h_bytes = d2h;
+  return GPD_OK;
+}
+
+}  // extern "C"

@@ -311,6 +311,37 @@ def test_detect_batch_reports_a_bad_cloud(ctx, cloud30k):
     assert n > 20
 
 
+@pytest.mark.parametrize("bad_at", [1, 3])
+def test_detect_batch_failed_job_leaves_neighbours_intact(ctx, bad_at):
+    """Four clouds, two per lane, one of them with an inf coordinate.  The C entry is called directly, so that the job
+    array survives the error: the batch returns the bad job's status and text, and every other job holds exactly the
+    records of a separate upload + detect.  bad_at = 1: the failed lane is used again by cloud 3; bad_at = 3: the
+    failure comes after cloud 2 was collected.  A clean batch on the same context afterwards gives the same bytes."""
+    clouds = [dict(synth.make_cloud(1100 + cid, 9000 + 1000 * cid)) for cid in range(4)]
+    samples = [synth.sample_indices(cl, 40 + 6 * cid) for cid, cl in enumerate(clouds)]
+    good = [cid for cid in range(4) if cid != bad_at]
+    bad = dict(clouds[bad_at])
+    bad["xyz"] = bad["xyz"].copy()
+    bad["xyz"][17, 1] = np.inf
+    jobs, keep = ctx.batch([bad if cid == bad_at else cl for cid, cl in enumerate(clouds)], samples, 0)
+    rc = api.lib().gpd_hip_detect_batch(ctx._h, jobs, len(jobs))
+    text = api.lib().gpd_hip_last_error().decode()
+    assert rc != 0 and rc == jobs[bad_at].status
+    assert "non-finite" in text
+    got = {}
+    for cid in good:
+        assert jobs[cid].status == 0
+        got[cid] = (keep[cid][5][: jobs[cid].num_hands].tobytes(), jobs[cid].num_sets, jobs[cid].num_candidates)
+    for cid in good:
+        cl = clouds[cid]
+        ctx.upload_cloud(cl["xyz"], cl["normals"], cl["cam_source"], cl["view_points"])
+        one, ns, nc = ctx.detect_select(samples[cid], 0)
+        assert nc > 20 and got[cid] == (one.tobytes(), ns, nc)
+    again = ctx.detect_batch([clouds[cid] for cid in good], [samples[cid] for cid in good], 0)
+    for cid, (hands, ns, nc, _) in zip(good, again):
+        assert got[cid] == (hands.tobytes(), ns, nc)
+
+
 def test_create_rejects_bad_parameters():
     for field, value in (("hand_axes", 3), ("volume_width", 0.0), ("hand_depth", -0.06), ("finger_width", float("nan")),
                          ("hand_depth", 0.9)):  # 178 deepening steps: beyond the 128-entry table
