@@ -67,6 +67,23 @@ class LabelViewJob(C.Structure):
     ]
 
 
+class SisJob(C.Structure):
+    """Mirror of `gpd_sis_job` (include/gpd_hip.h)."""
+    _fields_ = [
+        ("sample_indices", C.c_void_p), ("num_init_samples", C.c_int32), ("num_iterations", C.c_int32), ("num_samples", C.c_int32),
+        ("sampling_method", C.c_int32), ("prob_rand_samples", C.c_double), ("sigma", C.c_double), ("min_score", C.c_double),
+        ("workspace", C.c_double * 6), ("min_inliers", C.c_int32), ("remove_inliers", C.c_int32), ("seed", C.c_uint32),
+        ("proposal_block", C.c_int32), ("hands", C.c_void_p), ("capacity", C.c_int32), ("num_hands", C.c_int32),
+        ("rounds_run", C.c_int32), ("num_sets", C.c_int32), ("num_candidates", C.c_int32), ("centres_capacity", C.c_int32),
+        ("samples_out", C.c_void_p), ("centres_out", C.c_void_p), ("round_counts", C.c_void_p), ("d2h_bytes", C.c_int64),
+        ("stage_ms", C.c_float * 4),
+    ]
+
+
+# numpy mirror of `gpd_sis_proposal` (include/gpd_hip.h)
+SIS_PROPOSAL_DTYPE = np.dtype([("idx_raw", "<u8"), ("off", "<f8", (3,))], align=False)
+
+
 class TrainParams(C.Structure):
     """Mirror of `gpd_train_params` (include/gpd_hip.h)."""
     _fields_ = [("channels", C.c_int32), ("max_batch", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
@@ -114,6 +131,43 @@ def shuffle_orders(seed, sizes):
         raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
     edges = np.concatenate([[0], np.cumsum(sizes)])
     return [out[a:b].copy() for a, b in zip(edges[:-1], edges[1:])]
+
+
+def sis_proposals(seed, round, kind, first, count, sigma=0.02):
+    """gpd_hip_sis_proposals: proposals first .. first + count of a stream of importance-sampling round `round` (host only) ->
+    kind 0: SIS_PROPOSAL_DTYPE [count] (idx_raw, three Gaussian offsets); kind 1: u64 [count] (pos_raw)."""
+    out = np.zeros(max(int(count), 1), SIS_PROPOSAL_DTYPE if int(kind) == 0 else np.uint64)
+    rc = lib().gpd_hip_sis_proposals(int(seed) & 0xFFFFFFFF, int(round), int(kind), int(first), int(count), float(sigma), _ptr(out))
+    if rc != 0:
+        raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
+    return out[: int(count)].copy()
+
+
+def sis_select(centres, gauss, uniform, uniform_list, cloud_xyz, workspace, sampling_method, num_gauss, num_rand, state=None):
+    """gpd_hip_sis_select: the selection rule of an importance-sampling round over one block of each stream (host only).
+    state: the dict an earlier call on the round's previous blocks returned (None: the round's first blocks).
+    -> dict: samples f64 [num_gauss + num_rand, 3], accepted i32 [2], consumed i32 [2] (Gaussian, uniform), shortfall."""
+    cen = np.ascontiguousarray(centres, np.float64).reshape(-1, 3)
+    g = np.ascontiguousarray(gauss, SIS_PROPOSAL_DTYPE).reshape(-1)
+    u = np.ascontiguousarray(uniform, np.uint64).reshape(-1)
+    lst = None if uniform_list is None else np.ascontiguousarray(uniform_list, np.int32).reshape(-1)
+    xyz = np.ascontiguousarray(cloud_xyz, np.float32).reshape(-1, 3)
+    ws = np.ascontiguousarray(workspace, np.float64).reshape(6)
+    n = int(num_gauss) + int(num_rand)
+    if state is None:
+        samples, acc, used = np.zeros((max(n, 1), 3), np.float64), np.zeros(2, np.int32), np.zeros(2, np.int32)
+    else:
+        samples = np.zeros((max(n, 1), 3), np.float64)
+        samples[:n] = state["samples"]
+        acc, used = state["accepted"].astype(np.int32).copy(), state["consumed"].astype(np.int32).copy()
+    short = C.c_int(0)
+    rc = lib().gpd_hip_sis_select(_ptr(cen) if len(cen) else None, len(cen), _ptr(g) if len(g) else None, len(g),
+                                  _ptr(u) if len(u) else None, len(u), _ptr(lst) if lst is not None and len(lst) else None,
+                                  0 if lst is None else len(lst), _ptr(xyz) if len(xyz) else None, len(xyz), _ptr(ws),
+                                  int(sampling_method), int(num_gauss), int(num_rand), _ptr(samples), _ptr(acc), _ptr(used), C.byref(short))
+    if rc != 0:
+        raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
+    return dict(samples=samples[:n].copy(), accepted=acc, consumed=used, shortfall=int(short.value))
 
 
 TORCH_KEYS = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
@@ -176,7 +230,7 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals", "gpd_hip_sample_positions",
            "gpd_hip_set_lenet_conv_relu", "gpd_hip_lenet_from_torch",
            "gpd_hip_upload_ground_truth", "gpd_hip_label_view", "gpd_hip_balance_view", "gpd_hip_sizeof_label_view_job",
-           "gpd_hip_shuffle_orders",
+           "gpd_hip_shuffle_orders", "gpd_hip_sis_proposals", "gpd_hip_sis_select", "gpd_hip_detect_sis", "gpd_hip_sizeof_sis_job",
            "gpd_hip_train_default_params", "gpd_hip_train_create", "gpd_hip_train_destroy", "gpd_hip_train_init_state",
            "gpd_hip_train_set_state", "gpd_hip_train_get_state", "gpd_hip_train_set_data", "gpd_hip_train_steps",
            "gpd_hip_train_gradients", "gpd_hip_train_apply", "gpd_hip_train_eval", "gpd_hip_train_step_timed",
@@ -245,6 +299,10 @@ def lib():
         L.gpd_hip_label_view.argtypes = [C.c_void_p, C.POINTER(LabelViewJob)]
         L.gpd_hip_balance_view.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.gpd_hip_shuffle_orders.argtypes = [C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+        L.gpd_hip_sis_proposals.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_double, C.c_void_p]
+        L.gpd_hip_sis_select.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.gpd_hip_detect_sis.argtypes = [C.c_void_p, C.POINTER(SisJob)]
         L.gpd_hip_train_default_params.argtypes = [C.POINTER(TrainParams)]
         L.gpd_hip_train_default_params.restype = None
         L.gpd_hip_train_create.argtypes = [C.c_void_p, C.POINTER(TrainParams), C.POINTER(C.c_void_p)]
@@ -262,6 +320,7 @@ def lib():
         L.gpd_hip_train_kernel_name.argtypes = [C.c_int]
         L.gpd_hip_train_kernel_name.restype = C.c_char_p
         assert L.gpd_hip_sizeof_label_view_job() == C.sizeof(LabelViewJob)
+        assert L.gpd_hip_sizeof_sis_job() == C.sizeof(SisJob)
         _LIB = L
     return _LIB
 
@@ -387,6 +446,40 @@ class Context:
         if want_all_labels:
             out["all_labels"] = all_lab[: j.num_candidates].copy()
         return out
+
+    def detect_sis(self, sample_indices, num_iterations, num_samples, prob_rand_samples=0.3, sigma=0.02, sampling_method=0, min_score=0.0,
+                   workspace=(-1, 1, -1, 1, -1, 1), min_inliers=0, remove_inliers=False, seed=0, proposal_block=0, capacity=None):
+        """gpd_hip_detect_sis: SequentialImportanceSampling::detectGrasps on the uploaded cloud, the rounds kept on the device.
+        sample_indices: the initial pass (also the source of the uniform proposals).
+        -> dict: hands [n] (score > min_score, clustered when min_inliers > 0), samples f64 [rounds_run, num_samples, 3], centres f64
+        [num_sets, 3], round_counts i32 [1 + num_iterations, 4] (live sets, candidates, Gaussian / uniform proposals consumed),
+        rounds_run, num_sets, num_candidates, num_hands, stage_ms [4] (draw, search, images + accumulate, LeNet + select +
+        cluster), d2h_bytes."""
+        si = np.ascontiguousarray(sample_indices, np.int32).reshape(-1)
+        its, per = int(num_iterations), int(num_samples)
+        total = len(si) + max(its, 0) * max(per, 0)
+        cap = total * self.n_slots if capacity is None else int(capacity)
+        hands = np.zeros(max(cap, 1), HAND_DTYPE)
+        samples = np.zeros((max(its, 1), max(per, 1), 3), np.float64)
+        centres = np.zeros((max(total, 1), 3), np.float64)
+        counts = np.zeros((1 + max(its, 0), 4), np.int32)
+        j = SisJob()
+        j.sample_indices, j.num_init_samples = _ptr(si) if len(si) else None, len(si)
+        j.num_iterations, j.num_samples, j.sampling_method = its, per, int(sampling_method)
+        j.prob_rand_samples, j.sigma, j.min_score = float(prob_rand_samples), float(sigma), float(min_score)
+        j.workspace = (C.c_double * 6)(*[float(v) for v in workspace])
+        j.min_inliers, j.remove_inliers = int(min_inliers), int(bool(remove_inliers))
+        j.seed, j.proposal_block = int(seed) & 0xFFFFFFFF, int(proposal_block)
+        j.hands, j.capacity = (_ptr(hands) if cap > 0 else None), cap
+        j.samples_out, j.centres_out, j.centres_capacity, j.round_counts = _ptr(samples), _ptr(centres), total, _ptr(counts)
+        rc = lib().gpd_hip_detect_sis(self._h, C.byref(j))
+        self.last_sis_num_hands = int(j.num_hands)
+        self._check(rc)
+        r = int(j.rounds_run)
+        return dict(hands=hands[: j.num_hands].copy(), samples=samples[:r, :per].copy() if its > 0 else np.zeros((0, per, 3)),
+                    centres=centres[: j.num_sets].copy(), round_counts=counts.copy(), rounds_run=r, num_sets=int(j.num_sets),
+                    num_candidates=int(j.num_candidates), num_hands=int(j.num_hands), stage_ms=[float(x) for x in j.stage_ms],
+                    d2h_bytes=int(j.d2h_bytes))
 
     def search(self, sample_indices):
         """generateGraspCandidateSets -> hands[n_sets, n_slots]."""

@@ -154,6 +154,12 @@ __global__ __launch_bounds__(1024) void cluster_emit_kernel(ClusterParams P, gpd
   if (tid == 0) *num_out = s_carry;
 }
 
+// the scores of records that are on the device already, as the host mirror hands them over: (double) of the f32 score
+__global__ __launch_bounds__(256) void record_scores_kernel(const gpd_hand *__restrict__ hands, int n, double *__restrict__ scores) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) scores[i] = (double)hands[i].score;
+}
+
 }  // namespace
 
 void cluster_free(ClusterState &s) {
@@ -163,10 +169,7 @@ void cluster_free(ClusterState &s) {
   s = ClusterState();
 }
 
-int cluster_run(ClusterState &s, const gpd_hand *hands, const double *scores, int n, int min_inliers, int remove_inliers, gpd_hand *out,
-                double *out_scores, int32_t *out_src, int *num_out, hipStream_t stream) {
-  *num_out = 0;
-  if (n == 0) return GPD_OK;
+static int cluster_reserve(ClusterState &s, int n) {
   if (n > s.capacity) {
     const int cap = n + n / 4;
     cluster_free(s);
@@ -181,11 +184,14 @@ int cluster_run(ClusterState &s, const gpd_hand *hands, const double *scores, in
     HIP_RET(hipMalloc(&s.d_num, sizeof(int32_t)));
     s.capacity = cap;
   }
-  HIP_RET(hipMemcpyAsync(s.d_hands, hands, (size_t)n * sizeof(gpd_hand), hipMemcpyHostToDevice, stream));
-  HIP_RET(hipMemcpyAsync(s.d_scores, scores, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
+  return GPD_OK;
+}
+
+// the kernels over n records on the device (d_hands) with their scores in s.d_scores
+static int cluster_launch(ClusterState &s, const gpd_hand *d_hands, int n, int min_inliers, int remove_inliers, hipStream_t stream) {
   if (remove_inliers) HIP_RET(hipMemsetAsync(s.d_used, 0, (size_t)n, stream));
   ClusterParams P;
-  P.hands = s.d_hands;
+  P.hands = d_hands;
   P.scores = s.d_scores;
   P.n = n;
   P.min_inliers = min_inliers;
@@ -199,6 +205,28 @@ int cluster_run(ClusterState &s, const gpd_hand *hands, const double *scores, in
   cluster_kernel<<<remove_inliers ? 1 : n, CL_THREADS, 0, stream>>>(P);
   cluster_emit_kernel<<<1, 1024, 0, stream>>>(P, s.d_out, s.d_out_scores, s.d_out_src, s.d_num);
   HIP_RET(hipGetLastError());
+  return GPD_OK;
+}
+
+int cluster_run_resident(ClusterState &s, const gpd_hand *d_hands, int n, int min_inliers, int remove_inliers, hipStream_t stream) {
+  if (n <= 0) return GPD_OK;
+  int rc = cluster_reserve(s, n);
+  if (rc) return rc;
+  record_scores_kernel<<<(n + 255) / 256, 256, 0, stream>>>(d_hands, n, s.d_scores);
+  HIP_RET(hipGetLastError());
+  return cluster_launch(s, d_hands, n, min_inliers, remove_inliers, stream);
+}
+
+int cluster_run(ClusterState &s, const gpd_hand *hands, const double *scores, int n, int min_inliers, int remove_inliers, gpd_hand *out,
+                double *out_scores, int32_t *out_src, int *num_out, hipStream_t stream) {
+  *num_out = 0;
+  if (n == 0) return GPD_OK;
+  int rc = cluster_reserve(s, n);
+  if (rc) return rc;
+  HIP_RET(hipMemcpyAsync(s.d_hands, hands, (size_t)n * sizeof(gpd_hand), hipMemcpyHostToDevice, stream));
+  HIP_RET(hipMemcpyAsync(s.d_scores, scores, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
+  rc = cluster_launch(s, s.d_hands, n, min_inliers, remove_inliers, stream);
+  if (rc) return rc;
   int32_t k = 0;
   HIP_RET(hipMemcpyAsync(&k, s.d_num, sizeof(k), hipMemcpyDeviceToHost, stream));
   HIP_RET(hipStreamSynchronize(stream));

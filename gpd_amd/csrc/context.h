@@ -99,6 +99,7 @@ struct gpd_hip_ctx {
   gpd::PlaneState plane;  // gpd_hip_sample_above_plane
   gpd::RefineState refine;  // gpd_hip_refine_normals
   gpd::LabelState label;    // gpd_hip_upload_ground_truth / gpd_hip_label_view: the ground-truth slot and a view's accumulator
+  gpd::SisState sis;        // gpd_hip_detect_sis: the draw's buffers and the accumulators of the rounds
   std::vector<hipEvent_t> replay_events;  // 6 per gpd_hip_replay call: start, images done, conv1, conv2, fc1, end
   float replay_kernel_ms[4] = {0, 0, 0, 0};  // conv1, conv2, fc1, fc2 sums of the replays of the last gpd_hip_replay_times
   size_t replay_used = 0;

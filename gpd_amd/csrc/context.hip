@@ -15,6 +15,7 @@
 #include "context.h"
 #include "balance_model.h"
 #include "sample_model.h"
+#include "sis_model.h"
 
 namespace gpd {
 
@@ -337,6 +338,7 @@ void gpd_hip_destroy(gpd_hip_ctx *ctx) {
   plane_free(ctx->plane);
   refine_free(ctx->refine);
   label_free(ctx->label);
+  sis_free(ctx->sis);
   for (auto &e : ctx->pre.ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->pre.ev_keys) (void)hipEventDestroy(ctx->pre.ev_keys);
@@ -654,6 +656,59 @@ int gpd_hip_balance_view(const uint8_t *labels, int n, int max_grasps_per_view, 
   if (end > 0) std::memcpy(out_index, keep.data(), keep.size() * sizeof(int32_t));
   *num_out = 2 * end;
   *num_positives_out = end;
+  return GPD_OK;
+}
+
+int gpd_hip_sizeof_sis_job(void) { return (int)sizeof(gpd_sis_job); }
+
+int gpd_hip_sis_proposals(uint32_t seed, int round, int kind, long long first, int count, double sigma, void *out) {
+  if (round < 0 || first < 0 || count < 0 || (count > 0 && !out) || (kind != 0 && kind != 1) || (kind == 0 && !(sigma > 0.0))) {
+    set_error("gpd_hip_sis_proposals: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  sample::Stream st(sis::stream_seed(seed, round, kind));
+  sis::skip(st, (unsigned long long)first * (kind == 0 ? sis::kGaussDraws : 1));
+  if (kind == 0) {
+    static_assert(sizeof(gpd_sis_proposal) == sizeof(sis::Proposal), "gpd_sis_proposal");
+    sis::Proposal *o = static_cast<sis::Proposal *>(out);
+    for (int i = 0; i < count; i++) o[i] = sis::next_gauss(st, sigma);
+  } else {
+    uint64_t *o = static_cast<uint64_t *>(out);
+    for (int i = 0; i < count; i++) o[i] = st.next();
+  }
+  return GPD_OK;
+}
+
+int gpd_hip_sis_select(const double *centres, int num_centres, const gpd_sis_proposal *gauss, int num_gauss_proposals,
+                       const uint64_t *uniform, int num_uniform_proposals, const int32_t *uniform_list, int num_uniform_list,
+                       const float *cloud_xyz, int num_points, const double *workspace, int sampling_method, int num_gauss, int num_rand,
+                       double *samples, int32_t *accepted, int32_t *consumed, int *shortfall) {
+  if (num_centres < 0 || num_gauss_proposals < 0 || num_uniform_proposals < 0 || num_uniform_list < 0 || num_points < 0 || num_gauss < 0 ||
+      num_rand < 0 || !accepted || !consumed || !shortfall || (sampling_method != 0 && sampling_method != 1) ||
+      (num_gauss + num_rand > 0 && !samples) || (num_gauss > 0 && (num_centres < 1 || !centres)) || (num_gauss_proposals > 0 && !gauss) ||
+      (num_uniform_proposals > 0 && !uniform) || (num_uniform_list > 0 && !uniform_list) ||
+      (num_rand > 0 && (!cloud_xyz || !workspace || (num_uniform_list == 0 && num_points < 1)))) {
+    set_error("gpd_hip_sis_select: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < num_uniform_list; i++)
+    if (uniform_list[i] < 0 || uniform_list[i] >= num_points) {
+      set_error("gpd_hip_sis_select: uniform_list index %d out of range", uniform_list[i]);
+      return GPD_ERR_INVALID;
+    }
+  if (accepted[0] < 0 || accepted[0] > num_gauss || accepted[1] < 0 || accepted[1] > num_rand || consumed[0] < 0 || consumed[1] < 0) {
+    set_error("gpd_hip_sis_select: counts that no earlier block left");
+    return GPD_ERR_INVALID;
+  }
+  sis::Counts g = {accepted[0], consumed[0]}, u = {accepted[1], consumed[1]};
+  const double none[6] = {0, 0, 0, 0, 0, 0};
+  *shortfall = sis::select(centres, num_centres, reinterpret_cast<const sis::Proposal *>(gauss), num_gauss_proposals, uniform,
+                           num_uniform_proposals, num_uniform_list > 0 ? uniform_list : nullptr, num_uniform_list, cloud_xyz, num_points,
+                           workspace ? workspace : none, sampling_method, num_gauss, num_rand, samples, g, u);
+  accepted[0] = g.accepted;
+  consumed[0] = g.consumed;
+  accepted[1] = u.accepted;
+  consumed[1] = u.consumed;
   return GPD_OK;
 }
 

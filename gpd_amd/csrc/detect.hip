@@ -1,5 +1,6 @@
 // C-ABI of libgpd_hip.so (include/gpd_hip.h): the fused detect — its three steps, the single-cloud entries built on
-// them, and gpd_hip_label_view, whose round loop is the first step and a half with a tail of its own.
+// them, gpd_hip_label_view, whose round loop is the first step and a half with a tail of its own, and gpd_hip_detect_sis, whose
+// rounds are that step and a half behind a draw on the device (sis.hip), with one LeNet pass over everything at the end.
 //
 // A context owns two LANES — each a HIP stream with its own cloud, search buffers, candidate plan,
 // image buffers and LeNet scratch.  Every single-cloud entry point runs on lane 0.
@@ -27,6 +28,7 @@
 
 #include "context.h"
 #include "balance_model.h"
+#include "sis_model.h"
 
 using namespace gpd;
 
@@ -475,6 +477,282 @@ int gpd_hip_label_view(gpd_hip_ctx *ctx, gpd_label_view_job *job) {
   }
   j.num_out = (int)k;
   j.num_positives_out = end;
+  j.d2h_bytes = d2h;
+  return GPD_OK;
+}
+
+int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job) {
+  StageRange range_("gpd:detect_sis");
+  if (!ctx || !job) {
+    set_error("gpd_hip_detect_sis: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  gpd_sis_job &j = *job;
+  j.num_hands = j.rounds_run = j.num_sets = j.num_candidates = 0;
+  j.d2h_bytes = 0;
+  for (float &m : j.stage_ms) m = 0.f;
+  const long long all_samples = (long long)j.num_iterations * j.num_samples;
+  bool ws_ok = true;
+  for (double w : j.workspace) ws_ok = ws_ok && w == w;
+  if (j.num_init_samples < 0 || j.num_iterations < 0 || j.capacity < 0 || j.centres_capacity < 0 || j.proposal_block < 0 ||
+      (j.num_init_samples > 0 && !j.sample_indices) || (j.num_iterations > 0 && j.num_samples < 1) ||
+      !(j.prob_rand_samples >= 0.0 && j.prob_rand_samples <= 1.0) || !(j.sigma > 0.0) || (j.sampling_method != 0 && j.sampling_method != 1) ||
+      (j.capacity > 0 && !j.hands) || !ws_ok || !(j.min_score == j.min_score) || j.num_iterations >= (1 << 24) ||
+      (j.num_iterations > 0 && (all_samples > 0x7fffffffll / 3 || j.num_samples > (1 << 28)))) {
+    set_error("gpd_hip_detect_sis: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  if (ctx->in_batch) {
+    set_error("gpd_hip_detect_sis: gpd_hip_detect_batch is driving the lanes");
+    return GPD_ERR_STATE;
+  }
+  if (!ctx->lenet.channels) {
+    set_error("gpd_hip_detect_sis: LeNet weights not set");
+    return GPD_ERR_STATE;
+  }
+  Lane &L = ctx->lane[0];
+  SisState &ss = ctx->sis;
+  if (!L.cloud.num_points) {
+    set_error("gpd_hip_detect_sis: no cloud uploaded");
+    return GPD_ERR_STATE;
+  }
+  int rc = check_samples("gpd_hip_detect_sis", j.sample_indices, nullptr, j.num_init_samples, L.cloud.num_points);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  rc = sis_init(ss);
+  if (rc) return rc;
+  const gpd_params &p = ctx->params;
+  const size_t image_bytes = (size_t)kPix * p.image_num_channels;
+  const bool rounds = j.num_iterations > 0;
+  const int num_rand = rounds ? sis::num_rand_samples(j.prob_rand_samples, j.num_samples) : 0;
+  const int num_gauss = rounds ? j.num_samples - num_rand : 0;
+  // proposals per stream and block.  With proposal_block = 0 a block is sized to fill what is missing at the acceptance rate seen so
+  // far (a round's first block: the last round's), with a margin: a block that falls short costs the round a second search.  The
+  // result does not depend on the block sizes.
+  const int block_max = 1 << 22;
+  int block = j.proposal_block > 0 ? j.proposal_block : (int)std::min<long long>(2ll * j.num_samples + 64, block_max);
+  double rate_g = 1.0, rate_u = 1.0;
+  auto sized = [&](int missing, double rate) {
+    if (j.proposal_block > 0) return j.proposal_block;
+    return (int)std::min<double>((double)missing / std::max(rate, 1.0 / 256) * 1.25 + 64.0, (double)block_max);
+  };
+  constexpr int kMaxProposals = 1 << 20;  // of one stream in one round: a draw that has not filled its list by then never will
+  rc = sis_reserve_round(ss, rounds ? (size_t)j.num_samples : 0, j.samples_out ? (size_t)all_samples : 0, (size_t)j.num_init_samples,
+                         rounds ? (size_t)block : 0);
+  if (rc) return rc;
+  if (rounds && j.num_init_samples > 0)
+    HIP_TRY(hipMemcpyAsync(ss.d_uniform, j.sample_indices, (size_t)j.num_init_samples * sizeof(int32_t), hipMemcpyHostToDevice, L.stream));
+  HIP_TRY(hipMemsetAsync(ss.d_meta, 0, sizeof(SisMeta), L.stream));
+  *ss.h_meta = SisMeta();
+  if (j.round_counts) std::memset(j.round_counts, 0, (size_t)(1 + j.num_iterations) * 4 * sizeof(int32_t));
+  ss.grows = 0;
+  long long d2h = 0;
+  size_t acc = 0;               // candidates accumulated
+  int centres = 0;              // live hand sets accumulated
+  unsigned long long lcg = 0;   // shadow draws of the rounds so far: the collected list sits in ONE stream (:167)
+  bool img_pending = false;     // the image events of the last round have not been read yet
+  auto book_images = [&]() {
+    float ms = 0.f;
+    if (img_pending && hipEventElapsedTime(&ms, L.ev[4], ss.ev[2]) == hipSuccess) j.stage_ms[2] += ms;
+    img_pending = false;
+  };
+  int pass = 0;
+  for (; pass <= j.num_iterations; pass++) {
+    if (pass > 0 && centres == 0) break;  // the reference returns nothing after an initial pass without hand sets (:79-82)
+    const int r = pass - 1;
+    Job J;
+    J.mode = 1;
+    J.lcg_base = lcg;
+    if (pass == 0) {
+      J.sample_idx = j.sample_indices;
+      J.S = j.num_init_samples;
+    } else {
+      J.S = j.num_samples;
+      J.resident = true;
+      J.gather.d_xyz = ss.d_round_xyz;
+    }
+    sample::Stream sg(sis::stream_seed(j.seed, r < 0 ? 0 : r, 0)), su(sis::stream_seed(j.seed, r < 0 ? 0 : r, 1));
+    for (bool first = true;; first = false) {  // the draw and the search; redone from the draw when the proposal blocks fell short
+      if (pass > 0) {
+        if (first) HIP_TRY(hipMemsetAsync(ss.d_meta, 0, 4 * sizeof(int32_t), L.stream));  // the round's draw counts
+        const SisMeta left = first ? SisMeta() : *ss.h_meta;
+        if (!first) {
+          if (left.used_g > 0) rate_g = (double)left.acc_g / left.used_g;
+          if (left.used_u > 0) rate_u = (double)left.acc_u / left.used_u;
+        }
+        const int n_g = left.acc_g < num_gauss ? sized(num_gauss - left.acc_g, rate_g) : 0;
+        const int n_u = left.acc_u < num_rand ? sized(num_rand - left.acc_u, rate_u) : 0;
+        if (std::max(n_g, n_u) > block) {  // (nothing of the call is in flight on the buffers: the last wait is behind us)
+          block = std::max(n_g, n_u);
+          rc = sis_reserve_round(ss, (size_t)j.num_samples, j.samples_out ? (size_t)all_samples : 0, (size_t)j.num_init_samples, (size_t)block);
+          if (rc) return rc;
+        }
+        if ((n_g && left.used_g > kMaxProposals) || (n_u && left.used_u > kMaxProposals)) {
+          set_error("gpd_hip_detect_sis: round %d: %d Gaussian and %d uniform proposals gave %d of %d and %d of %d samples", r, left.used_g,
+                    left.used_u, left.acc_g, num_gauss, left.acc_u, num_rand);
+          return GPD_ERR_CAPACITY;
+        }
+        sis::Proposal *hg = reinterpret_cast<sis::Proposal *>(ss.h_block);
+        uint64_t *hu = reinterpret_cast<uint64_t *>(ss.h_block + ss.cap_block * sizeof(sis::Proposal));
+        for (int i = 0; i < n_g; i++) hg[i] = sis::next_gauss(sg, j.sigma);
+        for (int i = 0; i < n_u; i++) hu[i] = su.next();
+        HIP_TRY(hipEventRecord(ss.ev[0], L.stream));
+        rc = sis_draw(ss, L.cloud, centres, n_g, n_u, j.num_init_samples, j.workspace, j.sampling_method, num_gauss, num_rand, L.stream);
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(ss.ev[1], L.stream));
+      }
+      rc = job_begin(ctx, L, J);
+      if (rc) return rc;
+      if (!J.live) break;  // an initial pass without samples
+      const int cap_before = L.search.nn_cap;
+      rc = job_wait_plan(ctx, L, J);  // the round's one wait: plan summary, draw counts, capacity flags
+      if (rc) return rc;
+      d2h += (long long)sizeof(PlanSummary) * (L.search.nn_cap != cap_before ? 2 : 1) + (pass > 0 ? (long long)sizeof(SisMeta) : 0);
+      book_images();
+      float ms = 0.f;
+      (void)hipEventElapsedTime(&ms, L.ev[0], L.ev[1]);
+      j.stage_ms[1] += ms;
+      if (pass > 0) {
+        (void)hipEventElapsedTime(&ms, ss.ev[0], ss.ev[1]);
+        j.stage_ms[0] += ms;
+      }
+      if (ss.h_meta->img_status) {
+        set_images_status_error(ss.h_meta->img_status);
+        return GPD_ERR_CAPACITY;
+      }
+      if (pass == 0) break;
+      if (ss.h_meta->acc_g >= num_gauss && ss.h_meta->acc_u >= num_rand) {
+        if (ss.h_meta->used_g > 0) rate_g = (double)num_gauss / ss.h_meta->used_g;
+        if (ss.h_meta->used_u > 0) rate_u = (double)num_rand / ss.h_meta->used_u;
+        break;
+      }
+    }
+    if (!J.live) continue;
+    const PlanSummary sm = *L.plan.h_summary;
+    const int n = sm.num_candidates;
+    if (n > 0) {
+      HIP_TRY(hipEventRecord(L.ev[4], L.stream));
+      L.images.side_stream = true;
+      L.images.lcg_base = lcg;
+      {
+        StageRange r_("gpd:images (detect_sis round)");
+        rc = images_run(p, L.cloud, L.search, L.plan, L.images, L.stream);
+      }
+      if (rc) return rc;
+      HIP_TRY(hipEventRecord(L.ev[2], L.stream));
+      // the round joins the accumulators: images as the LeNet reads them, records as detect_select(0) returns them
+      rc = sis_reserve(ss, acc + (size_t)n, acc, (size_t)centres + (size_t)sm.live_sets, (size_t)centres, image_bytes, L.stream);
+      if (rc) return rc;
+      HIP_TRY(hipMemcpyAsync(ss.d_images + acc * image_bytes, L.images.d_images, (size_t)n * image_bytes, hipMemcpyDeviceToDevice, L.stream));
+      rc = plan_emit_hands(p, L.search, L.plan, nullptr, ss.d_hands + acc, true, L.stream);
+      if (rc) return rc;
+      rc = sis_accumulate(ss, acc, n, centres, L.images.d_status, L.stream);
+      if (rc) return rc;
+      HIP_TRY(hipEventRecord(ss.ev[2], L.stream));
+      img_pending = true;
+    } else {
+      L.images.num_candidates = 0;  // no candidate list of this round is resident
+    }
+    if (pass > 0 && j.samples_out)
+      HIP_TRY(hipMemcpyAsync(ss.d_samples + (size_t)r * j.num_samples * 3, ss.d_round_xyz, (size_t)j.num_samples * 3 * sizeof(double),
+                             hipMemcpyDeviceToDevice, L.stream));
+    if (j.round_counts) {
+      int32_t *rcnt = j.round_counts + 4 * (size_t)pass;
+      rcnt[0] = sm.live_sets;
+      rcnt[1] = n;
+      rcnt[2] = pass > 0 ? ss.h_meta->used_g : 0;
+      rcnt[3] = pass > 0 ? ss.h_meta->used_u : 0;
+    }
+    lcg += J.lcg_draws;
+    centres += sm.live_sets;
+    acc += (size_t)n;
+    if (acc > 0x7fffffffull) {
+      set_error("gpd_hip_detect_sis: more than 2^31 accumulated candidates");
+      return GPD_ERR_CAPACITY;
+    }
+  }
+  const int rounds_run = pass > 0 ? pass - 1 : 0;
+  const int N = (int)acc;
+  // classify everything at once (:164-167), cut at min_score, cluster (:175-181)
+  HIP_TRY(hipEventRecord(ss.ev[3], L.stream));
+  L.h_flags->lenet = 0;
+  if (N > 0) {
+    rc = reserve_scores(L, N);
+    if (rc) return rc;
+    {
+      StageRange r_("gpd:lenet (detect_sis: every accumulated image)");
+      HIP_TRY(lenet_forward(ctx->lenet, L.lenet_scratch, ss.d_images, N, L.d_scores, L.stream));
+    }
+    HIP_TRY(hipMemcpyAsync(&L.h_flags->lenet, L.lenet_scratch.c1_stats + 2, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+    rc = sis_select(ss, L.d_scores, N, j.min_score, L.stream);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(ss.h_meta, ss.d_meta, sizeof(SisMeta), hipMemcpyDeviceToHost, L.stream));
+  HIP_TRY(hipEventRecord(ss.ev[5], L.stream));
+  HIP_TRY(hipEventSynchronize(ss.ev[5]));
+  d2h += (long long)sizeof(SisMeta) + (N > 0 ? 4 : 0);
+  book_images();
+  if (ss.h_meta->img_status) {
+    set_images_status_error(ss.h_meta->img_status);
+    return GPD_ERR_CAPACITY;
+  }
+  if (L.h_flags->lenet) {
+    rc = lenet_check(L.lenet_scratch);  // clears the device word, sets the error text
+    return rc ? rc : GPD_ERR_HIP;
+  }
+  if (ss.h_meta->centres != centres || ss.h_meta->candidates != N) {
+    set_error("gpd_hip_detect_sis: the accumulated records form %d hand sets of %d candidates, the plans counted %d of %d", ss.h_meta->centres,
+              ss.h_meta->candidates, centres, N);
+    return GPD_ERR_STATE;
+  }
+  int k = N > 0 ? ss.h_meta->kept : 0;
+  const gpd_hand *d_res = ss.d_keep;
+  if (j.min_inliers > 0 && k > 0) {
+    StageRange r_("gpd:find_clusters (detect_sis)");
+    rc = cluster_run_resident(ctx->cluster, ss.d_keep, k, j.min_inliers, j.remove_inliers, L.stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(&ss.h_meta->kept, ctx->cluster.d_num, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+    HIP_TRY(hipStreamSynchronize(L.stream));
+    d2h += 4;
+    k = ss.h_meta->kept;
+    d_res = ctx->cluster.d_out;
+  }
+  j.num_hands = k;
+  j.rounds_run = rounds_run;
+  j.num_sets = centres;
+  j.num_candidates = N;
+  if (k > j.capacity) {
+    set_error("gpd_hip_detect_sis: %d hand records to return, the caller's buffer holds %d", k, j.capacity);
+    return GPD_ERR_CAPACITY;
+  }
+  if (j.centres_out && centres > j.centres_capacity) {
+    set_error("gpd_hip_detect_sis: %d live centres, centres_out holds %d", centres, j.centres_capacity);
+    return GPD_ERR_CAPACITY;
+  }
+  const size_t b_rec = (size_t)k * sizeof(gpd_hand);
+  const size_t b_smp = j.samples_out ? (size_t)rounds_run * j.num_samples * 3 * sizeof(double) : 0;
+  const size_t b_cen = j.centres_out ? (size_t)centres * 3 * sizeof(double) : 0;
+  if (b_rec + b_smp + b_cen > 0) {
+    if (b_rec + b_smp + b_cen > ss.h_out_bytes) {
+      note_alloc(__func__);
+      if (ss.h_out) (void)hipHostFree(ss.h_out);
+      ss.h_out = nullptr;
+      ss.h_out_bytes = 0;
+      const size_t cap = b_rec + b_smp + b_cen + (b_rec + b_smp + b_cen) / 8;
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ss.h_out), cap, 0));
+      ss.h_out_bytes = cap;
+    }
+    if (b_rec) HIP_TRY(hipMemcpyAsync(ss.h_out, d_res, b_rec, hipMemcpyDeviceToHost, L.stream));  // the result: one copy
+    if (b_smp) HIP_TRY(hipMemcpyAsync(ss.h_out + b_rec, ss.d_samples, b_smp, hipMemcpyDeviceToHost, L.stream));
+    if (b_cen) HIP_TRY(hipMemcpyAsync(ss.h_out + b_rec + b_smp, ss.d_centres, b_cen, hipMemcpyDeviceToHost, L.stream));
+  }
+  HIP_TRY(hipEventRecord(ss.ev[4], L.stream));
+  HIP_TRY(hipEventSynchronize(ss.ev[4]));
+  (void)hipEventElapsedTime(&j.stage_ms[3], ss.ev[3], ss.ev[4]);
+  d2h += (long long)(b_rec + b_smp + b_cen);
+  if (b_rec) std::memcpy(j.hands, ss.h_out, b_rec);
+  if (b_smp) std::memcpy(j.samples_out, ss.h_out + b_rec, b_smp);
+  if (b_cen) std::memcpy(j.centres_out, ss.h_out + b_rec + b_smp, b_cen);
   j.d2h_bytes = d2h;
   return GPD_OK;
 }

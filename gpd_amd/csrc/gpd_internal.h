@@ -144,6 +144,9 @@ struct ClusterState {
 void cluster_free(ClusterState &s);
 int cluster_run(ClusterState &s, const gpd_hand *hands, const double *scores, int n, int min_inliers, int remove_inliers, gpd_hand *out,
                 double *out_scores, int32_t *out_src, int *num_out, hipStream_t stream);
+// the same on n records that are on the device already (gpd_hip_detect_sis), scores = (double)record.score: the clusters are left
+// in s.d_out, their number in s.d_num; nothing waits for the device
+int cluster_run_resident(ClusterState &s, const gpd_hand *d_hands, int n, int min_inliers, int remove_inliers, hipStream_t stream);
 
 // ---- Cloud (search.hip) -----------------------------------------------------
 // Device copy of what the path reads from util::Cloud, as SoA for coalesced streaming.
@@ -255,6 +258,10 @@ struct SampleGather {
   const int32_t *d_list = nullptr;  // nullptr: the positions are the indices
   int list_size = 0;
   const int32_t *d_pos = nullptr;   // [S]
+  // non-null: the samples are these device-resident coordinates [S][3] instead (gpd_hip_detect_sis: sis_draw_kernel wrote
+  // them); the search reads them in place, with gpd_hip_search_samples' semantics — the queries use their float cast, the
+  // frames keep the doubles.  d_list / d_pos are not read then.
+  const double *d_xyz = nullptr;
 };
 int search_run(const gpd_params &p, const Cloud &c, SearchState &s, const int32_t *sample_idx, const double *sample_xyz, int S,
                hipStream_t stream, bool sync_counts = true, const SampleGather *resident = nullptr);
@@ -305,6 +312,56 @@ size_t label_out_layout(size_t k, size_t image_bytes, size_t off[4]);
 // balanceInstances over the n accumulated labels on the device (balance_model.h is the definition) and the gather of the `end`
 // kept positives and negatives into ls.d_out; nothing waits for the device
 int label_select_gather(LabelState &ls, int n, int end, hipStream_t stream);
+
+// ---- gpd_hip_detect_sis: the draw, the accumulators of the rounds, the final selection (sis.hip; the definition: sis_model.h) --
+constexpr int kSisDrawThreads = 512;  // sis_draw_kernel: proposals per step of its one workgroup
+constexpr int kSisCentreTile = 512;   // ... and centres per LDS tile of the nearest-centre test
+struct SisMeta {  // device words of a call; a copy travels to pinned memory behind every draw and at the end
+  int32_t acc_g, used_g, acc_u, used_u;  // the round's draw: samples accepted / proposals consumed per stream
+  int32_t centres;                       // live centres accumulated
+  int32_t candidates;                    // candidate records accumulated
+  int32_t kept;                          // records with score > min_score
+  int32_t img_status;                    // capacity flags of the image kernels of the rounds so far
+};
+struct SisState {
+  size_t cap = 0;                  // candidates the accumulators hold
+  size_t image_bytes = 0;          // 3600 * C
+  uint8_t *d_images = nullptr;     // [cap][C][60][60] planar, as the LeNet reads them
+  gpd_hand *d_hands = nullptr;     // [cap] candidate records, set_index = index in the accumulated live list
+  gpd_hand *d_keep = nullptr;      // [cap] the records with score > min_score, in order
+  double *d_centres = nullptr;     // [cap_centres][3] samples of the live hand sets, in accumulated order
+  size_t cap_centres = 0;
+  double *d_round_xyz = nullptr;   // [cap_round][3] the samples of the round in flight: sis_draw_kernel writes, the search reads
+  double *d_samples = nullptr;     // [cap_samples][3] the samples of every round, for samples_out
+  size_t cap_round = 0, cap_samples = 0;
+  int32_t *d_uniform = nullptr;    // [cap_uniform] the uniform source list
+  size_t cap_uniform = 0;
+  void *d_gauss = nullptr;         // [cap_block] sis::Proposal, the block in flight
+  unsigned long long *d_unif = nullptr;  // [cap_block] pos_raw
+  char *h_block = nullptr;         // pinned: [cap_block] Proposal, then [cap_block] pos_raw
+  size_t cap_block = 0;
+  SisMeta *d_meta = nullptr;
+  SisMeta *h_meta = nullptr;       // pinned
+  char *h_out = nullptr;           // pinned: records | samples | centres
+  size_t h_out_bytes = 0;
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // draw start / end, accumulate end, tail start / end, words
+  int grows = 0;
+};
+void sis_free(SisState &ss);
+int sis_init(SisState &ss);
+// room for `need` accumulated candidates and `centres` live centres, the first `used` / `used_centres` kept across a growth
+// (by half, device to device); GPD_ERR_CAPACITY beyond 16 GB
+int sis_reserve(SisState &ss, size_t need, size_t used, size_t centres, size_t used_centres, size_t image_bytes, hipStream_t stream);
+int sis_reserve_round(SisState &ss, size_t round_samples, size_t all_samples, size_t uniform, size_t block);
+// one block of each stream through the selection rule; continues from the counts in ss.d_meta.  Nothing waits for the device.
+int sis_draw(SisState &ss, const Cloud &c, int L, int n_gauss, int n_unif, int n_uniform_list, const double ws[6], int method, int num_gauss,
+             int num_rand, hipStream_t stream);
+// the round's n candidate records at ss.d_hands + acc (set-major, as plan_emit_hands left them): their live sets' samples join
+// the centre list behind the centres_before it holds, set_index becomes the index in the accumulated live list; the image kernels'
+// capacity flags (d_img_status) are folded into the call's
+int sis_accumulate(SisState &ss, size_t acc, int n, int centres_before, const int32_t *d_img_status, hipStream_t stream);
+// scores into the n accumulated records; those with score > min_score, in order, into ss.d_keep, their number into d_meta->kept
+int sis_select(SisState &ss, const float *d_scores, int n, double min_score, hipStream_t stream);
 
 // GraspDetector::filterGraspsWorkspace (grasp_detector.cpp:334-398) [+ filterGraspsDirection, :423-456] for one valid
 // hand: aperture and the workspace box around the hand's outline [, then the approach direction].  The reference computes right_top from left_bottom

@@ -2728,15 +2728,16 @@ int search_join(SearchState &s, hipStream_t stream) {
   return GPD_OK;
 }
 
-static int run_neighbourhoods(const gpd_params &p, const Cloud &c, SearchState &s, const HostConsts &hc, int S, int cap, bool by_xyz,
-                              int slots, bool want_height_list, hipStream_t stream, bool sync_counts) {
+static int run_neighbourhoods(const gpd_params &p, const Cloud &c, SearchState &s, const HostConsts &hc, int S, int cap,
+                              const double *d_xyz /* device; null: by index */, int slots, bool want_height_list, hipStream_t stream,
+                              bool sync_counts) {
   NbParams np;
   np.px = c.px; np.py = c.py; np.pz = c.pz; np.nx = c.nx; np.ny = c.ny; np.nz = c.nz;
   np.pxyz = c.pxyz;
   np.pnrm = c.pnrm;
   np.num_points = c.num_points;
   np.sample_idx = s.d_sample_idx;
-  np.sample_xyz = by_xyz ? s.d_sample_xyz : nullptr;
+  np.sample_xyz = d_xyz;
   // pcl::KdTreeFLANN::radiusSearch passes (float)(radius*radius) to FLANN
   const double r_all = std::fmax(hc.nn_radius_hands, std::fmax(hc.nn_radius_images, p.nn_radius_frames));
   np.r2_all = (float)(r_all * r_all);
@@ -2830,7 +2831,9 @@ static int neighbourhoods(const gpd_params &p, const Cloud &c, SearchState &s, c
   int rc = search_reserve(s, S, cap, slots);
   if (rc) return rc;
   for (;;) {
-    if (resident) {  // the indices are on the device already (and stay where they were: a retry gathers them again)
+    if (resident && resident->d_xyz) {
+      // coordinates on the device already: read where they are (a retry reads them again)
+    } else if (resident) {  // the indices are on the device already (and stay where they were: a retry gathers them again)
       sample_gather_kernel<<<(S + 255) / 256, 256, 0, stream>>>(resident->d_list, resident->list_size, resident->d_pos, S, s.d_sample_idx);
       HIP_RET(hipGetLastError());
     } else if (sample_xyz) {
@@ -2838,7 +2841,8 @@ static int neighbourhoods(const gpd_params &p, const Cloud &c, SearchState &s, c
     } else {
       HIP_RET(hipMemcpyAsync(s.d_sample_idx, sample_idx, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     }
-    rc = run_neighbourhoods(p, c, s, hc, S, cap, sample_xyz != nullptr, slots, want_height_list, stream, sync_counts);
+    rc = run_neighbourhoods(p, c, s, hc, S, cap, resident && resident->d_xyz ? resident->d_xyz : (sample_xyz ? s.d_sample_xyz : nullptr), slots,
+                            want_height_list, stream, sync_counts);
     if (rc) return rc;
     if (!sync_counts) break;  // the caller reads `worst found` from the plan summary and retries (search_next_capacity)
     int worst = 0;
@@ -3051,7 +3055,7 @@ int label_round(const gpd_params &p, const Cloud &gt, SearchState &gs, gpd_hand 
     if (rc) return rc;
     label_sets_kernel<<<1, 1024, 0, stream>>>(d_recs, n, d_cand_list, gs.d_sample_xyz, d_meta);
     HIP_RET(hipGetLastError());
-    rc = run_neighbourhoods(p, gt, gs, hc, lists, cap, /*by_xyz=*/true, slots, /*want_height_list=*/false, stream, /*sync_counts=*/false);
+    rc = run_neighbourhoods(p, gt, gs, hc, lists, cap, gs.d_sample_xyz, slots, /*want_height_list=*/false, stream, /*sync_counts=*/false);
     if (rc) return rc;
     {
       std::unique_lock<std::mutex> consts_lock;  // held until the kernel that reads c_hand is enqueued

@@ -108,6 +108,7 @@ class GraspDetector {
   const double *lastRuntimes() const { return runtimes_; }
 
  private:
+  friend class SequentialImportanceSampling;  // its resident route uploads the cloud and runs on this detector's context
   bool upload(const util::Cloud &cloud);
   // device search for the cloud's samples (coordinates if set, else indices); recs sized here
   bool searchDevice(const util::Cloud &cloud, bool fused, std::vector<gpd_hand> &recs, int &n_sets, int &n_cand);

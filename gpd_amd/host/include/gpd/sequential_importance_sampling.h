@@ -6,6 +6,9 @@
 // The reference draws with rand() and a std::random_device-seeded mt19937; here one seeded xorshift
 // generator (Box-Muller normals) so that runs are reproducible.  GPD_SIS_DUMP=<file> writes the
 // samples of every round (tests replay them through the oracle).
+// cfg hip_sis_resident = 1: detectGrasps is cloud.subsample(num_init_samples) plus ONE gpd_hip_detect_sis call — the rounds, the
+// draws (the seeded streams of gpd_amd/csrc/sis_model.h, seed = random_seed), the accumulated hand sets, the classification and
+// the clustering stay on the device; the default 0 is the host loop over the separate calls.
 #pragma once
 #include <array>
 #include <memory>
@@ -24,6 +27,7 @@ class SequentialImportanceSampling {
   GraspDetector &detector() { return *grasp_detector_; }
 
  private:
+  std::vector<std::unique_ptr<candidate::Hand>> detectGraspsResident(util::Cloud &cloud);
   void drawSamplesFromSumOfGaussians(const std::vector<std::unique_ptr<candidate::HandSet>> &hand_sets, double sigma, int num_gauss_samples,
                                      std::vector<double> &samples_out);
   void drawSamplesFromMaxOfGaussians(const std::vector<std::unique_ptr<candidate::HandSet>> &hand_sets, double sigma, int num_gauss_samples,
@@ -44,6 +48,8 @@ class SequentialImportanceSampling {
   std::array<double, 3> direction_;
   double thresh_rad_;
   unsigned long long rng_state_;
+  bool resident_ = false;  // cfg hip_sis_resident
+  unsigned seed_ = 0;      // cfg random_seed, as the resident route's streams take it
 };
 
 }  // namespace gpd

@@ -1385,6 +1385,8 @@ SequentialImportanceSampling::SequentialImportanceSampling(const std::string &co
   direction_ = {approach[0], approach[1], approach[2]};
   thresh_rad_ = config_file.getValueOfKey<double>("thresh_rad", 2.3);
   rng_state_ = 0x9E3779B97F4A7C15ull ^ (unsigned long long)config_file.getValueOfKey<int>("random_seed", 0);
+  seed_ = (unsigned)config_file.getValueOfKey<int>("random_seed", 0);
+  resident_ = config_file.getValueOfKey<int>("hip_sis_resident", 0) != 0;
   grasp_detector_ = std::make_unique<GraspDetector>(config_filename);
   clustering_ = std::make_unique<Clustering>(config_file.getValueOfKey<int>("min_inliers", 1));
   if (grasp_detector_->context()) clustering_->setContext(grasp_detector_->context());
@@ -1471,6 +1473,7 @@ std::vector<std::unique_ptr<candidate::Hand>> SequentialImportanceSampling::dete
     printf("Error: Point cloud is empty!");
     return none;
   }
+  if (resident_) return detectGraspsResident(cloud);
   const double t0 = now_s();
   FILE *dump = getenv("GPD_SIS_DUMP") ? fopen(getenv("GPD_SIS_DUMP"), "w") : nullptr;
   // 1. initial grasp hypotheses
@@ -1524,6 +1527,75 @@ std::vector<std::unique_ptr<candidate::Hand>> SequentialImportanceSampling::dete
     valid_grasps = clustering_->findClusters(valid_grasps);
     if (clustering_->failed()) printf("ERROR: the clustering step failed; no grasps returned.\n");
   }
+  printf("Final result: found %zu grasps.\n", valid_grasps.size());
+  printf("Total runtime: %3.4fs\n.\n", now_s() - t0);
+  return valid_grasps;
+}
+
+// :54-187 as ONE gpd_hip_detect_sis call (cfg hip_sis_resident = 1): the initial samples are drawn here, everything after them
+// happens on the device; the lines of the rounds are printed from round_counts, GPD_SIS_DUMP is written from samples_out
+std::vector<std::unique_ptr<candidate::Hand>> SequentialImportanceSampling::detectGraspsResident(util::Cloud &cloud) {
+  std::vector<std::unique_ptr<candidate::Hand>> none;
+  const double t0 = now_s();
+  cloud.setSamples({});
+  cloud.subsample(num_init_samples_);
+  if (!grasp_detector_->upload(cloud)) return none;
+  const std::vector<int> &idx = cloud.getSampleIndices();
+  const std::vector<int32_t> init(idx.begin(), idx.end());
+  const gpd_params &p = grasp_detector_->getParams();
+  const size_t slots = (size_t)p.num_hand_axes * p.num_orientations;
+  const size_t iters = (size_t)std::max(num_iterations_, 0), per = (size_t)std::max(num_samples_, 0);
+  std::vector<gpd_hand> recs(std::max((init.size() + iters * per) * slots, (size_t)1));
+  std::vector<double> samples(std::max(iters * per * 3, (size_t)1));
+  std::vector<int32_t> counts((1 + iters) * 4, 0);
+  gpd_sis_job job;
+  std::memset(&job, 0, sizeof(job));
+  job.sample_indices = init.data();
+  job.num_init_samples = (int)init.size();
+  job.num_iterations = num_iterations_;
+  job.num_samples = num_samples_;
+  job.sampling_method = sampling_method_;
+  job.prob_rand_samples = prob_rand_samples_;
+  job.sigma = radius_;
+  job.min_score = min_score_;
+  for (int a = 0; a < 6; a++) job.workspace[a] = workspace_[a];
+  job.min_inliers = clustering_->getMinInliers();
+  job.seed = seed_;
+  job.hands = recs.data();
+  job.capacity = (int)std::min(recs.size(), (size_t)0x7fffffff);
+  job.samples_out = samples.data();
+  job.round_counts = counts.data();
+  if (gpd_hip_detect_sis(grasp_detector_->context(), &job) != GPD_OK) {
+    printf("ERROR: %s\n", gpd_hip_last_error());
+    return none;
+  }
+  if (const char *path = getenv("GPD_SIS_DUMP")) {
+    if (FILE *dump = fopen(path, "w")) {
+      fprintf(dump, "INIT %zu\n", init.size());
+      for (int i : init) fprintf(dump, "%d\n", i);
+      for (int r = 0; r < job.rounds_run; r++) {
+        fprintf(dump, "ROUND %d %d\n", r, num_samples_);
+        const double *s = samples.data() + (size_t)r * per * 3;
+        for (size_t k = 0; k < per; k++) fprintf(dump, "%.17g %.17g %.17g\n", s[3 * k], s[3 * k + 1], s[3 * k + 2]);
+      }
+      fclose(dump);
+    }
+  }
+  printf("Grasps within workspace: %d\n", counts[0]);
+  const int num_gauss_samples = num_samples_ - (int)(prob_rand_samples_ * num_samples_);
+  int total = counts[0];
+  for (int r = 0; r < job.rounds_run; r++) {
+    std::cout << r << " " << num_gauss_samples << std::endl;
+    total += counts[4 * (r + 1)];
+    printf("Added %d grasp candidates in round %d. Total: %d.\n", counts[4 * (r + 1)], r, total);
+  }
+  std::vector<std::unique_ptr<candidate::Hand>> valid_grasps;
+  for (int k = 0; k < job.num_hands; k++) {
+    auto h = std::make_unique<candidate::Hand>(recs[k]);
+    h->setScore(recs[k].score);
+    valid_grasps.push_back(std::move(h));
+  }
+  if (job.min_inliers <= 0) printf("Valid grasps: %zu\n", valid_grasps.size());
   printf("Final result: found %zu grasps.\n", valid_grasps.size());
   printf("Total runtime: %3.4fs\n.\n", now_s() - t0);
   return valid_grasps;

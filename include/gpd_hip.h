@@ -317,6 +317,88 @@ typedef struct gpd_label_view_job {          /* zero it first */
 int gpd_hip_label_view(gpd_hip_ctx *ctx, gpd_label_view_job *job);
 int gpd_hip_sizeof_label_view_job(void);
 
+/* The draws of SequentialImportanceSampling::detectGrasps (sequential_importance_sampling.cpp:189-270) — host only, no context;
+ * the definition (gpd_amd/csrc/sis_model.h) the device draw of gpd_hip_detect_sis equals.  The reference draws from
+ * std::random_device, rand() and static std::normal_distributions; here round r (0-based, after the initial pass) has two
+ * xorshift64 streams (the one described at gpd_detect_job::num_draws), seeds in uint32 arithmetic: kind 0, the Gaussian
+ * proposals, seed + 1000003 * (2r); kind 1, the uniform ones, seed + 1000003 * (2r + 1).
+ * A Gaussian proposal takes 7 draws: idx_raw, then three offsets sigma * sqrt(-2 log u1) * cos(2 pi u2) of two draws each
+ * (u1 = ((draw >> 11) + 1) / (2^53 + 1), u2 = (draw >> 11) / 2^53, the host's libm).  A uniform proposal is one draw, pos_raw.
+ * gpd_hip_sis_proposals writes proposals first .. first + count of a stream: kind 0 into gpd_sis_proposal[count], kind 1 into
+ * uint64_t[count] (sigma is not read).  GPD_ERR_INVALID: a NULL out with count > 0, a negative round / first / count, a kind
+ * other than 0 or 1, sigma <= 0 for kind 0. */
+typedef struct gpd_sis_proposal {
+  uint64_t idx_raw;
+  double off[3];
+} gpd_sis_proposal;
+int gpd_hip_sis_proposals(uint32_t seed, int round, int kind, long long first, int count, double sigma, void *out);
+
+/* The selection rule over one block of each stream.  centres: the samples of the hand sets that keep a valid hand after
+ * filterGraspsWorkspace (and the direction filter), in accumulated order, num_centres >= 1.
+ *  - Gaussian: idx = idx_raw % num_centres, x = centre[idx] + off.  sampling_method 0 (SUM_OF_GAUSSIANS, :189-201) accepts every
+ *    proposal; 1 (MAX_OF_GAUSSIANS, :203-237) accepts iff d2(x, centre[idx]) <= min over k of d2(x, centre[k]), d2 = (dx*dx + dy*dy)
+ *    + dz*dz in double.  (The reference compares term * exp(-d2 / (2 sigma)) with >=: what is accepted here is accepted there.)
+ *  - uniform: the point uniform_list[pos_raw % num_uniform_list] (uniform_list NULL: the point pos_raw % num_points) as the float
+ *    coordinates of cloud_xyz cast to double, accepted iff inside workspace[6] with inclusive bounds (:263-265).
+ *  - samples ((num_gauss + num_rand) x 3 doubles): the first num_gauss accepted Gaussian proposals in proposal order, then the
+ *    first num_rand accepted uniform ones.
+ * accepted[2] / consumed[2] (Gaussian, uniform) are in/out: zero them for a round's first blocks, pass them on unchanged with the
+ * NEXT blocks of the streams when *shortfall (samples still missing) is > 0 — the result equals one long block.  consumed
+ * counts the proposals up to and including the one that filled the list.
+ * GPD_ERR_INVALID: a NULL argument that is needed, num_centres < 1 with num_gauss > 0, a method other than 0 or 1, an index of
+ * uniform_list out of range. */
+int gpd_hip_sis_select(const double *centres, int num_centres, const gpd_sis_proposal *gauss, int num_gauss_proposals,
+                       const uint64_t *uniform, int num_uniform_proposals, const int32_t *uniform_list, int num_uniform_list,
+                       const float *cloud_xyz, int num_points, const double *workspace, int sampling_method, int num_gauss, int num_rand,
+                       double *samples, int32_t *accepted, int32_t *consumed, int *shortfall);
+
+/* SequentialImportanceSampling::detectGrasps (sequential_importance_sampling.cpp:54-187) on the cloud uploaded last, the round
+ * loop kept on the device:
+ *  - the initial pass (:63-82) is the front half of gpd_hip_detect on sample_indices: index search, filterGraspsWorkspace, the
+ *    direction filter when set, images of the valid hands;
+ *  - round r (:95-160) draws num_samples samples around the live centres found so far (gpd_hip_sis_select on proposal blocks
+ *    the host generates, applied by a kernel that writes the samples where the search reads them), searches them by
+ *    coordinates (gpd_hip_search_samples' semantics) and appends live centres, candidate records and images to accumulators
+ *    on the device.  set_index of a record is the index of its hand set in the accumulated live list; the order is round-major,
+ *    set-major, slot-minor.  The shadow stream runs on through the rounds, so every hand set sits in it where ONE
+ *    createImages over the whole list (:167) puts it.  Rounds end after num_iterations or when no live centre exists (:79-82);
+ *  - ONE LeNet pass over all accumulated images (:164-167), in the context's LeNet mode; records with score > min_score (strict)
+ *    are kept in order; with min_inliers > 0 they go through Clustering::findClusters (:175-181) and `hands` receives what
+ *    gpd_hip_find_clusters returns on that list.
+ * Per round only small words come back (the plan summary, the draw counts, the capacity flags); the records leave in one copy.
+ * GPD_ERR_INVALID before any work: an index out of range, num_samples < 1 with num_iterations > 0, prob_rand_samples outside
+ * [0, 1], sigma <= 0, a method other than 0 or 1, a NULL hands with capacity > 0, a negative count.  GPD_ERR_STATE: no cloud, no
+ * weights, or a call while gpd_hip_detect_batch drives the lanes.  GPD_ERR_CAPACITY: capacity smaller than the result (num_hands
+ * still says how many there were), centres_capacity smaller than the live list, or accumulators beyond 16 GB. */
+typedef struct gpd_sis_job {                 /* zero it first */
+  const int32_t *sample_indices;             /* in: the initial pass; also the source of the uniform proposals (cloud.getSampleIndices(), */
+  int32_t num_init_samples;                  /*     :246-252); none: every point of the cloud is a uniform source                          */
+  int32_t num_iterations;                    /* rounds after the initial pass */
+  int32_t num_samples;                       /* samples per round */
+  int32_t sampling_method;                   /* 0: SUM_OF_GAUSSIANS, 1: MAX_OF_GAUSSIANS */
+  double prob_rand_samples;                  /* share of uniform samples per round: num_rand = (int)(prob * num_samples) */
+  double sigma;                              /* standard deviation of the Gaussian offsets */
+  double min_score;                          /* records are kept for score > min_score */
+  double workspace[6];                       /* of the uniform proposals (cfg workspace) */
+  int32_t min_inliers, remove_inliers;       /* clustering; min_inliers <= 0: none */
+  uint32_t seed;
+  int32_t proposal_block;                    /* proposals per stream and block; 0: sized from the acceptance rate so far */
+  gpd_hand *hands;                           /* out: capacity records */
+  int32_t capacity;
+  int32_t num_hands;                         /* out: records written (GPD_ERR_CAPACITY: records there were) */
+  int32_t rounds_run;                        /* out: rounds after the initial pass that ran */
+  int32_t num_sets, num_candidates;          /* out: accumulated live hand sets / candidates */
+  int32_t centres_capacity;                  /* in: centres centres_out can take */
+  double *samples_out;                       /* out, may be NULL: num_iterations x num_samples x 3, the samples of every round run */
+  double *centres_out;                       /* out, may be NULL: centres_capacity x 3, the accumulated live centres */
+  int32_t *round_counts;                    /* out, may be NULL: (1 + num_iterations) x {live sets, candidates, Gaussian proposals
+                                                consumed, uniform proposals consumed}; row 0 is the initial pass */
+  int64_t d2h_bytes;                         /* out: bytes this call copied device -> host */
+  float stage_ms[4];                         /* out: draw, search, images + accumulate, LeNet + select + cluster (HIP events) */
+} gpd_sis_job;
+int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job);
+int gpd_hip_sizeof_sis_job(void);
+
 /* Replaces ImageGenerator::createImages (image_generator.cpp:17-99) for hand
  * sets produced by the last gpd_hip_search / gpd_hip_detect on this context (optionally after
  * the host filters, grasp_detector.cpp:334-398 / :422-453, which clear `valid`: only the `valid`
