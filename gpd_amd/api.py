@@ -90,6 +90,19 @@ class TrainParams(C.Structure):
                 ("eps", C.c_double), ("weight_decay", C.c_double), ("input_scale", C.c_double)]
 
 
+class TrainRecipe(C.Structure):
+    """Mirror of `gpd_train_recipe` (include/gpd_hip.h)."""
+    _fields_ = [("network", C.c_int32), ("solver", C.c_int32), ("momentum", C.c_double), ("lr_policy", C.c_int32), ("stepsize", C.c_int32),
+                ("gamma", C.c_double), ("power", C.c_double), ("lr_mult", C.c_double * 8), ("decay_mult", C.c_double * 8)]
+
+
+# gpd_train_recipe's enums, and the solver file's base_lr (it belongs in TrainParams.lr)
+NET_TORCH, NET_CAFFE = 0, 1
+SOLVER_ADAM, SOLVER_SGD = 0, 1
+LR_FIXED, LR_STEP, LR_EXP, LR_INV = 0, 1, 2, 3
+CAFFE_BASE_LR = 0.01
+
+
 class GpdHipError(RuntimeError):
     pass
 
@@ -234,7 +247,9 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_train_default_params", "gpd_hip_train_create", "gpd_hip_train_destroy", "gpd_hip_train_init_state",
            "gpd_hip_train_set_state", "gpd_hip_train_get_state", "gpd_hip_train_set_data", "gpd_hip_train_steps",
            "gpd_hip_train_gradients", "gpd_hip_train_apply", "gpd_hip_train_eval", "gpd_hip_train_step_timed",
-           "gpd_hip_train_kernel_name"]
+           "gpd_hip_train_kernel_name", "gpd_hip_sizeof_train_recipe", "gpd_hip_train_default_recipe", "gpd_hip_train_create_recipe",
+           "gpd_hip_train_init_xavier", "gpd_hip_train_learning_rate", "gpd_hip_train_get_solver_state",
+           "gpd_hip_train_set_solver_state", "gpd_hip_train_kernel_name_of"]
 
 
 def build(prof=True):
@@ -319,6 +334,15 @@ def lib():
         L.gpd_hip_train_step_timed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.gpd_hip_train_kernel_name.argtypes = [C.c_int]
         L.gpd_hip_train_kernel_name.restype = C.c_char_p
+        L.gpd_hip_train_default_recipe.argtypes = [C.POINTER(TrainRecipe), C.c_int]
+        L.gpd_hip_train_create_recipe.argtypes = [C.c_void_p, C.POINTER(TrainParams), C.POINTER(TrainRecipe), C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_init_xavier.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_learning_rate.argtypes = [C.POINTER(TrainRecipe), C.c_double, C.c_longlong, C.POINTER(C.c_float)]
+        L.gpd_hip_train_get_solver_state.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
+        L.gpd_hip_train_set_solver_state.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_longlong]
+        L.gpd_hip_train_kernel_name_of.argtypes = [C.c_void_p, C.c_int]
+        L.gpd_hip_train_kernel_name_of.restype = C.c_char_p
+        assert L.gpd_hip_sizeof_train_recipe() == C.sizeof(TrainRecipe)
         assert L.gpd_hip_sizeof_label_view_job() == C.sizeof(LabelViewJob)
         assert L.gpd_hip_sizeof_sis_job() == C.sizeof(SisJob)
         _LIB = L
@@ -815,13 +839,60 @@ def init_state(channels, seed=0):
     return dict(zip(TORCH_KEYS, arrs))
 
 
-class Trainer:
-    """One gpd_hip_trainer on a Context's device and stream: Net (pytorch/network.py) under softmax cross-entropy and Adam, as
-    pytorch/train_net3.py trains it.  The state travels as a dict of numpy arrays in torch layout, both ways.  Close it before
-    its context."""
+def _lib_check(rc):
+    if rc != 0:
+        raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
 
-    def __init__(self, ctx, params=None, **kw):
+
+def train_default_recipe(which=0, **kw):
+    """gpd_hip_train_default_recipe: 0 — today's trainer (Net, Adam, fixed rate); 1 — the reference's Caffe files (the network
+    without conv ReLUs, SGD with momentum 0.9, lr_policy inv with gamma 1e-4 and power 0.75; their base_lr CAFFE_BASE_LR goes
+    into TrainParams.lr).  kw: fields to change; lr_mult / decay_mult take eight values or a {tensor name: value} dict."""
+    r = TrainRecipe()
+    _lib_check(lib().gpd_hip_train_default_recipe(C.byref(r), int(which)))
+    for k, v in kw.items():
+        if k not in dict(TrainRecipe._fields_):
+            raise TypeError("gpd_train_recipe has no field %r" % k)
+        if k in ("lr_mult", "decay_mult"):
+            cur = list(getattr(r, k))
+            if isinstance(v, dict):
+                for name, x in v.items():
+                    cur[TORCH_KEYS.index(name)] = float(x)
+            else:
+                cur = [float(x) for x in v]
+                if len(cur) != 8:
+                    raise ValueError("%s takes eight values" % k)
+            v = (C.c_double * 8)(*cur)
+        setattr(r, k, v)
+    return r
+
+
+def init_xavier(channels, seed=0):
+    """gpd_hip_train_init_xavier: Caffe's xavier filler from the project's seeded stream — weights U(-sqrt(3 / fan_in),
+    sqrt(3 / fan_in)), biases 0 (host only) -> {key: f32 array in torch layout}."""
+    if int(channels) not in (1, 3, 12, 15):
+        raise GpdHipError("libgpd_hip error -1: init_xavier: %d channels (1, 3, 12 or 15)" % int(channels))
+    arrs, ptrs = _state_buffers(channels)
+    _lib_check(lib().gpd_hip_train_init_xavier(int(channels), int(seed) & 0xFFFFFFFF, ptrs))
+    return dict(zip(TORCH_KEYS, arrs))
+
+
+def learning_rate(recipe, base_lr, it):
+    """gpd_hip_train_learning_rate: the rate of update `it` (0-based) under the recipe's policy, as the step uses it -> np.float32"""
+    lr = C.c_float(0)
+    _lib_check(lib().gpd_hip_train_learning_rate(C.byref(recipe), float(base_lr), int(it), C.byref(lr)))
+    return np.float32(lr.value)
+
+
+class Trainer:
+    """One gpd_hip_trainer on a Context's device and stream.  Without a recipe: Net (pytorch/network.py) under softmax
+    cross-entropy and Adam, as pytorch/train_net3.py trains it.  recipe (train_default_recipe): the network with or without conv
+    ReLUs, Adam or Caffe's SGD, a learning-rate policy.  The state travels as a dict of numpy arrays in torch layout, both ways.
+    Close it before its context."""
+
+    def __init__(self, ctx, params=None, recipe=None, **kw):
         self.params = params if params is not None else train_default_params(ctx.params.image_num_channels)
+        self.recipe = recipe
         for k, v in kw.items():
             if k not in dict(TrainParams._fields_):
                 raise TypeError("gpd_train_params has no field %r" % k)
@@ -829,7 +900,12 @@ class Trainer:
         self.channels = int(self.params.channels)
         self._ctx = ctx  # keeps the context (the stream) alive
         self._h = C.c_void_p()
-        self._check(lib().gpd_hip_train_create(ctx._h, C.byref(self.params), C.byref(self._h)))
+        if recipe is None:
+            self._check(lib().gpd_hip_train_create(ctx._h, C.byref(self.params), C.byref(self._h)))
+        else:
+            self._check(lib().gpd_hip_train_create_recipe(ctx._h, C.byref(self.params), C.byref(recipe), C.byref(self._h)))
+        self.caffe_network = recipe is not None and recipe.network == NET_CAFFE
+        self.sgd = recipe is not None and recipe.solver == SOLVER_SGD
 
     _check = Context._check
 
@@ -845,7 +921,7 @@ class Trainer:
             pass
 
     def set_state(self, state):
-        """The eight tensors; Adam's moments and the step count start again."""
+        """The eight tensors; the solver's buffers (Adam's moments, SGD's history) and the update count start again."""
         arrs, ptrs = _state_pointers(state, self.channels)
         self._check(lib().gpd_hip_train_set_state(self._h, ptrs))
 
@@ -853,6 +929,20 @@ class Trainer:
         arrs, ptrs = _state_buffers(self.channels)
         self._check(lib().gpd_hip_train_get_state(self._h, ptrs))
         return dict(zip(TORCH_KEYS, arrs))
+
+    def get_solver_state(self):
+        """-> dict(count = updates since set_state, m = {key: array}: Adam's exp_avg or SGD's history, v = Adam's exp_avg_sq or None)"""
+        m, mp = _state_buffers(self.channels)
+        v, vp = _state_buffers(self.channels) if not self.sgd else (None, None)
+        n = C.c_longlong(0)
+        self._check(lib().gpd_hip_train_get_solver_state(self._h, mp, vp, C.byref(n)))
+        return dict(count=int(n.value), m=dict(zip(TORCH_KEYS, m)), v=dict(zip(TORCH_KEYS, v)) if v is not None else None)
+
+    def set_solver_state(self, solver_state):
+        """What get_solver_state returned, after set_state: the run continues byte for byte."""
+        m, mp = _state_pointers(solver_state["m"], self.channels)
+        v, vp = (None, None) if self.sgd or solver_state.get("v") is None else _state_pointers(solver_state["v"], self.channels)
+        self._check(lib().gpd_hip_train_set_solver_state(self._h, mp, vp, int(solver_state["count"])))
 
     def set_data(self, images, labels, which=0):
         """The resident set `which` (0: training, 1: test): images u8 [n,60,60,C], labels u8 [n] of 0 / 1."""
@@ -863,7 +953,7 @@ class Trainer:
         self._check(lib().gpd_hip_train_set_data(self._h, int(which), _ptr(images), _ptr(labels), len(labels)))
 
     def steps(self, indices, batch=None):
-        """Adam steps on the training set: indices i32 [num_steps, batch] (or flat with `batch` given) -> each step's loss f32."""
+        """Steps of the recipe's solver (default Adam) on the training set: indices i32 [num_steps, batch] (or flat with `batch` given) -> each step's loss f32."""
         idx = np.ascontiguousarray(indices, np.int32)
         if batch is None:
             idx = idx.reshape(1, -1) if idx.ndim < 2 else idx
@@ -882,7 +972,7 @@ class Trainer:
         return dict(zip(TORCH_KEYS, arrs)), float(loss.value)
 
     def apply(self, grads):
-        """One Adam step from the host's gradients (a dict like gradients() returns)."""
+        """One step of the solver from the host's gradients (a dict like gradients() returns)."""
         arrs, ptrs = _state_pointers(grads, self.channels)
         self._check(lib().gpd_hip_train_apply(self._h, ptrs))
 
@@ -901,9 +991,12 @@ class Trainer:
         ms = np.zeros(32, np.float32)
         k = C.c_int(0)
         self._check(lib().gpd_hip_train_step_timed(self._h, _ptr(idx), len(idx), _ptr(ms), len(ms), C.byref(k)))
-        return [(lib().gpd_hip_train_kernel_name(i).decode(), float(ms[i])) for i in range(k.value)]
+        return [(lib().gpd_hip_train_kernel_name_of(self._h, i).decode(), float(ms[i])) for i in range(k.value)]
 
     def install(self, ctx=None, input_scale=None):
-        """get_state followed by Context.set_lenet_torch: the trained network becomes `ctx`'s (default: the trainer's own) scoring network."""
+        """get_state followed by Context.set_lenet_torch: the trained network becomes `ctx`'s (default: the trainer's own) scoring
+        network, with the conv ReLUs on for Net and off for the Caffe network."""
         ctx = self._ctx if ctx is None else ctx
         ctx.set_lenet_torch(self.get_state(), float(self.params.input_scale) if input_scale is None else input_scale)
+        if self.caffe_network:
+            ctx.set_lenet_conv_relu(False)

@@ -1,4 +1,5 @@
-// Training of pytorch/network.py::Net on the device: forward with pooling argmax, backward, Adam.
+// Training of pytorch/network.py::Net and of the Caffe LeNet (the same network without the ReLUs behind the convolutions) on
+// the device: forward with pooling argmax, backward, Adam or Caffe's SGD.
 //
 // Every GEMM-shaped pass is one instantiation of gemm32: a wave owns a 32 x 32 tile of the result and walks its K range with
 // v_mfma_f32_32x32x2_f32, whose result is a k-ascending f32 fmaf chain.  The operands are never materialised: an operand type
@@ -173,7 +174,9 @@ struct WeightByChannel {
 
 // ---- epilogues: lane (r = lane & 31, h = lane >> 5) holds column n0 + r, rows m0 + 8 (reg >> 2) + 4 h + (reg & 3) -----------
 
-// bias, 2 x 2 max-pool over the four consecutive rows of a register quad (first maximum in row-major window order), ReLU
+// bias, 2 x 2 max-pool over the four consecutive rows of a register quad (first maximum in row-major window order); RELU: the
+// pooled value clamped at zero and kMasked for a clamped one, otherwise (the Caffe network) the value as it is and its position
+template <bool RELU>
 struct PoolStore {
   const float *bias;
   float *out;
@@ -195,8 +198,13 @@ struct PoolStore {
         if (v > best) best = v, w = j;
       }
       const long long o = ((long long)(pm / pp) * F + f) * pp + pm % pp;
-      out[o] = best > 0.f ? best : 0.f;
-      arg[o] = (uint8_t)(best > 0.f ? w : kMasked);
+      if constexpr (RELU) {
+        out[o] = best > 0.f ? best : 0.f;
+        arg[o] = (uint8_t)(best > 0.f ? w : kMasked);
+      } else {
+        out[o] = best;
+        arg[o] = (uint8_t)w;
+      }
     }
   }
 };
@@ -216,7 +224,8 @@ struct RawStore {
   }
 };
 
-// the gradient of a pooled, clamped tensor [m / ip][N][ip]: zero where the ReLU clamped
+// the gradient of a pooled tensor [m / ip][N][ip]; RELU: zero where the ReLU clamped (no ReLU: arg is not read)
+template <bool RELU>
 struct MaskStore {
   float *out;
   const uint8_t *arg;
@@ -229,7 +238,10 @@ struct MaskStore {
       const int m = m0 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
       if (m >= M) continue;
       const long long o = ((long long)(m / ip) * N + n) * ip + m % ip;
-      out[o] = arg[o] != kMasked ? acc[r] : 0.f;
+      if constexpr (RELU)
+        out[o] = arg[o] != kMasked ? acc[r] : 0.f;
+      else
+        out[o] = acc[r];
     }
   }
 };
@@ -406,10 +418,34 @@ __global__ void adam_kernel(float *p, const float *g, float *m, float *v, int n,
   p[i] = pi - step_size * (mi / denom);
 }
 
+// Caffe's SGDSolver over the same buffer: tensor t of eight (its end at off[t + 1]) has its own rate lr_s * lr_mult[t] and decay
+// weight_decay * decay_mult[t], both products made on the host
+struct SgdTensors {
+  int end[8];
+  float rate[8], decay[8];
+};
+
+__global__ void sgd_kernel(float *p, const float *g, float *h, int n, SgdTensors ts, float momentum) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int t = 0;
+#pragma unroll
+  for (int j = 0; j < 7; j++) t += i >= ts.end[j];
+  float rate = ts.rate[0], decay = ts.decay[0];
+#pragma unroll
+  for (int j = 1; j < 8; j++)
+    if (t == j) rate = ts.rate[j], decay = ts.decay[j];
+  const float pi = p[i];
+  const float d = fmaf(decay, pi, g[i]);
+  const float hi = fmaf(momentum, h[i], rate * d);
+  h[i] = hi;
+  p[i] = pi - hi;
+}
+
 const char *const kKernelNames[] = {"conv1_forward", "conv2_forward", "fc1_forward", "fc1_sum_relu", "head", "loss", "fc2_backward",
                                     "head_grads", "fc1_dw", "fc1_dx", "conv2_db", "conv2_dw", "conv2_dw_sum", "conv2_dx", "conv1_db",
-                                    "conv1_dw", "conv1_dw_sum", "adam"};
-constexpr int kNumKernels = sizeof(kKernelNames) / sizeof(kKernelNames[0]);
+                                    "conv1_dw", "conv1_dw_sum", "adam", "sgd"};
+constexpr int kNumKernels = sizeof(kKernelNames) / sizeof(kKernelNames[0]) - 1;  // of one step: it ends in adam or in sgd
 static_assert(kNumKernels + 1 <= kMaxKernels, "events");
 
 bool channels_ok(int c) { return c == 1 || c == 3 || c == 12 || c == 15; }
@@ -425,10 +461,11 @@ struct gpd_hip_trainer {
   int device = 0;
   hipStream_t stream = nullptr;
   gpd_train_params p;
+  gpd_train_recipe r;
   int C = 0, maxb = 0;
   size_t off[9] = {0};                                                // the eight tensors inside the four parameter-sized buffers
-  float *d_p = nullptr, *d_g = nullptr, *d_m = nullptr, *d_v = nullptr;
-  long long step = 0;
+  float *d_p = nullptr, *d_g = nullptr, *d_m = nullptr, *d_v = nullptr;  // SGD: d_m is the history, d_v stays null
+  long long step = 0;                                                 // updates since the last set_state
   uint8_t *d_img[2] = {nullptr, nullptr}, *d_lab[2] = {nullptr, nullptr};
   int n[2] = {0, 0};
   int *d_idx = nullptr;        // [kIdxCap]
@@ -450,17 +487,18 @@ void mark(gpd_hip_trainer *t, bool timed, int &k) {
 }
 
 // forward over batch B of set `which` on the indices at d_idx; train: the loss of the batch into *d_loss_out and dlogits
-void enqueue_forward(gpd_hip_trainer *t, int which, const int *d_idx, int B, bool train, float *d_loss_out, bool timed, int &k) {
+template <bool RELU>
+void forward_passes(gpd_hip_trainer *t, int which, const int *d_idx, int B, bool train, float *d_loss_out, bool timed, int &k) {
   hipStream_t st = t->stream;
   const int C = t->C;
   const float *p = t->d_p;
   const Input<uint8_t> img{t->d_img[which], d_idx, (long long)kPix * C, 1, kImg * C, C, (float)t->p.input_scale};
   launch_gemm(st, PatchByPos<uint8_t>{img, kP1W, kP1, B * kO1}, Plain{p + t->off[0], (long long)C * kTaps, 1, kF1},
-              PoolStore{p + t->off[1], t->d_pool1, t->d_arg1, kF1, kP1, B * kP1}, B * kO1, kF1, C * kTaps, (C * kTaps + 1) & ~1);
+              PoolStore<RELU>{p + t->off[1], t->d_pool1, t->d_arg1, kF1, kP1, B * kP1}, B * kO1, kF1, C * kTaps, (C * kTaps + 1) & ~1);
   mark(t, timed, k);
   const Input<float> p1{t->d_pool1, nullptr, (long long)kF1 * kP1, kP1, kP1W, 1, 1.f};
   launch_gemm(st, PatchByPos<float>{p1, kP2W, kP2, B * kO2}, Plain{p + t->off[2], (long long)kF1 * kTaps, 1, kF2},
-              PoolStore{p + t->off[3], t->d_pool2, t->d_arg2, kF2, kP2, B * kP2}, B * kO2, kF2, kF1 * kTaps, kF1 * kTaps);
+              PoolStore<RELU>{p + t->off[3], t->d_pool2, t->d_arg2, kF2, kP2, B * kP2}, B * kO2, kF2, kF1 * kTaps, kF1 * kTaps);
   mark(t, timed, k);
   launch_gemm(st, Plain{t->d_pool2, kFc1In, 1, B}, Plain{p + t->off[4], kFc1In, 1, kFc1Out}, RawStore{t->d_part, B, kFc1Out}, B, kFc1Out,
               kFc1In, kFc1In / kFc1Splits);
@@ -476,7 +514,8 @@ void enqueue_forward(gpd_hip_trainer *t, int which, const int *d_idx, int B, boo
   mark(t, timed, k);
 }
 
-void enqueue_backward(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, int &k) {
+template <bool RELU>
+void backward_passes(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, int &k) {
   hipStream_t st = t->stream;
   const int C = t->C;
   const float *p = t->d_p;
@@ -490,8 +529,8 @@ void enqueue_backward(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, i
   launch_gemm(st, Plain{t->d_dz1, 1, kFc1Out, kFc1Out}, Plain{t->d_pool2, 1, kFc1In, kFc1In}, RawStore{g + t->off[4], kFc1Out, kFc1In},
               kFc1Out, kFc1In, B, (B + 1) & ~1);
   mark(t, timed, k);
-  // dPool2 [B][7200] = dZ1 W1, K = 500, zero where conv2's ReLU clamped
-  launch_gemm(st, Plain{t->d_dz1, kFc1Out, 1, B}, Plain{p + t->off[4], 1, kFc1In, kFc1In}, MaskStore{t->d_dpool2, t->d_arg2, B, kFc1In, 1},
+  // dPool2 [B][7200] = dZ1 W1, K = 500, zero where conv2's ReLU (Net) clamped
+  launch_gemm(st, Plain{t->d_dz1, kFc1Out, 1, B}, Plain{p + t->off[4], 1, kFc1In, kFc1In}, MaskStore<RELU>{t->d_dpool2, t->d_arg2, B, kFc1In, 1},
               B, kFc1In, kFc1Out, kFc1Out);
   mark(t, timed, k);
   hipLaunchKernelGGL(bias_grad_kernel, dim3(kF2), dim3(256), 0, st, t->d_dpool2, B, kF2, kP2, g + t->off[3]);
@@ -505,8 +544,8 @@ void enqueue_backward(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, i
   hipLaunchKernelGGL(sum_partials<false>, dim3((kF2 * kF1 * kTaps + 255) / 256), dim3(256), 0, st, t->d_part, B, kF2 * kF1 * kTaps, nullptr, 1,
                      g + t->off[2]);
   mark(t, timed, k);
-  // dPool1 [B][20][784] = transposed convolution of the expanded dPool2, K = 1250, zero where conv1's ReLU clamped
-  launch_gemm(st, GradByPos{pg2, kP1W, kP1, kO2W, B * kP1}, WeightByChannel{p + t->off[2], kF1}, MaskStore{t->d_dpool1, t->d_arg1, B * kP1, kF1, kP1},
+  // dPool1 [B][20][784] = transposed convolution of the expanded dPool2, K = 1250, zero where conv1's ReLU (Net) clamped
+  launch_gemm(st, GradByPos{pg2, kP1W, kP1, kO2W, B * kP1}, WeightByChannel{p + t->off[2], kF1}, MaskStore<RELU>{t->d_dpool1, t->d_arg1, B * kP1, kF1, kP1},
               B * kP1, kF1, kF2 * kTaps, kF2 * kTaps);
   mark(t, timed, k);
   hipLaunchKernelGGL(bias_grad_kernel, dim3(kF1), dim3(256), 0, st, t->d_dpool1, B, kF1, kP1, g + t->off[1]);
@@ -522,14 +561,88 @@ void enqueue_backward(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, i
   mark(t, timed, k);
 }
 
+// the network is chosen where the kernels are instantiated: no pass tests a flag per element
+void enqueue_forward(gpd_hip_trainer *t, int which, const int *d_idx, int B, bool train, float *d_loss_out, bool timed, int &k) {
+  if (t->r.network == GPD_TRAIN_NET_TORCH)
+    forward_passes<true>(t, which, d_idx, B, train, d_loss_out, timed, k);
+  else
+    forward_passes<false>(t, which, d_idx, B, train, d_loss_out, timed, k);
+}
+
+void enqueue_backward(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, int &k) {
+  if (t->r.network == GPD_TRAIN_NET_TORCH)
+    backward_passes<true>(t, d_idx, B, timed, k);
+  else
+    backward_passes<false>(t, d_idx, B, timed, k);
+}
+
+// the learning rate of update `it` in double; the recipe has been checked
+double learning_rate(const gpd_train_recipe &r, double base_lr, long long it) {
+  switch (r.lr_policy) {
+    case GPD_LR_STEP: return base_lr * std::pow(r.gamma, (double)(it / r.stepsize));
+    case GPD_LR_EXP: return base_lr * std::pow(r.gamma, (double)it);
+    case GPD_LR_INV: return base_lr * std::pow(1.0 + r.gamma * (double)it, -r.power);
+    default: return base_lr;
+  }
+}
+
+int check_recipe(const char *who, const gpd_train_recipe &r) {
+  const char *bad = nullptr;
+  if (r.network != GPD_TRAIN_NET_TORCH && r.network != GPD_TRAIN_NET_CAFFE)
+    bad = "unknown network";
+  else if (r.solver != GPD_TRAIN_SOLVER_ADAM && r.solver != GPD_TRAIN_SOLVER_SGD)
+    bad = "unknown solver";
+  else if (r.lr_policy < GPD_LR_FIXED || r.lr_policy > GPD_LR_INV)
+    bad = "unknown lr_policy";
+  else if (!(r.momentum >= 0 && r.momentum < 1))
+    bad = "momentum is outside [0, 1)";
+  else if (r.lr_policy == GPD_LR_STEP && r.stepsize < 1)
+    bad = "stepsize < 1 under the step policy";
+  else if (!std::isfinite(r.gamma) || !std::isfinite(r.power))
+    bad = "gamma or power is not finite";
+  else if (r.lr_policy == GPD_LR_INV && r.gamma < 0)
+    bad = "a negative gamma under the inv policy";
+  for (int i = 0; i < 8 && !bad; i++) {
+    if (!(r.lr_mult[i] >= 0 && std::isfinite(r.lr_mult[i])) || !(r.decay_mult[i] >= 0 && std::isfinite(r.decay_mult[i])))
+      bad = "a multiplier is negative or not finite";
+    else if (r.solver == GPD_TRAIN_SOLVER_ADAM && (r.lr_mult[i] != 1.0 || r.decay_mult[i] != 1.0))
+      bad = "multipliers other than 1 belong to the SGD solver";
+  }
+  if (!bad) return GPD_OK;
+  set_error("%s: recipe: %s", who, bad);
+  return GPD_ERR_INVALID;
+}
+
+void enqueue_sgd(gpd_hip_trainer *t, bool timed, int &k) {
+  const float lr = (float)learning_rate(t->r, t->p.lr, t->step);
+  t->step++;
+  SgdTensors ts;
+  for (int i = 0; i < 8; i++) {
+    ts.end[i] = (int)t->off[i + 1];
+    ts.rate[i] = lr * (float)t->r.lr_mult[i];
+    ts.decay[i] = (float)t->p.weight_decay * (float)t->r.decay_mult[i];
+  }
+  const int n = (int)t->off[8];
+  hipLaunchKernelGGL(sgd_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, t->d_p, t->d_g, t->d_m, n, ts, (float)t->r.momentum);
+  mark(t, timed, k);
+}
+
 void enqueue_adam(gpd_hip_trainer *t, bool timed, int &k) {
+  const double lr = learning_rate(t->r, t->p.lr, t->step);  // fixed: p.lr itself
   t->step++;
   const gpd_train_params &q = t->p;
   const double bc1 = 1.0 - std::pow(q.beta1, (double)t->step), bc2 = 1.0 - std::pow(q.beta2, (double)t->step);
   const int n = (int)t->off[8];
   hipLaunchKernelGGL(adam_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, t->d_p, t->d_g, t->d_m, t->d_v, n, (float)q.weight_decay,
-                     (float)q.beta1, (float)(1.0 - q.beta1), (float)q.beta2, (float)(1.0 - q.beta2), (float)(q.lr / bc1), (float)std::sqrt(bc2), (float)q.eps);
+                     (float)q.beta1, (float)(1.0 - q.beta1), (float)q.beta2, (float)(1.0 - q.beta2), (float)(lr / bc1), (float)std::sqrt(bc2), (float)q.eps);
   mark(t, timed, k);
+}
+
+void enqueue_update(gpd_hip_trainer *t, bool timed, int &k) {
+  if (t->r.solver == GPD_TRAIN_SOLVER_SGD)
+    enqueue_sgd(t, timed, k);
+  else
+    enqueue_adam(t, timed, k);
 }
 
 int check_indices(const char *who, const int32_t *indices, long long count, int n) {
@@ -580,10 +693,51 @@ void gpd_hip_train_default_params(gpd_train_params *p) {
   p->input_scale = 1.0 / 256;
 }
 
+int gpd_hip_sizeof_train_recipe(void) { return (int)sizeof(gpd_train_recipe); }
+
+int gpd_hip_train_default_recipe(gpd_train_recipe *r, int which) {
+  if (!r || which < 0 || which > 1) {
+    set_error("gpd_hip_train_default_recipe: a null recipe or which = %d (0 or 1)", which);
+    return GPD_ERR_INVALID;
+  }
+  std::memset(r, 0, sizeof(*r));
+  r->network = which ? GPD_TRAIN_NET_CAFFE : GPD_TRAIN_NET_TORCH;
+  r->solver = which ? GPD_TRAIN_SOLVER_SGD : GPD_TRAIN_SOLVER_ADAM;
+  r->momentum = which ? 0.9 : 0.0;
+  r->lr_policy = which ? GPD_LR_INV : GPD_LR_FIXED;
+  r->stepsize = 1;
+  r->gamma = which ? 0.0001 : 1.0;
+  r->power = which ? 0.75 : 0.0;
+  for (int i = 0; i < 8; i++) r->lr_mult[i] = r->decay_mult[i] = 1.0;
+  return GPD_OK;
+}
+
+int gpd_hip_train_learning_rate(const gpd_train_recipe *recipe, double base_lr, long long it, float *lr) {
+  if (!recipe || !lr || it < 0 || !(base_lr >= 0 && std::isfinite(base_lr))) {
+    set_error("gpd_hip_train_learning_rate: a null argument, a negative count or a base_lr that is negative or not finite");
+    return GPD_ERR_INVALID;
+  }
+  const int rc = check_recipe("gpd_hip_train_learning_rate", *recipe);
+  if (rc) return rc;
+  *lr = (float)learning_rate(*recipe, base_lr, it);
+  return GPD_OK;
+}
+
 int gpd_hip_train_create(gpd_hip_ctx *ctx, const gpd_train_params *params, gpd_hip_trainer **out) {
+  return gpd_hip_train_create_recipe(ctx, params, nullptr, out);
+}
+
+int gpd_hip_train_create_recipe(gpd_hip_ctx *ctx, const gpd_train_params *params, const gpd_train_recipe *recipe, gpd_hip_trainer **out) {
   if (!ctx || !params || !out) {
     set_error("gpd_hip_train_create: null argument");
     return GPD_ERR_INVALID;
+  }
+  gpd_train_recipe r;
+  (void)gpd_hip_train_default_recipe(&r, 0);
+  if (recipe) {
+    r = *recipe;
+    const int rc = check_recipe("gpd_hip_train_create_recipe", r);
+    if (rc) return rc;
   }
   const gpd_train_params &q = *params;
   if (!channels_ok(q.channels)) {
@@ -603,6 +757,7 @@ int gpd_hip_train_create(gpd_hip_ctx *ctx, const gpd_train_params *params, gpd_h
   gpd_hip_trainer *t = new gpd_hip_trainer();
   ctx_device_stream(ctx, &t->device, &t->stream);
   t->p = q;
+  t->r = r;
   t->C = q.channels;
   t->maxb = q.max_batch;
   size_t sz[8];
@@ -614,7 +769,7 @@ int gpd_hip_train_create(gpd_hip_ctx *ctx, const gpd_train_params *params, gpd_h
   if (e == hipSuccess) e = dev_alloc(&t->d_p, total);
   if (e == hipSuccess) e = dev_alloc(&t->d_g, total);
   if (e == hipSuccess) e = dev_alloc(&t->d_m, total);
-  if (e == hipSuccess) e = dev_alloc(&t->d_v, total);
+  if (e == hipSuccess && r.solver == GPD_TRAIN_SOLVER_ADAM) e = dev_alloc(&t->d_v, total);
   if (e == hipSuccess) e = dev_alloc(&t->d_idx, (size_t)kIdxCap);
   if (e == hipSuccess) e = dev_alloc(&t->d_loss, (size_t)kIdxCap);
   if (e == hipSuccess) e = dev_alloc(&t->d_pool1, B * kF1 * kP1);
@@ -632,7 +787,7 @@ int gpd_hip_train_create(gpd_hip_ctx *ctx, const gpd_train_params *params, gpd_h
   for (int i = 0; i < kMaxKernels && e == hipSuccess; i++) e = hipEventCreate(&t->ev[i]);
   if (e == hipSuccess) e = hipMemsetAsync(t->d_p, 0, total * sizeof(float), t->stream);
   if (e == hipSuccess) e = hipMemsetAsync(t->d_m, 0, total * sizeof(float), t->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_v, 0, total * sizeof(float), t->stream);
+  if (e == hipSuccess && t->d_v) e = hipMemsetAsync(t->d_v, 0, total * sizeof(float), t->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
   if (e != hipSuccess) {
     set_error("gpd_hip_train_create: %s", hipGetErrorString(e));
@@ -695,7 +850,7 @@ int gpd_hip_train_set_state(gpd_hip_trainer *t, const float *const tensors[8]) {
   const size_t bytes = t->off[8] * sizeof(float);
   HIP_TRY(hipMemcpyAsync(t->d_p, t->h_all.data(), bytes, hipMemcpyHostToDevice, t->stream));
   HIP_TRY(hipMemsetAsync(t->d_m, 0, bytes, t->stream));
-  HIP_TRY(hipMemsetAsync(t->d_v, 0, bytes, t->stream));
+  if (t->d_v) HIP_TRY(hipMemsetAsync(t->d_v, 0, bytes, t->stream));
   HIP_TRY(hipStreamSynchronize(t->stream));
   t->step = 0;
   return GPD_OK;
@@ -715,6 +870,83 @@ int gpd_hip_train_get_state(gpd_hip_trainer *t, float *const tensors[8]) {
   HIP_TRY(hipMemcpyAsync(t->h_all.data(), t->d_p, t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
   HIP_TRY(hipStreamSynchronize(t->stream));
   for (int i = 0; i < 8; i++) std::memcpy(tensors[i], t->h_all.data() + t->off[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
+  return GPD_OK;
+}
+
+int gpd_hip_train_init_xavier(int channels, uint32_t seed, float *const tensors[8]) {
+  if (!channels_ok(channels) || !tensors) {
+    set_error("gpd_hip_train_init_xavier: %d channels (1, 3, 12 or 15) or a null argument", channels);
+    return GPD_ERR_INVALID;
+  }
+  size_t sz[8];
+  tensor_sizes(channels, sz);
+  for (int i = 0; i < 8; i++)
+    if (!tensors[i]) {
+      set_error("gpd_hip_train_init_xavier: tensor %d is null", i);
+      return GPD_ERR_INVALID;
+    }
+  const int fan_in[4] = {channels * kTaps, kF1 * kTaps, kFc1In, kFc1Out};
+  sample::Stream st(seed);
+  for (int i = 0; i < 8; i++) {
+    if (i & 1) {  // a bias: constant filler 0, no draw
+      std::fill(tensors[i], tensors[i] + sz[i], 0.f);
+      continue;
+    }
+    const double bound = std::sqrt(3.0 / (double)fan_in[i / 2]);
+    // 24 bits of the draw -> the centres of 2^24 equal cells of (-bound, bound); the rounding to float never leaves the bound
+    for (size_t j = 0; j < sz[i]; j++) {
+      float w = (float)((2.0 * ((double)(st.next() >> 40) + 0.5) / 16777216.0 - 1.0) * bound);
+      if (std::fabs((double)w) > bound) w = std::nextafterf(w, 0.f);
+      tensors[i][j] = w;
+    }
+  }
+  return GPD_OK;
+}
+
+int gpd_hip_train_get_solver_state(gpd_hip_trainer *t, float *const m[8], float *const v[8], long long *count) {
+  if (!t || !m || !count || (t->d_v && !v)) {
+    set_error("gpd_hip_train_get_solver_state: null argument");
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < 8; i++)
+    if (!m[i] || (t->d_v && !v[i])) {
+      set_error("gpd_hip_train_get_solver_state: tensor %d is null", i);
+      return GPD_ERR_INVALID;
+    }
+  HIP_TRY(hipSetDevice(t->device));
+  const float *src[2] = {t->d_m, t->d_v};
+  float *const *dst[2] = {m, v};
+  for (int b = 0; b < 2; b++) {
+    if (!src[b]) continue;
+    HIP_TRY(hipMemcpyAsync(t->h_all.data(), src[b], t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    for (int i = 0; i < 8; i++) std::memcpy(dst[b][i], t->h_all.data() + t->off[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
+  }
+  *count = t->step;
+  return GPD_OK;
+}
+
+int gpd_hip_train_set_solver_state(gpd_hip_trainer *t, const float *const m[8], const float *const v[8], long long count) {
+  if (!t || !m || (t->d_v && !v) || count < 0) {
+    set_error("gpd_hip_train_set_solver_state: null argument or a negative count");
+    return GPD_ERR_INVALID;
+  }
+  const float *const *src[2] = {m, t->d_v ? v : nullptr};
+  for (int b = 0; b < 2; b++)
+    for (int i = 0; i < 8 && src[b]; i++)
+      if (!src[b][i] || !all_finite(src[b][i], t->off[i + 1] - t->off[i])) {
+        set_error("gpd_hip_train_set_solver_state: buffer %d, tensor %d is null or holds a non-finite value", b, i);
+        return GPD_ERR_INVALID;
+      }
+  HIP_TRY(hipSetDevice(t->device));
+  float *dst[2] = {t->d_m, t->d_v};
+  for (int b = 0; b < 2; b++) {
+    if (!src[b]) continue;
+    for (int i = 0; i < 8; i++) std::memcpy(t->h_all.data() + t->off[i], src[b][i], (t->off[i + 1] - t->off[i]) * sizeof(float));
+    HIP_TRY(hipMemcpyAsync(dst[b], t->h_all.data(), t->off[8] * sizeof(float), hipMemcpyHostToDevice, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+  }
+  t->step = count;
   return GPD_OK;
 }
 
@@ -768,7 +1000,7 @@ int gpd_hip_train_steps(gpd_hip_trainer *t, const int32_t *indices, int num_step
       const int *idx = t->d_idx + (size_t)s * batch;
       enqueue_forward(t, 0, idx, batch, true, t->d_loss + s, false, k);
       enqueue_backward(t, idx, batch, false, k);
-      enqueue_adam(t, false, k);
+      enqueue_update(t, false, k);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(losses + s0, t->d_loss, (size_t)ns * sizeof(float), hipMemcpyDeviceToHost, t->stream));
@@ -818,7 +1050,7 @@ int gpd_hip_train_apply(gpd_hip_trainer *t, const float *const grads[8]) {
   HIP_TRY(hipSetDevice(t->device));
   HIP_TRY(hipMemcpyAsync(t->d_g, t->h_all.data(), t->off[8] * sizeof(float), hipMemcpyHostToDevice, t->stream));
   int k = 0;
-  enqueue_adam(t, false, k);
+  enqueue_update(t, false, k);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(t->stream));
   return GPD_OK;
@@ -877,7 +1109,7 @@ int gpd_hip_train_step_timed(gpd_hip_trainer *t, const int32_t *indices, int bat
   mark(t, true, k);
   enqueue_forward(t, 0, t->d_idx, batch, true, t->d_loss, true, k);
   enqueue_backward(t, t->d_idx, batch, true, k);
-  enqueue_adam(t, true, k);
+  enqueue_update(t, true, k);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(t->stream));
   for (int i = 0; i + 1 < k; i++) HIP_TRY(hipEventElapsedTime(&ms[i], t->ev[i], t->ev[i + 1]));
@@ -886,5 +1118,9 @@ int gpd_hip_train_step_timed(gpd_hip_trainer *t, const int32_t *indices, int bat
 }
 
 const char *gpd_hip_train_kernel_name(int i) { return i >= 0 && i < kNumKernels ? kKernelNames[i] : ""; }
+
+const char *gpd_hip_train_kernel_name_of(const gpd_hip_trainer *t, int i) {
+  return t && t->r.solver == GPD_TRAIN_SOLVER_SGD && i == kNumKernels - 1 ? kKernelNames[kNumKernels] : gpd_hip_train_kernel_name(i);
+}
 
 }  // extern "C"

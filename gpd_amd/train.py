@@ -10,6 +10,20 @@ accuracy on the test set, as the script does.
 
 DIR receives what gpd_amd.torch_export writes — the eight tensors in torch layout and network.cfg (layout = torch) — and, where
 torch imports, model.pwf (torch.save of the state dict, what the script saves).
+
+python -m gpd_amd.train TRAIN_DIR [--test TEST_DIR] --recipe caffe [--max-iter 10000] [--snapshot N] [--resume DIR]
+                        [--init DIR] [--freeze NAME[,NAME...]] [--seed S] --out DIR
+
+trains the network the context scores by default — the reference's Caffe LeNet, no ReLU behind the convolutions — with the
+reference's Caffe recipe (models/caffe/15channels/lenet_solver_15_channels.prototxt and the train_val prototxt): xavier
+initialisation (the seeded gpd_hip_train_init_xavier), SGD with momentum 0.9, base_lr 0.01, weight_decay 5e-4, lr_policy inv
+(gamma 1e-4, power 0.75), batches of 64 walked through shuffled passes over the set, --max-iter iterations, a test phase every
+100 iterations over min(10000, n_test) test images that prints iteration, learning rate, loss and accuracy.  --snapshot N
+writes OUT/snapshot_<iteration>/ (state.npz, solver.npz) every N iterations and --resume continues from such a directory, byte
+for byte.  --init DIR starts from an Eigen-layout parameter directory and --freeze sets the named tensors' lr_mult to 0
+(conv1.weight ... fc2.bias; a layer name such as conv1 means both of its tensors): together they fit a missing ip1 under
+shipped convolutions (a file the --init DIR lacks starts from the xavier filler).  DIR receives what gpd_amd.eigen_export
+writes: the eight files of the reference's EigenClassifier, ready to be a `weights_file`.
 """
 import argparse
 import os
@@ -17,7 +31,7 @@ import sys
 
 import numpy as np
 
-from gpd_amd import api, torch_export
+from gpd_amd import api, eigen_export, torch_export
 
 
 def load_set(directory, prefix, channels=None):
@@ -47,6 +61,103 @@ def train(trainer, n, epochs, batch, seed, n_test=0, log=print):
     return trainer.get_state()
 
 
+TEST_INTERVAL, TEST_IMAGES = 100, 10000  # the solver file's test_interval; test_iter 100 of batches of 100
+
+
+def batch_rows(seed, n, batch, first, count):
+    """Rows first .. first + count of the endless list of full batches: pass e over the set is gpd_hip_shuffle_orders' order
+    number e, cut into n // batch rows (Caffe's data layer wraps around; here every pass is shuffled and its tail dropped)."""
+    per = n // batch
+    if per < 1:
+        raise ValueError("the training set has %d images, a batch needs %d" % (n, batch))
+    e0, e1 = first // per, (first + count - 1) // per
+    orders = api.shuffle_orders(seed, [n] * (e1 + 1))[e0:]
+    rows = np.concatenate([o[:per * batch].reshape(per, batch) for o in orders])
+    return rows[first - e0 * per:first - e0 * per + count]
+
+
+def write_snapshot(trainer, directory):
+    os.makedirs(directory, exist_ok=True)
+    s = trainer.get_solver_state()
+    np.savez(os.path.join(directory, "state.npz"), **trainer.get_state())
+    np.savez(os.path.join(directory, "solver.npz"), count=np.int64(s["count"]), **{"m." + k: v for k, v in s["m"].items()})
+
+
+def read_snapshot(trainer, directory):
+    """-> the iteration the snapshot was taken at"""
+    with np.load(os.path.join(directory, "state.npz")) as z:
+        trainer.set_state({k: z[k] for k in api.TORCH_KEYS})
+    with np.load(os.path.join(directory, "solver.npz")) as z:
+        count = int(z["count"])
+        trainer.set_solver_state(dict(count=count, m={k: z["m." + k] for k in api.TORCH_KEYS}, v=None))
+    return count
+
+
+def train_caffe(trainer, n, max_iter, batch, seed, n_test=0, start=0, snapshot=0, out=None, log=print):
+    """Iterations start .. max_iter of the Caffe recipe over the trainer's resident sets -> the final state."""
+    n_test = min(TEST_IMAGES, n_test)
+    it = start
+    while it < max_iter:
+        stop = min(max_iter, (it // TEST_INTERVAL + 1) * TEST_INTERVAL)
+        if snapshot:
+            stop = min(stop, (it // snapshot + 1) * snapshot)
+        losses = trainer.steps(batch_rows(seed, n, batch, it, stop - it))
+        it = stop
+        if it % TEST_INTERVAL == 0 or it == max_iter:
+            lr = float(api.learning_rate(trainer.recipe, trainer.params.lr, it - 1))
+            line = "Iteration %d, lr = %.6g, loss = %.6g" % (it, lr, float(losses[-1]))
+            if n_test:
+                _, correct = trainer.eval(n=n_test, which=1)
+                line += ", accuracy = %.4f" % (correct / n_test)
+            log(line)
+        if snapshot and it % snapshot == 0:
+            write_snapshot(trainer, os.path.join(out, "snapshot_%d" % it))
+    return trainer.get_state()
+
+
+def frozen_names(spec):
+    names = []
+    for name in [s for s in spec.split(",") if s]:
+        hit = [k for k in api.TORCH_KEYS if k == name or k.split(".")[0] == name]
+        if not hit:
+            raise ValueError("--freeze: no tensor %r (%s)" % (name, ", ".join(api.TORCH_KEYS)))
+        names += hit
+    return names
+
+
+def main_caffe(a):
+    img, lab = load_set(a.train_dir, "train")
+    C = img.shape[3]
+    recipe = api.train_default_recipe(1, lr_mult={k: 0.0 for k in frozen_names(a.freeze or "")})
+    ctx = api.Context(api.default_params(C), device=a.device)
+    trainer = api.Trainer(ctx, recipe=recipe, max_batch=a.batch, lr=api.CAFFE_BASE_LR)
+    try:
+        scale = float(trainer.params.input_scale)
+        start = 0
+        if a.resume:
+            start = read_snapshot(trainer, a.resume)
+        elif a.init:
+            # a file the directory lacks (the reference's snapshot: ip1_weights.bin) starts from the xavier filler
+            fill = api.lenet_from_torch(api.init_xavier(C, a.seed), C, scale)
+            trainer.set_state(eigen_export.to_torch(eigen_export.load(a.init, fill), scale))
+        else:
+            trainer.set_state(api.init_xavier(C, a.seed))
+        trainer.set_data(img, lab, 0)
+        n_test = 0
+        if a.test:
+            timg, tlab = load_set(a.test, "test", C)
+            trainer.set_data(timg, tlab, 1)
+            n_test = len(tlab)
+        print("training on %d images of %d channels from iteration %d to %d%s" % (len(lab), C, start, a.max_iter, ", testing on %d" % min(TEST_IMAGES, n_test) if n_test else ""))
+        state = train_caffe(trainer, len(lab), a.max_iter, a.batch, a.seed, n_test, start, a.snapshot, a.out)
+        names = eigen_export.export(state, a.out, scale)
+    finally:
+        trainer.close()
+        ctx.close()
+    print("wrote %s: %s" % (a.out, " ".join(names)))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m gpd_amd.train", description="train the grasp network on the device")
     ap.add_argument("train_dir", help="directory with train_images.npy and train_labels.npy (generate_data)")
@@ -56,7 +167,17 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="of the initial state and of the epochs' orders")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", required=True, help="parameter directory to write")
+    ap.add_argument("--recipe", choices=["torch", "caffe"], default="torch", help="caffe: the deployed LeNet under the reference's Caffe solver")
+    ap.add_argument("--max-iter", type=int, default=10000, help="caffe: iterations (the solver file's max_iter)")
+    ap.add_argument("--snapshot", type=int, default=0, help="caffe: write state and solver state every N iterations")
+    ap.add_argument("--resume", help="caffe: a snapshot directory to continue from")
+    ap.add_argument("--init", help="caffe: an Eigen-layout parameter directory to start from")
+    ap.add_argument("--freeze", help="caffe: tensors or layers whose lr_mult is 0, comma-separated")
     a = ap.parse_args(argv)
+    if a.recipe == "caffe":
+        return main_caffe(a)
+    if a.resume or a.init or a.freeze or a.snapshot:
+        ap.error("--snapshot, --resume, --init and --freeze need --recipe caffe")
     img, lab = load_set(a.train_dir, "train")
     C = img.shape[3]
     ctx = api.Context(api.default_params(C), device=a.device)

@@ -692,6 +692,56 @@ int gpd_hip_train_eval(gpd_hip_trainer *t, int which, const int32_t *indices, in
 int gpd_hip_train_step_timed(gpd_hip_trainer *t, const int32_t *indices, int batch, float *ms, int capacity, int *num);
 const char *gpd_hip_train_kernel_name(int i);
 
+/* ---- a second recipe: the deployed LeNet under Caffe's solver -----------------------------------------------
+ * network 1 is the network the context scores by default — EigenClassifier's, models/caffe/15channels/
+ * lenet_15_channels_train_val.prototxt: conv, 2x2 max-pool twice with NO ReLU behind the convolutions, fc1 (ip1), ReLU, fc2
+ * (ip2), SoftmaxWithLoss.  solver 1 is Caffe's SGDSolver, per tensor t and in f32:
+ *     d = g + (weight_decay * decay_mult[t]) * w;   h = momentum * h + (lr_s * lr_mult[t]) * d;   w = w - h
+ * with params->lr as base_lr and params->weight_decay as weight_decay (beta1, beta2 and eps are ignored); L2 decay reaches the
+ * biases too unless decay_mult says otherwise, lr_mult[t] = 0 freezes tensor t.  lr_s is the learning rate of the step's
+ * 0-based update count `it` since the last gpd_hip_train_set_state (gpd_hip_train_learning_rate): evaluated on the host in
+ * double, rounded to float once, handed to the step's launch.  Under solver 0 (Adam) the policy scales lr the same way (in
+ * double; "fixed" is today's trainer to the byte) and multipliers other than 1 are refused. */
+enum { GPD_TRAIN_NET_TORCH = 0, GPD_TRAIN_NET_CAFFE = 1 };
+enum { GPD_TRAIN_SOLVER_ADAM = 0, GPD_TRAIN_SOLVER_SGD = 1 };
+enum { GPD_LR_FIXED = 0, GPD_LR_STEP = 1, GPD_LR_EXP = 2, GPD_LR_INV = 3 };
+#define GPD_TRAIN_CAFFE_BASE_LR 0.01 /* lenet_solver_15_channels.prototxt: base_lr, for gpd_train_params.lr */
+typedef struct gpd_train_recipe {
+  int32_t network;      /* GPD_TRAIN_NET_* */
+  int32_t solver;       /* GPD_TRAIN_SOLVER_* */
+  double momentum;      /* [0, 1); solver 1 only */
+  int32_t lr_policy;    /* GPD_LR_*: fixed lr; step lr * gamma^floor(it / stepsize); exp lr * gamma^it; inv lr * (1 + gamma * it)^-power */
+  int32_t stepsize;     /* >= 1 under step */
+  double gamma, power;
+  double lr_mult[8], decay_mult[8]; /* Caffe's param { lr_mult decay_mult }, the eight tensors in state order */
+} gpd_train_recipe;
+int gpd_hip_sizeof_train_recipe(void);
+/* which = 0: today's trainer (Net, Adam, fixed, multipliers 1).  which = 1: the two prototxt files — the Caffe network, SGD
+ * with momentum 0.9, inv with gamma 1e-4 and power 0.75, multipliers 1; their base_lr 0.01 and weight_decay 5e-4 belong in
+ * gpd_train_params (GPD_TRAIN_CAFFE_BASE_LR; the default weight_decay is the solver file's already), max_iter 10000 and the
+ * batch of 64 in the caller's loop.  Anything else: GPD_ERR_INVALID. */
+int gpd_hip_train_default_recipe(gpd_train_recipe *r, int which);
+/* gpd_hip_train_create with a recipe; NULL is gpd_hip_train_create.  GPD_ERR_INVALID beyond gpd_hip_train_create's: an unknown
+ * network, solver or policy, a non-finite or negative multiplier, a multiplier other than 1 under Adam, momentum outside
+ * [0, 1), stepsize < 1 under step, a non-finite gamma or power, a negative gamma under inv. */
+int gpd_hip_train_create_recipe(gpd_hip_ctx *ctx, const gpd_train_params *params, const gpd_train_recipe *recipe, gpd_hip_trainer **out);
+/* Host only: Caffe's "xavier" filler as the train_val prototxt asks for it — weights U(-sqrt(3 / fan_in), sqrt(3 / fan_in)),
+ * fan_in 25 C, 500, 7200, 500, biases 0 — from the project's seeded xorshift64 stream like gpd_hip_train_init_state (the
+ * weight tensors in order, no draw for a bias); NOT Caffe's bits.  No weight lies outside its bound. */
+int gpd_hip_train_init_xavier(int channels, uint32_t seed, float *const tensors[8]);
+/* Host only: the learning rate of update `it` (0-based) under the recipe's policy, the double result rounded to float once:
+ * the definition the step uses.  GPD_ERR_INVALID: a null pointer, it < 0, a non-finite or negative base_lr, a policy the
+ * recipe check above refuses. */
+int gpd_hip_train_learning_rate(const gpd_train_recipe *recipe, double base_lr, long long it, float *lr);
+/* The optimiser's buffers as eight tensors in state layout, and the update count.  Adam: m = exp_avg, v = exp_avg_sq; SGD:
+ * m = the momentum history h, v is not touched and may be NULL.  gpd_hip_train_set_state clears all of it, so a resumed run is
+ * set_state followed by set_solver_state: it then continues byte for byte.  GPD_ERR_INVALID (nothing changed): a NULL where
+ * the solver has a buffer, a non-finite value, a negative count. */
+/* gpd_hip_train_kernel_name for the launches of this trainer's timed step: the last one is "sgd" under solver 1. */
+const char *gpd_hip_train_kernel_name_of(const gpd_hip_trainer *t, int i);
+int gpd_hip_train_get_solver_state(gpd_hip_trainer *t, float *const m[8], float *const v[8], long long *count);
+int gpd_hip_train_set_solver_state(gpd_hip_trainer *t, const float *const m[8], const float *const v[8], long long count);
+
 #ifdef __cplusplus
 }
 #endif
