@@ -249,7 +249,9 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_train_gradients", "gpd_hip_train_apply", "gpd_hip_train_eval", "gpd_hip_train_step_timed",
            "gpd_hip_train_kernel_name", "gpd_hip_sizeof_train_recipe", "gpd_hip_train_default_recipe", "gpd_hip_train_create_recipe",
            "gpd_hip_train_init_xavier", "gpd_hip_train_learning_rate", "gpd_hip_train_get_solver_state",
-           "gpd_hip_train_set_solver_state", "gpd_hip_train_kernel_name_of"]
+           "gpd_hip_train_set_solver_state", "gpd_hip_train_kernel_name_of",
+           "gpd_hip_train_reserve", "gpd_hip_train_count", "gpd_hip_train_append_data", "gpd_hip_train_get_data",
+           "gpd_hip_train_reorder", "gpd_hip_train_append_view"]
 
 
 def build(prof=True):
@@ -342,6 +344,12 @@ def lib():
         L.gpd_hip_train_set_solver_state.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_longlong]
         L.gpd_hip_train_kernel_name_of.argtypes = [C.c_void_p, C.c_int]
         L.gpd_hip_train_kernel_name_of.restype = C.c_char_p
+        L.gpd_hip_train_reserve.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.gpd_hip_train_count.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.gpd_hip_train_append_data.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.gpd_hip_train_get_data.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.gpd_hip_train_reorder.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.gpd_hip_train_append_view.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(LabelViewJob)]
         assert L.gpd_hip_sizeof_train_recipe() == C.sizeof(TrainRecipe)
         assert L.gpd_hip_sizeof_label_view_job() == C.sizeof(LabelViewJob)
         assert L.gpd_hip_sizeof_sis_job() == C.sizeof(SisJob)
@@ -951,6 +959,69 @@ class Trainer:
         if images.shape != (len(labels), 60, 60, self.channels):
             raise ValueError("images %s do not match %d labels of %d channels" % (images.shape, len(labels), self.channels))
         self._check(lib().gpd_hip_train_set_data(self._h, int(which), _ptr(images), _ptr(labels), len(labels)))
+
+    def _images_labels(self, images, labels):
+        images = np.ascontiguousarray(images, np.uint8)
+        labels = np.ascontiguousarray(labels, np.uint8).reshape(-1)
+        if images.shape != (len(labels), 60, 60, self.channels):
+            raise ValueError("images %s do not match %d labels of %d channels" % (images.shape, len(labels), self.channels))
+        return images, labels
+
+    def reserve(self, capacity, which=0):
+        """gpd_hip_train_reserve: room for max(capacity, n) images in set `which`; the images of the set stay."""
+        self._check(lib().gpd_hip_train_reserve(self._h, int(which), int(capacity)))
+
+    def count(self, which=0):
+        """-> (images in set `which`, images its pool has room for)"""
+        n, cap = C.c_int(0), C.c_int(0)
+        self._check(lib().gpd_hip_train_count(self._h, int(which), C.byref(n), C.byref(cap)))
+        return int(n.value), int(cap.value)
+
+    def append_data(self, images, labels, which=0):
+        """gpd_hip_train_append_data: host images u8 [n,60,60,C] and labels u8 [n] behind the last image of set `which` -> the
+        position of the first appended image."""
+        images, labels = self._images_labels(images, labels)
+        first = self.count(which)[0]
+        self._check(lib().gpd_hip_train_append_data(self._h, int(which), _ptr(images), _ptr(labels), len(labels)))
+        return first
+
+    def get_data(self, first=0, count=None, which=0):
+        """gpd_hip_train_get_data: images [first, first + count) of set `which` (count None: to the end) -> (images u8
+        [count,60,60,C], labels u8 [count])."""
+        count = self.count(which)[0] - int(first) if count is None else int(count)
+        images = np.zeros((max(count, 0), 60, 60, self.channels), np.uint8)
+        labels = np.zeros(max(count, 0), np.uint8)
+        self._check(lib().gpd_hip_train_get_data(self._h, int(which), int(first), count, _ptr(images), _ptr(labels)))
+        return images, labels
+
+    def reorder(self, first, order, which=0):
+        """gpd_hip_train_reorder: images and labels of [first, first + len(order)) become new[k] = old[first + order[k]], on the
+        device; `order` is a permutation of 0 .. len(order) - 1."""
+        order = np.ascontiguousarray(order, np.int32).reshape(-1)
+        self._check(lib().gpd_hip_train_reorder(self._h, int(which), int(first), len(order), _ptr(order)))
+
+    def append_view(self, ctx, sample_rounds, min_positives, max_grasps_per_view, which=0, want_all_labels=False):
+        """gpd_hip_train_append_view: Context.label_view on `ctx` (this trainer's context or another on the same device) whose kept
+        images and labels go straight behind the last image of set `which` and never cross to the host -> label_view's dict
+        without images, labels, hands and src_index, plus first: the position of the first appended image."""
+        sr = np.ascontiguousarray(sample_rounds, np.int32)
+        sr = sr.reshape(sr.shape[0] if sr.ndim > 1 else (1 if sr.size else 0), -1)
+        rounds, per = sr.shape
+        counts = np.zeros((max(rounds, 1), 2), np.int32)
+        all_cap = rounds * per * ctx.n_slots if want_all_labels else 0
+        all_lab = np.zeros(max(all_cap, 1), np.uint8) if want_all_labels else None
+        j = LabelViewJob()
+        j.sample_indices, j.samples_per_round, j.max_rounds = _ptr(sr), per, rounds
+        j.min_positives, j.max_grasps_per_view = int(min_positives), int(max_grasps_per_view)
+        j.all_labels, j.all_labels_capacity, j.round_counts = _ptr(all_lab), all_cap, _ptr(counts)
+        first = self.count(which)[0]
+        self._check(lib().gpd_hip_train_append_view(self._h, int(which), ctx._h, C.byref(j)))
+        out = dict(first=first, rounds_run=int(j.rounds_run), num_candidates=int(j.num_candidates), num_positives=int(j.num_positives),
+                   num_out=int(j.num_out), num_positives_out=int(j.num_positives_out), gt_neighbourhoods=int(j.gt_neighbourhoods),
+                   d2h_bytes=int(j.d2h_bytes), stage_ms=[float(x) for x in j.stage_ms], round_counts=counts[:rounds].copy())
+        if want_all_labels:
+            out["all_labels"] = all_lab[: j.num_candidates].copy()
+        return out
 
     def steps(self, indices, batch=None):
         """Steps of the recipe's solver (default Adam) on the training set: indices i32 [num_steps, batch] (or flat with `batch` given) -> each step's loss f32."""

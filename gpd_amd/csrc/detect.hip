@@ -242,6 +242,169 @@ int job_end(gpd_hip_ctx *ctx, Lane &L, Job &J) {
   return GPD_OK;
 }
 
+// gpd_hip_label_view, and gpd_hip_train_append_view through a sink (train.hip): the rounds and the selection are one code
+int label_view_run(gpd_hip_ctx *ctx, gpd_label_view_job *job, const char *who, const LabelSink *sink) {
+  StageRange range_("gpd:label_view");
+  if (!ctx || !job) {
+    set_error("%s: bad argument", who);
+    return GPD_ERR_INVALID;
+  }
+  gpd_label_view_job &j = *job;
+  j.rounds_run = j.num_candidates = j.num_positives = j.num_out = j.num_positives_out = j.gt_neighbourhoods = 0;
+  j.d2h_bytes = 0;
+  for (float &m : j.stage_ms) m = 0.f;
+  const int half = j.max_grasps_per_view > 0 ? j.max_grasps_per_view / 2 : 0;
+  const long long total_samples = (long long)j.samples_per_round * j.max_rounds;
+  if (j.samples_per_round < 0 || j.max_rounds < 0 || (total_samples > 0 && !j.sample_indices) || total_samples > 0x7fffffffll ||
+      (!sink && (j.capacity < 0 || (j.capacity > 0 && (!j.images || !j.labels)))) || (j.all_labels && j.all_labels_capacity < 0)) {
+    set_error("%s: bad argument", who);
+    return GPD_ERR_INVALID;
+  }
+  if (!sink && (long long)j.capacity < 2ll * half) {
+    set_error("%s: capacity %d, up to %d instances are kept at max_grasps_per_view = %d", who, j.capacity, 2 * half,
+              j.max_grasps_per_view);
+    return GPD_ERR_INVALID;
+  }
+  Lane &L = ctx->lane[0];
+  LabelState &ls = ctx->label;
+  if (!L.cloud.num_points) {
+    set_error("%s: no cloud uploaded", who);
+    return GPD_ERR_STATE;
+  }
+  if (!ls.gt.num_points) {
+    set_error("%s: no ground truth uploaded (gpd_hip_upload_ground_truth)", who);
+    return GPD_ERR_STATE;
+  }
+  int rc = check_samples(who, j.sample_indices, nullptr, (int)total_samples, L.cloud.num_points);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  rc = label_init(ls);
+  if (rc) return rc;
+  if (j.round_counts) std::memset(j.round_counts, 0, (size_t)j.max_rounds * 2 * sizeof(int32_t));
+  const gpd_params &p = ctx->params;
+  const int C = p.image_num_channels;
+  const size_t image_bytes = (size_t)kPix * C;
+  ls.grows = 0;
+  long long d2h = 0;
+  size_t acc = 0;  // candidates accumulated
+  int positives = 0, lists = 0, r = 0;
+  for (; r < j.max_rounds && positives < j.min_positives; r++) {
+    // createGraspImages (grasp_detector.cpp:458-521): what a fused detect builds before the LeNet
+    Job J;
+    J.sample_idx = j.sample_indices + (size_t)r * j.samples_per_round;
+    J.S = j.samples_per_round;
+    J.mode = 1;
+    rc = job_begin(ctx, L, J);
+    if (rc) return rc;
+    if (!J.live) continue;  // a round without samples
+    const int cap_before = L.search.nn_cap;
+    rc = job_wait_plan(ctx, L, J);
+    if (rc) return rc;
+    d2h += (long long)sizeof(PlanSummary) * (L.search.nn_cap != cap_before ? 2 : 1);
+    const PlanSummary sm = *L.plan.h_summary;
+    const int n = sm.num_candidates;
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, L.ev[0], L.ev[1]);
+    j.stage_ms[0] += ms;
+    int round_pos = 0;
+    if (n > 0) {
+      HIP_TRY(hipEventRecord(L.ev[4], L.stream));
+      L.images.side_stream = true;
+      L.images.lcg_base = 0;  // every round is an ordinary call: its shadow stream starts at 0
+      {
+        StageRange r_("gpd:images (label_view round)");
+        rc = images_run(p, L.cloud, L.search, L.plan, L.images, L.stream);
+      }
+      if (rc) return rc;
+      HIP_TRY(hipEventRecord(L.ev[2], L.stream));
+      // the round joins the view's accumulator: images in the caller's layout, records as detect_select(0) returns them
+      HIP_TRY(hipEventRecord(ls.ev[0], L.stream));
+      rc = label_reserve(ls, acc + (size_t)n, acc, image_bytes, (size_t)n, L.stream);
+      if (rc) return rc;
+      HIP_TRY(planar_to_hwc(L.images.d_images, ls.d_images + acc * image_bytes, n, C, L.stream));
+      rc = plan_emit_hands(p, L.search, L.plan, nullptr, ls.d_hands + acc, true, L.stream);
+      if (rc) return rc;
+      // evalGroundTruth (grasp_detector.cpp:522-526) on the records where they are
+      int img_status = 0;
+      {
+        StageRange r_("gpd:labels (ground-truth neighbourhoods per hand set, reevaluateHypotheses)");
+        rc = label_round(p, ls.gt, ls.gt_search, ls.d_hands + acc, ls.d_labels + acc, n, sm.live_sets, ls.d_cand_list, ls.d_meta, ls.h_meta,
+                         L.images.d_status, &img_status, &round_pos, &d2h, L.stream);
+      }
+      if (img_status) set_images_status_error(img_status);
+      if (rc) return rc;
+      HIP_TRY(hipEventRecord(ls.ev[1], L.stream));
+      HIP_TRY(hipEventSynchronize(ls.ev[1]));
+      (void)hipEventElapsedTime(&ms, L.ev[4], L.ev[2]);
+      j.stage_ms[1] += ms;
+      (void)hipEventElapsedTime(&ms, ls.ev[0], ls.ev[1]);
+      j.stage_ms[2] += ms;
+      lists += sm.live_sets;
+    } else {
+      L.images.num_candidates = 0;  // no candidate list of this round is resident
+    }
+    if (j.round_counts) {
+      j.round_counts[2 * r] = n;
+      j.round_counts[2 * r + 1] = round_pos;
+    }
+    acc += (size_t)n;
+    positives += round_pos;
+    if (acc > 0x7fffffffull) {
+      set_error("%s: more than 2^31 accumulated candidates", who);
+      return GPD_ERR_CAPACITY;
+    }
+  }
+  j.rounds_run = r;
+  j.num_candidates = (int)acc;
+  j.num_positives = positives;
+  j.gt_neighbourhoods = lists;
+  // balanceInstances (data_generator.cpp:406-430): P and N are known here, the indices are the device's business
+  const int end = balance::kept_per_class(positives, (long long)acc - positives, j.max_grasps_per_view);
+  const size_t k = (size_t)2 * end;
+  const size_t all = j.all_labels ? std::min(acc, (size_t)j.all_labels_capacity) : 0;
+  size_t off[4];
+  const size_t out_bytes = sink ? 0 : label_out_layout(k, image_bytes, off);  // what the kept set takes in the pinned block
+  if (k + all > 0) {
+    if (out_bytes + all > ls.h_out_bytes) {
+      note_alloc(__func__);
+      if (ls.h_out) (void)hipHostFree(ls.h_out);
+      ls.h_out = nullptr;
+      ls.h_out_bytes = 0;
+      const size_t cap = out_bytes + all + (out_bytes + all) / 8;
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ls.h_out), cap, 0));
+      ls.h_out_bytes = cap;
+    }
+    HIP_TRY(hipEventRecord(ls.ev[2], L.stream));
+    if (sink && k > 0) {  // the kept set stays on the device: straight behind what the sink holds
+      uint8_t *to_images = nullptr, *to_labels = nullptr;
+      rc = sink->place(sink->self, k, &to_images, &to_labels);
+      if (rc) return rc;
+      HIP_TRY(hipSetDevice(ctx->device));
+      rc = label_select_gather(ls, (int)acc, end, L.stream, to_images, to_labels);
+    } else {
+      rc = label_select_gather(ls, (int)acc, end, L.stream);
+    }
+    if (rc) return rc;
+    if (k > 0 && !sink) HIP_TRY(hipMemcpyAsync(ls.h_out, ls.d_out, out_bytes, hipMemcpyDeviceToHost, L.stream));  // the kept set: one copy
+    if (all > 0) HIP_TRY(hipMemcpyAsync(ls.h_out + out_bytes, ls.d_labels, all, hipMemcpyDeviceToHost, L.stream));
+    HIP_TRY(hipEventRecord(ls.ev[3], L.stream));
+    HIP_TRY(hipEventSynchronize(ls.ev[3]));
+    (void)hipEventElapsedTime(&j.stage_ms[3], ls.ev[2], ls.ev[3]);
+    d2h += (long long)(k > 0 ? out_bytes : 0) + (long long)all;
+    if (k > 0 && !sink) {
+      std::memcpy(j.images, ls.h_out + off[0], k * image_bytes);
+      if (j.hands) std::memcpy(j.hands, ls.h_out + off[1], k * sizeof(gpd_hand));
+      if (j.src_index) std::memcpy(j.src_index, ls.h_out + off[2], k * sizeof(int32_t));
+      std::memcpy(j.labels, ls.h_out + off[3], k);
+    }
+    if (all > 0) std::memcpy(j.all_labels, ls.h_out + out_bytes, all);
+  }
+  j.num_out = (int)k;
+  j.num_positives_out = end;
+  j.d2h_bytes = d2h;
+  return GPD_OK;
+}
+
 }  // namespace gpd
 
 extern "C" {
@@ -327,159 +490,7 @@ int gpd_hip_detect_select(gpd_hip_ctx *ctx, const int32_t *sample_indices, int n
                     num_candidates, num_hands);
 }
 
-int gpd_hip_label_view(gpd_hip_ctx *ctx, gpd_label_view_job *job) {
-  StageRange range_("gpd:label_view");
-  if (!ctx || !job) {
-    set_error("gpd_hip_label_view: bad argument");
-    return GPD_ERR_INVALID;
-  }
-  gpd_label_view_job &j = *job;
-  j.rounds_run = j.num_candidates = j.num_positives = j.num_out = j.num_positives_out = j.gt_neighbourhoods = 0;
-  j.d2h_bytes = 0;
-  for (float &m : j.stage_ms) m = 0.f;
-  const int half = j.max_grasps_per_view > 0 ? j.max_grasps_per_view / 2 : 0;
-  const long long total_samples = (long long)j.samples_per_round * j.max_rounds;
-  if (j.samples_per_round < 0 || j.max_rounds < 0 || (total_samples > 0 && !j.sample_indices) || total_samples > 0x7fffffffll ||
-      j.capacity < 0 || (j.capacity > 0 && (!j.images || !j.labels)) || (j.all_labels && j.all_labels_capacity < 0)) {
-    set_error("gpd_hip_label_view: bad argument");
-    return GPD_ERR_INVALID;
-  }
-  if ((long long)j.capacity < 2ll * half) {
-    set_error("gpd_hip_label_view: capacity %d, up to %d instances are kept at max_grasps_per_view = %d", j.capacity, 2 * half,
-              j.max_grasps_per_view);
-    return GPD_ERR_INVALID;
-  }
-  Lane &L = ctx->lane[0];
-  LabelState &ls = ctx->label;
-  if (!L.cloud.num_points) {
-    set_error("gpd_hip_label_view: no cloud uploaded");
-    return GPD_ERR_STATE;
-  }
-  if (!ls.gt.num_points) {
-    set_error("gpd_hip_label_view: no ground truth uploaded (gpd_hip_upload_ground_truth)");
-    return GPD_ERR_STATE;
-  }
-  int rc = check_samples("gpd_hip_label_view", j.sample_indices, nullptr, (int)total_samples, L.cloud.num_points);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(ctx->device));
-  rc = label_init(ls);
-  if (rc) return rc;
-  if (j.round_counts) std::memset(j.round_counts, 0, (size_t)j.max_rounds * 2 * sizeof(int32_t));
-  const gpd_params &p = ctx->params;
-  const int C = p.image_num_channels;
-  const size_t image_bytes = (size_t)kPix * C;
-  ls.grows = 0;
-  long long d2h = 0;
-  size_t acc = 0;  // candidates accumulated
-  int positives = 0, lists = 0, r = 0;
-  for (; r < j.max_rounds && positives < j.min_positives; r++) {
-    // createGraspImages (grasp_detector.cpp:458-521): what a fused detect builds before the LeNet
-    Job J;
-    J.sample_idx = j.sample_indices + (size_t)r * j.samples_per_round;
-    J.S = j.samples_per_round;
-    J.mode = 1;
-    rc = job_begin(ctx, L, J);
-    if (rc) return rc;
-    if (!J.live) continue;  // a round without samples
-    const int cap_before = L.search.nn_cap;
-    rc = job_wait_plan(ctx, L, J);
-    if (rc) return rc;
-    d2h += (long long)sizeof(PlanSummary) * (L.search.nn_cap != cap_before ? 2 : 1);
-    const PlanSummary sm = *L.plan.h_summary;
-    const int n = sm.num_candidates;
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, L.ev[0], L.ev[1]);
-    j.stage_ms[0] += ms;
-    int round_pos = 0;
-    if (n > 0) {
-      HIP_TRY(hipEventRecord(L.ev[4], L.stream));
-      L.images.side_stream = true;
-      L.images.lcg_base = 0;  // every round is an ordinary call: its shadow stream starts at 0
-      {
-        StageRange r_("gpd:images (label_view round)");
-        rc = images_run(p, L.cloud, L.search, L.plan, L.images, L.stream);
-      }
-      if (rc) return rc;
-      HIP_TRY(hipEventRecord(L.ev[2], L.stream));
-      // the round joins the view's accumulator: images in the caller's layout, records as detect_select(0) returns them
-      HIP_TRY(hipEventRecord(ls.ev[0], L.stream));
-      rc = label_reserve(ls, acc + (size_t)n, acc, image_bytes, (size_t)n, L.stream);
-      if (rc) return rc;
-      HIP_TRY(planar_to_hwc(L.images.d_images, ls.d_images + acc * image_bytes, n, C, L.stream));
-      rc = plan_emit_hands(p, L.search, L.plan, nullptr, ls.d_hands + acc, true, L.stream);
-      if (rc) return rc;
-      // evalGroundTruth (grasp_detector.cpp:522-526) on the records where they are
-      int img_status = 0;
-      {
-        StageRange r_("gpd:labels (ground-truth neighbourhoods per hand set, reevaluateHypotheses)");
-        rc = label_round(p, ls.gt, ls.gt_search, ls.d_hands + acc, ls.d_labels + acc, n, sm.live_sets, ls.d_cand_list, ls.d_meta, ls.h_meta,
-                         L.images.d_status, &img_status, &round_pos, &d2h, L.stream);
-      }
-      if (img_status) set_images_status_error(img_status);
-      if (rc) return rc;
-      HIP_TRY(hipEventRecord(ls.ev[1], L.stream));
-      HIP_TRY(hipEventSynchronize(ls.ev[1]));
-      (void)hipEventElapsedTime(&ms, L.ev[4], L.ev[2]);
-      j.stage_ms[1] += ms;
-      (void)hipEventElapsedTime(&ms, ls.ev[0], ls.ev[1]);
-      j.stage_ms[2] += ms;
-      lists += sm.live_sets;
-    } else {
-      L.images.num_candidates = 0;  // no candidate list of this round is resident
-    }
-    if (j.round_counts) {
-      j.round_counts[2 * r] = n;
-      j.round_counts[2 * r + 1] = round_pos;
-    }
-    acc += (size_t)n;
-    positives += round_pos;
-    if (acc > 0x7fffffffull) {
-      set_error("gpd_hip_label_view: more than 2^31 accumulated candidates");
-      return GPD_ERR_CAPACITY;
-    }
-  }
-  j.rounds_run = r;
-  j.num_candidates = (int)acc;
-  j.num_positives = positives;
-  j.gt_neighbourhoods = lists;
-  // balanceInstances (data_generator.cpp:406-430): P and N are known here, the indices are the device's business
-  const int end = balance::kept_per_class(positives, (long long)acc - positives, j.max_grasps_per_view);
-  const size_t k = (size_t)2 * end;
-  const size_t all = j.all_labels ? std::min(acc, (size_t)j.all_labels_capacity) : 0;
-  size_t off[4];
-  const size_t out_bytes = label_out_layout(k, image_bytes, off);
-  if (out_bytes + all > 0) {
-    if (out_bytes + all > ls.h_out_bytes) {
-      note_alloc(__func__);
-      if (ls.h_out) (void)hipHostFree(ls.h_out);
-      ls.h_out = nullptr;
-      ls.h_out_bytes = 0;
-      const size_t cap = out_bytes + all + (out_bytes + all) / 8;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ls.h_out), cap, 0));
-      ls.h_out_bytes = cap;
-    }
-    HIP_TRY(hipEventRecord(ls.ev[2], L.stream));
-    rc = label_select_gather(ls, (int)acc, end, L.stream);
-    if (rc) return rc;
-    if (k > 0) HIP_TRY(hipMemcpyAsync(ls.h_out, ls.d_out, out_bytes, hipMemcpyDeviceToHost, L.stream));  // the kept set: one copy
-    if (all > 0) HIP_TRY(hipMemcpyAsync(ls.h_out + out_bytes, ls.d_labels, all, hipMemcpyDeviceToHost, L.stream));
-    HIP_TRY(hipEventRecord(ls.ev[3], L.stream));
-    HIP_TRY(hipEventSynchronize(ls.ev[3]));
-    (void)hipEventElapsedTime(&j.stage_ms[3], ls.ev[2], ls.ev[3]);
-    d2h += (long long)(k > 0 ? out_bytes : 0) + (long long)all;
-    if (k > 0) {
-      std::memcpy(j.images, ls.h_out + off[0], k * image_bytes);
-      if (j.hands) std::memcpy(j.hands, ls.h_out + off[1], k * sizeof(gpd_hand));
-      if (j.src_index) std::memcpy(j.src_index, ls.h_out + off[2], k * sizeof(int32_t));
-      std::memcpy(j.labels, ls.h_out + off[3], k);
-    }
-    if (all > 0) std::memcpy(j.all_labels, ls.h_out + out_bytes, all);
-  }
-  j.num_out = (int)k;
-  j.num_positives_out = end;
-  j.d2h_bytes = d2h;
-  return GPD_OK;
-}
+int gpd_hip_label_view(gpd_hip_ctx *ctx, gpd_label_view_job *job) { return label_view_run(ctx, job, "gpd_hip_label_view", nullptr); }
 
 int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job) {
   StageRange range_("gpd:detect_sis");

@@ -310,8 +310,19 @@ int label_reserve(LabelState &ls, size_t need, size_t used, size_t image_bytes, 
 // offsets of the four parts of the contiguous output for k kept instances; returns the total
 size_t label_out_layout(size_t k, size_t image_bytes, size_t off[4]);
 // balanceInstances over the n accumulated labels on the device (balance_model.h is the definition) and the gather of the `end`
-// kept positives and negatives into ls.d_out; nothing waits for the device
-int label_select_gather(LabelState &ls, int n, int end, hipStream_t stream);
+// kept positives and negatives into ls.d_out; nothing waits for the device.  sink_images != null: the images [2 end][image_bytes]
+// and the labels [2 end] go there instead (device memory of the caller's, 16-byte aligned), and ls.d_out is not touched
+int label_select_gather(LabelState &ls, int n, int end, hipStream_t stream, uint8_t *sink_images = nullptr, uint8_t *sink_labels = nullptr);
+// gpd_hip_train_append_view: where a view's kept instances go instead of the host.  place() is called once, when their number k
+// (> 0) is known and before the gather is enqueued; it returns device room for k images and k labels that stays put until the
+// call returns
+struct LabelSink {
+  void *self;
+  int (*place)(void *self, size_t k, uint8_t **images, uint8_t **labels);
+};
+// the body of gpd_hip_label_view (detect.hip); sink != null: the kept images and labels go to the sink, and job->images, labels,
+// hands, src_index and capacity are not read
+int label_view_run(gpd_hip_ctx *ctx, gpd_label_view_job *job, const char *who, const LabelSink *sink);
 
 // ---- gpd_hip_detect_sis: the draw, the accumulators of the rounds, the final selection (sis.hip; the definition: sis_model.h) --
 constexpr int kSisDrawThreads = 512;  // sis_draw_kernel: proposals per step of its one workgroup

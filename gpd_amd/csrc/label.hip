@@ -89,6 +89,17 @@ __global__ __launch_bounds__(256) void label_gather_kernel(GatherParams P) {
   }
 }
 
+// the same into a caller's pool: images and labels only, destination offsets in 64 bits
+__global__ __launch_bounds__(256) void label_gather_sink_kernel(const uint4 *__restrict__ images, const uint8_t *__restrict__ labels,
+                                                                const int32_t *__restrict__ sel, uint4 *__restrict__ out_images,
+                                                                uint8_t *__restrict__ out_labels, unsigned img_units, unsigned blocks_per) {
+  const unsigned j = blockIdx.x / blocks_per, b = blockIdx.x - j * blocks_per;
+  const unsigned u = b * 256 + threadIdx.x;
+  const size_t src = (size_t)sel[j];
+  if (u < img_units) out_images[(size_t)j * img_units + u] = images[src * img_units + u];
+  if (u == 0) out_labels[j] = labels[src];
+}
+
 }  // namespace
 
 void label_free(LabelState &ls) {
@@ -166,7 +177,7 @@ size_t label_out_layout(size_t k, size_t image_bytes, size_t off[4]) {
   return off[3] + up16(k);
 }
 
-int label_select_gather(LabelState &ls, int n, int end, hipStream_t stream) {
+int label_select_gather(LabelState &ls, int n, int end, hipStream_t stream, uint8_t *sink_images, uint8_t *sink_labels) {
   const size_t k = (size_t)2 * end;
   if (k == 0) return GPD_OK;
   if (k > ls.cap_sel) {
@@ -179,7 +190,7 @@ int label_select_gather(LabelState &ls, int n, int end, hipStream_t stream) {
   }
   size_t off[4];
   const size_t bytes = label_out_layout(k, ls.image_bytes, off);
-  if (bytes > ls.d_out_bytes) {
+  if (!sink_images && bytes > ls.d_out_bytes) {
     note_alloc(__func__);
     if (ls.d_out) (void)hipFree(ls.d_out);
     ls.d_out = nullptr;
@@ -189,6 +200,17 @@ int label_select_gather(LabelState &ls, int n, int end, hipStream_t stream) {
   }
   balance_select_kernel<<<1, SEL_T, 0, stream>>>(ls.d_labels, n, end, ls.d_sel);
   HIP_RET(hipGetLastError());
+  if (sink_images) {
+    const unsigned units = (unsigned)(ls.image_bytes / 16), per = (units + 255) / 256;
+    if (k * per > 0x7fffffffull) {
+      set_error("label_view: %zu kept instances are more than one gather launch takes", k);
+      return GPD_ERR_CAPACITY;
+    }
+    label_gather_sink_kernel<<<(unsigned)(k * per), 256, 0, stream>>>(reinterpret_cast<const uint4 *>(ls.d_images), ls.d_labels, ls.d_sel,
+                                                                      reinterpret_cast<uint4 *>(sink_images), sink_labels, units, per);
+    HIP_RET(hipGetLastError());
+    return GPD_OK;
+  }
   GatherParams gp;
   gp.images = reinterpret_cast<const uint4 *>(ls.d_images);
   gp.hands = reinterpret_cast<const uint4 *>(ls.d_hands);

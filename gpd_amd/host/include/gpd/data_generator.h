@@ -25,15 +25,20 @@ class DataGenerator {
   explicit DataGenerator(const std::string &config_filename);
   ~DataGenerator();
   bool ok() const { return detector_ && detector_->ok(); }
-  // writes output_root + {train,test}_{images,labels}.npy; false when a file or a device call fails
-  bool generateData();
+  // writes output_root + {train,test}_{images,labels}.npy; false when a file or a device call fails.
+  // sink != nullptr: no file is opened; every view is one gpd_hip_train_append_view into the trainer's resident sets (train
+  // views: set 0, test views: set 1) and after each object its range of each set is put into the stored order on the device
+  // (gpd_hip_train_reorder, the same shuffle stream consumed in the same sequence): the sets end up holding the bytes the
+  // four files would hold, and no image crosses to the host
+  bool generateData(gpd_hip_trainer *sink = nullptr);
   int numTrain() const { return train_.count; }
   int numTest() const { return test_.count; }
 
  private:
   // the kept instances of an object's views, in view order: images back to back (60 * 60 * C bytes each), one label each
   struct SetData {
-    std::vector<uint8_t> images, labels;
+    std::vector<uint8_t> images, labels;  // stay empty under a sink
+    int count = 0;
   };
   // one growing pair of NumPy 1.0 files: a fixed-size header, rewritten with the final row count on close
   struct NpySet {
@@ -47,7 +52,8 @@ class DataGenerator {
   bool writeHeader(FILE *f, int rows, bool images) const;
   // Cloud::calculateNormals on the device at normals_radius, negated when `reverse`
   bool estimateNormals(util::Cloud &cloud, bool reverse);
-  bool labelView(int object, int view, util::Cloud &cloud, SetData &into);
+  // sink != nullptr: the kept instances go behind the last image of the trainer's set `which` instead of `into`'s vectors
+  bool labelView(int object, int view, util::Cloud &cloud, SetData &into, gpd_hip_trainer *sink, int which);
 
   std::unique_ptr<GraspDetector> detector_;
   std::string data_root_, objects_file_location_, output_root_;

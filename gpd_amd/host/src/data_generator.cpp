@@ -147,7 +147,7 @@ bool DataGenerator::estimateNormals(util::Cloud &cloud, bool reverse) {
 }
 
 // steps 1-5 of a view (data_generator.cpp:126-201): preprocess, then ONE gpd_hip_label_view call
-bool DataGenerator::labelView(int object, int view, util::Cloud &cloud, SetData &into) {
+bool DataGenerator::labelView(int object, int view, util::Cloud &cloud, SetData &into, gpd_hip_trainer *sink, int which) {
   gpd_hip_ctx *ctx = detector_->context();
   const int n = (int)cloud.size(), cams = cloud.numCameras();
   std::vector<float> xyz((size_t)n * 3);
@@ -181,7 +181,7 @@ bool DataGenerator::labelView(int object, int view, util::Cloud &cloud, SetData 
   }
   const size_t bytes = (size_t)kImageSize * kImageSize * detector_->getParams().image_num_channels;
   const int capacity = 2 * (std::max(max_grasps_per_view_, 0) / 2);
-  std::vector<uint8_t> images((size_t)capacity * bytes + 1), labels((size_t)capacity + 1);
+  std::vector<uint8_t> images(sink ? 1 : (size_t)capacity * bytes + 1), labels(sink ? 1 : (size_t)capacity + 1);
   gpd_label_view_job job;
   std::memset(&job, 0, sizeof(job));
   job.sample_indices = samples.data();
@@ -189,27 +189,34 @@ bool DataGenerator::labelView(int object, int view, util::Cloud &cloud, SetData 
   job.max_rounds = rounds;
   job.min_positives = min_grasps_per_view_;
   job.max_grasps_per_view = max_grasps_per_view_;
-  job.images = images.data();
-  job.labels = labels.data();
-  job.capacity = capacity;
-  if (gpd_hip_label_view(ctx, &job) != GPD_OK) {
+  if (!sink) {
+    job.images = images.data();
+    job.labels = labels.data();
+    job.capacity = capacity;
+  }
+  if ((sink ? gpd_hip_train_append_view(sink, which, ctx, &job) : gpd_hip_label_view(ctx, &job)) != GPD_OK) {
     printf("ERROR: %s\n", gpd_hip_last_error());
     return false;
   }
   printf("rounds: %d, #grasps: %d\n", job.rounds_run, job.num_candidates);
   printf("positives, negatives found for this view: %d, %d\n", job.num_positives, job.num_candidates - job.num_positives);
   printf("#positives: %d, #negatives: %d\n", job.num_positives_out, job.num_out - job.num_positives_out);
+  into.count += job.num_out;
+  if (sink) return true;
   into.images.insert(into.images.end(), images.begin(), images.begin() + (size_t)job.num_out * bytes);
   into.labels.insert(into.labels.end(), labels.begin(), labels.begin() + job.num_out);
   return true;
 }
 
-bool DataGenerator::generateData() {
+bool DataGenerator::generateData(gpd_hip_trainer *sink) {
   if (!ok()) return false;
   gpd_hip_ctx *ctx = detector_->context();
   const std::vector<std::string> objects = loadObjectNames(objects_file_location_);
   const int num_objects = (int)objects.size();
-  if (!openSet(train_, "train") || !openSet(test_, "test")) return false;
+  if (sink)
+    train_.count = test_.count = 0;
+  else if (!openSet(train_, "train") || !openSet(test_, "test"))
+    return false;
   sample::Stream shuffle(shuffle_seed_);  // one stream through every stored set
   double total_time = 0.0;
   for (int i = 0; i < num_objects; i++) {
@@ -231,6 +238,11 @@ bool DataGenerator::generateData() {
       return false;
     }
     SetData train_data, test_data;
+    int first[2] = {0, 0};  // under a sink: where this object's range of each resident set begins
+    if (sink && (gpd_hip_train_count(sink, 0, &first[0], nullptr) != GPD_OK || gpd_hip_train_count(sink, 1, &first[1], nullptr) != GPD_OK)) {
+      printf("ERROR: %s\n", gpd_hip_last_error());
+      return false;
+    }
     for (int j = 0; j < num_views_per_object_; j++) {
       printf("===> Processing view %d/%d\n", j + 1, num_views_per_object_);
       util::Cloud cloud(prefix + "_" + std::to_string(j + 1) + ".pcd", {0.0, 0.0, 0.0});
@@ -241,16 +253,25 @@ bool DataGenerator::generateData() {
       // 6. the view's instances go to the training or the test data (data_generator.cpp:204-212)
       const bool is_test = std::find(test_views_.begin(), test_views_.end(), j) != test_views_.end();
       SetData &into = is_test ? test_data : train_data;
-      if (!labelView(i, j, cloud, into)) return false;
-      std::cout << (is_test ? "test view, # test data: " : "train view, # train data: ") << into.labels.size() << "\n";
+      if (!labelView(i, j, cloud, into, sink, is_test ? 1 : 0)) return false;
+      std::cout << (is_test ? "test view, # test data: " : "train view, # train data: ") << into.count << "\n";
       printf("------------------------------------\n");
     }
     // store_step is 1: shuffle and store after every object (:217-228)
     std::vector<int32_t> order;
-    balance::shuffle_order((int)train_data.labels.size(), shuffle, order);
-    if (!appendSet(train_, train_data, order)) return false;
-    balance::shuffle_order((int)test_data.labels.size(), shuffle, order);
-    if (!appendSet(test_, test_data, order)) return false;
+    SetData *const data[2] = {&train_data, &test_data};
+    NpySet *const sets[2] = {&train_, &test_};
+    for (int w = 0; w < 2; w++) {  // one stream: the training set's order, then the test set's
+      balance::shuffle_order(data[w]->count, shuffle, order);
+      if (!sink) {
+        if (!appendSet(*sets[w], *data[w], order)) return false;
+      } else if (gpd_hip_train_reorder(sink, w, first[w], data[w]->count, order.data()) != GPD_OK) {
+        printf("ERROR: %s\n", gpd_hip_last_error());
+        return false;
+      } else {
+        sets[w]->count += data[w]->count;
+      }
+    }
     printf("train_offset: %d, test_offset: %d\n", train_.count, test_.count);
     const double ti = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     total_time += ti;
@@ -267,7 +288,7 @@ bool DataGenerator::generateData() {
   train_.count = n_train;
   test_.count = n_test;
   printf("Generated %d training and test %d instances\n", n_train, n_test);
-  printf("Wrote data to training and test databases\n");
+  printf(sink ? "Left the data in the trainer's resident sets\n" : "Wrote data to training and test databases\n");
   return true;
 }
 

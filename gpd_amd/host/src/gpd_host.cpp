@@ -14,6 +14,7 @@
 #include <set>
 
 #include "gpd/clustering.h"
+#include "gpd/data_generator.h"
 #include "gpd/grasp_detector.h"
 #include "gpd/sequential_importance_sampling.h"
 #include "gpd/util/config_file.h"
@@ -1764,4 +1765,16 @@ extern "C" int gpd_host_load_normals_csv(const char *pcd_path, const char *csv_p
   const int n = (int)cloud.size(), m = n < cap ? n : cap;
   std::memcpy(normals, cloud.getNormals().data(), (size_t)m * 3 * sizeof(float));
   return n;
+}
+
+// DataGenerator::generateData into the resident sets of a trainer (gpd_hip_trainer *) instead of .npy files: 0 and the
+// generated counts, or -1
+extern "C" int gpd_host_generate_data(const char *config, void *trainer, int *n_train, int *n_test) {
+  if (!config || !trainer) return -1;
+  gpd::DataGenerator generator(config);
+  if (!generator.ok() || !generator.generateData(static_cast<gpd_hip_trainer *>(trainer))) return -1;
+  if (n_train) *n_train = generator.numTrain();
+  if (n_test) *n_test = generator.numTest();
+  fflush(stdout);
+  return 0;
 }

@@ -120,3 +120,16 @@ def load_pcd(path, cap=1 << 22):
     n = L.gpd_host_load_pcd(str(path).encode(), xyz.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p), cap, C.byref(has))
     n = min(n, cap)
     return xyz[:n].copy(), (nrm[:n].copy() if has.value else None)
+
+
+def generate_data(config, trainer):
+    """DataGenerator::generateData(sink) of the config file into the resident sets of `trainer` (api.Trainer): every view is one
+    gpd_hip_train_append_view, every object's ranges are shuffled on the device, no .npy file is written -> (n_train, n_test)
+    generated."""
+    L = lib()
+    L.gpd_host_generate_data.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.gpd_host_generate_data.restype = C.c_int
+    n_train, n_test = C.c_int(0), C.c_int(0)
+    if L.gpd_host_generate_data(str(config).encode(), trainer._h, C.byref(n_train), C.byref(n_test)) != 0:
+        raise RuntimeError("generate_data into the trainer failed (the C++ side printed why)")
+    return int(n_train.value), int(n_test.value)

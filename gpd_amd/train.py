@@ -24,6 +24,13 @@ for byte.  --init DIR starts from an Eigen-layout parameter directory and --free
 (conv1.weight ... fc2.bias; a layer name such as conv1 means both of its tensors): together they fit a missing ip1 under
 shipped convolutions (a file the --init DIR lacks starts from the xavier filler).  DIR receives what gpd_amd.eigen_export
 writes: the eight files of the reference's EigenClassifier, ready to be a `weights_file`.
+
+python -m gpd_amd.train --generate CONFIG [--epochs ... | --recipe caffe ...] --out DIR
+
+takes no TRAIN_DIR: CONFIG is a generate_data configuration, and the two resident sets are filled on the device by
+gpd_amd.hostlib.generate_data — every view one gpd_hip_train_append_view, every object's ranges shuffled by
+gpd_hip_train_reorder — to the bytes the four .npy files would hold, which are never written; the trainer has CONFIG's
+image_num_channels and runs on its hip_device.  Training then goes on exactly as above.
 """
 import argparse
 import os
@@ -42,6 +49,43 @@ def load_set(directory, prefix, channels=None):
     if channels is not None and img.shape[3] != channels:
         raise ValueError("%s: %d channels, the training set has %d" % (directory, img.shape[3], channels))
     return np.ascontiguousarray(img, np.uint8), np.ascontiguousarray(lab, np.uint8)
+
+
+def config_values(path):
+    """The `key = value` lines of a generate_data configuration -> {key: value string}"""
+    values = {}
+    with open(path) as f:
+        for line in f:
+            line = line.split("#", 1)[0]
+            if "=" in line:
+                k, v = line.split("=", 1)
+                values[k.strip()] = v.strip()
+    return values
+
+
+def fill_sets(trainer, a, train_set=None):
+    """The trainer's two resident sets, from --generate's configuration or from the .npy pairs -> (n, n_test)"""
+    if a.generate:
+        from gpd_amd import hostlib
+        hostlib.generate_data(a.generate, trainer)
+        return trainer.count(0)[0], trainer.count(1)[0]
+    img, lab = train_set
+    trainer.set_data(img, lab, 0)
+    n_test = 0
+    if a.test:
+        timg, tlab = load_set(a.test, "test", img.shape[3])
+        trainer.set_data(timg, tlab, 1)
+        n_test = len(tlab)
+    return len(lab), n_test
+
+
+def open_sets(a):
+    """-> (channels, device, the loaded training pair or None under --generate)"""
+    if a.generate:
+        cfg = config_values(a.generate)
+        return int(cfg.get("image_num_channels", 15)), int(cfg.get("hip_device", a.device)), None
+    train_set = load_set(a.train_dir, "train")
+    return train_set[0].shape[3], a.device, train_set
 
 
 def train(trainer, n, epochs, batch, seed, n_test=0, log=print):
@@ -126,10 +170,9 @@ def frozen_names(spec):
 
 
 def main_caffe(a):
-    img, lab = load_set(a.train_dir, "train")
-    C = img.shape[3]
+    C, device, train_set = open_sets(a)
     recipe = api.train_default_recipe(1, lr_mult={k: 0.0 for k in frozen_names(a.freeze or "")})
-    ctx = api.Context(api.default_params(C), device=a.device)
+    ctx = api.Context(api.default_params(C), device=device)
     trainer = api.Trainer(ctx, recipe=recipe, max_batch=a.batch, lr=api.CAFFE_BASE_LR)
     try:
         scale = float(trainer.params.input_scale)
@@ -142,14 +185,9 @@ def main_caffe(a):
             trainer.set_state(eigen_export.to_torch(eigen_export.load(a.init, fill), scale))
         else:
             trainer.set_state(api.init_xavier(C, a.seed))
-        trainer.set_data(img, lab, 0)
-        n_test = 0
-        if a.test:
-            timg, tlab = load_set(a.test, "test", C)
-            trainer.set_data(timg, tlab, 1)
-            n_test = len(tlab)
-        print("training on %d images of %d channels from iteration %d to %d%s" % (len(lab), C, start, a.max_iter, ", testing on %d" % min(TEST_IMAGES, n_test) if n_test else ""))
-        state = train_caffe(trainer, len(lab), a.max_iter, a.batch, a.seed, n_test, start, a.snapshot, a.out)
+        n, n_test = fill_sets(trainer, a, train_set)
+        print("training on %d images of %d channels from iteration %d to %d%s" % (n, C, start, a.max_iter, ", testing on %d" % min(TEST_IMAGES, n_test) if n_test else ""))
+        state = train_caffe(trainer, n, a.max_iter, a.batch, a.seed, n_test, start, a.snapshot, a.out)
         names = eigen_export.export(state, a.out, scale)
     finally:
         trainer.close()
@@ -158,9 +196,10 @@ def main_caffe(a):
     return 0
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m gpd_amd.train", description="train the grasp network on the device")
-    ap.add_argument("train_dir", help="directory with train_images.npy and train_labels.npy (generate_data)")
+    ap.add_argument("train_dir", nargs="?", help="directory with train_images.npy and train_labels.npy (generate_data)")
+    ap.add_argument("--generate", metavar="CONFIG", help="a generate_data configuration: fill the resident sets on the device instead of reading TRAIN_DIR")
     ap.add_argument("--test", help="directory with test_images.npy and test_labels.npy")
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64)
@@ -174,24 +213,27 @@ def main(argv=None):
     ap.add_argument("--init", help="caffe: an Eigen-layout parameter directory to start from")
     ap.add_argument("--freeze", help="caffe: tensors or layers whose lr_mult is 0, comma-separated")
     a = ap.parse_args(argv)
+    if a.generate and (a.train_dir or a.test):
+        ap.error("--generate fills both sets itself: it goes without TRAIN_DIR and --test")
+    if not a.generate and not a.train_dir:
+        ap.error("TRAIN_DIR or --generate CONFIG is needed")
+    if a.recipe != "caffe" and (a.resume or a.init or a.freeze or a.snapshot):
+        ap.error("--snapshot, --resume, --init and --freeze need --recipe caffe")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     if a.recipe == "caffe":
         return main_caffe(a)
-    if a.resume or a.init or a.freeze or a.snapshot:
-        ap.error("--snapshot, --resume, --init and --freeze need --recipe caffe")
-    img, lab = load_set(a.train_dir, "train")
-    C = img.shape[3]
-    ctx = api.Context(api.default_params(C), device=a.device)
+    C, device, train_set = open_sets(a)
+    ctx = api.Context(api.default_params(C), device=device)
     trainer = api.Trainer(ctx, max_batch=a.batch)
     try:
         trainer.set_state(api.init_state(C, a.seed))
-        trainer.set_data(img, lab, 0)
-        n_test = 0
-        if a.test:
-            timg, tlab = load_set(a.test, "test", C)
-            trainer.set_data(timg, tlab, 1)
-            n_test = len(tlab)
-        print("training on %d images of %d channels%s" % (len(lab), C, ", testing on %d" % n_test if n_test else ""))
-        state = train(trainer, len(lab), a.epochs, a.batch, a.seed, n_test)
+        n, n_test = fill_sets(trainer, a, train_set)
+        print("training on %d images of %d channels%s" % (n, C, ", testing on %d" % n_test if n_test else ""))
+        state = train(trainer, n, a.epochs, a.batch, a.seed, n_test)
         names = torch_export.export(state, a.out, float(trainer.params.input_scale))
     finally:
         trainer.close()

@@ -676,6 +676,32 @@ int gpd_hip_train_get_state(gpd_hip_trainer *t, float *const tensors[8]);
 /* The resident set `which` (0: training, 1: test): images u8 [n][60][60][C] HWC, labels u8 [n] (0 / 1, GPD_ERR_INVALID
  * otherwise).  n = 0 clears the slot.  GPD_ERR_CAPACITY: more than 4 GiB of images in one slot. */
 int gpd_hip_train_set_data(gpd_hip_trainer *t, int which, const uint8_t *images_hwc, const uint8_t *labels, int n);
+/* A resident set is a pool: n images in room for `capacity`, which grows.  Pools carry no 4 GiB limit (gpd_hip_train_set_data
+ * keeps its own); the image count is an int, every byte offset 64 bits wide.  Each entry below synchronises the trainer's
+ * stream before it moves or frees a pool, and returns after its copies and kernels have completed.
+ *  - reserve: room for exactly max(capacity_images, n) images, the n images of the set kept (moved device to device when the
+ *    pool is reallocated).  GPD_ERR_CAPACITY: the device has no such room; the pool is as it was.
+ *  - count: *n images, room for *capacity (may be NULL).
+ *  - append_data: n host images and labels behind the set's last image; labels checked as set_data checks them (nothing
+ *    changes on GPD_ERR_INVALID).  A pool that is too small grows to max(need, 1.5 x capacity).  A set made by set_data can be
+ *    appended to.
+ *  - get_data: images [first, first + count) and their labels to the host.  GPD_ERR_INVALID: a range outside [0, n).
+ *  - reorder: images and labels of [first, first + count) become new[k] = old[first + order[k]], by a copy of the range to a
+ *    scratch block and a gather back on the device.  GPD_ERR_INVALID (nothing changed): a range outside [0, n), or an order
+ *    that is no permutation of 0 .. count - 1 (checked on the host). */
+int gpd_hip_train_reserve(gpd_hip_trainer *t, int which, int capacity_images);
+int gpd_hip_train_count(gpd_hip_trainer *t, int which, int *n, int *capacity);
+int gpd_hip_train_append_data(gpd_hip_trainer *t, int which, const uint8_t *images_hwc, const uint8_t *labels, int n);
+int gpd_hip_train_get_data(gpd_hip_trainer *t, int which, int first, int count, uint8_t *images_hwc, uint8_t *labels);
+int gpd_hip_train_reorder(gpd_hip_trainer *t, int which, int first, int count, const int32_t *order);
+/* gpd_hip_label_view whose kept instances never leave the device: the rounds and the balance selection of `job` run on `ctx`
+ * (the trainer's own context or another one on the same device, with the trainer's channel count: GPD_ERR_INVALID before any
+ * work otherwise), and the gather writes the kept images and labels straight behind the n images of set `which`, the pool grown
+ * first when needed.  job->images, labels, hands, src_index and capacity are not read; all_labels, round_counts, the counters and
+ * stage_ms are gpd_hip_label_view's; d2h_bytes holds no image byte (plan summaries, counts, all_labels).  The first appended
+ * image is at the n gpd_hip_train_count returned before the call, num_out images follow.  Returns after the gather has
+ * completed; on any error n is unchanged.  Errors beyond these: gpd_hip_label_view's. */
+int gpd_hip_train_append_view(gpd_hip_trainer *t, int which, gpd_hip_ctx *ctx, gpd_label_view_job *job);
 /* num_steps Adam steps on the training set, step s on the images indices[s * batch .. (s + 1) * batch), 1 <= batch <= max_batch;
  * losses [num_steps]: each step's loss before its update.  The steps are enqueued back to back and waited for once (calls
  * with more than 2^20 indices: once per 2^20).  GPD_ERR_INVALID before anything is launched: an index outside [0, n). */
