@@ -251,7 +251,10 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_train_init_xavier", "gpd_hip_train_learning_rate", "gpd_hip_train_get_solver_state",
            "gpd_hip_train_set_solver_state", "gpd_hip_train_kernel_name_of",
            "gpd_hip_train_reserve", "gpd_hip_train_count", "gpd_hip_train_append_data", "gpd_hip_train_get_data",
-           "gpd_hip_train_reorder", "gpd_hip_train_append_view"]
+           "gpd_hip_train_reorder", "gpd_hip_train_append_view",
+           "gpd_hip_train_group_mean", "gpd_hip_train_group_slices", "gpd_hip_train_group_schedule", "gpd_hip_train_group_create",
+           "gpd_hip_train_group_destroy", "gpd_hip_train_group_broadcast", "gpd_hip_train_group_steps", "gpd_hip_train_group_verify",
+           "gpd_hip_train_group_last_bytes"]
 
 
 def build(prof=True):
@@ -350,6 +353,16 @@ def lib():
         L.gpd_hip_train_get_data.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.gpd_hip_train_reorder.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.gpd_hip_train_append_view.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(LabelViewJob)]
+        L.gpd_hip_train_group_mean.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_size_t, C.c_void_p]
+        L.gpd_hip_train_group_slices.argtypes = [C.c_size_t, C.c_int, C.c_void_p]
+        L.gpd_hip_train_group_schedule.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.gpd_hip_train_group_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_group_destroy.argtypes = [C.c_void_p]
+        L.gpd_hip_train_group_destroy.restype = None
+        L.gpd_hip_train_group_broadcast.argtypes = [C.c_void_p, C.c_int]
+        L.gpd_hip_train_group_steps.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.gpd_hip_train_group_verify.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        L.gpd_hip_train_group_last_bytes.argtypes = [C.c_void_p, C.c_void_p]
         assert L.gpd_hip_sizeof_train_recipe() == C.sizeof(TrainRecipe)
         assert L.gpd_hip_sizeof_label_view_job() == C.sizeof(LabelViewJob)
         assert L.gpd_hip_sizeof_sis_job() == C.sizeof(SisJob)
@@ -1071,3 +1084,95 @@ class Trainer:
         ctx.set_lenet_torch(self.get_state(), float(self.params.input_scale) if input_scale is None else input_scale)
         if self.caffe_network:
             ctx.set_lenet_conv_relu(False)
+
+
+# ---- training on several replicas (gpd_hip_train_group_*) ----
+
+GROUP_OP_DTYPE = np.dtype([("kind", "<i4"), ("stream", "<i4"), ("peer", "<i4"), ("slice", "<i4"), ("event", "<i4")], align=False)
+OP_BACKWARD, OP_WAIT, OP_RECORD, OP_COPY, OP_SUM, OP_UPDATE = range(6)
+
+
+def train_group_mean(grads):
+    """gpd_hip_train_group_mean: the mean of G equally shaped f32 arrays in rank order, ((g0 + g1) + ...) * f32(1 / G), every
+    operation rounded to f32 (host only) -> f32 array of their shape."""
+    arrs = [np.ascontiguousarray(g, np.float32) for g in grads]
+    if not arrs or any(a.shape != arrs[0].shape for a in arrs):
+        raise ValueError("train_group_mean takes at least one array, all of one shape")
+    out = np.zeros(arrs[0].shape, np.float32)
+    ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    _lib_check(lib().gpd_hip_train_group_mean(ptrs, len(arrs), arrs[0].size, _ptr(out)))
+    return out
+
+
+def train_group_slices(n, G):
+    """gpd_hip_train_group_slices: the G + 1 boundaries of the slices of a buffer of n floats (host only) -> i64 [G + 1]."""
+    first = np.zeros(max(int(G), 0) + 1, np.int64)
+    _lib_check(lib().gpd_hip_train_group_slices(int(n), int(G), _ptr(first)))
+    return first
+
+
+def train_group_schedule(G, num_steps):
+    """gpd_hip_train_group_schedule: the operations TrainerGroup.steps enqueues for num_steps steps of G replicas, in enqueue
+    order (host only) -> GROUP_OP_DTYPE array."""
+    k = C.c_int(0)
+    _lib_check(lib().gpd_hip_train_group_schedule(int(G), int(num_steps), None, 0, C.byref(k)))
+    ops = np.zeros(max(k.value, 1), GROUP_OP_DTYPE)
+    _lib_check(lib().gpd_hip_train_group_schedule(int(G), int(num_steps), _ptr(ops), len(ops), C.byref(k)))
+    return ops[: k.value].copy()
+
+
+class TrainerGroup:
+    """One gpd_hip_train_group over Trainers of one recipe and one set of hyper-parameters, each on a Context of its own (on
+    different devices, or several on one).  A step runs every replica's batch and applies the mean of the gradients on every
+    replica.  The group owns none of its trainers: close it before them."""
+
+    def __init__(self, trainers):
+        self.trainers = list(trainers)  # keeps them alive
+        self._h = C.c_void_p()
+        hs = (C.c_void_p * max(len(self.trainers), 1))(*[t._h.value for t in self.trainers])
+        self._check(lib().gpd_hip_train_group_create(hs, len(self.trainers), C.byref(self._h)))
+
+    _check = Context._check
+
+    def __len__(self):
+        return len(self.trainers)
+
+    def close(self):
+        if self._h:
+            lib().gpd_hip_train_group_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def broadcast(self, src=0):
+        """Replica src's parameters, solver buffers and update count into every other replica, device to device."""
+        self._check(lib().gpd_hip_train_group_broadcast(self._h, int(src)))
+
+    def steps(self, indices):
+        """indices i32 [G, num_steps, batch], replica r's into its own resident training set -> (each step's loss f32
+        [num_steps]: the mean of the replicas', each replica's losses f32 [G, num_steps])."""
+        idx = np.ascontiguousarray(indices, np.int32)
+        if idx.ndim != 3 or idx.shape[0] != len(self.trainers) or idx.shape[2] < 1:
+            raise ValueError("indices %s are not [%d replicas, steps, batch]" % (idx.shape, len(self.trainers)))
+        G, steps, batch = idx.shape
+        ptrs = (C.c_void_p * G)(*[idx[r].ctypes.data for r in range(G)])
+        losses, each = np.zeros(steps, np.float32), np.zeros((G, steps), np.float32)
+        self._check(lib().gpd_hip_train_group_steps(self._h, ptrs, steps, batch, _ptr(losses), _ptr(each)))
+        return losses, each
+
+    def verify(self):
+        """-> the 32-bit words of parameters and solver buffers that differ from replica 0's, plus the replicas whose update
+        count differs: 0 for replicas in step."""
+        n = C.c_longlong(0)
+        self._check(lib().gpd_hip_train_group_verify(self._h, C.byref(n)))
+        return int(n.value)
+
+    def last_bytes(self):
+        """-> (bytes moved between replicas, bytes moved between host and devices) by the last broadcast / steps / verify."""
+        out = np.zeros(2, np.int64)
+        self._check(lib().gpd_hip_train_group_last_bytes(self._h, _ptr(out)))
+        return int(out[0]), int(out[1])

@@ -1,0 +1,50 @@
+// What the trainer's translation units share (train.hip, train_group.hip): the trainer and the three enqueues a
+// training step is made of.
+#pragma once
+
+#include <vector>
+
+#include "gpd_internal.h"
+
+namespace gpd {
+
+constexpr int kIdxCap = 1 << 20;  // indices of one enqueue
+constexpr int kMaxKernels = 24;
+
+}  // namespace gpd
+
+struct gpd_hip_trainer {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  gpd_train_params p;
+  gpd_train_recipe r;
+  int C = 0, maxb = 0;
+  size_t off[9] = {0};                                                // the eight tensors inside the four parameter-sized buffers
+  float *d_p = nullptr, *d_g = nullptr, *d_m = nullptr, *d_v = nullptr;  // SGD: d_m is the history, d_v stays null
+  long long step = 0;                                                 // updates since the last set_state
+  uint8_t *d_img[2] = {nullptr, nullptr}, *d_lab[2] = {nullptr, nullptr};
+  int n[2] = {0, 0};
+  int cap[2] = {0, 0};         // images the pools hold: n <= cap
+  int *d_idx = nullptr;        // [kIdxCap]
+  float *d_loss = nullptr;     // [kIdxCap] one per step of an enqueue
+  float *d_pool1 = nullptr, *d_pool2 = nullptr, *d_dpool1 = nullptr, *d_dpool2 = nullptr;  // [maxb][20][784], [maxb][7200]
+  uint8_t *d_arg1 = nullptr, *d_arg2 = nullptr;
+  float *d_a1 = nullptr, *d_dz1 = nullptr;  // [maxb][500]
+  float *d_logits = nullptr, *d_dl = nullptr, *d_loss_b = nullptr;
+  float *d_part = nullptr;     // split-K partials of fc1 forward, conv2 dW, conv1 dW
+  hipEvent_t ev[gpd::kMaxKernels] = {nullptr};
+  std::vector<float> h_all;    // host staging of a parameter-sized buffer
+};
+
+namespace gpd {
+
+// ---- train.hip: launches on the trainer's stream, the caller has made its device current.  timed: an event of t->ev behind
+// every kernel; k counts the kernels ----
+// forward over batch B of set `which` on the indices at d_idx; train: the loss of the batch into *d_loss_out and dlogits
+void enqueue_forward(gpd_hip_trainer *t, int which, const int *d_idx, int B, bool train, float *d_loss_out, bool timed, int &k);
+// the eight gradients of the batch into t->d_g (every element is written)
+void enqueue_backward(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, int &k);
+// the recipe's solver from t->d_g; counts the update (t->step)
+void enqueue_update(gpd_hip_trainer *t, bool timed, int &k);
+
+}  // namespace gpd

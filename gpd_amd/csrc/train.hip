@@ -17,6 +17,7 @@
 
 #include "context.h"
 #include "sample_model.h"
+#include "train.h"
 
 using namespace gpd;
 
@@ -40,9 +41,7 @@ constexpr int kO1 = 3136, kO1W = 56;   // conv1 output: 56 x 56
 constexpr int kO2 = 576, kO2W = 24;    // conv2 output: 24 x 24
 constexpr int kMasked = 4;             // argmax byte of a pooled value the ReLU clamped (value <= 0)
 constexpr int kFc1Splits = 16;         // fc1 forward: K = 7200 in 16 ranges of 450
-constexpr int kIdxCap = 1 << 20;       // indices of one enqueue
 constexpr int kMaxBatch = 1024;
-constexpr int kMaxKernels = 24;
 
 // ---- operands: ctx(i) once per lane, at(ctx, k) once per k step --------------------------------------------------------------
 
@@ -469,29 +468,6 @@ void tensor_sizes(int C, size_t n[8]) {
 
 }  // namespace
 
-struct gpd_hip_trainer {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  gpd_train_params p;
-  gpd_train_recipe r;
-  int C = 0, maxb = 0;
-  size_t off[9] = {0};                                                // the eight tensors inside the four parameter-sized buffers
-  float *d_p = nullptr, *d_g = nullptr, *d_m = nullptr, *d_v = nullptr;  // SGD: d_m is the history, d_v stays null
-  long long step = 0;                                                 // updates since the last set_state
-  uint8_t *d_img[2] = {nullptr, nullptr}, *d_lab[2] = {nullptr, nullptr};
-  int n[2] = {0, 0};
-  int cap[2] = {0, 0};         // images the pools hold: n <= cap
-  int *d_idx = nullptr;        // [kIdxCap]
-  float *d_loss = nullptr;     // [kIdxCap] one per step of an enqueue
-  float *d_pool1 = nullptr, *d_pool2 = nullptr, *d_dpool1 = nullptr, *d_dpool2 = nullptr;  // [maxb][20][784], [maxb][7200]
-  uint8_t *d_arg1 = nullptr, *d_arg2 = nullptr;
-  float *d_a1 = nullptr, *d_dz1 = nullptr;  // [maxb][500]
-  float *d_logits = nullptr, *d_dl = nullptr, *d_loss_b = nullptr;
-  float *d_part = nullptr;     // split-K partials of fc1 forward, conv2 dW, conv1 dW
-  hipEvent_t ev[kMaxKernels] = {nullptr};
-  std::vector<float> h_all;    // host staging of a parameter-sized buffer
-};
-
 namespace {
 
 void mark(gpd_hip_trainer *t, bool timed, int &k) {
@@ -574,20 +550,24 @@ void backward_passes(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, in
   mark(t, timed, k);
 }
 
+}  // namespace
+
 // the network is chosen where the kernels are instantiated: no pass tests a flag per element
-void enqueue_forward(gpd_hip_trainer *t, int which, const int *d_idx, int B, bool train, float *d_loss_out, bool timed, int &k) {
+void gpd::enqueue_forward(gpd_hip_trainer *t, int which, const int *d_idx, int B, bool train, float *d_loss_out, bool timed, int &k) {
   if (t->r.network == GPD_TRAIN_NET_TORCH)
     forward_passes<true>(t, which, d_idx, B, train, d_loss_out, timed, k);
   else
     forward_passes<false>(t, which, d_idx, B, train, d_loss_out, timed, k);
 }
 
-void enqueue_backward(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, int &k) {
+void gpd::enqueue_backward(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, int &k) {
   if (t->r.network == GPD_TRAIN_NET_TORCH)
     backward_passes<true>(t, d_idx, B, timed, k);
   else
     backward_passes<false>(t, d_idx, B, timed, k);
 }
+
+namespace {
 
 // the learning rate of update `it` in double; the recipe has been checked
 double learning_rate(const gpd_train_recipe &r, double base_lr, long long it) {
@@ -651,12 +631,16 @@ void enqueue_adam(gpd_hip_trainer *t, bool timed, int &k) {
   mark(t, timed, k);
 }
 
-void enqueue_update(gpd_hip_trainer *t, bool timed, int &k) {
+}  // namespace
+
+void gpd::enqueue_update(gpd_hip_trainer *t, bool timed, int &k) {
   if (t->r.solver == GPD_TRAIN_SOLVER_SGD)
     enqueue_sgd(t, timed, k);
   else
     enqueue_adam(t, timed, k);
 }
+
+namespace {
 
 int check_indices(const char *who, const int32_t *indices, long long count, int n) {
   for (long long i = 0; i < count; i++)

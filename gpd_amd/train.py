@@ -31,6 +31,18 @@ takes no TRAIN_DIR: CONFIG is a generate_data configuration, and the two residen
 gpd_amd.hostlib.generate_data — every view one gpd_hip_train_append_view, every object's ranges shuffled by
 gpd_hip_train_reorder — to the bytes the four .npy files would hold, which are never written; the trainer has CONFIG's
 image_num_channels and runs on its hip_device.  Training then goes on exactly as above.
+
+python -m gpd_amd.train TRAIN_DIR ... --devices 0,1,...
+
+trains on several devices as pytorch/train_net3.py does under nn.DataParallel (:97-99), with either recipe: one replica per
+listed device — a device listed twice carries two — each on a context of its own, stepped together by api.TrainerGroup
+(gpd_hip_train_group_steps: every replica applies the fixed-order mean of the replicas' gradients, and no parameter leaves the
+devices).  --batch stays the GLOBAL batch and must be divisible by the number of replicas G.  Replica r holds training images
+r, r + G, r + 2 G, ... and walks them in its own orders, gpd_hip_shuffle_orders((seed + 1000003 (r + 1)) & 0xffffffff, ...) over
+its shard; an epoch (a pass, under the Caffe recipe) is min_r(n_r) // (batch / G) steps.  A departure from the single-device
+route: the TAILS ARE DROPPED — no short last batch, and the images a larger shard has beyond the smallest sit the epoch out.
+The test set, eval, snapshots and the export live on replica 0; --resume and --init set replica 0 and broadcast.  --generate
+with --devices is refused.  Without --devices the tool behaves to the byte as before.
 """
 import argparse
 import os
@@ -108,10 +120,11 @@ def train(trainer, n, epochs, batch, seed, n_test=0, log=print):
 TEST_INTERVAL, TEST_IMAGES = 100, 10000  # the solver file's test_interval; test_iter 100 of batches of 100
 
 
-def batch_rows(seed, n, batch, first, count):
+def batch_rows(seed, n, batch, first, count, per=None):
     """Rows first .. first + count of the endless list of full batches: pass e over the set is gpd_hip_shuffle_orders' order
-    number e, cut into n // batch rows (Caffe's data layer wraps around; here every pass is shuffled and its tail dropped)."""
-    per = n // batch
+    number e, cut into n // batch rows (Caffe's data layer wraps around; here every pass is shuffled and its tail dropped).
+    per: rows taken from a pass where that is fewer than n // batch (a replica beside one with a smaller shard)."""
+    per = n // batch if per is None else per
     if per < 1:
         raise ValueError("the training set has %d images, a batch needs %d" % (n, batch))
     e0, e1 = first // per, (first + count - 1) // per
@@ -137,15 +150,57 @@ def read_snapshot(trainer, directory):
     return count
 
 
-def train_caffe(trainer, n, max_iter, batch, seed, n_test=0, start=0, snapshot=0, out=None, log=print):
-    """Iterations start .. max_iter of the Caffe recipe over the trainer's resident sets -> the final state."""
+def replica_seed(seed, r):
+    """The seed of replica r's orders"""
+    return (int(seed) + 1000003 * (r + 1)) & 0xFFFFFFFF
+
+
+def shard_steps(shards, batch):
+    """Steps of an epoch over shards of these sizes at a batch of `batch` per replica: the smallest shard's full batches"""
+    per = min(shards) // batch
+    if per < 1:
+        raise ValueError("the smallest shard has %d images, a replica's batch needs %d" % (min(shards), batch))
+    return per
+
+
+def train_group(group, shards, epochs, batch, seed, n_test=0, log=print):
+    """train() over a TrainerGroup: `batch` is the global batch, shards the replicas' image counts -> replica 0's final state."""
+    G = len(group)
+    b = batch // G
+    per = shard_steps(shards, b)
+    orders = [api.shuffle_orders(replica_seed(seed, r), [shards[r]] * epochs) for r in range(G)]
+    first = group.trainers[0]
+    for epoch in range(epochs):
+        losses, _ = group.steps(np.stack([orders[r][epoch][:per * b].reshape(per, b) for r in range(G)]))
+        for i in range(999, len(losses), 1000):
+            log("[%d, %5d] loss: %.3f" % (epoch + 1, i + 1, float(losses[i - 999:i + 1].mean())))
+        if len(losses) % 1000:
+            log("[%d, %5d] loss: %.3f" % (epoch + 1, len(losses), float(losses[len(losses) // 1000 * 1000:].mean())))
+        if n_test:
+            _, correct = first.eval(n=n_test, which=1)
+            log("epoch: %d, correct: %d, total: %d, accuracy: %.3f" % (epoch + 1, correct, n_test, correct / n_test))
+    return first.get_state()
+
+
+def group_rows(seed, shards, batch, first, count):
+    """batch_rows for every replica of a group (batch: per replica) -> i32 [G, count, batch]"""
+    per = shard_steps(shards, batch)
+    return np.stack([batch_rows(replica_seed(seed, r), n, batch, first, count, per) for r, n in enumerate(shards)])
+
+
+def train_caffe(trainer, n, max_iter, batch, seed, n_test=0, start=0, snapshot=0, out=None, log=print, group=None):
+    """Iterations start .. max_iter of the Caffe recipe over the trainer's resident sets -> the final state.  group: a
+    TrainerGroup whose replica 0 is `trainer`; n is then the list of the replicas' image counts and batch the global batch."""
     n_test = min(TEST_IMAGES, n_test)
     it = start
     while it < max_iter:
         stop = min(max_iter, (it // TEST_INTERVAL + 1) * TEST_INTERVAL)
         if snapshot:
             stop = min(stop, (it // snapshot + 1) * snapshot)
-        losses = trainer.steps(batch_rows(seed, n, batch, it, stop - it))
+        if group is None:
+            losses = trainer.steps(batch_rows(seed, n, batch, it, stop - it))
+        else:
+            losses, _ = group.steps(group_rows(seed, n, batch // len(group), it, stop - it))
         it = stop
         if it % TEST_INTERVAL == 0 or it == max_iter:
             lr = float(api.learning_rate(trainer.recipe, trainer.params.lr, it - 1))
@@ -169,11 +224,49 @@ def frozen_names(spec):
     return names
 
 
+class Replicas:
+    """--devices: a context and a trainer per listed device and the group over them, closed in order.  Replica r holds the
+    training images r, r + G, ...; the test set lives on replica 0."""
+
+    def __init__(self, a, train_set, **trainer_kw):
+        img, lab = train_set
+        C, G = img.shape[3], len(a.devices)
+        self.ctxs, self.trainers, self.group = [], [], None
+        try:
+            for d in a.devices:
+                self.ctxs.append(api.Context(api.default_params(C), device=d))
+                self.trainers.append(api.Trainer(self.ctxs[-1], max_batch=a.batch // G, **trainer_kw))
+            self.group = api.TrainerGroup(self.trainers)
+            for r, t in enumerate(self.trainers):
+                t.set_data(img[r::G], lab[r::G], 0)
+            self.shards = [len(lab[r::G]) for r in range(G)]
+            self.n_test = 0
+            if a.test:
+                timg, tlab = load_set(a.test, "test", C)
+                self.trainers[0].set_data(timg, tlab, 1)
+                self.n_test = len(tlab)
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        if self.group is not None:
+            self.group.close()
+        for t in self.trainers:
+            t.close()
+        for c in self.ctxs:
+            c.close()
+
+
 def main_caffe(a):
     C, device, train_set = open_sets(a)
     recipe = api.train_default_recipe(1, lr_mult={k: 0.0 for k in frozen_names(a.freeze or "")})
-    ctx = api.Context(api.default_params(C), device=device)
-    trainer = api.Trainer(ctx, recipe=recipe, max_batch=a.batch, lr=api.CAFFE_BASE_LR)
+    reps = Replicas(a, train_set, recipe=recipe, lr=api.CAFFE_BASE_LR) if a.devices else None
+    if reps:
+        ctx, trainer = None, reps.trainers[0]
+    else:
+        ctx = api.Context(api.default_params(C), device=device)
+        trainer = api.Trainer(ctx, recipe=recipe, max_batch=a.batch, lr=api.CAFFE_BASE_LR)
     try:
         scale = float(trainer.params.input_scale)
         start = 0
@@ -185,13 +278,23 @@ def main_caffe(a):
             trainer.set_state(eigen_export.to_torch(eigen_export.load(a.init, fill), scale))
         else:
             trainer.set_state(api.init_xavier(C, a.seed))
-        n, n_test = fill_sets(trainer, a, train_set)
-        print("training on %d images of %d channels from iteration %d to %d%s" % (n, C, start, a.max_iter, ", testing on %d" % min(TEST_IMAGES, n_test) if n_test else ""))
-        state = train_caffe(trainer, n, a.max_iter, a.batch, a.seed, n_test, start, a.snapshot, a.out)
+        if reps:
+            reps.group.broadcast(0)
+            n, n_test = sum(reps.shards), reps.n_test
+            print("training on %d images of %d channels over %d replicas from iteration %d to %d%s"
+                  % (n, C, len(reps.shards), start, a.max_iter, ", testing on %d" % min(TEST_IMAGES, n_test) if n_test else ""))
+            state = train_caffe(trainer, reps.shards, a.max_iter, a.batch, a.seed, n_test, start, a.snapshot, a.out, group=reps.group)
+        else:
+            n, n_test = fill_sets(trainer, a, train_set)
+            print("training on %d images of %d channels from iteration %d to %d%s" % (n, C, start, a.max_iter, ", testing on %d" % min(TEST_IMAGES, n_test) if n_test else ""))
+            state = train_caffe(trainer, n, a.max_iter, a.batch, a.seed, n_test, start, a.snapshot, a.out)
         names = eigen_export.export(state, a.out, scale)
     finally:
-        trainer.close()
-        ctx.close()
+        if reps:
+            reps.close()
+        else:
+            trainer.close()
+            ctx.close()
     print("wrote %s: %s" % (a.out, " ".join(names)))
     return 0
 
@@ -205,6 +308,7 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--seed", type=int, default=0, help="of the initial state and of the epochs' orders")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--devices", help="train on several replicas: a comma-separated device list, one replica each (a device listed twice carries two)")
     ap.add_argument("--out", required=True, help="parameter directory to write")
     ap.add_argument("--recipe", choices=["torch", "caffe"], default="torch", help="caffe: the deployed LeNet under the reference's Caffe solver")
     ap.add_argument("--max-iter", type=int, default=10000, help="caffe: iterations (the solver file's max_iter)")
@@ -219,6 +323,17 @@ def parse_args(argv=None):
         ap.error("TRAIN_DIR or --generate CONFIG is needed")
     if a.recipe != "caffe" and (a.resume or a.init or a.freeze or a.snapshot):
         ap.error("--snapshot, --resume, --init and --freeze need --recipe caffe")
+    if a.devices is not None:
+        if a.generate:
+            ap.error("--generate with --devices: generating over several devices is not there yet; write the set with generate_data and pass TRAIN_DIR")
+        try:
+            a.devices = [int(d) for d in a.devices.split(",")]
+        except ValueError:
+            ap.error("--devices takes a comma-separated list of device numbers")
+        if not 1 <= len(a.devices) <= 16 or min(a.devices) < 0:
+            ap.error("--devices takes 1 .. 16 device numbers")
+        if a.batch % len(a.devices):
+            ap.error("--batch %d is the global batch: it must be divisible by the %d replicas" % (a.batch, len(a.devices)))
     return a
 
 
@@ -227,17 +342,29 @@ def main(argv=None):
     if a.recipe == "caffe":
         return main_caffe(a)
     C, device, train_set = open_sets(a)
-    ctx = api.Context(api.default_params(C), device=device)
-    trainer = api.Trainer(ctx, max_batch=a.batch)
+    reps = Replicas(a, train_set) if a.devices else None
+    if reps:
+        ctx, trainer = None, reps.trainers[0]
+    else:
+        ctx = api.Context(api.default_params(C), device=device)
+        trainer = api.Trainer(ctx, max_batch=a.batch)
     try:
         trainer.set_state(api.init_state(C, a.seed))
-        n, n_test = fill_sets(trainer, a, train_set)
-        print("training on %d images of %d channels%s" % (n, C, ", testing on %d" % n_test if n_test else ""))
-        state = train(trainer, n, a.epochs, a.batch, a.seed, n_test)
+        if reps:
+            reps.group.broadcast(0)
+            print("training on %d images of %d channels over %d replicas%s" % (sum(reps.shards), C, len(reps.shards), ", testing on %d" % reps.n_test if reps.n_test else ""))
+            state = train_group(reps.group, reps.shards, a.epochs, a.batch, a.seed, reps.n_test)
+        else:
+            n, n_test = fill_sets(trainer, a, train_set)
+            print("training on %d images of %d channels%s" % (n, C, ", testing on %d" % n_test if n_test else ""))
+            state = train(trainer, n, a.epochs, a.batch, a.seed, n_test)
         names = torch_export.export(state, a.out, float(trainer.params.input_scale))
     finally:
-        trainer.close()
-        ctx.close()
+        if reps:
+            reps.close()
+        else:
+            trainer.close()
+            ctx.close()
     try:
         import torch
     except ImportError:

@@ -768,6 +768,58 @@ const char *gpd_hip_train_kernel_name_of(const gpd_hip_trainer *t, int i);
 int gpd_hip_train_get_solver_state(gpd_hip_trainer *t, float *const m[8], float *const v[8], long long *count);
 int gpd_hip_train_set_solver_state(gpd_hip_trainer *t, const float *const m[8], const float *const v[8], long long count);
 
+/* ---- training on several replicas (train_group.hip, group_model.h) ---------------------------------------------
+ * What pytorch/train_net3.py:97-99 gets from nn.DataParallel: G trainers ("replicas"), each on a context of its own — on G
+ * devices, or several on one device — run forward and backward on a batch each, and every replica's solver applies the MEAN
+ * of the G gradients.  The definition is the composed route — gpd_hip_train_gradients on every replica,
+ * gpd_hip_train_group_mean on the host, gpd_hip_train_apply on every replica — and gpd_hip_train_group_steps is held to it
+ * byte for byte while no parameter-sized buffer leaves the devices.
+ *
+ * Host only, the definition:
+ *  - mean: per element s = g[0]; s = s + g[r] for r = 1 .. G - 1 in rank order; out = s * (float)(1.0 / G), every operation a
+ *    rounded f32 operation, nothing fused.  G = 1: g[0]'s bits.  A step's loss is the same expression over the replicas' losses.
+ *  - slices: [0, n) cut into G contiguous slices first[o] .. first[o + 1] (first holds G + 1 entries); every boundary but n is
+ *    a multiple of 4 floats, the sizes differ by at most 4 floats.  Replica o sums slice o.
+ *  - schedule: the list of operations gpd_hip_train_group_steps enqueues for num_steps steps, in the order in which it
+ *    enqueues them from its one host thread (a stream's wait binds to the record enqueued last, so the order is part of the
+ *    list's correctness).  An operation is five int32 {kind, stream, peer, slice, event}; stream = the replica on whose
+ *    stream it goes; peer, slice, event are -1 where the kind has none.  kind 0: forward and backward of the replica's next
+ *    batch; 1: wait on `event`; 2: record `event`; 3: copy slice `slice` of replica `peer`'s gradient buffer — slice ==
+ *    stream: into the replica's gather row of `peer`, otherwise to the same place of its own gradient buffer; 4: the
+ *    replica's own slice = the mean of its buffer and its gather rows, in place; 5: the solver's update.  Events: r = the
+ *    gradients of replica r, G + o = the sum of owner o, 2 G + r = replica r holds every sum.  ops may be NULL (count only);
+ *    *num = the operations of the list; GPD_ERR_CAPACITY if capacity is smaller.
+ * GPD_ERR_INVALID: a null argument, G outside 1 .. 16, a negative count. */
+int gpd_hip_train_group_mean(const float *const *g, int G, size_t n, float *out);
+int gpd_hip_train_group_slices(size_t n, int G, long long *first);
+int gpd_hip_train_group_schedule(int G, int num_steps, void *ops, int capacity, int *num);
+
+typedef struct gpd_hip_train_group gpd_hip_train_group;
+/* 1 <= num <= 16 trainers.  The group takes no ownership: it is destroyed before its trainers, and a trainer may still be
+ * stepped alone (gpd_hip_train_group_verify then tells).  GPD_ERR_INVALID before anything is allocated: a null or repeated
+ * trainer, two trainers on one context, channel counts, gpd_train_params (apart from max_batch) or recipes that differ.
+ * Allocates per replica a gather block of G - 1 slices and three events; never enables peer access. */
+int gpd_hip_train_group_create(gpd_hip_trainer *const *trainers, int num, gpd_hip_train_group **out);
+void gpd_hip_train_group_destroy(gpd_hip_train_group *g);
+/* Replica src's parameters, solver buffers and update count into every other replica, device to device; returns after the
+ * copies.  How a group starts (gpd_hip_train_set_state on one replica, then this) and how a snapshot resumes. */
+int gpd_hip_train_group_broadcast(gpd_hip_train_group *g, int src);
+/* num_steps updates.  In step s replica r runs forward and backward on the images indices[r][s * batch .. (s + 1) * batch) of
+ * ITS OWN resident training set, the mean of the G gradients is formed on the devices (each replica sums one slice and hands
+ * it round: 2 (G - 1) / G of a buffer moved per replica and step) and every replica's solver applies it: the replicas end
+ * with identical bytes without a parameter broadcast.  losses [num_steps]: the mean of the replicas' losses by the same
+ * expression; replica_losses (may be NULL) [num][num_steps].  The steps are enqueued back to back and waited for once (once per
+ * 2^20 indices of a replica); no parameter-sized copy crosses to or from the host.  GPD_ERR_INVALID before anything is
+ * launched, naming replica and position: a batch outside 1 .. max_batch of a replica, an index outside a replica's set. */
+int gpd_hip_train_group_steps(gpd_hip_train_group *g, const int32_t *const *indices, int num_steps, int batch, float *losses,
+                              float *replica_losses);
+/* *num_different = the 32-bit words of the parameters and the solver buffers of replicas 1 .. num - 1 that differ from
+ * replica 0's, counted on the devices (replica 0's buffers come over slice by slice), plus 1 for each replica whose update
+ * count differs: 0 for a group that has only been stepped together since its broadcast. */
+int gpd_hip_train_group_verify(gpd_hip_train_group *g, long long *num_different);
+/* Bytes the last broadcast / steps / verify call moved: out[0] between replicas, out[1] between host and devices. */
+int gpd_hip_train_group_last_bytes(gpd_hip_train_group *g, long long out[2]);
+
 #ifdef __cplusplus
 }
 #endif
