@@ -12,15 +12,6 @@
 #include "gpd_internal.h"
 #include <cmath>
 
-#define HIP_RET(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return GPD_ERR_HIP;                                                                   \
-    }                                                                                       \
-  } while (0)
-
 namespace gpd {
 
 namespace {
@@ -125,6 +116,7 @@ __global__ __launch_bounds__(1024) void cluster_emit_kernel(ClusterParams P, gpd
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) s_carry = 0;
   __syncthreads();
+  // (the scan of wave_ops.h block_scan_step written out: the emit sits between its barriers — behind them it costs two VGPRs)
   for (int base = 0; base < P.n; base += 1024) {
     const int i = base + tid;
     const int v = i < P.n ? P.keep[i] : 0;

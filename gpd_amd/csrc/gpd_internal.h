@@ -75,6 +75,14 @@ int lenet_check(LeNetScratch &s);
 void lenet_scratch_free(LeNetScratch &s);
 
 void set_error(const char *fmt, ...);
+#define HIP_RET(expr)                                                                       \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if (e_ != hipSuccess) {                                                                 \
+      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+      return GPD_ERR_HIP;                                                                   \
+    }                                                                                       \
+  } while (0)
 // the device and the first lane's stream of a context (context.hip): what a trainer (train.hip) runs on
 void ctx_device_stream(gpd_hip_ctx *ctx, int *device, hipStream_t *stream);
 // every growth of a device / pinned buffer (hipFree + hipMalloc: a device stall) is counted per host thread; the batch
@@ -148,7 +156,7 @@ int cluster_run(ClusterState &s, const gpd_hand *hands, const double *scores, in
 // in s.d_out, their number in s.d_num; nothing waits for the device
 int cluster_run_resident(ClusterState &s, const gpd_hand *d_hands, int n, int min_inliers, int remove_inliers, hipStream_t stream);
 
-// ---- Cloud (search.hip) -----------------------------------------------------
+// ---- Cloud (cloud.hip) ------------------------------------------------------
 // Device copy of what the path reads from util::Cloud, as SoA for coalesced streaming.
 // cameras of a cloud: the kernels carry "which cameras see this neighbourhood" as a 32-bit mask and the view points
 // as a kernel argument (768 bytes)
@@ -157,7 +165,7 @@ constexpr int kMaxCams = 32;
 // memory: 44 bytes per list entry and sample).  Beyond 65535 entries hand_eval_kernel walks the full list instead of its
 // LDS table, whose neighbour ranks are 16 bits wide.
 constexpr int kNnCapMax = (1 << 20) - 1;
-// scratch of Cloud::calculateNormals on the device (search.hip normals_run): per-point neighbour lists in one array
+// scratch of Cloud::calculateNormals on the device (normals.hip normals_run): per-point neighbour lists in one array
 struct NormalsScratch {
   int cap_points = 0;
   long long arena_cap = 0;         // 8-byte units
@@ -219,7 +227,7 @@ int cloud_reserve(Cloud &c, int n, int num_cams);
 int cloud_from_device(Cloud &c, const float *d_xyz, const int32_t *d_cam, int n, int num_cams, const double *view_points, hipStream_t stream);
 int cloud_reserve_grid(Cloud &c, int cells);
 void cloud_free(Cloud &c);
-int normals_run(Cloud &c, double radius, float *normals_out, hipStream_t stream);
+int normals_run(Cloud &c, double radius, float *normals_out, hipStream_t stream);  // normals.hip
 
 // ---- Candidate search (search.hip) -----------------------------------------------
 struct SearchState {
@@ -536,6 +544,26 @@ struct HostConsts {
   double nn_radius_hands, nn_radius_images;
 };
 void host_consts(const gpd_params &p, HostConsts &h);
+
+// ---- Launchers for other units (a kernel is launched from the unit that defines it).  Hand kernels (hands.hip): what the
+// drivers of search.hip enqueue on the lists of a SearchState ------------------------------------------------------------
+// Each takes the lock of the device's constant block (uploading p / hc when they differ from the loaded ones), launches and
+// drops the lock.  cap: the list capacity the neighbourhoods were built with.
+#pragma GCC visibility push(hidden)  // calls between two units of the library: not part of its dynamic symbol table
+// hand_eval_kernel over S samples: s.d_hands, s.d_fvalid
+int hands_enqueue_eval(const gpd_params &p, const HostConsts &hc, SearchState &s, int cap, int S, hipStream_t stream);
+// reeval_kernel over the n records in s.d_hands (one per sample slot): their flags, s.d_labels
+int hands_enqueue_reeval(const gpd_params &p, const HostConsts &hc, SearchState &s, int cap, int n, hipStream_t stream);
+// label_kernel over the n records d_recs, candidate c on list d_cand_list[c] of the `lists` in gs: their flags, d_labels8
+int hands_enqueue_label(const gpd_params &p, const HostConsts &hc, SearchState &gs, int cap, int lists, gpd_hand *d_recs, int n,
+                        const int32_t *d_cand_list, uint8_t *d_labels8, hipStream_t stream);
+// label_sets_kernel / label_meta_kernel (one workgroup each) around it
+int hands_enqueue_label_sets(const gpd_hand *d_recs, int n, int32_t *d_cand_list, double *d_sample_xyz, int32_t *d_meta, hipStream_t stream);
+int hands_enqueue_label_meta(const int32_t *d_counts, int lists, const uint8_t *d_labels8, int n, const int32_t *d_img_status, int32_t *d_meta,
+                             hipStream_t stream);
+// (cloud.hip, for normals.hip) the planes of c again, its coordinates as staged and the normals d_nrm [num_points][3]
+int cloud_set_normals(Cloud &c, const float *d_nrm, hipStream_t stream);
+#pragma GCC visibility pop
 
 // ---- Cloud::sampleAbovePlane on the device (plane.hip; the definition: plane_model.h) ------------------------
 constexpr int kPlaneMaxHyp = 1024;   // hypotheses per call: max_iterations <= 1023

@@ -1,5 +1,6 @@
-// Device pieces the radius searches (search.hip) and the k-nearest-neighbour search (refine.hip) share: the cell of a
-// coordinate in the cloud's uniform grid, and the in-register bitonic sort of (d2 bits, index) keys.
+// Device pieces the grid build (cloud.hip), the radius searches (search.hip, normals.hip) and the k-nearest-neighbour
+// search (refine.hip) share: the cell of a coordinate in the cloud's uniform grid, the visit of the cells around a query,
+// the in-register bitonic sort of (d2 bits, index) keys, and the test that certifies an order-free fp64 sum of floats.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,45 @@ namespace gpd {
 __device__ inline int grid_coord(const GridView &g, int axis, float v) {
   int k = (int)floorf((v - g.lo[axis]) / g.cell);
   return k < 0 ? 0 : (k > g.dim[axis] - 1 ? g.dim[axis] - 1 : k);
+}
+
+// Visits every point of the cells overlapping the cube of half-edge `reach` around q: calls
+// visit(original index, x, y, z).  Wave w takes (x, y) cell columns w, w + nwaves, ...; a column's
+// cells are contiguous in memory (z fastest), its lanes stride the point range.  All lanes of a
+// wave run the same number of iterations, so `visit` may use wave-wide operations.
+template <class Visit>
+__device__ inline void grid_visit(const GridView &g, float qx, float qy, float qz, float reach, int wave, int nwaves, int lane,
+                                  Visit visit) {
+  const int x0 = grid_coord(g, 0, qx - reach), x1 = grid_coord(g, 0, qx + reach);
+  const int y0 = grid_coord(g, 1, qy - reach), y1 = grid_coord(g, 1, qy + reach);
+  const int z0 = grid_coord(g, 2, qz - reach), z1 = grid_coord(g, 2, qz + reach);
+  const int ny = y1 - y0 + 1;
+  const int ncol = (x1 - x0 + 1) * ny;
+  for (int col = wave; col < ncol; col += nwaves) {
+    const int cx = x0 + col / ny, cy = y0 + col % ny;
+    const int cbase = (cx * g.dim[1] + cy) * g.dim[2];
+    const int b = g.start[cbase + z0], e = g.start[cbase + z1 + 1];
+    for (int t0 = b; t0 < e; t0 += 64) {
+      const int t = t0 + lane;
+      const bool in = t < e;
+      const int tt = in ? t : b;
+      const float4 p = g.p[tt];
+      visit(in, __float_as_int(p.w), p.x, p.y, p.z);
+    }
+  }
+}
+
+// Is the fp64 sum of n floats exact in every order?  emin / emax: smallest / largest biased exponent among the non-zero addends
+// (denormals count as exponent 1; no non-zero addend: emin = 255 > emax = 0).  Every addend is a multiple of 2^(emin - 150) and
+// below 2^(emax - 126) in magnitude, so every partial sum of every subset is a multiple of the former below n 2^(emax - 126);
+// fp64 holds every multiple of 2^L below 2^(L + 53): exact when ceil(log2 n) + emax - 126 <= emin - 150 + 53.  One more bit is
+// left as margin; infinities / NaNs (emax = 255) never pass.
+__host__ __device__ inline bool centre_exact(int emin, int emax, int n) {
+  if (emax == 0) return true;  // nothing but zeros
+  if (emax >= 255) return false;
+  int lg = 0;
+  while ((1ll << lg) < (long long)n) lg++;
+  return lg + emax - emin <= 28;
 }
 
 // Bitonic sort of 64 K keys held K per lane, element e = lane * K + r, ascending — in the formulation whose every

@@ -16,19 +16,11 @@
 // decision for every float (plane_model.h).  -ffp-contract=off (Makefile): every expression is evaluated unfused.
 #include "gpd_internal.h"
 #include "plane_model.h"
+#include "wave_ops.h"
 
 #include <cstdio>
 #include <cstring>
 #include <vector>
-
-#define HIP_RET(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return GPD_ERR_HIP;                                                                   \
-    }                                                                                       \
-  } while (0)
 
 namespace gpd {
 
@@ -225,26 +217,13 @@ __global__ __launch_bounds__(kFlagThreads) void flag_count_kernel(const float *_
 __global__ __launch_bounds__(1024) void scan_kernel(const int32_t *__restrict__ block_count, int nblocks, int32_t *__restrict__ block_off, PlaneMeta *meta) {
   __shared__ int s_part[16];
   __shared__ int s_carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   if (tid == 0) s_carry = 0;
   __syncthreads();
   for (int base = 0; base < nblocks; base += 1024) {
     const int i = base + tid;
-    const int v = i < nblocks ? block_count[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    int before = s_carry;
-    for (int w = 0; w < wave; w++) before += s_part[w];
-    if (i < nblocks) block_off[i] = before + incl - v;
-    __syncthreads();
-    if (tid == 1023) s_carry = before + incl;
-    __syncthreads();
+    const int before = block_scan_step(i < nblocks ? block_count[i] : 0, s_part, s_carry);
+    if (i < nblocks) block_off[i] = before;
   }
   if (tid == 0) meta->total = s_carry;
 }

@@ -22,6 +22,7 @@
 // against 1.5 ms this way and 7.9 ms for the std::set itself — DESIGN §8.)  Everything around it (keys, minimum, gather
 // of the kept voxels) is data parallel and stays on the device.
 #include "gpd_internal.h"
+#include "wave_ops.h"
 #include <cfloat>
 #include <cmath>
 #include <cstddef>
@@ -29,15 +30,6 @@
 #include <cstring>
 #include <mutex>
 #include <vector>
-
-#define HIP_RET(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return GPD_ERR_HIP;                                                                   \
-    }                                                                                       \
-  } while (0)
 
 namespace gpd {
 
@@ -124,20 +116,8 @@ __global__ __launch_bounds__(1024) void ws_scan_kernel(const int32_t *__restrict
     const int v = i < nblocks ? block_count[i] : 0;
     if (i < nblocks)
       for (int a = 0; a < 3; a++) lo[a] = fminf(lo[a], block_lo[3 * i + a]);
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    int before = s_carry;
-    for (int w = 0; w < wave; w++) before += s_part[w];
-    if (i < nblocks) block_off[i] = before + incl - v;
-    __syncthreads();
-    if (tid == 1023) s_carry = before + incl;
-    __syncthreads();
+    const int before = block_scan_step(v, s_part, s_carry);
+    if (i < nblocks) block_off[i] = before;
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1)

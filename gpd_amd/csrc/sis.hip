@@ -9,15 +9,6 @@
 
 #include "sis_model.h"
 
-#define HIP_RET(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return GPD_ERR_HIP;                                                                   \
-    }                                                                                       \
-  } while (0)
-
 namespace gpd {
 
 namespace {

@@ -21,15 +21,6 @@
 
 using namespace gpd;
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess) {                                                             \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return GPD_ERR_HIP;                                                               \
-    }                                                                                   \
-  } while (0)
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

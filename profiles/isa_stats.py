@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gpd_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-UNITS = ("context", "lenet", "lenet_fast", "search", "images", "plan", "preprocess", "cluster", "sis")
+UNITS = ("context", "lenet", "lenet_fast", "cloud", "normals", "search", "hands", "images", "plan", "preprocess", "cluster", "sis")
 
 
 def _run(*a):

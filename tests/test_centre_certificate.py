@@ -1,6 +1,6 @@
 """The centre of a sample's image neighbourhood (HandSet::calculateShadow, hand_set.cpp:131-133: points.rowwise().sum() / size)
 is an fp64 sum of float coordinates.  The oracle sums sequentially in neighbour order, Eigen reduces in packets; the neighbourhood
-kernel takes an order-free sum and certifies it (search.hip centre_exact): every addend is a multiple of 2^(emin - 150) and below
+kernel takes an order-free sum and certifies it (grid_sort.h centre_exact): every addend is a multiple of 2^(emin - 150) and below
 2^(emax - 126), so with ceil(log2 n) + emax - emin <= 28 every partial sum of every order is exact in fp64.  CPU: the certificate's
 arithmetic as a property of numpy floats.  GPU: both routes against the oracle, the serial-chain fallback forced by points
 micrometres from a coordinate plane."""
@@ -13,7 +13,7 @@ from gpd_amd import api, synth
 
 
 def centre_exact(x):
-    """the certificate of gpd_amd/csrc/search.hip centre_exact, on a float32 vector"""
+    """the certificate of gpd_amd/csrc/grid_sort.h centre_exact, on a float32 vector"""
     b = x.view(np.uint32)
     nz = (b & 0x7FFFFFFF) != 0
     if not nz.any():

@@ -651,7 +651,7 @@ def test_neighbourhoods_beyond_65535_points(oracle_mod):
 
 
 def test_normals_of_a_cloud_beyond_one_tile_of_points(oracle_mod):
-    """The normals kernels work through a cloud in tiles of 65536 points that share one lists array (search.hip kNormalsTile):
+    """The normals kernels work through a cloud in tiles of 65536 points that share one lists array (normals.hip kNormalsTile):
     a 150k-point cloud takes three passes, the last one ragged — normals bit for bit against the oracle, then a small cloud on
     the same context."""
     cl = synth.make_cloud(31, 150000)

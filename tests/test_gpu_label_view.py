@@ -171,6 +171,41 @@ def test_ground_truth_lists_beyond_the_lds_capacities(oracle_mod, cloud30k):
         ctx.close()
 
 
+def test_ground_truth_list_retry_to_16384_entries(oracle_mod):
+    """The round's list-capacity retry 8192 -> 16384 entries (the in-place bitonic sort), which the dense ground truth above jumps
+    over: a ground truth of 1000 scattered points plus 9000 jittered copies of the points within 5 cm of one of the round's four
+    samples, so that sample's list holds more than 8192 and fewer than 16384 points.  Then a sparse ground truth on the same
+    context.  Both views byte for byte against the oracle."""
+    om = oracle_mod
+    op = om.default_params(15)
+    cl = rcs.cloud()
+    xyz, nrm = cl["xyz"], cl["normals"]
+    rounds = _rounds(cl, 6)[2:3, 12:]  # four samples: two hand sets with candidates
+    sparse = np.arange(0, len(xyz), 8)
+    ball = np.flatnonzero(np.linalg.norm(xyz - xyz[rounds[0, 3]], axis=1) < 0.05)
+    rng = np.random.RandomState(11)
+    idx = ball[rng.randint(0, len(ball), 9000)]
+    dense_xyz = np.concatenate([xyz[sparse], (xyz[idx] + rng.uniform(-0.0003, 0.0003, (9000, 3))).astype(np.float32)])
+    dense_nrm = np.concatenate([nrm[sparse], nrm[idx]])
+    ctx = api.Context(api.default_params(15))
+    try:
+        ctx.upload_cloud(xyz, nrm, cl["cam_source"], cl["view_points"])
+        for what, gt, gn in (("dense cluster", dense_xyz, dense_nrm), ("sparse", xyz[sparse].copy(), nrm[sparse].copy())):
+            want = lvc.expected_view(om, op, xyz, nrm, cl["cam_source"], cl["view_points"], gt, gn, rounds, 10 ** 6, 500)
+            assert want["num_candidates"] == 9
+            sizes = [len(om.radius_search(gt, s.astype(np.float32), 0.11)[0]) for s in np.unique(want["all_hands"]["sample"], axis=0)]
+            if what == "sparse":
+                assert max(sizes) < 8192 and want["num_positives"] == 0
+            else:  # the cluster decides a label: without it the view has no positive
+                assert 8192 < max(sizes) < 16384 and min(sizes) < 8192 and want["num_positives"] == 1, sizes
+            ctx.upload_ground_truth(gt, gn)
+            got = ctx.label_view(rounds, 10 ** 6, 500, want_all_labels=True)
+            lvc.assert_view(got, want, what)
+            assert got["gt_neighbourhoods"] == 2
+    finally:
+        ctx.close()
+
+
 # ---- 5. edges --------------------------------------------------------------------------------------------------------------
 def _raw_job(ctx, rounds, min_positives, max_grasps, capacity):
     j = api.LabelViewJob()

@@ -1,7 +1,7 @@
 """Forms that share no code with either the oracle or the HIP path: numpy Rodrigues rotations, numpy `eigh`
 (incl. degenerate and nearly degenerate matrices), scipy's k-d tree.  The oracle is checked in the CPU suite, the
 product (through the C-ABI) in the GPU suite — so a misreading of Eigen's AngleAxis / SelfAdjointEigenSolver
-semantics that the oracle and the kernels had in common (the eigensolver in search.hip is a port of the oracle's,
+semantics that the oracle and the kernels had in common (the eigensolver in eigen3.h is a port of the oracle's,
 host_math.cpp's angle_axis has the oracle's form) would show up here."""
 import math
 
