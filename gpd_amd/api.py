@@ -183,6 +183,25 @@ def sis_select(centres, gauss, uniform, uniform_list, cloud_xyz, workspace, samp
     return dict(samples=samples[:n].copy(), accepted=acc, consumed=used, shortfall=int(short.value))
 
 
+class ImageModel(C.Structure):
+    """Mirror of `gpd_image_model` (include/gpd_hip.h)."""
+    _fields_ = [("window_class", C.c_int32), ("set_sd", C.c_int32), ("set_sr", C.c_int32), ("num_shadow", C.c_int32),
+                ("stride_a", C.c_uint32), ("stride_c", C.c_uint32), ("true_div", C.c_int32), ("reserved_", C.c_int32),
+                ("thr", (C.c_double * 61) * 3)]
+
+
+def image_model(params):
+    """gpd_hip_image_model: what the image stage derives from the geometry in `params` (host only) -> dict: window_class,
+    set_sd, set_sr, num_shadow, stride_a, stride_c, true_div and thr f64 [3, 61]."""
+    m = ImageModel()
+    rc = lib().gpd_hip_image_model(C.byref(params), C.byref(m))
+    if rc != 0:
+        raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
+    out = {k: int(getattr(m, k)) for k in ("window_class", "set_sd", "set_sr", "num_shadow", "stride_a", "stride_c", "true_div")}
+    out["thr"] = np.array(m.thr, np.float64).reshape(3, 61)
+    return out
+
+
 TORCH_KEYS = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
 
 
@@ -244,6 +263,7 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_set_lenet_conv_relu", "gpd_hip_lenet_from_torch",
            "gpd_hip_upload_ground_truth", "gpd_hip_label_view", "gpd_hip_balance_view", "gpd_hip_sizeof_label_view_job",
            "gpd_hip_shuffle_orders", "gpd_hip_sis_proposals", "gpd_hip_sis_select", "gpd_hip_detect_sis", "gpd_hip_sizeof_sis_job",
+           "gpd_hip_image_model",
            "gpd_hip_train_default_params", "gpd_hip_train_create", "gpd_hip_train_destroy", "gpd_hip_train_init_state",
            "gpd_hip_train_set_state", "gpd_hip_train_get_state", "gpd_hip_train_set_data", "gpd_hip_train_steps",
            "gpd_hip_train_gradients", "gpd_hip_train_apply", "gpd_hip_train_eval", "gpd_hip_train_step_timed",
@@ -323,6 +343,7 @@ def lib():
         L.gpd_hip_sis_select.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.gpd_hip_detect_sis.argtypes = [C.c_void_p, C.POINTER(SisJob)]
+        L.gpd_hip_image_model.argtypes = [C.POINTER(Params), C.POINTER(ImageModel)]
         L.gpd_hip_train_default_params.argtypes = [C.POINTER(TrainParams)]
         L.gpd_hip_train_default_params.restype = None
         L.gpd_hip_train_create.argtypes = [C.c_void_p, C.POINTER(TrainParams), C.POINTER(C.c_void_p)]

@@ -489,7 +489,7 @@ int gather_records(const gpd_hand *d_all, const int32_t *d_sel, int k, gpd_hand 
 // the largest k select_topk takes; beyond it the fused entries select with std::partial_sort on the downloaded scores
 int select_topk_capacity();
 
-// ---- Grasp images (images.hip) ---------------------------------------------------
+// ---- Grasp images (image_state.hip; images.hip: images_launch and the layout converters) ------------
 struct ImageState {
   unsigned long long lcg_base = 0;    // shadow draws consumed before this list's first hand set (a sample range of a sharded cloud)
   int num_candidates = 0;
@@ -498,7 +498,7 @@ struct ImageState {
   uint8_t *d_images_hwc = nullptr;    // [n][60][60][C], only when the caller downloads pixels
   uint32_t *d_set_bits = nullptr;     // [sets][SETWORDS] shadow voxel bitsets
   int num_shadow_sets = 0, cap_shadow_sets = 0;
-  bool wide = false;                  // the shadow kernels' wide voxel windows (images.hip Vox<WIDE>), picked from the image volume
+  bool wide = false;                  // the shadow kernels' wide voxel windows (image_model.h Vox<WIDE>), picked from the image volume
   bool huge = false;                  // ... or beyond those: the general shadow kernel, a set region of run-time size
   int set_sd = 0, set_sr = 0;         // edge / radius (voxels) of the region shadow_set_kernel fills around a sample
   size_t cap_setwords = 0;            // words per row of d_set_bits
@@ -529,7 +529,6 @@ void images_status_text(int status, char *buf, size_t len);
 int images_routes(const ImageState &im, int32_t *route, long long info[8]);
 hipError_t planar_to_hwc(const uint8_t *src, uint8_t *dst, int n, int C, hipStream_t stream);
 hipError_t hwc_to_planar(const uint8_t *src, uint8_t *dst, int n, int C, hipStream_t stream);
-void image_cell_thresholds(double len, double *out);  // 61 doubles
 void images_free(ImageState &im);
 
 // Host-side constants of the path (host_math.cpp), computed with libm exactly as the

@@ -24,6 +24,7 @@
 
 #include <mutex>
 
+#include "const_block.h"
 #include "gpd_internal.h"
 #include "wave_ops.h"
 
@@ -620,12 +621,7 @@ __global__ __launch_bounds__(256) void hand_eval_kernel(HandParams P) {
 #undef HTICK
 }
 
-// c_hand is ONE block per device, shared by every context of the process on that device.  A context
-// whose constants differ from the loaded ones waits for the device (kernels of another context, on
-// another stream, may still be reading the block) before it overwrites them; the lock is handed
-// back to the caller, who keeps it until its kernels that read the block are enqueued.
-static std::mutex g_hand_mutex;
-static std::vector<unsigned char> g_hand_loaded[64];
+static ConstBlock g_hand_block;  // c_hand on every device (const_block.h)
 
 static int upload_hand_consts(const gpd_params &p, const HostConsts &hc, int slots, hipStream_t stream,
                               std::unique_lock<std::mutex> &lock) {
@@ -666,19 +662,7 @@ static int upload_hand_consts(const gpd_params &p, const HostConsts &hc, int slo
   hk.hand_height = p.hand_height;
   hk.init_bite = p.init_bite;
   hk.filter = filter_consts(p);
-  lock = std::unique_lock<std::mutex>(g_hand_mutex);
-  int dev = 0;
-  HIP_RET(hipGetDevice(&dev));
-  std::vector<unsigned char> &loaded = g_hand_loaded[dev & 63];
-  const unsigned char *bytes = reinterpret_cast<const unsigned char *>(&hk);
-  if (loaded.size() == sizeof(hk) && std::memcmp(loaded.data(), bytes, sizeof(hk)) == 0) return GPD_OK;
-  if (!loaded.empty()) HIP_RET(hipDeviceSynchronize());
-  HIP_RET(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_hand), &hk, sizeof(hk), 0, hipMemcpyHostToDevice, stream));
-  // the block counts as loaded only once the copy has landed: a context with the same values skips
-  // the copy and launches on ITS stream, which is not ordered after this one
-  HIP_RET(hipStreamSynchronize(stream));
-  loaded.assign(bytes, bytes + sizeof(hk));
-  return GPD_OK;
+  return g_hand_block.load(c_hand, &hk, sizeof(hk), stream, lock);
 }
 
 // ---------------------------------------------------------------------------

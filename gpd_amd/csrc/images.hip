@@ -30,6 +30,11 @@
 //
 // Device images are planar u8 [n][C][60][60]; the cv::Mat HWC layout of the reference
 // interface is produced by planar_to_hwc_kernel when the caller asks for the pixels.
+//
+// This is the stage's ONE device unit: every image kernel reads c_img, so the kernels, the block's load and
+// images_launch are here.  The caps, the voxel windows and the contents of the block are image_model.h (plain C++),
+// the helpers and LDS structs the per-candidate bodies share image_device.h, and the host state around a launch —
+// buffers, the window class, the block's values — image_state.hip.
 #include <cfloat>
 #include <cmath>
 #include <cstddef>
@@ -38,49 +43,13 @@
 #include <cstring>
 
 #include <mutex>
-#include <type_traits>
 
+#include "const_block.h"
 #include "gpd_internal.h"
+#include "image_model.h"
 
 namespace gpd {
 
-constexpr int IMG_THREADS = 512;   // 256 VGPRs per lane: no spills (1024 threads measured equally fast but spilled)
-constexpr int SET_THREADS = 1024;  // shadow_set_kernel
-constexpr int IMG_WAVES = IMG_THREADS / 64;
-constexpr int PT_CAP = 1024;  // in-box points per candidate on the two-per-CU instantiation (mean ~380 on the 3 mm benchmark clouds; entry
-                              // indices are packed into 11 bits of the segment words); fuller boxes go to the large instantiation
-constexpr int PT_CAP_BIG = 32768;  // fallback instantiation of the points kernel: storage in a global scratch row (its segment table, 64 KB, is what fills the CU's LDS)
-constexpr int SH_CAP = 6144;      // in-box shadow voxels per candidate (two workgroups per CU)
-constexpr int SH_CAP_BIG = 12288;  // fallback instantiation, one workgroup per CU
-// Voxel windows of the shadow kernels.  Default geometry (image box diagonal 0.1233 m, every box of a hand set within
-// 0.1233 m of the sample): a 46^3 window per candidate and an 86^3 region per set, the latter an LDS bitset.  WIDE — picked
-// on the host for image volumes that do not fit those (images_run: up to ~0.18 m of box diagonal / 0.19 m of reach, e.g.
-// volume_width 0.16): 64^3 / 128^3, the set region filled with global-memory atomics (256 KB per set and camera).  The
-// reference has no such limits (hand_set.cpp:138); beyond WIDE the kernels still report GPD_ERR_CAPACITY.
-template <bool WIDE>
-struct Vox {
-  static constexpr int VD = WIDE ? 64 : 46;   // candidate window edge (a window row = VD bits along world z, one 64-bit word)
-  static constexpr int SD = WIDE ? 128 : 86;  // set region edge: offsets -SR .. SD - SR - 1 from the sample's voxel
-  static constexpr int SR = WIDE ? 64 : 43;   // (default: 41.1 voxels of reach -> 42 whole ones, one more on the low side;
-                                              //  86^3 bits = 79.5 KB: two shadow_set workgroups per CU)
-  static constexpr int LB = 18;               // bits of a voxel position inside the window: iz | iy << 6 | ix << 12 (ascending = lexicographic)
-  static constexpr int SETWORDS = (SD * SD * SD + 31) / 32;
-};
-
-struct ImgConsts {
-  double vol_depth, vol_width, vol_height, half_od, dbl_h;
-  int C, nproj, per;
-  double shadow_length, voxel, voxel_mult, rand_inv;
-  int num_shadow;
-  uint32_t stride_a, stride_c;  // LCG jump by SET_THREADS * num_shadow draws
-  double len[3];                // box extent per hand axis: vol_depth, vol_width, dbl_h
-  double inv_cell[3];           // approximate cells per metre (first guess only)
-  double thr[3][kImg + 1];      // thr[a][k] = smallest x with floor((x/len[a])/(1/60)) >= k
-  double inv_len[3];            // RN(1/len[a]) for the division by a constant below
-  int true_div;                 // 1: the host self-check of div_len failed for these extents, divide for real
-  int set_sd, set_sr;           // edge / radius of the voxel region shadow_set_kernel fills around a sample: 86 / 43, 128 / 64 (WIDE) or,
-                                // for image volumes beyond those windows, whatever the geometry needs (images_reserve)
-};
 __constant__ ImgConsts c_img;
 
 struct ImgParams {
@@ -106,653 +75,12 @@ struct ImgParams {
   char *huge_scratch;           // shadow_image_any_kernel: HUGE_SCRATCH_BYTES per workgroup of its grid
 };
 
-struct Box {
-  double F[9];
-  double sample[3];
-  double off[3];  // x_a = t_a - off[a]: bottom, center - half_od, -vol_height
-  double lo[3], hi[3];
-};
+}  // namespace gpd
 
-// points kernel: in-box points cached once, one projection's normals (3 planes) + depth at a time.
-// BIG (the overflow fallback, up to PT_CAP_BIG in-box points): the point arrays live in a global
-// scratch row instead of LDS.
-constexpr size_t PTS_SCRATCH_BYTES = (size_t)PT_CAP_BIG * (3 * sizeof(double) + sizeof(float4) + sizeof(uint32_t));  // + the in-box points' neighbour indices, 32 bits wide
-struct PointArrays {
-  double t[3][PT_CAP];  // hand-frame coordinates of the in-box points
-  float4 an[PT_CAP];    // |normal| in the hand frame (x, y, z) and, as bits in w, the cell key
-                        // cx | cy << 6 | cz << 12: one 16-byte read per visit
-};
-struct NoPointArrays {};
-// Under 80 KB for the small instantiation, so that two workgroups — two grasp_image ones, or one of them next to a
-// shadow_image one of another stream — share a CU (the kernels wait on LDS round trips and barriers most of their
-// time; the second resident workgroup fills those gaps).  What made it 155 KB before: three normal planes + a depth
-// plane held at once (57.6 KB) and 2048-point arrays.  Now the walks leave their four values per NON-EMPTY pixel
-// (at most one per in-box point) and the planes are rebuilt one after the other in the storage of the segment
-// counters, dilated straight into registers.
-template <bool BIG>
-struct __attribute__((aligned(16))) SmemPts {
-  typename std::conditional<BIG, NoPointArrays, PointArrays>::type p;
-  __attribute__((aligned(16))) uint32_t cells[kPix];   // (segment start << 16) | count of a pixel; after the walks: the index raster, then the staged bytes
-  uint16_t place[BIG ? PT_CAP_BIG : PT_CAP];  // segment table: entry numbers (entries are numbered in neighbour order)
-  float4 nzv[(BIG ? kPix : PT_CAP) + 1];      // slot 0: the empty pixel (zeros); slot q + 1: the three normal values and the
-                                              // depth value of the q-th non-empty pixel
-  uint16_t nzlist[BIG ? kPix : PT_CAP];       // the non-empty pixels, longest segment first
-  double thr[3][kImg + 1];
-  double recip[128];  // 1.0 / k
-  float red_f[4 * IMG_WAVES];
-  int red_i[IMG_WAVES];
-  int counter;
-  int flag;
-  int nnz;  // non-empty pixels of the projection (scan_cells_hist)
-};
-typedef SmemPts<false> Smem;
-// shadow kernel: kept under 80 KB (SHC = 6144) so that two workgroups share a CU
-template <int SHC, bool WIDE>
-struct __attribute__((aligned(16))) SmemShadow {
-  __attribute__((aligned(16))) float raster0[kPix];
-  __attribute__((aligned(16))) uint32_t cells[kPix];
-  uint32_t lin[SHC];  // set bits inside the box, ascending: voxel position (iz | iy << 6 | ix << 12) | cell x << LB | cell y << (LB + 6)
-  union {
-    struct {                        // while the list is built: per row of the voxel window (a line along world z) ...
-      uint16_t rowbase[Vox<WIDE>::VD * Vox<WIDE>::VD];  // ... where its in-box voxels start in `lin`
-      uint8_t rowcnt[Vox<WIDE>::VD * Vox<WIDE>::VD];    // ... and how many they are
-    } rows;
-    uint16_t place[SHC];  // afterwards: segment table of the counting sort
-  } bp;
-  uint16_t nz[kPix];
-  uint8_t cz[SHC];  // cell z of the list entries
-  double thr[3][kImg + 1];
-  double recip[128];
-  float red_f[4 * IMG_WAVES];
-  int red_i[IMG_WAVES];
-  int vorg[3];
-  int flag;
-  int nnz;  // non-empty pixels of the projection (scan_cells_hist)
-};
+#include "image_device.h"  // reads c_img: behind its definition
 
-// a workgroup-uniform double moved to scalar registers (the candidate's box is the same for
-// all 1024 lanes; keeping its 21 doubles in SGPRs frees ~40 VGPRs per lane)
-__device__ inline double uniform_f64(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
+namespace gpd {
 
-// wave-wide max / min of a float, the result in every lane: four DPP steps inside the rows of 16 lanes, two row
-// broadcasts, one v_readlane — 7 VALU instructions where six __shfl_xor steps are 6 ds_bpermute + ~25 VALU.  (A lane
-// whose DPP source is masked keeps its own value: max(v, v) = v.)
-template <class OP>
-__device__ inline float wave_reduce_f32(float v, OP op) {
-  auto dpp = [](float x, auto ctrl, auto rmask) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), decltype(ctrl)::value, decltype(rmask)::value, 0xf, false));
-  };
-  using std::integral_constant;
-  v = op(v, dpp(v, integral_constant<int, 0xB1>(), integral_constant<int, 0xf>()));   // quad_perm [1,0,3,2]
-  v = op(v, dpp(v, integral_constant<int, 0x4E>(), integral_constant<int, 0xf>()));   // quad_perm [2,3,0,1]
-  v = op(v, dpp(v, integral_constant<int, 0x141>(), integral_constant<int, 0xf>()));  // row_half_mirror
-  v = op(v, dpp(v, integral_constant<int, 0x140>(), integral_constant<int, 0xf>()));  // row_mirror
-  v = op(v, dpp(v, integral_constant<int, 0x142>(), integral_constant<int, 0xa>()));  // row_bcast:15 into rows 1, 3
-  v = op(v, dpp(v, integral_constant<int, 0x143>(), integral_constant<int, 0xc>()));  // row_bcast:31 into rows 2, 3
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ inline float wave_max_f32(float v) { return wave_reduce_f32(v, [](float a, float b) { return fmaxf(a, b); }); }
-__device__ inline float wave_min_f32(float v) { return wave_reduce_f32(v, [](float a, float b) { return fminf(a, b); }); }
-
-// wave-wide inclusive prefix sum of an int: row_shr 1 / 2 / 4 / 8 inside the rows of 16 lanes, then the row totals carried
-// over by row_bcast:15 / :31 — the sequence LLVM's atomic optimiser emits for gfx9; lanes without a source add 0
-__device__ inline int wave_incl_scan_i32(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);  // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);  // row_shr:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
-  return v;
-}
-
-// hand-frame coordinates of a world point: t = F^T (w - sample)  (image_strategy.cpp:36-40)
-__device__ inline void to_hand(const Box &B, double w0, double w1, double w2, double t[3]) {
-  const double c0 = w0 - B.sample[0], c1 = w1 - B.sample[1], c2 = w2 - B.sample[2];
-  t[0] = B.F[0] * c0 + B.F[3] * c1 + B.F[6] * c2;
-  t[1] = B.F[1] * c0 + B.F[4] * c1 + B.F[7] * c2;
-  t[2] = B.F[2] * c0 + B.F[5] * c1 + B.F[8] * c2;
-}
-// findPointsInUnitImage (image_strategy.cpp:53-70): strict box test
-__device__ inline bool in_box(const Box &B, const double t[3]) {
-  return (t[0] > B.lo[0]) && (t[0] < B.hi[0]) && (t[1] > B.lo[1]) && (t[1] < B.hi[1]) && (t[2] > B.lo[2]) && (t[2] < B.hi[2]);
-}
-// min(floor(((t - off)/len)/(1/60)), 59) by exact thresholds (see file header)
-template <class SM>
-__device__ inline int cell_coord(const SM &S, int axis, double x) {
-  int k = (int)(x * c_img.inv_cell[axis]);
-  k = k < 0 ? 0 : (k > kImg - 1 ? kImg - 1 : k);
-  // both neighbours of the guess at once (one LDS round trip; the guess is off by one at most, the loops are for the proof)
-  const double t0 = S.thr[axis][k], t1 = S.thr[axis][k + 1];
-  if (k > 0 && x < t0) {
-    k--;
-    while (k > 0 && x < S.thr[axis][k]) k--;
-  } else if (k < kImg - 1 && x >= t1) {
-    k++;
-    while (k < kImg - 1 && x >= S.thr[axis][k + 1]) k++;
-  }
-  return k;
-}
-template <class SM>
-__device__ inline uint32_t cells_of(const SM &S, const Box &B, const double t[3]) {
-  const int cx = cell_coord(S, 0, t[0] - B.off[0]);
-  const int cy = cell_coord(S, 1, t[1] - B.off[1]);
-  const int cz = cell_coord(S, 2, t[2] - B.off[2]);
-  return (uint32_t)cx | ((uint32_t)cy << 6) | ((uint32_t)cz << 12);
-}
-// projections by cumulative row swaps 0<->2 then 1<->2: (x,y,z), (z,y,x), (z,x,y);
-// cell = horizontal + 60 * vertical (image_strategy.cpp:92-102)
-__device__ inline int cell_of_key(uint32_t key, int pr) {
-  const int cx = key & 63, cy = (key >> 6) & 63, cz = (key >> 12) & 63;
-  const int v = pr == 0 ? cx : cz;
-  const int h = pr == 2 ? cx : cy;
-  return h + v * kImg;
-}
-__device__ inline int depth_axis(int pr) { return pr == 0 ? 2 : (pr == 1 ? 0 : 1); }
-
-// x / len[axis], correctly rounded, without a division: q = x*y, r = x - len*q (exact, FMA),
-// q' = q + r*y with y = RN(1/len) (Markstein).  Bit-identical to the IEEE quotient for the
-// image extents; images_run() checks that on the host and falls back to a real division.
-__device__ inline double div_len(double x, int axis) {
-  const ImgConsts &K = c_img;
-  if (K.true_div) return x / K.len[axis];
-  const double y = K.inv_len[axis];
-  const double q = x * y;
-  const double r = __builtin_fma(-K.len[axis], q, x);
-  return __builtin_fma(r, y, q);
-}
-// 1.0 / (double)count for the running means (image_strategy.cpp:170, 206)
-template <int NTAB>
-__device__ inline double recip_count(const double *tab, float fc) {
-  const int k = (int)fc;
-  return k < NTAB ? tab[k] : 1.0 / (double)fc;
-}
-
-__device__ inline uint32_t lcg_step(uint32_t &s) {  // HandSet::fastrand (hand_set.cpp:263-266)
-  s = 214013u * s + 2531011u;
-  return (uint32_t)(((int32_t)s >> 16) & 0x7FFF);
-}
-__device__ inline uint32_t lcg_jump(uint32_t s, unsigned long long n) {
-  uint32_t a = 214013u, c = 2531011u, A = 1u, Cc = 0u;
-  while (n) {
-    if (n & 1ull) {
-      A = a * A;
-      Cc = a * Cc + c;
-    }
-    c = (a + 1u) * c;
-    a = a * a;
-    n >>= 1;
-  }
-  return A * s + Cc;
-}
-
-// block-wide exclusive scan of one int per thread; returns the exclusive prefix, total in *total.
-// ONE barrier.  (There was a second one in front of the red_i stores, against a reader of red_i that is still on its
-// way.  No call site has one: each is entered through a barrier of its own — the row counts / the pixel counts that
-// are summed here were written by other threads — and red_i is not read between that barrier and this call: its
-// last readers, the previous scan's sums below (in the general shadow kernel also the `return S.red_i[0]` of
-// list_nonempty_cells and the mask flags of its walk), lie several barriers back, for the persistent kernels the one
-// at the loop head included.  A new call site has to keep that: a barrier between the last read of red_i and the call.)
-template <class SM>
-__device__ inline int block_excl_scan(SM &S, int v, int *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int incl = wave_incl_scan_i32(v);
-  if (lane == 63) S.red_i[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < IMG_WAVES; w++) {
-    const int x = S.red_i[w];
-    if (w < wave) base += x;
-    tot += x;
-  }
-  *total = tot;
-  return base + incl - v;
-}
-
-// exclusive scan of cells[].count into the start field; returns the total
-template <class SM>
-__device__ int scan_cells(SM &S) {
-  const int tid = threadIdx.x;
-  constexpr int PER = 8;  // consecutive cells per thread: two 16-byte LDS accesses each way (450 threads hold the 3600 cells)
-  static_assert(kPix % PER == 0 && kPix / PER <= IMG_THREADS, "scan_cells: cells per thread");
-  uint4 *c4 = reinterpret_cast<uint4 *>(S.cells);
-  if (tid < 32) reinterpret_cast<int *>(S.red_f)[tid] = 0;  // the histogram of list_nonempty_cells (two barriers from here; its last readers, the scale factors of the final phase, are behind that phase's closing barrier)
-  uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
-  if (tid < kPix / PER) {
-    a = c4[2 * tid];
-    b = c4[2 * tid + 1];
-  }
-  const int c[PER] = {(int)(a.x & 0xffffu), (int)(a.y & 0xffffu), (int)(a.z & 0xffffu), (int)(a.w & 0xffffu),
-                      (int)(b.x & 0xffffu), (int)(b.y & 0xffffu), (int)(b.z & 0xffffu), (int)(b.w & 0xffffu)};
-  int sum = 0;
-#pragma unroll
-  for (int k = 0; k < PER; k++) sum += c[k];
-  int total;
-  int run = block_excl_scan(S, sum, &total);
-  uint32_t o[PER];
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    o[k] = (uint32_t)(run < 0xffff ? run : 0xffff) << 16;
-    run += c[k];
-  }
-  if (tid < kPix / PER) {
-    c4[2 * tid] = make_uint4(o[0], o[1], o[2], o[3]);
-    c4[2 * tid + 1] = make_uint4(o[4], o[5], o[6], o[7]);
-  }
-  __syncthreads();
-  return total;
-}
-
-// list of the non-empty cells, ordered by their point count, descending (counting sort into 32
-// buckets; counts >= 31 share the first).  The walks give one pixel to one lane, so a wave runs as
-// long as its longest pixel: with equal lengths side by side the waves execute ~40 % fewer
-// (mostly idle) iterations than in cell order.  Pixels are independent, their order is free.
-// Returns the number of non-empty cells.
-template <class SM>
-__device__ int list_nonempty_cells(SM &S, uint16_t *nz) {
-  const int tid = threadIdx.x;
-  constexpr int PER = (kPix + IMG_THREADS - 1) / IMG_THREADS;
-  int *hist = reinterpret_cast<int *>(S.red_f);  // 32 counters, cleared by scan_cells; red_f is idle until the final phase
-  static_assert(PER == 8, "two 16-byte reads per thread");
-  uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
-  if (tid < kPix / PER) {
-    a = reinterpret_cast<const uint4 *>(S.cells)[2 * tid];
-    b = reinterpret_cast<const uint4 *>(S.cells)[2 * tid + 1];
-  }
-  const uint32_t cw[PER] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  int bucket[PER];
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    const int cn = (int)(cw[k] & 0xffffu);
-    bucket[k] = cn ? 31 - (cn < 31 ? cn : 31) : -1;
-    if (cn) atomicAdd(&hist[bucket[k]], 1);
-  }
-  __syncthreads();
-  if (tid < 64) {
-    const int v = tid < 32 ? hist[tid] : 0;
-    const int incl = wave_incl_scan_i32(v);
-    if (tid < 32) hist[tid] = incl - v;
-    if (tid == 31) S.red_i[0] = incl;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < PER; k++)
-    if (bucket[k] >= 0) nz[atomicAdd(&hist[bucket[k]], 1)] = (uint16_t)(tid * PER + k);
-  __syncthreads();
-  return S.red_i[0];
-}
-
-// scan_cells and list_nonempty_cells in the phases of ONE scan, for the per-candidate kernels: two barriers and a share of
-// the caller's next phase where the pair above takes six.  A thread holds the counts of its eight pixels anyway, so
-//   - scan_cells_hist: the histogram of the list is filled beside the wave scan (the caller has cleared S.red_f in the
-//     phase of its count: the last readers of red_f are behind the closing barrier of the final phase) | barrier | the
-//     segment starts go to `cells`, and the first wave turns the histogram into bucket offsets and leaves the number of
-//     non-empty pixels in S.nnz | barrier.  The eight buckets stay with the thread, a byte each (0: empty pixel);
-//   - scatter_nonempty: the list itself, in the phase in which the caller fills its segment table — both only read what
-//     the second barrier published, the list is first read behind the barrier that ends that phase, and so is S.nnz.
-// Same list as list_nonempty_cells up to the order inside a bucket, which is the order of LDS atomics there as here.
-template <class SM>
-__device__ inline void scan_cells_hist(SM &S, uint32_t (&pk)[2]) {
-  const int tid = threadIdx.x;
-  constexpr int PER = 8;
-  static_assert(kPix % PER == 0 && kPix / PER <= IMG_THREADS, "scan_cells_hist: cells per thread");
-  uint4 *c4 = reinterpret_cast<uint4 *>(S.cells);
-  int *hist = reinterpret_cast<int *>(S.red_f);
-  uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
-  if (tid < kPix / PER) {
-    a = c4[2 * tid];
-    b = c4[2 * tid + 1];
-  }
-  const int c[PER] = {(int)(a.x & 0xffffu), (int)(a.y & 0xffffu), (int)(a.z & 0xffffu), (int)(a.w & 0xffffu),
-                      (int)(b.x & 0xffffu), (int)(b.y & 0xffffu), (int)(b.z & 0xffffu), (int)(b.w & 0xffffu)};
-  int sum = 0;
-  pk[0] = pk[1] = 0u;
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    sum += c[k];
-    if (c[k]) {
-      const int bucket = 31 - (c[k] < 31 ? c[k] : 31);  // 0 .. 30: counter 31 stays zero
-      atomicAdd(&hist[bucket], 1);
-      pk[k >> 2] |= (uint32_t)(bucket + 1) << (8 * (k & 3));
-    }
-  }
-  int total;
-  int run = block_excl_scan(S, sum, &total);
-  uint32_t o[PER];
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    o[k] = (uint32_t)(run < 0xffff ? run : 0xffff) << 16;
-    run += c[k];
-  }
-  if (tid < kPix / PER) {
-    c4[2 * tid] = make_uint4(o[0], o[1], o[2], o[3]);
-    c4[2 * tid + 1] = make_uint4(o[4], o[5], o[6], o[7]);
-  }
-  if (tid < 64) {
-    const int v = tid < 32 ? hist[tid] : 0;
-    const int incl = wave_incl_scan_i32(v);
-    if (tid < 32) hist[tid] = incl - v;
-    if (tid == 31) S.nnz = incl;
-  }
-  __syncthreads();
-}
-template <class SM>
-__device__ inline void scatter_nonempty(SM &S, uint16_t *nz, const uint32_t (&pk)[2]) {
-  int *hist = reinterpret_cast<int *>(S.red_f);
-  // (the pixel numbers are made here, from a value the optimiser cannot follow: hoisted out of the callers' projection
-  // loops they were registers held through every phase of kernels that sit on their 128-register cap)
-  int first = threadIdx.x * 8;
-  asm volatile("" : "+v"(first));
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const int b = (int)((pk[k >> 2] >> (8 * (k & 3))) & 0xffu);
-    if (b) nz[atomicAdd(&hist[b - 1], 1)] = (uint16_t)(first + k);
-  }
-}
-
-// 3x3 rect max-dilate (border ignored), NORM_MINMAX to [0,1], u8 = round-half-even(v*255)
-// (image_strategy.cpp:144-153, 178-187, 221-230; cv::dilate / cv::normalize / convertTo).
-// Planes are in cell-index order (cell row = 59 - image row; the 3x3 window is symmetric).
-// NPL planes are finished in one pass; planes with the same norm group share min/max (the three
-// normal channels are normalised jointly, depth/shadow on their own).  Each thread owns groups of
-// 4 consecutive pixels: three 16-byte LDS reads + two edge reads per row (indices clamped to the
-// image: a clamped duplicate cannot change a max), one dword store.
-// planes 0..2 (or 0 alone) start at p012 and are kPix apart; plane 3, if present, is p3 and is
-// normalised on its own; output channels are consecutive planes starting at out.
-//
-// finalize_planes_ex is the same pass with three hooks for a caller that folds neighbouring phases into it:
-//   fold(x)   applied to every value as it is loaded (a pure function of the stored word: the dilation, the min / max
-//             and the bytes see fold(x) wherever the plain pass sees x);
-//   tail()    run by every thread in the last phase, behind the barrier that ends all reads of the planes — work that
-//             only has to be done before the caller's next phase rides on the closing barrier;
-//   OWN_RED   false (NPL == 1 only): the caller still reads red_f[4 * w + 2] and [4 * w + 3] when it enters, so the pass
-//             writes just the two slots per wave that one norm group needs and does without the barrier in front of them
-//             (nothing reads slots 4 * w + 0 / + 1 between the caller's previous barrier and this pass).
-template <int NPL, bool OWN_RED, class SM, class FOLD, class TAIL>
-__device__ __forceinline__ void finalize_planes_ex(SM &S, const float *p012, const float *p3, uint8_t *out, FOLD fold, TAIL tail) {
-  static_assert(OWN_RED || NPL == 1, "the shared reduction slots hold one norm group");
-  const int tid = threadIdx.x;
-  constexpr int GROUPS = NPL * 900;
-  constexpr int PER = (GROUPS + IMG_THREADS - 1) / IMG_THREADS;
-  float d[PER][4];
-  float mn[2] = {FLT_MAX, FLT_MAX}, mx[2] = {-FLT_MAX, -FLT_MAX};
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    const int g = tid + k * IMG_THREADS;
-    if (g < GROUPS) {
-      const int ch = g / 900, rem = g - ch * 900;
-      const int r = rem / 15, c0 = (rem - r * 15) * 4;
-      const float *pl = (ch < 3) ? p012 + ch * kPix : p3;
-      const int rm = r > 0 ? r - 1 : 0, rp = r < kImg - 1 ? r + 1 : kImg - 1;
-      const int cl = c0 > 0 ? c0 - 1 : 0, cr = c0 + 4 < kImg ? c0 + 4 : kImg - 1;
-      const float4 a = *reinterpret_cast<const float4 *>(pl + rm * kImg + c0);
-      const float4 b = *reinterpret_cast<const float4 *>(pl + r * kImg + c0);
-      const float4 c = *reinterpret_cast<const float4 *>(pl + rp * kImg + c0);
-      const float el = fmaxf(fmaxf(fold(pl[rm * kImg + cl]), fold(pl[r * kImg + cl])), fold(pl[rp * kImg + cl]));
-      const float er = fmaxf(fmaxf(fold(pl[rm * kImg + cr]), fold(pl[r * kImg + cr])), fold(pl[rp * kImg + cr]));
-      const float m0 = fmaxf(fmaxf(fold(a.x), fold(b.x)), fold(c.x)), m1 = fmaxf(fmaxf(fold(a.y), fold(b.y)), fold(c.y));
-      const float m2 = fmaxf(fmaxf(fold(a.z), fold(b.z)), fold(c.z)), m3 = fmaxf(fmaxf(fold(a.w), fold(b.w)), fold(c.w));
-      d[k][0] = fmaxf(fmaxf(el, m0), m1);
-      d[k][1] = fmaxf(fmaxf(m0, m1), m2);
-      d[k][2] = fmaxf(fmaxf(m1, m2), m3);
-      d[k][3] = fmaxf(fmaxf(m2, m3), er);
-      const float lo = fminf(fminf(d[k][0], d[k][1]), fminf(d[k][2], d[k][3]));
-      const float hi = fmaxf(fmaxf(d[k][0], d[k][1]), fmaxf(d[k][2], d[k][3]));
-      if (ch < 3) {
-        mn[0] = fminf(mn[0], lo);
-        mx[0] = fmaxf(mx[0], hi);
-      } else {
-        mn[1] = fminf(mn[1], lo);
-        mx[1] = fmaxf(mx[1], hi);
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 2; q++) {
-    mn[q] = wave_min_f32(mn[q]);
-    mx[q] = wave_max_f32(mx[q]);
-  }
-  if constexpr (OWN_RED) __syncthreads();
-  if ((tid & 63) == 0) {
-    S.red_f[4 * (tid >> 6) + 0] = mn[0];
-    S.red_f[4 * (tid >> 6) + 1] = mx[0];
-    if constexpr (OWN_RED) {
-      S.red_f[4 * (tid >> 6) + 2] = mn[1];
-      S.red_f[4 * (tid >> 6) + 3] = mx[1];
-    }
-  }
-  __syncthreads();
-  float fs[2] = {0.f, 0.f}, fb[2] = {0.f, 0.f};
-#pragma unroll
-  for (int q = 0; q < (OWN_RED ? 2 : 1); q++) {
-    float a = S.red_f[2 * q], b = S.red_f[2 * q + 1];
-#pragma unroll
-    for (int w = 1; w < IMG_WAVES; w++) {
-      a = fminf(a, S.red_f[4 * w + 2 * q]);
-      b = fmaxf(b, S.red_f[4 * w + 2 * q + 1]);
-    }
-    const double smin = (double)a, smax = (double)b;
-    const double scale = 1.0 * ((smax - smin) > DBL_EPSILON ? 1.0 / (smax - smin) : 0.0);
-    const double shift = 0.0 - smin * scale;
-    fs[q] = (float)scale;
-    fb[q] = (float)shift;
-  }
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    const int g = tid + k * IMG_THREADS;
-    if (g < GROUPS) {
-      const int ch = g / 900, rem = g - ch * 900;
-      const int r = rem / 15, c0 = (rem - r * 15) * 4;
-      const int q = ch < 3 ? 0 : 1;
-      uint32_t packed = 0;
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const float v = d[k][j] * fs[q] + fb[q];
-        const float u = v * 255.0f + 0.0f;
-        float t = rintf(u);
-        t = t < 0.f ? 0.f : (t > 255.f ? 255.f : t);
-        packed |= (uint32_t)(int)t << (8 * j);
-      }
-      // image row = 59 - cell row (image_strategy.cpp:128-129)
-      *reinterpret_cast<uint32_t *>(out + (size_t)ch * kPix + (kImg - 1 - r) * kImg + c0) = packed;
-    }
-  }
-  tail();
-  __syncthreads();
-}
-template <int NPL, class SM>
-__device__ void finalize_planes(SM &S, const float *p012, const float *p3, uint8_t *out) {
-  finalize_planes_ex<NPL, true>(S, p012, p3, out, [](float x) { return x; }, [] {});
-}
-
-// ---- one plane at a time (grasp_image_kernel): the same arithmetic as finalize_planes, with the dilated values
-//      of a thread's pixel groups kept in registers across the planes that are normalised together
-constexpr int GPT = (900 + IMG_THREADS - 1) / IMG_THREADS;  // groups of 4 pixels per thread and plane
-__device__ inline void dilate_plane(const float *pl, float (&d)[GPT][4], float &mn, float &mx) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < GPT; k++) {
-    const int g = tid + k * IMG_THREADS;
-    if (g < 900) {
-      const int r = g / 15, c0 = (g - r * 15) * 4;
-      const int rm = r > 0 ? r - 1 : 0, rp = r < kImg - 1 ? r + 1 : kImg - 1;
-      const int cl = c0 > 0 ? c0 - 1 : 0, cr = c0 + 4 < kImg ? c0 + 4 : kImg - 1;
-      const float4 a = *reinterpret_cast<const float4 *>(pl + rm * kImg + c0);
-      const float4 b = *reinterpret_cast<const float4 *>(pl + r * kImg + c0);
-      const float4 c = *reinterpret_cast<const float4 *>(pl + rp * kImg + c0);
-      const float el = fmaxf(fmaxf(pl[rm * kImg + cl], pl[r * kImg + cl]), pl[rp * kImg + cl]);
-      const float er = fmaxf(fmaxf(pl[rm * kImg + cr], pl[r * kImg + cr]), pl[rp * kImg + cr]);
-      const float m0 = fmaxf(fmaxf(a.x, b.x), c.x), m1 = fmaxf(fmaxf(a.y, b.y), c.y);
-      const float m2 = fmaxf(fmaxf(a.z, b.z), c.z), m3 = fmaxf(fmaxf(a.w, b.w), c.w);
-      d[k][0] = fmaxf(fmaxf(el, m0), m1);
-      d[k][1] = fmaxf(fmaxf(m0, m1), m2);
-      d[k][2] = fmaxf(fmaxf(m1, m2), m3);
-      d[k][3] = fmaxf(fmaxf(m2, m3), er);
-      mn = fminf(mn, fminf(fminf(d[k][0], d[k][1]), fminf(d[k][2], d[k][3])));
-      mx = fmaxf(mx, fmaxf(fmaxf(d[k][0], d[k][1]), fmaxf(d[k][2], d[k][3])));
-    }
-  }
-}
-// block-wide min / max -> the scale and shift of cv::normalize(NORM_MINMAX) as floats (image_strategy.cpp:144-153)
-template <class SM>
-__device__ inline void minmax_scale(SM &S, float mn, float mx, float &fs, float &fb) {
-  const int tid = threadIdx.x;
-  mn = wave_min_f32(mn);
-  mx = wave_max_f32(mx);
-  __syncthreads();
-  if ((tid & 63) == 0) {
-    S.red_f[2 * (tid >> 6)] = mn;
-    S.red_f[2 * (tid >> 6) + 1] = mx;
-  }
-  __syncthreads();
-  float a = S.red_f[0], b = S.red_f[1];
-#pragma unroll
-  for (int w = 1; w < IMG_WAVES; w++) {
-    a = fminf(a, S.red_f[2 * w]);
-    b = fmaxf(b, S.red_f[2 * w + 1]);
-  }
-  const double smin = (double)a, smax = (double)b;
-  const double scale = 1.0 * ((smax - smin) > DBL_EPSILON ? 1.0 / (smax - smin) : 0.0);
-  const double shift = 0.0 - smin * scale;
-  fs = (float)scale;
-  fb = (float)shift;
-}
-__device__ inline void store_plane(const float (&d)[GPT][4], float fs, float fb, uint8_t *out) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < GPT; k++) {
-    const int g = tid + k * IMG_THREADS;
-    if (g < 900) {
-      const int r = g / 15, c0 = (g - r * 15) * 4;
-      uint32_t packed = 0;
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const float v = d[k][j] * fs + fb;
-        const float u = v * 255.0f + 0.0f;
-        float t = rintf(u);
-        t = t < 0.f ? 0.f : (t > 255.f ? 255.f : t);
-        packed |= (uint32_t)(int)t << (8 * j);
-      }
-      // image row = 59 - cell row (image_strategy.cpp:128-129)
-      *reinterpret_cast<uint32_t *>(out + (kImg - 1 - r) * kImg + c0) = packed;
-    }
-  }
-}
-
-template <int N>
-__device__ inline void sort_u16_regs(uint16_t *p, int n);
-__device__ inline void sort_u16(uint16_t *p, int n) {
-  if (n <= 8) return sort_u16_regs<8>(p, n);
-  if (n <= 16) return sort_u16_regs<16>(p, n);
-  if (n <= 32) return sort_u16_regs<32>(p, n);
-  for (int i = 1; i < n; i++) {
-    const uint16_t v = p[i];
-    int j = i - 1;
-    while (j >= 0 && p[j] > v) {
-      p[j + 1] = p[j];
-      j--;
-    }
-    p[j + 1] = v;
-  }
-}
-// The same with at most 16 keys in registers at a time (grasp_image_kernel is held to 128 VGPRs; the 32-key network
-// alone costs it 21 spilled registers = 0.2 GB of scratch traffic per 5000 candidates).  17..32 keys: both halves
-// through the 16-key network, the cross step of the bitonic merge element by element through LDS, then each half —
-// a bitonic sequence now — through the 16-key merge network.  Same 240 compare-exchanges, five LDS round trips
-// instead of one, and only for the few pixels that hold more than 16 points.
-template <int N>
-__device__ inline void merge_regs(uint32_t (&k)[N]) {  // bitonic -> ascending
-#pragma unroll
-  for (int stride = N >> 1; stride > 0; stride >>= 1) {
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-      const int j = i ^ stride;
-      if (j > i) {
-        const uint32_t lo = min(k[i], k[j]), hi = max(k[i], k[j]);
-        k[i] = lo;
-        k[j] = hi;
-      }
-    }
-  }
-}
-template <int N>
-__device__ inline void sort_regs(uint32_t (&k)[N]);
-__device__ inline void sort_u16_lean(uint16_t *p, int n) {
-  if (n <= 8) return sort_u16_regs<8>(p, n);
-  if (n <= 16) return sort_u16_regs<16>(p, n);
-  if (n > 32) return sort_u16(p, n);
-  uint32_t k[16];
-#pragma unroll
-  for (int q = 0; q < 16; q++) k[q] = p[q];
-  sort_regs<16>(k);
-#pragma unroll
-  for (int q = 0; q < 16; q++) p[q] = (uint16_t)k[q];
-#pragma unroll
-  for (int q = 0; q < 16; q++) k[q] = 16 + q < n ? (uint32_t)p[16 + q] : 0xffffffffu;
-  sort_regs<16>(k);
-#pragma unroll
-  for (int q = 0; q < 16; q++)
-    if (16 + q < n) p[16 + q] = (uint16_t)k[q];
-  // cross step: element i against element 31 - i (missing ones are +inf and stay where they are)
-#pragma unroll
-  for (int i = 0; i < 16; i++) {
-    if (31 - i < n) {
-      const uint16_t a = p[i], b = p[31 - i];
-      p[i] = a < b ? a : b;
-      p[31 - i] = a < b ? b : a;
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 16; q++) k[q] = p[q];
-  merge_regs<16>(k);
-#pragma unroll
-  for (int q = 0; q < 16; q++) p[q] = (uint16_t)k[q];
-#pragma unroll
-  for (int q = 0; q < 16; q++) k[q] = 16 + q < n ? (uint32_t)p[16 + q] : 0xffffffffu;
-  merge_regs<16>(k);
-#pragma unroll
-  for (int q = 0; q < 16; q++)
-    if (16 + q < n) p[16 + q] = (uint16_t)k[q];
-}
-// N keys in registers, ascending (bitonic network, fully unrolled: 24 / 80 / 240 compare-exchanges
-// for N = 8 / 16 / 32).  The walks order their short per-pixel segments through registers: N
-// independent LDS reads, the network, N writes — one LDS round trip instead of the dependent
-// read-compare-write chain of an insertion sort (~300 cycles per step, O(n^2) steps).
-template <int N>
-__device__ inline void sort_regs(uint32_t (&k)[N]) {
-#pragma unroll
-  for (int size = 2; size <= N; size <<= 1) {
-#pragma unroll
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-#pragma unroll
-      for (int i = 0; i < N; i++) {
-        const int j = i ^ stride;
-        if (j > i) {
-          const uint32_t lo = min(k[i], k[j]), hi = max(k[i], k[j]);
-          const bool up = (i & size) == 0;
-          k[i] = up ? lo : hi;
-          k[j] = up ? hi : lo;
-        }
-      }
-    }
-  }
-}
-template <int N>
-__device__ inline void sort_u16_regs(uint16_t *p, int n) {
-  uint32_t k[N];
-#pragma unroll
-  for (int q = 0; q < N; q++) k[q] = q < n ? (uint32_t)p[q] : 0xffffffffu;
-  sort_regs<N>(k);
-#pragma unroll
-  for (int q = 0; q < N; q++)
-    if (q < n) p[q] = (uint16_t)k[q];
-}
 #define TICK(k)                                                     \
   do {                                                              \
     if (P.dbg && tid == 0) {                                        \
@@ -761,26 +89,6 @@ __device__ inline void sort_u16_regs(uint16_t *p, int n) {
       t_last = now_;                                                \
     }                                                               \
   } while (0)
-
-// the candidate's box in scalar registers, bounds exactly as findPointsInUnitImage /
-// transformPointsToUnitImage evaluate them (image_strategy.cpp:53-90)
-__device__ inline void load_box(const gpd_hand &H, Box &B) {
-  const ImgConsts &K = c_img;
-#pragma unroll
-  for (int i = 0; i < 9; i++) B.F[i] = uniform_f64(H.frame[i]);
-#pragma unroll
-  for (int i = 0; i < 3; i++) B.sample[i] = uniform_f64(H.sample[i]);
-  const double hb = uniform_f64(H.bottom), hc = uniform_f64(H.center);
-  B.off[0] = hb;
-  B.off[1] = uniform_f64(hc - K.half_od);
-  B.off[2] = uniform_f64(-K.vol_height);  // (t2 + height) == t2 - (-height)
-  B.lo[0] = hb;
-  B.hi[0] = uniform_f64(hb + K.vol_depth);
-  B.lo[1] = B.off[1];
-  B.hi[1] = uniform_f64(hc + K.half_od);
-  B.lo[2] = uniform_f64(-1.0 * K.vol_height);
-  B.hi[2] = uniform_f64(K.vol_height);
-}
 
 // ---------------------------------------------------------------------------
 // shadow_image_kernel: the shadow channel of the three projections of one candidate
@@ -1159,10 +467,6 @@ __device__ __forceinline__ void shadow_image_body(const ImgParams &P, SmemShadow
   if (tid == 0 && S.flag) atomicOr(P.status, S.flag);
 }
 
-// LGRID workgroups of the large instantiations walk the queue of the small one; the queue length is read
-// on the device, so the host enqueues them without waiting for it (an empty queue costs an empty launch)
-constexpr int LGRID = 256;
-
 template <int SHC, bool WIDE>
 __global__ __launch_bounds__(IMG_THREADS, SHC <= SH_CAP ? 4 : 2) void shadow_image_kernel(ImgParams P) {
   __shared__ SmemShadow<SHC, WIDE> S;
@@ -1189,9 +493,6 @@ __global__ __launch_bounds__(IMG_THREADS, SHC <= SH_CAP ? 4 : 2) void shadow_ima
 // with the list, its cell keys and the segment table in a scratch row in global memory and none of the register tricks.
 // A persistent launch: workgroup b takes entries b, b + grid, ... of its list.
 // ---------------------------------------------------------------------------
-constexpr int HUGE_CAP = 65535;       // in-box voxels (segment starts are 16 bits wide in the pixel table)
-constexpr int HUGE_WIN = 256;         // window edge in voxels
-constexpr size_t HUGE_SCRATCH_BYTES = (size_t)HUGE_WIN * HUGE_WIN * sizeof(int32_t) + (size_t)(HUGE_CAP + 1) * (2 * sizeof(uint32_t) + sizeof(uint16_t)) + 64;
 struct __attribute__((aligned(16))) SmemAny {
   __attribute__((aligned(16))) float raster0[kPix];
   __attribute__((aligned(16))) uint32_t cells[kPix];
@@ -1977,247 +1278,28 @@ hipError_t hwc_to_planar(const uint8_t *src, uint8_t *dst, int n, int C, hipStre
 }
 
 // ---------------------------------------------------------------------------
-// Host side
+// Host side: one enqueue per kernel, under the lock of c_img (const_block.h).
 // ---------------------------------------------------------------------------
-// smallest positive double x with floor((x/len)/(1.0/60)) >= k — the exact image of the
-// reference's cell formula (image_strategy.cpp:92-102 applied to transformPointsToUnitImage's
-// quotient, :72-90), found by bisection on the bit pattern with the same IEEE operations.
-static double cell_threshold(double len, int k) {
-  const double cellsize = 1.0 / (double)kImg;
-  auto f = [&](double x) { return std::floor((x / len) / cellsize) >= (double)k; };
-  uint64_t lo = 0, hi;  // f(bits lo) false, f(bits hi) true
-  double top = len * 2.0;
-  std::memcpy(&hi, &top, sizeof(hi));
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    double x;
-    std::memcpy(&x, &mid, sizeof(x));
-    if (f(x))
-      hi = mid;
-    else
-      lo = mid;
-  }
-  double x;
-  std::memcpy(&x, &hi, sizeof(x));
-  return x;
-}
+static ConstBlock g_img_block;
 
-void image_cell_thresholds(double len, double *out) {
-  out[0] = 0.0;
-  for (int k = 1; k < kImg; k++) out[k] = cell_threshold(len, k);
-  out[kImg] = DBL_MAX;
-}
-
-void images_free(ImageState &im) {
-  void *ptrs[] = {im.d_images, im.d_images_hwc, im.d_status, im.d_set_bits, im.d_overflow, im.d_overflow2, im.d_pts_overflow, im.d_pts_scratch, im.d_huge_scratch};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  if (im.ev_fork) (void)hipEventDestroy(im.ev_fork);
-  if (im.ev_join) (void)hipEventDestroy(im.ev_join);
-  if (im.aux) (void)hipStreamDestroy(im.aux);
-  im = ImageState();
-}
-
-// Image buffers for up to n candidates and `shadow_sets` (live hand set, camera) voxel bitsets of the geometry in p
-// (grow with 25 % slack, never shrink; a growth stalls the device).
-int images_reserve(const gpd_params &p, ImageState &im, int n, int shadow_sets) {
-  const int C = p.image_num_channels;
-  if (!im.d_status) {
-    HIP_RET(hipMalloc(&im.d_status, 4 * sizeof(int32_t)));  // [0] flags, [1..3] the counters of the three overflow lists: ONE memset per launch
-    HIP_RET(hipMemset(im.d_status, 0, 4 * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&im.d_pts_scratch, (size_t)LGRID * PTS_SCRATCH_BYTES));
-  }
-  if (n > im.capacity) {
-    note_alloc(__func__);
-    void *ptrs[] = {im.d_images, im.d_images_hwc, im.d_overflow, im.d_overflow2, im.d_pts_overflow};
-    for (void *q : ptrs)
-      if (q) (void)hipFree(q);
-    im.d_overflow = nullptr;
-    im.d_overflow2 = nullptr;
-    im.d_pts_overflow = nullptr;
-    im.d_images = nullptr;
-    im.d_images_hwc = nullptr;
-    im.capacity = 0;
-    const int cap = n + n / 4;  // slack: the clouds of a batch differ a little
-    HIP_RET(hipMalloc(&im.d_images, (size_t)cap * kPix * C));
-    HIP_RET(hipMalloc(&im.d_overflow, (size_t)cap * sizeof(int32_t)));  // list (its counter: d_status[1])
-    HIP_RET(hipMalloc(&im.d_overflow2, (size_t)cap * sizeof(int32_t)));  // ... of the large instantiation, for the general kernel
-    HIP_RET(hipMalloc(&im.d_pts_overflow, (size_t)cap * sizeof(int32_t)));
-    im.capacity = cap;
-  }
-  {
-    // which voxel windows the shadow kernels need (Vox<WIDE>): the window of a candidate must hold the diagonal of the
-    // image box (+ 3 voxels of margins), the region of a set every box of the set.  A box spans x in [bottom, bottom + depth]
-    // with init_bite - hand_depth <= bottom <= 0, y in center -+ width / 2 with |center| <= (outer_diameter - finger_width) / 2,
-    // |z| <= height (finger_hand.cpp:155-168, image_strategy.cpp:53-70).
-    const double vox = 0.003;
-    const double diag = std::sqrt(p.volume_depth * p.volume_depth + p.volume_width * p.volume_width + 4.0 * p.volume_height * p.volume_height);
-    const double rx = std::fmax(p.hand_depth - p.init_bite, p.volume_depth);
-    const double ry = 0.5 * (p.hand_outer_diameter - p.finger_width) + 0.5 * p.volume_width;
-    const double reach = std::sqrt(rx * rx + ry * ry + p.volume_height * p.volume_height);
-    const double need_win = std::ceil(diag / vox) + 3.0, need_reach = std::ceil(reach / vox) + 1.0;
-    im.wide = need_win > (double)Vox<false>::VD || need_reach > (double)(Vox<false>::SR - 1);
-    // beyond the wide windows as well: the general shadow kernel with a set region of the size this geometry needs
-    // (the reference has no limit, hand_set.cpp:138; what is left of ours: 256 voxels = 0.77 m of window edge, 65535 voxels in a box)
-    im.huge = need_win > (double)Vox<true>::VD || need_reach > (double)(Vox<true>::SR - 1);
-    if (im.huge) {
-      if (need_reach + 2.0 > 640.0) {  // 1280^3 bits = 262 MB per hand set and camera: an image volume of metres is a mistake, not a gripper
-        set_error("images: an image volume with %.2f m of reach is beyond the shadow region this library allocates", reach);
-        return GPD_ERR_CAPACITY;
-      }
-      im.set_sr = (int)need_reach + 2;
-      im.set_sd = 2 * im.set_sr;
-    } else {
-      im.set_sr = im.wide ? Vox<true>::SR : Vox<false>::SR;
-      im.set_sd = im.wide ? Vox<true>::SD : Vox<false>::SD;
-    }
-  }
-  const size_t setwords = (size_t)(((long long)im.set_sd * im.set_sd * im.set_sd + 31) / 32);
-  if (C == 15 && (shadow_sets > im.cap_shadow_sets || setwords > im.cap_setwords)) {
-    note_alloc(__func__);
-    if (im.d_set_bits) (void)hipFree(im.d_set_bits);
-    im.d_set_bits = nullptr;
-    im.cap_shadow_sets = 0;
-    const int want = shadow_sets > im.cap_shadow_sets ? shadow_sets : im.cap_shadow_sets;
-    const int cap = want + want / 4;
-    const size_t words = setwords > im.cap_setwords ? setwords : im.cap_setwords;
-    HIP_RET(hipMalloc(&im.d_set_bits, (size_t)cap * words * sizeof(uint32_t)));
-    // defined contents from the first launch on: shadow_set_kernel<0> writes only the rows its candidates' windows cover, and
-    // the words around them keep what is there (zero, or an earlier launch's voxels — see the reader's note in shadow_image_kernel)
-    HIP_RET(hipMemset(im.d_set_bits, 0, (size_t)cap * words * sizeof(uint32_t)));
-    im.cap_shadow_sets = cap;
-    im.cap_setwords = words;  // (a larger row also serves the smaller regions)
-  }
-  if (C == 15 && (im.wide || im.huge) && !im.d_huge_scratch) {
-    // the general shadow kernel's list rows, one per workgroup of its persistent grid; the default geometry cannot reach it
-    // (its box holds fewer voxel cells than the large instantiation lists)
-    note_alloc(__func__);
-    HIP_RET(hipMalloc(&im.d_huge_scratch, (size_t)LGRID * HUGE_SCRATCH_BYTES));
-  }
-  return GPD_OK;
-}
-
-// The candidate list itself (which hands, in which order, where each hand set starts in the LCG stream) is
-// built on the device by plan_kernel; its sizes are in pl.h_summary by now.  This sizes the image buffers,
-// prepares the constant block of the image geometry and launches the kernels.
-int images_run(const gpd_params &p, const Cloud &c, const SearchState &s, const Plan &pl, ImageState &im, hipStream_t stream) {
-  const int C = p.image_num_channels;
-  const PlanSummary &sm = *pl.h_summary;
-  const int n = sm.num_candidates;
-  im.num_candidates = n;
-  im.channels = C;
-  im.slots = p.num_hand_axes * p.num_orientations;
-  im.stat_sets = sm.live_sets;
-  im.stat_sum_set_ni = sm.sum_set_ni;
-  im.stat_sum_cand_ni = sm.sum_cand_ni;
-  im.num_shadow_sets = sm.num_shadow_sets;
-  std::memcpy(im.view_points, c.view_points, sizeof(im.view_points));
-  {
-    const int rc = images_reserve(p, im, n, im.num_shadow_sets);
-    if (rc) return rc;
-  }
-  HIP_RET(hipMemsetAsync(im.d_status, 0, 4 * sizeof(int32_t), stream));  // the flags and the overflow counters of this launch
-  if (n == 0) return GPD_OK;
-  ImgConsts k;
-  std::memset(&k, 0, sizeof(k));
-  k.vol_depth = p.volume_depth;
-  k.vol_width = p.volume_width;
-  k.vol_height = p.volume_height;
-  k.half_od = p.volume_width / 2.0;
-  k.dbl_h = 2.0 * p.volume_height;
-  k.C = C;
-  k.nproj = (C <= 3) ? 1 : 3;
-  k.per = (C == 15) ? 5 : (C == 12 ? 4 : C);
-  // shadow_length_ = max(volume_depth, volume_height/2, volume_width) (image_15_channels_strategy.h:70-75)
-  k.shadow_length = std::fmax(std::fmax(p.volume_depth, p.volume_height / 2.0), p.volume_width);
-  k.voxel = 0.003;
-  k.voxel_mult = 1.0 / 0.003;
-  k.rand_inv = 1.0 / 32767.0;
-  k.num_shadow = (int)std::floor(k.shadow_length / k.voxel);  // plan_kernel places the sets in the LCG stream with the same count
-  k.len[0] = k.vol_depth;
-  k.len[1] = k.vol_width;
-  k.len[2] = k.dbl_h;
-  k.true_div = 0;
-  k.set_sd = im.set_sd;
-  k.set_sr = im.set_sr;
-  {
-    // thresholds and the div_len() self-check depend on the box extents only: computed once per
-    // geometry (the self-check alone is ~2 ms of host time)
-    struct AxisCache {
-      double len = -1.0, thr[kImg + 1], inv_len = 0.0;
-      int true_div = 0;
-    };
-    static AxisCache cache[3];
-    static std::mutex cache_mutex;
-    std::lock_guard<std::mutex> lock(cache_mutex);
-    for (int a = 0; a < 3; a++) {
-      AxisCache &ac = cache[a];
-      if (ac.len != k.len[a]) {
-        ac.len = k.len[a];
-        image_cell_thresholds(k.len[a], ac.thr);
-        ac.inv_len = 1.0 / k.len[a];
-        ac.true_div = 0;
-        // self-check of div_len(): the FMA sequence must reproduce the IEEE quotient
-        uint64_t rs = 88172645463325252ull;
-        for (int i = 0; i < 200000 && !ac.true_div; i++) {
-          rs ^= rs << 13;
-          rs ^= rs >> 7;
-          rs ^= rs << 17;
-          double x = (double)(rs >> 11) * (1.0 / 9007199254740992.0) * k.len[a];
-          if (i & 1) x = (double)(float)x;
-          if (i < kImg) x = ac.thr[i];
-          const double q = x * ac.inv_len;
-          const double r = std::fma(-k.len[a], q, x);
-          if (std::fma(r, ac.inv_len, q) != x / k.len[a]) ac.true_div = 1;
-        }
-      }
-      k.inv_cell[a] = (double)kImg / k.len[a];
-      std::memcpy(k.thr[a], ac.thr, sizeof(ac.thr));
-      k.inv_len[a] = ac.inv_len;
-      if (ac.true_div) k.true_div = 1;
-    }
-  }
-  {  // affine map of SET_THREADS * num_shadow LCG steps
-    uint32_t a = 214013u, cc = 2531011u, A = 1u, Cc = 0u;
-    unsigned long long nsteps = (unsigned long long)SET_THREADS * (unsigned)k.num_shadow;
-    while (nsteps) {
-      if (nsteps & 1ull) {
-        A = a * A;
-        Cc = a * Cc + cc;
-      }
-      cc = (a + 1u) * cc;
-      a = a * a;
-      nsteps >>= 1;
-    }
-    k.stride_a = A;
-    k.stride_c = Cc;
-  }
-  const unsigned char *kb = reinterpret_cast<const unsigned char *>(&k);
-  if (im.consts.size() != sizeof(k) || std::memcmp(im.consts.data(), kb, sizeof(k)) != 0) im.consts.assign(kb, kb + sizeof(k));
-  return images_launch(s, pl, im, stream, /*counters_clean=*/true);
-}
-
-// c_img is ONE block per device, shared by every context of the process on that device.  Under the
-// lock: a context whose block (geometry, view points of its cloud) differs from the loaded one waits
-// for the device — kernels of another context, on another stream, may still be reading it — and
-// loads its own; the caller keeps the lock until its kernels are enqueued.  Same-stream order covers
-// the context's own earlier kernels.
-static std::mutex g_img_mutex;
-static std::vector<unsigned char> g_img_loaded[64];
-
-static int load_img_consts(const std::vector<unsigned char> &want, hipStream_t stream) {
-  if (want.size() != sizeof(ImgConsts)) return GPD_ERR_STATE;
-  int dev = 0;
-  HIP_RET(hipGetDevice(&dev));
-  std::vector<unsigned char> &loaded = g_img_loaded[dev & 63];
-  if (loaded == want) return GPD_OK;
-  if (!loaded.empty()) HIP_RET(hipDeviceSynchronize());
-  HIP_RET(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_img), want.data(), sizeof(ImgConsts), 0, hipMemcpyHostToDevice, stream));
-  // the block counts as loaded only once the copy has landed: a context with the same values skips
-  // the copy and launches on ITS stream, which is not ordered after this one
-  HIP_RET(hipStreamSynchronize(stream));
-  loaded = want;
-  return GPD_OK;
+// what every image kernel reads: the search's lists and records, the plan's candidate list, the images and the status
+// word; the queues, overflow targets and scratch rows of one launch alone are off
+static ImgParams img_params(const SearchState &s, const Plan &pl, const ImageState &im, unsigned long long *dbg) {
+  ImgParams ip;
+  std::memset(&ip, 0, sizeof(ip));
+  ip.nn = s.d_nn;
+  ip.cap = s.nn_cap;
+  ip.centers = s.d_centers;
+  ip.hands = s.d_hands;
+  ip.cand_hand = pl.d_cand_hand;
+  ip.meta = pl.d_cand_meta;
+  ip.set_bits = im.d_set_bits;
+  ip.images = im.d_images;
+  ip.status = im.d_status;
+  ip.num_cand = im.num_candidates;
+  ip.dbg = dbg;
+  ip.exit_after = prof_env("GPD_IMG_EXIT") ? atoi(prof_env("GPD_IMG_EXIT")) : 0;
+  return ip;
 }
 
 // Launches the image kernels over the candidate list resident on the device.  Nothing here waits for the
@@ -2228,38 +1310,25 @@ int images_launch(const SearchState &s, const Plan &pl, ImageState &im, hipStrea
   if (n <= 0) return GPD_OK;
   // the three overflow counters of the launch (the flags in d_status[0] accumulate over re-launches)
   if (!counters_clean) HIP_RET(hipMemsetAsync(im.d_status + 1, 0, 3 * sizeof(int32_t), stream));
-  std::lock_guard<std::mutex> consts_lock(g_img_mutex);
+  if (im.consts.size() != sizeof(ImgConsts)) return GPD_ERR_STATE;
+  std::unique_lock<std::mutex> consts_lock;  // held until every kernel below is enqueued
   {
-    const int rc = load_img_consts(im.consts, stream);
+    const int rc = g_img_block.load(c_img, im.consts.data(), sizeof(ImgConsts), stream, consts_lock);
     if (rc) return rc;
   }
-  ImgParams ip;
-  std::memset(&ip, 0, sizeof(ip));
-  ip.nn = s.d_nn;
-  ip.cap = s.nn_cap;
-  ip.centers = s.d_centers;
-  ip.hands = s.d_hands;
-  ip.cand_hand = pl.d_cand_hand;
-  ip.meta = pl.d_cand_meta;
-  ip.images = im.d_images;
-  ip.status = im.d_status;
   static unsigned long long *d_dbg = nullptr;
-  ip.dbg = nullptr;
-  ip.exit_after = prof_env("GPD_IMG_EXIT") ? atoi(prof_env("GPD_IMG_EXIT")) : 0;
+  unsigned long long *dbg = nullptr;
   if (prof_env("GPD_IMG_TIMING")) {
     if (!d_dbg) HIP_RET(hipMalloc(&d_dbg, 32 * sizeof(unsigned long long)));
     HIP_RET(hipMemsetAsync(d_dbg, 0, 32 * sizeof(unsigned long long), stream));
-    ip.dbg = d_dbg;
+    dbg = d_dbg;
   }
-  ip.set_bits = im.d_set_bits;
-  ip.cand_list = nullptr;
-  ip.cand_count = nullptr;
-  ip.num_cand = n;
-  ip.overflow_list = nullptr;
-  ip.overflow_count = nullptr;
-  // normals + depth on the side stream (15 channels: beside the shadow kernels).  Nearly every box holds fewer than
-  // PT_CAP points; the others are queued and redone by the instantiation that keeps its point arrays in a global
-  // scratch row.
+  const ImgParams base = img_params(s, pl, im, dbg);
+  // the three queues of the stage: list and length (a counter of d_status), filled by one kernel and walked by the next
+  int32_t *const pts_queue = im.d_pts_overflow, *const pts_queued = im.d_status + 3;  // more than PT_CAP in-box points
+  int32_t *const sh_queue = im.d_overflow, *const sh_queued = im.d_status + 1;        // more than SH_CAP voxels in the box
+  int32_t *const any_queue = im.d_overflow2, *const any_queued = im.d_status + 2;     // more than SH_CAP_BIG (wide windows only)
+  const unsigned all = 8 * ((n + 7) / 8);  // grid of the kernels that take every candidate (xcd_candidate)
   if (!im.aux) {
     HIP_RET(hipStreamCreate(&im.aux));
     HIP_RET(hipEventCreateWithFlags(&im.ev_fork, hipEventDisableTiming));
@@ -2268,28 +1337,27 @@ int images_launch(const SearchState &s, const Plan &pl, ImageState &im, hipStrea
   static const bool serial = prof_env("GPD_IMG_SERIAL") != nullptr;  // profiling aid: each image kernel alone on the chip
   // profiling aid: unused dynamic LDS per workgroup of the two per-candidate kernels (8192: one workgroup per CU instead of two)
   static const size_t lds_pad = prof_env("GPD_IMG_LDS_PAD") ? (size_t)atoi(prof_env("GPD_IMG_LDS_PAD")) : 0;
-  hipStream_t pts_stream = (im.channels == 15 && !ip.dbg && im.side_stream && !serial) ? im.aux : stream;
+  // normals + depth on the side stream (15 channels: beside the shadow kernels)
+  hipStream_t pts_stream = (im.channels == 15 && !dbg && im.side_stream && !serial) ? im.aux : stream;
   if (pts_stream != stream) {
     HIP_RET(hipEventRecord(im.ev_fork, stream));
     HIP_RET(hipStreamWaitEvent(pts_stream, im.ev_fork, 0));
   }
-  ip.pts_overflow_list = im.d_pts_overflow;
-  ip.pts_overflow_count = im.d_status + 3;
-  ip.pts_scratch = nullptr;
-  grasp_image_kernel<false><<<8 * ((n + 7) / 8), IMG_THREADS, lds_pad, pts_stream>>>(ip);
-  HIP_RET(hipGetLastError());
-  {
-    ImgParams ib = ip;
-    ib.cand_list = im.d_pts_overflow;
-    ib.cand_count = im.d_status + 3;
-    ib.pts_overflow_list = nullptr;
-    ib.pts_overflow_count = nullptr;
-    ib.pts_scratch = im.d_pts_scratch;
-    grasp_image_kernel<true><<<LGRID, IMG_THREADS, 0, pts_stream>>>(ib);
+  {  // every candidate.  Nearly every box holds fewer than PT_CAP points; the others are queued ...
+    ImgParams ip = base;
+    ip.pts_overflow_list = pts_queue;
+    ip.pts_overflow_count = pts_queued;
+    grasp_image_kernel<false><<<all, IMG_THREADS, lds_pad, pts_stream>>>(ip);
     HIP_RET(hipGetLastError());
   }
-  ip.pts_overflow_list = nullptr;
-  ip.pts_overflow_count = nullptr;
+  {  // ... and redone by the instantiation that keeps its point arrays in a global scratch row
+    ImgParams ip = base;
+    ip.cand_list = pts_queue;
+    ip.cand_count = pts_queued;
+    ip.pts_scratch = im.d_pts_scratch;
+    grasp_image_kernel<true><<<LGRID, IMG_THREADS, 0, pts_stream>>>(ip);
+    HIP_RET(hipGetLastError());
+  }
   if (im.num_shadow_sets > 0) {
     SetParams sp;
     sp.nn = s.d_nn;
@@ -2315,51 +1383,56 @@ int images_launch(const SearchState &s, const Plan &pl, ImageState &im, hipStrea
     }
     HIP_RET(hipGetLastError());
   }
-  ip.cand_list = nullptr;
-  ip.cand_count = nullptr;
-  ip.num_cand = n;
-  ip.overflow_list = im.d_overflow;
-  ip.overflow_count = im.d_status + 1;
-  if (im.channels == 15) {
-    // most boxes fit the two-per-CU instantiation; the few that do not are queued by it and
-    // redone by the large one
-    ImgParams ib = ip;
-    ib.cand_list = im.d_overflow;
-    ib.cand_count = im.d_status + 1;
-    ib.overflow_list = nullptr;
-    ib.overflow_count = nullptr;
-    if (im.huge) {
-      // an image volume beyond the windows of the tuned kernels: every candidate through the general one
-      ImgParams ia = ip;
-      ia.overflow_list = nullptr;
-      ia.overflow_count = nullptr;
-      ia.huge_scratch = im.d_huge_scratch;
-      shadow_image_any_kernel<<<LGRID, IMG_THREADS, 0, stream>>>(ia);
-    } else if (im.wide) {
-      // a wide box can hold more voxels than the large instantiation lists: it queues those for the general kernel
-      ib.overflow_list = im.d_overflow2;
-      ib.overflow_count = im.d_status + 2;
-      shadow_image_kernel<SH_CAP, true><<<8 * ((n + 7) / 8), IMG_THREADS, 0, stream>>>(ip);
-      HIP_RET(hipGetLastError());
-      shadow_image_kernel<SH_CAP_BIG, true><<<LGRID, IMG_THREADS, 0, stream>>>(ib);
-      HIP_RET(hipGetLastError());
-      ImgParams ia = ip;
-      ia.cand_list = im.d_overflow2;
-      ia.cand_count = im.d_status + 2;
-      ia.overflow_list = nullptr;
-      ia.overflow_count = nullptr;
-      ia.huge_scratch = im.d_huge_scratch;
-      shadow_image_any_kernel<<<LGRID, IMG_THREADS, 0, stream>>>(ia);
-    } else {
-      shadow_image_kernel<SH_CAP, false><<<8 * ((n + 7) / 8), IMG_THREADS, lds_pad, stream>>>(ip);
-      HIP_RET(hipGetLastError());
-      shadow_image_kernel<SH_CAP_BIG, false><<<LGRID, IMG_THREADS, 0, stream>>>(ib);
-    }
+  if (im.channels == 15 && im.huge) {
+    // an image volume beyond the windows of the tuned kernels: every candidate through the general one
+    ImgParams ip = base;
+    ip.huge_scratch = im.d_huge_scratch;
+    shadow_image_any_kernel<<<LGRID, IMG_THREADS, 0, stream>>>(ip);
     HIP_RET(hipGetLastError());
+  } else if (im.channels == 15 && im.wide) {
+    {  // every candidate; the boxes with more than SH_CAP voxels are queued ...
+      ImgParams ip = base;
+      ip.overflow_list = sh_queue;
+      ip.overflow_count = sh_queued;
+      shadow_image_kernel<SH_CAP, true><<<all, IMG_THREADS, 0, stream>>>(ip);
+      HIP_RET(hipGetLastError());
+    }
+    {  // ... for the large instantiation; a wide box can hold more voxels than that one lists: it queues those ...
+      ImgParams ip = base;
+      ip.cand_list = sh_queue;
+      ip.cand_count = sh_queued;
+      ip.overflow_list = any_queue;
+      ip.overflow_count = any_queued;
+      shadow_image_kernel<SH_CAP_BIG, true><<<LGRID, IMG_THREADS, 0, stream>>>(ip);
+      HIP_RET(hipGetLastError());
+    }
+    {  // ... for the general kernel
+      ImgParams ip = base;
+      ip.cand_list = any_queue;
+      ip.cand_count = any_queued;
+      ip.huge_scratch = im.d_huge_scratch;
+      shadow_image_any_kernel<<<LGRID, IMG_THREADS, 0, stream>>>(ip);
+      HIP_RET(hipGetLastError());
+    }
+  } else if (im.channels == 15) {
+    {  // every candidate.  Most boxes fit the two-per-CU instantiation; the few that do not are queued by it ...
+      ImgParams ip = base;
+      ip.overflow_list = sh_queue;
+      ip.overflow_count = sh_queued;
+      shadow_image_kernel<SH_CAP, false><<<all, IMG_THREADS, lds_pad, stream>>>(ip);
+      HIP_RET(hipGetLastError());
+    }
+    {  // ... and redone by the large one (the default box holds fewer voxel cells than it lists: no further queue)
+      ImgParams ip = base;
+      ip.cand_list = sh_queue;
+      ip.cand_count = sh_queued;
+      shadow_image_kernel<SH_CAP_BIG, false><<<LGRID, IMG_THREADS, 0, stream>>>(ip);
+      HIP_RET(hipGetLastError());
+    }
   }
   HIP_RET(hipEventRecord(im.ev_join, pts_stream));
   if (pts_stream != stream) HIP_RET(hipStreamWaitEvent(stream, im.ev_join, 0));
-  if (ip.dbg) {
+  if (dbg) {
     unsigned long long h[32];
     HIP_RET(hipMemcpyAsync(h, d_dbg, sizeof(h), hipMemcpyDeviceToHost, stream));
     HIP_RET(hipStreamSynchronize(stream));
@@ -2377,52 +1450,6 @@ int images_launch(const SearchState &s, const Plan &pl, ImageState &im, hipStrea
               100.0 * h[i] / (double)tot);
     fprintf(stderr, "[img-timing] shadow voxels in box: max %llu mean %.0f; in-box points: max %llu mean %.0f\n", h[28],
             (double)h[29] / n, h[30], (double)h[31] / n);
-  }
-  return GPD_OK;
-}
-
-// text of the capacity flags an image kernel left in d_status
-void images_status_text(int status, char *buf, size_t len) {
-  snprintf(buf, len, "images: kernel capacity exceeded (flags %d: 1 image box beyond %d voxels of window edge, 2 in-box points > %d, "
-           "4 shadow voxels in a box > %d)", status, HUGE_WIN, PT_CAP_BIG, HUGE_CAP);
-}
-
-// The routes of the last launch from the three queues images_launch hands the kernels (d_overflow / d_status[1],
-// d_overflow2 / [2], d_pts_overflow / [3]); the caller has waited for the lane's stream.
-int images_routes(const ImageState &im, int32_t *route, long long info[8]) {
-  const int n = im.num_candidates;
-  info[0] = n;
-  info[1] = im.huge ? 2 : (im.wide ? 1 : 0);
-  info[2] = (n > 0 && im.num_shadow_sets > 0) ? (int)info[1] : -1;  // images_launch's condition for shadow_set_kernel
-  info[3] = 0;
-  info[4] = PT_CAP;
-  info[5] = PT_CAP_BIG;
-  info[6] = SH_CAP;
-  info[7] = SH_CAP_BIG;
-  if (n <= 0 || !im.d_status) return GPD_OK;
-  std::memset(route, 0, (size_t)n * sizeof(int32_t));
-  int32_t st[4];
-  HIP_RET(hipMemcpy(st, im.d_status, sizeof(st), hipMemcpyDeviceToHost));
-  info[3] = st[0];
-  const int32_t *lists[3] = {im.d_overflow, im.d_overflow2, im.d_pts_overflow};
-  const int bits[3] = {1, 2, 4};
-  std::vector<int32_t> h;
-  for (int l = 0; l < 3; l++) {
-    const int cnt = st[1 + l];
-    if (cnt == 0) continue;
-    if (cnt < 0 || cnt > n || !lists[l]) {
-      set_error("gpd_hip_last_image_routes: queue %d holds %d entries for %d candidates", l + 1, cnt, n);
-      return GPD_ERR_STATE;
-    }
-    h.resize((size_t)cnt);
-    HIP_RET(hipMemcpy(h.data(), lists[l], (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int i = 0; i < cnt; i++) {
-      if (h[i] < 0 || h[i] >= n || (route[h[i]] & bits[l])) {
-        set_error("gpd_hip_last_image_routes: queue %d entry %d is %d (candidates: %d, or queued twice)", l + 1, i, h[i], n);
-        return GPD_ERR_STATE;
-      }
-      route[h[i]] |= bits[l];
-    }
   }
   return GPD_OK;
 }

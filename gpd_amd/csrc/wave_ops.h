@@ -1,5 +1,5 @@
-// Wave- and workgroup-wide device helpers: the DPP reductions of the hand kernels (hands.hip) and one tile of the
-// running scan of a 1024-thread workgroup (cloud.hip, plane.hip, preprocess.hip).
+// Wave- and workgroup-wide device helpers: the DPP reductions of the hand kernels (hands.hip) and of the image kernels
+// (images.hip), and one tile of the running scan of a 1024-thread workgroup (cloud.hip, plane.hip, preprocess.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,6 +54,45 @@ __device__ inline double lane63_f64(double v) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
   const unsigned lo = lane63_u32((unsigned)b), hi = lane63_u32((unsigned)(b >> 32));
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// ---- what the image kernels use (images.hip, image_device.h): 512-thread workgroups, the wave's result in every lane
+
+// a workgroup-uniform double moved to scalar registers (the candidate's box is the same for
+// all 1024 lanes; keeping its 21 doubles in SGPRs frees ~40 VGPRs per lane)
+__device__ inline double uniform_f64(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// wave-wide max / min of a float, the result in every lane: GPD_WAVE_REDUCE and one v_readlane — 7 VALU instructions.
+// (A lane whose DPP source is masked keeps its own value: max(v, v) = v.)
+template <int CTRL, int RMASK>
+__device__ inline float dpp_f32(float x) {
+  return __uint_as_float(dpp_u32<CTRL, RMASK>(__float_as_uint(x)));
+}
+__device__ inline float lane63_f32(float v) { return __uint_as_float(lane63_u32(__float_as_uint(v))); }
+__device__ inline float wave_max_f32(float v) {
+  GPD_WAVE_REDUCE(v, fmaxf, dpp_f32);
+  return lane63_f32(v);
+}
+__device__ inline float wave_min_f32(float v) {
+  GPD_WAVE_REDUCE(v, fminf, dpp_f32);
+  return lane63_f32(v);
+}
+
+// wave-wide inclusive prefix sum of an int: row_shr 1 / 2 / 4 / 8 inside the rows of 16 lanes, then the row totals carried
+// over by row_bcast:15 / :31 — the sequence LLVM's atomic optimiser emits for gfx9; lanes without a source add 0
+__device__ inline int wave_incl_scan_i32(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);  // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);  // row_shr:8
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
+  return v;
 }
 
 // Block-wide helpers (256 threads = 4 waves).

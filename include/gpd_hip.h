@@ -317,6 +317,27 @@ typedef struct gpd_label_view_job {          /* zero it first */
 int gpd_hip_label_view(gpd_hip_ctx *ctx, gpd_label_view_job *job);
 int gpd_hip_sizeof_label_view_job(void);
 
+/* What the image stage derives from a geometry before it launches a kernel — host only, no context; the definition
+ * (gpd_amd/csrc/image_model.h) images_reserve / images_run use.
+ *  - window_class: which voxel windows the shadow kernels take for the image volume: 0 the default (a 46^3 window per candidate,
+ *    a region of 86^3 voxels per hand set), 1 the wide ones (64^3 / 128^3), 2 the general kernel with a region of the size the
+ *    geometry needs; set_sd / set_sr: edge and radius of that region in voxels of 3 mm.
+ *  - num_shadow = floor(shadow_length / 0.003) draws per point of a hand set, shadow_length = max(volume_depth,
+ *    volume_height / 2, volume_width) (image_15_channels_strategy.h:70-75); (stride_a, stride_c): the
+ *    affine map s -> stride_a * s + stride_c (mod 2^32) of 1024 * num_shadow steps of HandSet::fastrand (hand_set.cpp:263-266).
+ *  - thr[a][k], a = depth, width, 2 * height: the smallest double x with floor((x / len_a) / (1.0 / 60)) >= k, the cell
+ *    formula of image_strategy.cpp:92-102 in its own IEEE operations; thr[a][0] = 0, thr[a][60] = DBL_MAX.
+ *  - true_div: 1 when the kernels' division by len_a through RN(1 / len_a) and two FMAs was seen to differ from the IEEE
+ *    quotient for one of the extents (they divide for real then).
+ * GPD_ERR_INVALID: a NULL argument.  GPD_ERR_CAPACITY: an image volume whose shadow region would exceed 1280^3 voxels. */
+typedef struct gpd_image_model {
+  int32_t window_class, set_sd, set_sr, num_shadow;
+  uint32_t stride_a, stride_c;
+  int32_t true_div, reserved_;
+  double thr[3][61];
+} gpd_image_model;
+int gpd_hip_image_model(const gpd_params *params, gpd_image_model *out);
+
 /* The draws of SequentialImportanceSampling::detectGrasps (sequential_importance_sampling.cpp:189-270) — host only, no context;
  * the definition (gpd_amd/csrc/sis_model.h) the device draw of gpd_hip_detect_sis equals.  The reference draws from
  * std::random_device, rand() and static std::normal_distributions; here round r (0-based, after the initial pass) has two

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 BIT_SHADOW_BIG, BIT_SHADOW_ANY, BIT_POINTS_BIG = 1, 2, 4
 FLAG_POINTS, FLAG_VOXELS = 2, 4
 
-# image volumes of the three window classes (images.hip images_reserve)
+# image volumes of the three window classes (image_model.h image::window_class, called by image_state.hip images_reserve)
 WIDE = dict(volume_width=0.16, volume_height=0.028)  # box diagonal 0.180 m: 63 of the 64 voxels of a wide window
 HUGE = dict(volume_width=0.16, volume_depth=0.10)    # box diagonal 0.193 m: beyond the wide windows
 HUGE_DEEP = dict(volume_width=0.30, volume_depth=0.20, volume_height=0.10)  # 0.3 x 0.2 x 0.2 m boxes, 444k voxel cells

@@ -15,7 +15,7 @@ from test_gpu_image_paths import (BIT_POINTS_BIG, BIT_SHADOW_ANY, BIT_SHADOW_BIG
 
 pytestmark = pytest.mark.gpu
 
-LGRID = 256  # workgroups of the large instantiations (images.hip): a longer queue gives a workgroup several candidates in a row
+LGRID = 256  # workgroups of the large instantiations (image_model.h): a longer queue gives a workgroup several candidates in a row
 
 
 def _planes_constant(img):

@@ -34,7 +34,7 @@ VARIANTS = {
     "six_placements_wide_fingers": dict(num_finger_placements=6, finger_width=0.015),
     "small_hand": dict(hand_outer_diameter=0.09, hand_depth=0.045, hand_height=0.015, init_bite=0.008),
     "other_image_volume": dict(volume_width=0.08, volume_depth=0.05, volume_height=0.03),
-    "wide_image_volume": dict(volume_width=0.16),  # box diagonal 0.176 m: the 64^3 / 128^3 voxel windows (images.hip Vox<WIDE>)
+    "wide_image_volume": dict(volume_width=0.16),  # box diagonal 0.176 m: the 64^3 / 128^3 voxel windows (image_model.h Vox<WIDE>)
     "huge_image_volume": dict(volume_width=0.16, volume_depth=0.10),  # box diagonal 0.193 m: beyond the 64-voxel windows, the general shadow kernel
     "long_fingers": dict(hand_depth=0.20),  # 38 deepening steps (two rounds of 32), 0.2 m hand neighbourhoods
     "friction_viable_aperture": dict(friction_coeff=35.0, min_viable=2, min_aperture=0.02, max_aperture=0.07),
