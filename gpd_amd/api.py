@@ -263,7 +263,7 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_set_lenet_conv_relu", "gpd_hip_lenet_from_torch",
            "gpd_hip_upload_ground_truth", "gpd_hip_label_view", "gpd_hip_balance_view", "gpd_hip_sizeof_label_view_job",
            "gpd_hip_shuffle_orders", "gpd_hip_sis_proposals", "gpd_hip_sis_select", "gpd_hip_detect_sis", "gpd_hip_sizeof_sis_job",
-           "gpd_hip_image_model",
+           "gpd_hip_image_model", "gpd_hip_given_check", "gpd_hip_images_given", "gpd_hip_score_given",
            "gpd_hip_train_default_params", "gpd_hip_train_create", "gpd_hip_train_destroy", "gpd_hip_train_init_state",
            "gpd_hip_train_set_state", "gpd_hip_train_get_state", "gpd_hip_train_set_data", "gpd_hip_train_steps",
            "gpd_hip_train_gradients", "gpd_hip_train_apply", "gpd_hip_train_eval", "gpd_hip_train_step_timed",
@@ -344,6 +344,11 @@ def lib():
                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.gpd_hip_detect_sis.argtypes = [C.c_void_p, C.POINTER(SisJob)]
         L.gpd_hip_image_model.argtypes = [C.POINTER(Params), C.POINTER(ImageModel)]
+        L.gpd_hip_given_check.argtypes = [C.POINTER(Params), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.gpd_hip_images_given.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                           C.POINTER(C.c_uint64)]
+        L.gpd_hip_score_given.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                          C.POINTER(C.c_uint64)]
         L.gpd_hip_train_default_params.argtypes = [C.POINTER(TrainParams)]
         L.gpd_hip_train_default_params.restype = None
         L.gpd_hip_train_create.argtypes = [C.c_void_p, C.POINTER(TrainParams), C.POINTER(C.c_void_p)]
@@ -389,6 +394,20 @@ def lib():
         assert L.gpd_hip_sizeof_sis_job() == C.sizeof(SisJob)
         _LIB = L
     return _LIB
+
+
+def given_check(params, hands):
+    """gpd_hip_given_check: may these hand sets [num_sets, slots] be handed to Context.images_given / score_given?  Host only.
+    -> None, or (set, slot, reason) of the first record outside the domain."""
+    hands = np.ascontiguousarray(hands, HAND_DTYPE)
+    slots = params.num_hand_axes * params.num_orientations
+    if hands.ndim != 2 or hands.shape[1] != slots:
+        raise ValueError("hands must be [num_sets, %d] records, set-major" % slots)
+    bs, bj = C.c_int(-1), C.c_int(-1)
+    rc = lib().gpd_hip_given_check(C.byref(params), _ptr(hands), hands.shape[0], C.byref(bs), C.byref(bj))
+    if rc == 0:
+        return None
+    return int(bs.value), int(bj.value), lib().gpd_hip_last_error().decode()
 
 
 def default_params(channels=15):
@@ -588,6 +607,37 @@ class Context:
         self._check(lib().gpd_hip_images(self._h, _ptr(hands), hands.shape[0], _ptr(img), _ptr(cand), C.byref(n)))
         assert n.value == nv
         return img, cand[:nv]
+
+    def _given(self, hands):
+        hands = np.ascontiguousarray(hands, HAND_DTYPE)
+        if hands.ndim != 2 or hands.shape[1] != self.n_slots:
+            raise ValueError("hands must be [num_sets, %d] records, set-major" % self.n_slots)
+        return hands, int(hands["valid"].astype(bool).sum())
+
+    def images_given(self, hands, lcg_base=0, download=True):
+        """gpd_hip_images_given: ImageGenerator::createImages for hand sets the caller supplies (given_check is the domain), on the
+        uploaded cloud -> (images [n,60,60,C] or None: kept on the device for score(None, n), cand_index [n], lcg_draws)."""
+        hands, nv = self._given(hands)
+        img = np.zeros((nv, 60, 60, self.params.image_num_channels), np.uint8) if download else None
+        cand = np.zeros(max(nv, 1), np.int32)
+        n, draws = C.c_int(0), C.c_uint64(0)
+        self._check(lib().gpd_hip_images_given(self._h, _ptr(hands), hands.shape[0], int(lcg_base), _ptr(img), _ptr(cand), C.byref(n),
+                                               C.byref(draws)))
+        assert n.value == nv
+        return img, cand[:nv], int(draws.value)
+
+    def score_given(self, hands, lcg_base=0):
+        """gpd_hip_score_given: images_given + the LeNet in the context's mode -> (a copy of hands with `score` written into the
+        valid records, scores f32 [n], cand_index [n], lcg_draws)."""
+        hands, nv = self._given(hands)
+        hands = hands.copy()
+        scores = np.zeros(max(nv, 1), np.float32)
+        cand = np.zeros(max(nv, 1), np.int32)
+        n, draws = C.c_int(0), C.c_uint64(0)
+        self._check(lib().gpd_hip_score_given(self._h, _ptr(hands), hands.shape[0], int(lcg_base), _ptr(scores), _ptr(cand), C.byref(n),
+                                              C.byref(draws)))
+        assert n.value == nv
+        return hands, scores[:nv], cand[:nv], int(draws.value)
 
     def detect(self, sample_indices):
         """detectGrasps steps 1-4 -> (hands[n_sets, n_slots] with scores, n_candidates)."""

@@ -281,6 +281,12 @@ int search_join(SearchState &s, hipStream_t stream);
 int search_force_capacity(SearchState &s, int cap);
 // HandSearch::reevaluateHypotheses on the uploaded cloud; invalidates the search state
 int reevaluate_run(const gpd_params &p, const Cloud &c, SearchState &s, gpd_hand *hands, int n, int32_t *labels, hipStream_t stream);
+// gpd_hip_images_given: the neighbourhood lists of S samples given by coordinates and nothing else (no hand is evaluated);
+// invalidates the search state, the side stream is joined on return
+int given_lists_run(const gpd_params &p, const Cloud &c, SearchState &s, const double *sample_xyz, int S, hipStream_t stream);
+// ... and the caller's records [S][slots] (host) as the lists' hand sets: into d_hands, their flags into d_fvalid, every
+// sample a hand set for plan_kernel (given.hip)
+int given_ingest(SearchState &s, const gpd_hand *hands, int S, int slots, hipStream_t stream);
 int search_download(const gpd_params &p, SearchState &s, gpd_hand *hands, int *num_sets, hipStream_t stream);
 void search_free(SearchState &s);
 // gpd_hip_label_view, one round: reevaluateHypotheses of n candidate records on the device (set-major, `lists` hand sets among

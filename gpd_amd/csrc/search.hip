@@ -1211,6 +1211,21 @@ int reevaluate_run(const gpd_params &p, const Cloud &c, SearchState &s, gpd_hand
   return GPD_OK;
 }
 
+// gpd_hip_images_given: the neighbourhood lists of S samples given by coordinates, through the capacity retry, and nothing
+// else — no hand is evaluated (no height list either).  The centre sums are joined: the caller goes on to write into d_counts.
+int given_lists_run(const gpd_params &p, const Cloud &c, SearchState &s, const double *sample_xyz, int S, hipStream_t stream) {
+  const int slots = p.num_hand_axes * p.num_orientations;
+  HostConsts hc;
+  host_consts(p, hc);
+  s.num_samples = 0;  // the buffers are reused: hands of an earlier search can no longer be imaged
+  s.h_set_sample.clear();
+  s.h_samples.clear();
+  int cap = 0;
+  int rc = neighbourhoods(p, c, s, hc, nullptr, sample_xyz, S, slots, &cap, stream, true, /*want_height_list=*/false);
+  if (rc) return rc;
+  return search_join(s, stream);
+}
+
 // gpd_hip_label_view, one round: reevaluateHypotheses of the n candidate records d_recs (device, set-major) against the ground
 // truth `gt`, one neighbourhood list per hand set with a candidate (`lists` of them: the plan's live sets).  Rewrites the records'
 // flags, writes d_labels8 [n]; only 8 bytes (largest neighbourhood — or the capacity flags d_img_status[0] of the round's image kernels,

@@ -1124,6 +1124,25 @@ std::vector<gpd_hand> GraspDetector::flatten(const std::vector<std::unique_ptr<c
   return recs;
 }
 
+// the flat record array gpd_hip_images_given / gpd_hip_score_given read: the listed hand sets in the order listed (empty ones
+// left out), one row of slots each, set_index as listed; slots a set does not have stay invalid
+static std::vector<gpd_hand> given_records(const std::vector<std::unique_ptr<candidate::HandSet>> &sets, int slots) {
+  std::vector<gpd_hand> recs;
+  int n = 0;
+  for (const auto &hs : sets) {
+    if (!hs || hs->getHands().empty()) continue;
+    recs.resize((size_t)(n + 1) * slots, gpd_hand());
+    for (int j = 0; j < slots && j < (int)hs->getHands().size(); j++) {
+      gpd_hand r = hs->getHands()[j]->record();
+      r.set_index = n;
+      r.valid = hs->getIsValid()[j] ? 1 : 0;
+      recs[(size_t)n * slots + j] = r;
+    }
+    n++;
+  }
+  return recs;
+}
+
 // grasp_detector.cpp:528-551
 std::vector<std::unique_ptr<candidate::Hand>> GraspDetector::pruneGraspCandidates(
     const util::Cloud &cloud, const std::vector<std::unique_ptr<candidate::HandSet>> &hand_set_list, double min_score) {
@@ -1140,51 +1159,36 @@ std::vector<std::unique_ptr<candidate::Hand>> GraspDetector::pruneGraspCandidate
     for (int r = 0; r < 3 && resident; r++) resident = last_samples_[3 * (size_t)r0.set_index + r] == r0.sample[r];
   }
   std::vector<gpd_hand> recs;
-  int n_sets = last_num_sets_;
+  std::vector<int32_t> cand;
+  std::vector<float> scores;
+  int n_cand = 0;
   if (resident) {
     recs = flatten(hand_set_list);
-  } else {
-    // a list gathered over several searches: search the neighbourhoods of its samples again (the
-    // samples are the same doubles, so the neighbourhoods are the same) and number the sets as listed
-    if (!upload(cloud)) return hands_out;
-    std::vector<double> samples;
-    std::vector<const candidate::HandSet *> sets;
-    for (const auto &hs : hand_set_list) {
-      if (!hs || hs->getHands().empty()) continue;
-      const gpd_hand &r0 = hs->getHands()[0]->record();
-      for (int r = 0; r < 3; r++) samples.push_back(r0.sample[r]);
-      sets.push_back(hs.get());
-    }
-    if (sets.empty()) return hands_out;
-    std::vector<gpd_hand> fresh(sets.size() * slots);
-    if (gpd_hip_search_samples(ctx_, samples.data(), (int)sets.size(), fresh.data(), &n_sets) != GPD_OK) {
+    size_t nv = 0;
+    for (const gpd_hand &r : recs) nv += r.valid;
+    cand.resize(nv);
+    scores.resize(nv);
+    if (gpd_hip_images(ctx_, recs.data(), last_num_sets_, nullptr, cand.data(), &n_cand) != GPD_OK ||
+        (n_cand > 0 && gpd_hip_score(ctx_, nullptr, n_cand, scores.data()) != GPD_OK)) {
       printf("ERROR: %s\n", gpd_hip_last_error());
       return hands_out;
     }
-    if (n_sets != (int)sets.size()) {
-      printf("ERROR: pruneGraspCandidates: %zu hand sets do not belong to this cloud\n", sets.size() - (size_t)n_sets);
+  } else {
+    // a list gathered over several searches, or hands of another cloud: the records themselves go to the device
+    // (gpd_hip_score_given), sets numbered as listed; no second search
+    if (!upload(cloud)) return hands_out;
+    recs = given_records(hand_set_list, slots);
+    if (recs.empty()) return hands_out;
+    size_t nv = 0;
+    for (const gpd_hand &r : recs) nv += r.valid;
+    cand.resize(nv + 1);
+    scores.resize(nv + 1);
+    last_num_sets_ = 0;  // the device search buffers are reused
+    last_samples_.clear();
+    if (gpd_hip_score_given(ctx_, recs.data(), (int)(recs.size() / slots), 0, scores.data(), cand.data(), &n_cand, nullptr) != GPD_OK) {
+      printf("ERROR: %s\n", gpd_hip_last_error());
       return hands_out;
     }
-    last_num_sets_ = n_sets;
-    last_samples_ = samples;
-    recs.assign((size_t)n_sets * slots, gpd_hand());
-    for (int s = 0; s < n_sets; s++)
-      for (int j = 0; j < slots && j < (int)sets[s]->getHands().size(); j++) {
-        gpd_hand r = sets[s]->getHands()[j]->record();
-        r.set_index = s;
-        r.valid = sets[s]->getIsValid()[j] ? 1 : 0;
-        recs[(size_t)s * slots + j] = r;
-      }
-  }
-  size_t nv = 0;
-  for (const gpd_hand &r : recs) nv += r.valid;
-  std::vector<int32_t> cand(nv);
-  std::vector<float> scores(nv);
-  int n_cand = 0;
-  if (gpd_hip_images(ctx_, recs.data(), n_sets, nullptr, cand.data(), &n_cand) != GPD_OK ||
-      (n_cand > 0 && gpd_hip_score(ctx_, nullptr, n_cand, scores.data()) != GPD_OK)) {
-    printf("ERROR: %s\n", gpd_hip_last_error());
-    return hands_out;
   }
   for (int k = 0; k < n_cand; k++) {
     if (scores[k] > min_score) {
@@ -1199,23 +1203,42 @@ std::vector<std::unique_ptr<candidate::Hand>> GraspDetector::pruneGraspCandidate
 bool GraspDetector::createImages(const util::Cloud &cloud, const std::vector<std::unique_ptr<candidate::HandSet>> &hand_set_list,
                                  std::vector<std::unique_ptr<net::Image>> &images_out,
                                  std::vector<std::unique_ptr<candidate::Hand>> &hands_out) {
-  (void)cloud;
   images_out.clear();
   hands_out.clear();
   if (!ctx_) return false;
   if (hand_set_list.empty()) return true;
-  if ((int)hand_set_list.size() != last_num_sets_) {
-    printf("ERROR: createImages: the hand sets are not those of the last generateGraspCandidates call\n");
-    return false;
-  }
-  for (size_t s = 0; s < hand_set_list.size(); s++) {
+  // the hand sets of the last generateGraspCandidates call are on the device already; any others travel there
+  bool resident = (int)hand_set_list.size() == last_num_sets_;
+  for (size_t s = 0; s < hand_set_list.size() && resident; s++) {
     const auto &hs = hand_set_list[s];
-    bool same = hs && !hs->getHands().empty() && hs->getHands()[0]->record().set_index == (int)s;
-    for (int r = 0; r < 3 && same; r++) same = last_samples_[3 * s + r] == hs->getHands()[0]->record().sample[r];
-    if (!same) {
-      printf("ERROR: createImages: the hand sets are not those of the last generateGraspCandidates call\n");
+    resident = hs && !hs->getHands().empty() && hs->getHands()[0]->record().set_index == (int)s;
+    for (int r = 0; r < 3 && resident; r++) resident = last_samples_[3 * s + r] == hs->getHands()[0]->record().sample[r];
+  }
+  if (!resident) {
+    // ImageGenerator::createImages(cloud, hand_set_list) images whatever it is handed (image_generator.cpp:17-99)
+    if (!upload(cloud)) return false;
+    const int slots = params_.num_hand_axes * params_.num_orientations;
+    std::vector<gpd_hand> recs = given_records(hand_set_list, slots);
+    if (recs.empty()) return true;
+    const size_t bytes = (size_t)60 * 60 * params_.image_num_channels;
+    size_t nv = 0;
+    for (const gpd_hand &r : recs) nv += r.valid;
+    std::vector<uint8_t> pix(nv * bytes + 1);
+    std::vector<int32_t> cand(nv + 1);
+    int n_cand = 0;
+    last_num_sets_ = 0;  // the device search buffers are reused
+    last_samples_.clear();
+    if (gpd_hip_images_given(ctx_, recs.data(), (int)(recs.size() / slots), 0, pix.data(), cand.data(), &n_cand, nullptr) != GPD_OK) {
+      printf("ERROR: %s\n", gpd_hip_last_error());
       return false;
     }
+    for (int k = 0; k < n_cand; k++) {
+      auto im = std::make_unique<net::Image>(60, 60, params_.image_num_channels);
+      std::memcpy(im->data.data(), pix.data() + (size_t)k * bytes, bytes);
+      images_out.push_back(std::move(im));
+      hands_out.push_back(std::make_unique<candidate::Hand>(recs[cand[k]]));
+    }
+    return true;
   }
   std::vector<gpd_hand> recs = flatten(hand_set_list);
   const size_t bytes = (size_t)60 * 60 * params_.image_num_channels;

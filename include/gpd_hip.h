@@ -431,6 +431,40 @@ int gpd_hip_sizeof_sis_job(void);
 int gpd_hip_images(gpd_hip_ctx *ctx, const gpd_hand *hands, int num_sets,
                    uint8_t *images, int32_t *cand_index, int *num_candidates);
 
+/* Hand sets the CALLER supplies — from another sampler, a file, an earlier frame, a perturbation of a good grasp, a list
+ * gathered over several searches — instead of the last search's: ImageGenerator::createImages(cloud, hand_set_list)
+ * (image_generator.cpp:17-99) images whatever it is handed.
+ *
+ * gpd_hip_given_check (host only, no context; the definition is csrc/given_model.h): what may be supplied.  The layout is
+ * gpd_hip_images': num_sets x slots records, set-major, slots = num_hand_axes * num_orientations.  A set's sample is slot 0's
+ * `sample` and must be finite even when slot 0 is not valid.  Every record with valid != 0 must have
+ *   - `sample` equal to the set's sample bit for bit (the reference's HandSet has one sample),
+ *   - finite `frame`, `bottom`, `center`; `frame` a rotation: every entry of F^T F - I within 1e-6,
+ *   - init_bite - hand_depth <= bottom <= 0 and |center| <= (hand_outer_diameter - finger_width) / 2, each with 1e-9 of slack:
+ *     the ranges the voxel windows of the image kernels are sized for (hands outside them are refused, not routed elsewhere).
+ * Records with valid == 0 are husks: nothing but slot 0's sample is read from them.  GPD_ERR_INVALID outside that domain, the
+ * first offending set / slot in *bad_set / *bad_slot (may be NULL; -1 / -1 on GPD_OK), the reason in gpd_hip_last_error().
+ *
+ * gpd_hip_images_given: the images of such hand sets on the context's uploaded cloud.  A set's image neighbourhood is the
+ * nn_radius_images sphere around the float cast of its sample, in (d2, index) order; sets without a valid hand are skipped and
+ * consume no shadow draws, the others take their place in the one shadow LCG stream in the order given, starting at lcg_base
+ * (0: a whole cloud); candidates are the valid hands, set-major and slot-minor.  Every set is a set: no frame is estimated and
+ * no hand evaluated here, so a sample without a point inside nn_radius_frames is kept.  images (may be NULL: keep on the device,
+ * for gpd_hip_score(ctx, NULL, n, ...)), cand_index, num_candidates as gpd_hip_images; lcg_draws (may be NULL): the shadow draws
+ * the sets consumed.
+ *
+ * gpd_hip_score_given: the same followed by the LeNet in the context's mode and ReLU setting.  `score` of every valid record is
+ * written; no other byte of `hands` changes.  scores (may be NULL): one per candidate.
+ *
+ * Both reuse the search buffers, as gpd_hip_reevaluate does: hands of an earlier gpd_hip_search can no longer be passed to
+ * gpd_hip_images afterwards.  GPD_ERR_STATE without a cloud (or weights, for the scoring entry); GPD_ERR_INVALID from the
+ * check, made before anything is enqueued: the context is as it was. */
+int gpd_hip_given_check(const gpd_params *params, const gpd_hand *hands, int num_sets, int *bad_set, int *bad_slot);
+int gpd_hip_images_given(gpd_hip_ctx *ctx, const gpd_hand *hands, int num_sets, uint64_t lcg_base, uint8_t *images,
+                         int32_t *cand_index, int *num_candidates, uint64_t *lcg_draws);
+int gpd_hip_score_given(gpd_hip_ctx *ctx, gpd_hand *hands, int num_sets, uint64_t lcg_base, float *scores, int32_t *cand_index,
+                        int *num_candidates, uint64_t *lcg_draws);
+
 /* Fused path used by GraspDetector::detectGrasps steps 1-4
  * (grasp_detector.cpp:222-273): search, workspace/aperture filter
  * (filterGraspsWorkspace, :238, :334-398), images, scores, score write-back (:269-273).
