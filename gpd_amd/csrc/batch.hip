@@ -372,7 +372,7 @@ int gpd_hip_detect_batch(gpd_hip_ctx *ctx, gpd_detect_job *jobs, int num_jobs) {
     set_error("gpd_hip_detect_batch: LeNet weights not set");
     return GPD_ERR_STATE;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   BatchRun b(ctx, jobs, num_jobs);
   int rc = b.validate();
   if (rc) return rc;

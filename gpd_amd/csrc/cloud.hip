@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "gpd_internal.h"
+#include "buffers.h"
 #include "grid_sort.h"
 #include "wave_ops.h"
 
@@ -74,10 +75,8 @@ __global__ void grid_scatter_kernel(GridView g, const float *px, const float *py
 
 void cloud_free(Cloud &c) {
   normals_free(c.normals);
-  void *ptrs[] = {c.px, c.py, c.pz, c.nx, c.ny, c.nz, c.cam_source, c.staging, c.g_start, c.g_cursor, c.g_p, c.pxyz, c.pnrm};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  if (c.h_pin) (void)hipHostFree(c.h_pin);
+  device_release(c.px, c.py, c.pz, c.nx, c.ny, c.nz, c.cam_source, c.staging, c.g_start, c.g_cursor, c.g_p, c.pxyz, c.pnrm);
+  pinned_release(c.h_pin);
   c = Cloud();
 }
 
@@ -88,23 +87,23 @@ int cloud_reserve(Cloud &c, int n, int num_cams) {
   if (n <= c.capacity && num_cams <= c.cap_cams) return GPD_OK;
   note_alloc(__func__);
   const uint64_t gen = c.generation;
-  const int cap = n > c.capacity ? n + n / 4 : c.capacity;  // slack: clouds of a batch differ by a few points
+  const int cap = n > c.capacity ? slack_cap(n, 4) : c.capacity;  // slack: clouds of a batch differ by a few points
   const int cams = num_cams > c.cap_cams ? num_cams : c.cap_cams;
   const int cells_cap = c.g_cells_cap;
   cloud_free(c);  // hipFree waits for the device: kernels of an earlier cloud on this stream are done
   c.generation = gen;
   float **planes[] = {&c.px, &c.py, &c.pz, &c.nx, &c.ny, &c.nz};
-  for (float **p : planes) HIP_RET(hipMalloc(p, (size_t)cap * sizeof(float)));
+  for (float **p : planes) HIP_RET(device_alloc(*p, (size_t)cap));
   float4 **quads[] = {&c.g_p, &c.pxyz, &c.pnrm};
-  for (float4 **p : quads) HIP_RET(hipMalloc(p, (size_t)cap * sizeof(float4)));
-  HIP_RET(hipMalloc(&c.cam_source, (size_t)cap * cams * sizeof(int32_t)));
-  HIP_RET(hipMalloc(&c.staging, ((size_t)cap * 6 + 8) * sizeof(float)));  // + 8: the bounds of a cloud handed over on the device
-  HIP_RET(hipHostMalloc(reinterpret_cast<void **>(&c.h_pin), (size_t)cap * (6 * sizeof(float) + cams * sizeof(int32_t)) + 32, 0));
+  for (float4 **p : quads) HIP_RET(device_alloc(*p, (size_t)cap));
+  HIP_RET(device_alloc(c.cam_source, (size_t)cap * cams));
+  HIP_RET(device_alloc(c.staging, (size_t)cap * 6 + 8));  // + 8: the bounds of a cloud handed over on the device
+  HIP_RET(pinned_alloc(c.h_pin, (size_t)cap * (6 * sizeof(float) + cams * sizeof(int32_t)) + 32));
   c.capacity = cap;
   c.cap_cams = cams;
   if (cells_cap > 0) {  // the grid tables keep their size across a growth of the point buffers
-    HIP_RET(hipMalloc(&c.g_start, (size_t)(cells_cap + 1) * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&c.g_cursor, (size_t)cells_cap * sizeof(int32_t)));
+    HIP_RET(device_alloc(c.g_start, (size_t)cells_cap + 1));
+    HIP_RET(device_alloc(c.g_cursor, (size_t)cells_cap));
     c.g_cells_cap = cells_cap;
   }
   return GPD_OK;
@@ -114,13 +113,10 @@ int cloud_reserve(Cloud &c, int n, int num_cams) {
 int cloud_reserve_grid(Cloud &c, int cells) {
   if (cells <= c.g_cells_cap) return GPD_OK;
   note_alloc(__func__);
-  if (c.g_start) (void)hipFree(c.g_start);
-  if (c.g_cursor) (void)hipFree(c.g_cursor);
-  c.g_start = nullptr;
-  c.g_cursor = nullptr;
+  device_release(c.g_start, c.g_cursor);
   c.g_cells_cap = 0;
-  HIP_RET(hipMalloc(&c.g_start, (size_t)(cells + 1) * sizeof(int32_t)));
-  HIP_RET(hipMalloc(&c.g_cursor, (size_t)cells * sizeof(int32_t)));
+  HIP_RET(device_alloc(c.g_start, (size_t)cells + 1));
+  HIP_RET(device_alloc(c.g_cursor, (size_t)cells));
   c.g_cells_cap = cells;
   return GPD_OK;
 }

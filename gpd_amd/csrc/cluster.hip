@@ -10,6 +10,7 @@
 // skipped by the later seeds, :36, :70-72): the same workgroup code walks the seeds one after the other.
 // A one-workgroup scan then writes the clusters in seed order.  fp64, unfused, sums in the reference's order.
 #include "gpd_internal.h"
+#include "buffers.h"
 #include <cmath>
 
 namespace gpd {
@@ -155,25 +156,23 @@ __global__ __launch_bounds__(256) void record_scores_kernel(const gpd_hand *__re
 }  // namespace
 
 void cluster_free(ClusterState &s) {
-  void *dev[] = {s.d_hands, s.d_scores, s.d_used, s.d_keep, s.d_res, s.d_out, s.d_out_scores, s.d_out_src, s.d_num};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
+  device_release(s.d_hands, s.d_scores, s.d_used, s.d_keep, s.d_res, s.d_out, s.d_out_scores, s.d_out_src, s.d_num);
   s = ClusterState();
 }
 
 static int cluster_reserve(ClusterState &s, int n) {
   if (n > s.capacity) {
-    const int cap = n + n / 4;
-    cluster_free(s);
-    HIP_RET(hipMalloc(&s.d_hands, (size_t)cap * sizeof(gpd_hand)));
-    HIP_RET(hipMalloc(&s.d_scores, (size_t)cap * sizeof(double)));
-    HIP_RET(hipMalloc(&s.d_used, (size_t)cap));
-    HIP_RET(hipMalloc(&s.d_keep, (size_t)cap * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_res, (size_t)cap * 4 * sizeof(double)));
-    HIP_RET(hipMalloc(&s.d_out, (size_t)cap * sizeof(gpd_hand)));
-    HIP_RET(hipMalloc(&s.d_out_scores, (size_t)cap * sizeof(double)));
-    HIP_RET(hipMalloc(&s.d_out_src, (size_t)cap * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_num, sizeof(int32_t)));
+    const int cap = slack_cap(n, 4);
+    cluster_free(s);  // (never booked: note_alloc's comment in gpd_internal.h)
+    HIP_RET(device_alloc(s.d_hands, (size_t)cap));
+    HIP_RET(device_alloc(s.d_scores, (size_t)cap));
+    HIP_RET(device_alloc(s.d_used, (size_t)cap));
+    HIP_RET(device_alloc(s.d_keep, (size_t)cap));
+    HIP_RET(device_alloc(s.d_res, (size_t)cap * 4));
+    HIP_RET(device_alloc(s.d_out, (size_t)cap));
+    HIP_RET(device_alloc(s.d_out_scores, (size_t)cap));
+    HIP_RET(device_alloc(s.d_out_src, (size_t)cap));
+    HIP_RET(device_alloc(s.d_num, 1));
     s.capacity = cap;
   }
   return GPD_OK;

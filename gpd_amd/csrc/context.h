@@ -6,15 +6,6 @@
 
 #include "gpd_internal.h"
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess) {                                                             \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return GPD_ERR_HIP;                                                               \
-    }                                                                                   \
-  } while (0)
-
 namespace gpd {
 
 constexpr int kLanes = 2;

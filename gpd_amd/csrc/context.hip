@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "context.h"
+#include "buffers.h"
 #include "balance_model.h"
 #include "sample_model.h"
 #include "sis_model.h"
@@ -51,14 +52,14 @@ int lane_init(Lane &L, hipStream_t shared) {
   if (shared) {
     L.stream = shared;
   } else {
-    HIP_TRY(hipStreamCreate(&L.stream));
+    HIP_RET(hipStreamCreate(&L.stream));
     L.owns_stream = true;
   }
-  for (auto &e : L.ev) HIP_TRY(hipEventCreate(&e));
-  HIP_TRY(hipEventCreate(&L.ev_plan));
-  HIP_TRY(hipEventCreate(&L.ev_done));
-  for (auto &e : L.ev_chunk) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&L.h_flags), sizeof(HostFlags), 0));
+  for (auto &e : L.ev) HIP_RET(hipEventCreate(&e));
+  HIP_RET(hipEventCreate(&L.ev_plan));
+  HIP_RET(hipEventCreate(&L.ev_done));
+  for (auto &e : L.ev_chunk) HIP_RET(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  HIP_RET(pinned_alloc(L.h_flags, 1));
   std::memset(L.h_flags, 0, sizeof(HostFlags));
   return GPD_OK;
 }
@@ -76,12 +77,9 @@ static void lane_free(Lane &L) {
   images_free(L.images);
   plane_free(L.plane);
   refine_free(L.refine);
-  if (L.h_pos) (void)hipHostFree(L.h_pos);
-  void *dev[] = {L.d_scores, L.d_out, L.d_sel, L.d_all, L.d_img_in, L.d_img_planar, L.d_pos};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
-  if (L.h_out) (void)hipHostFree(L.h_out);
-  if (L.h_flags) (void)hipHostFree(L.h_flags);
+  pinned_release(L.h_pos);
+  device_release(L.d_scores, L.d_out, L.d_sel, L.d_all, L.d_img_in, L.d_img_planar, L.d_pos);
+  pinned_release(L.h_out, L.h_flags);
   for (auto &e : L.ev)
     if (e) (void)hipEventDestroy(e);
   if (L.ev_plan) (void)hipEventDestroy(L.ev_plan);
@@ -92,66 +90,34 @@ static void lane_free(Lane &L) {
   L = Lane();
 }
 
-// One device buffer that only grows: `need` elements within its capacity cost nothing; beyond it the buffer is freed and
-// allocated again with a quarter of slack, booked on `who` (note_alloc).  A failed allocation leaves it empty.
-template <typename T, typename N>
-static int grow_device(T *&p, N &cap, N need, const char *who) {
-  if (need <= cap) return GPD_OK;
-  note_alloc(who);
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  const N grown = need + need / 4;
-  HIP_TRY(hipMalloc(&p, (size_t)grown * sizeof(T)));
-  cap = grown;
-  return GPD_OK;
-}
-
-int reserve_scores(Lane &L, int n) { return grow_device(L.d_scores, L.d_scores_cap, n, __func__); }
+int reserve_scores(Lane &L, int n) { return grow_device(L.d_scores, L.d_scores_cap, n, slack_cap(n, 4), __func__); }
 
 int reserve_out(Lane &L, size_t records, size_t extra_bytes) {
-  const int rc = grow_device(L.d_out, L.d_out_cap, records, __func__);
+  const int rc = grow_device(L.d_out, L.d_out_cap, records, slack_cap(records, 4), __func__);
   if (rc) return rc;
   const size_t bytes = L.d_out_cap * sizeof(gpd_hand) + extra_bytes;
-  if (bytes > L.h_out_bytes) {
-    note_alloc(__func__);
-    if (L.h_out) (void)hipHostFree(L.h_out);
-    L.h_out = nullptr;
-    L.h_out_bytes = 0;
-    const size_t cap = bytes + bytes / 8;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&L.h_out), cap, 0));
-    L.h_out_bytes = cap;
-  }
-  return GPD_OK;
+  return grow_pinned(L.h_out, L.h_out_bytes, bytes, slack_cap(bytes, 8), __func__);
 }
 
 // the draw positions of up to n samples and the sample indices that come back
 int reserve_draws(Lane &L, int n) {
   if (n <= L.draw_cap) return GPD_OK;
   note_alloc(__func__);
-  if (L.d_pos) (void)hipFree(L.d_pos);
-  if (L.h_pos) (void)hipHostFree(L.h_pos);
-  L.d_pos = L.h_pos = nullptr;
+  device_release(L.d_pos);
+  pinned_release(L.h_pos);
   L.draw_cap = 0;
-  const int cap = n + n / 4;
-  HIP_TRY(hipMalloc(&L.d_pos, (size_t)cap * sizeof(int32_t)));
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&L.h_pos), (size_t)cap * 3 * sizeof(int32_t), 0));
+  const int cap = slack_cap(n, 4);
+  HIP_RET(device_alloc(L.d_pos, (size_t)cap));
+  HIP_RET(pinned_alloc(L.h_pos, (size_t)cap * 3));
   L.draw_cap = cap;
   return GPD_OK;
 }
 
 // selections (num_selected > 0): the winners' ordinals + tie flag, and the job's own list of every scored candidate
 int reserve_selection(Lane &L, int k, int n) {
-  if (k + 1 > L.d_sel_cap) {
-    note_alloc(__func__);
-    if (L.d_sel) (void)hipFree(L.d_sel);
-    L.d_sel = nullptr;
-    L.d_sel_cap = 0;
-    const int cap = k + 1 + k / 4;  // (the slack is a quarter of k, not of k + 1)
-    HIP_TRY(hipMalloc(&L.d_sel, (size_t)cap * sizeof(int32_t)));
-    L.d_sel_cap = cap;
-  }
-  return grow_device(L.d_all, L.d_all_cap, (size_t)n, __func__);
+  const int rc = grow_device(L.d_sel, L.d_sel_cap, k + 1, slack_cap(k, 4) + 1, __func__);  // (the slack is a quarter of k, not of k + 1)
+  if (rc) return rc;
+  return grow_device(L.d_all, L.d_all_cap, (size_t)n, slack_cap((size_t)n, 4), __func__);
 }
 
 // the most candidates `samples` samples can give (every slot a valid hand), cut to what `budget` bytes hold: per candidate
@@ -178,7 +144,7 @@ int lane_reserve(gpd_hip_ctx *ctx, Lane &L, int points, int cams, int samples, i
   const long long sets = std::min((long long)samples, (long long)candidates) * cams;  // (live hand set, camera) voxel bitsets
   rc = images_reserve(p, L.images, candidates, p.image_num_channels == 15 ? (int)sets : 0);
   if (rc) return rc;
-  HIP_TRY(lenet_scratch_reserve(L.lenet_scratch, std::min(candidates, kLeNetChunk)));
+  HIP_RET(lenet_scratch_reserve(L.lenet_scratch, std::min(candidates, kLeNetChunk)));
   rc = reserve_scores(L, candidates);
   if (rc) return rc;
   if (selected >= 0) {
@@ -311,12 +277,12 @@ int gpd_hip_create(int device, const gpd_params *params, gpd_hip_ctx **out) {
     }
   }
   int count = 0;
-  HIP_TRY(hipGetDeviceCount(&count));
+  HIP_RET(hipGetDeviceCount(&count));
   if (device < 0 || device >= count) {
     set_error("gpd_hip_create: device %d out of range (%d devices)", device, count);
     return GPD_ERR_INVALID;
   }
-  HIP_TRY(hipSetDevice(device));
+  HIP_RET(hipSetDevice(device));
   gpd_hip_ctx *ctx = new gpd_hip_ctx();
   ctx->device = device;
   ctx->params = *params;
@@ -344,14 +310,13 @@ void gpd_hip_destroy(gpd_hip_ctx *ctx) {
   if (ctx->pre.ev_keys) (void)hipEventDestroy(ctx->pre.ev_keys);
   float **ws[] = {&ctx->lenet.c1w, &ctx->lenet.c1b, &ctx->lenet.c2w, &ctx->lenet.c2b,
                   &ctx->lenet.f1w, &ctx->lenet.f1b, &ctx->lenet.f2w, &ctx->lenet.f2b, &ctx->lenet.c1wp, &ctx->lenet.c2wt};
-  for (float **p : ws)
-    if (*p) (void)hipFree(*p);
+  for (float **p : ws) device_release(*p);
   lenet_fast_free(ctx->lenet.fast);
   for (auto &e : ctx->replay_events) (void)hipEventDestroy(e);
   if (ctx->pipe_stream) {
     (void)hipStreamSynchronize(ctx->pipe_stream);
     (void)hipStreamDestroy(ctx->pipe_stream);
-    if (ctx->pipe_images[1]) (void)hipFree(ctx->pipe_images[1]);
+    device_release(ctx->pipe_images[1]);
     for (int b = 0; b < 2; b++) {
       (void)hipEventDestroy(ctx->pipe_filled[b]);
       (void)hipEventDestroy(ctx->pipe_read[b]);
@@ -365,13 +330,13 @@ int gpd_hip_reserve(gpd_hip_ctx *ctx, int max_points, int max_cams, int max_samp
     set_error("gpd_hip_reserve: bad argument");
     return GPD_ERR_INVALID;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   const int cand = max_candidates > 0 ? max_candidates : candidate_bound(ctx->params, max_samples, max_cams);
   for (int l = 0; l < kLanes; l++) {
     int rc = lane_init(ctx->lane[l]);
     if (rc) return rc;
     Lane &L = ctx->lane[l];
-    HIP_TRY(hipStreamSynchronize(L.stream));
+    HIP_RET(hipStreamSynchronize(L.stream));
     // lane 0 also serves the single-cloud entries (all slots of all sets back); both serve the batch (candidates / winners)
     if (l == 0) {
       rc = lane_reserve(ctx, L, max_points, max_cams, max_samples, cand, -1);
@@ -395,7 +360,7 @@ int gpd_hip_set_lenet_weights(gpd_hip_ctx *ctx, int channels, const float *conv1
     set_error("gpd_hip_set_lenet_weights: channels %d != image_num_channels %d", channels, ctx->params.image_num_channels);
     return GPD_ERR_INVALID;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   struct Item {
     float **dst;
     const float *src;
@@ -421,15 +386,14 @@ int gpd_hip_set_lenet_weights(gpd_hip_ctx *ctx, int channels, const float *conv1
         }
   }
   for (auto &L : ctx->lane)
-    if (L.stream) HIP_TRY(hipStreamSynchronize(L.stream));  // no kernel still reads the old weights
+    if (L.stream) HIP_RET(hipStreamSynchronize(L.stream));  // no kernel still reads the old weights
   // from here until every upload has succeeded the context holds NO weights: an update that fails half way (out of memory in
   // lenet_fast_prepare, say) leaves scoring calls refused with "LeNet weights not set" instead of launching on freed tables
   ctx->lenet.channels = 0;
   for (auto &it : items) {
-    if (*it.dst) (void)hipFree(*it.dst);
-    *it.dst = nullptr;
-    HIP_TRY(hipMalloc(it.dst, it.n * sizeof(float)));
-    HIP_TRY(hipMemcpy(*it.dst, it.src, it.n * sizeof(float), hipMemcpyHostToDevice));
+    device_release(*it.dst);
+    HIP_RET(device_alloc(*it.dst, it.n));
+    HIP_RET(hipMemcpy(*it.dst, it.src, it.n * sizeof(float), hipMemcpyHostToDevice));
   }
   // device-side layouts of the conv weights (file layout is [filter][k], conv_layer.cpp:35-36):
   // conv1 rows padded from 25 to 28 taps per channel, conv2 k-major
@@ -446,13 +410,12 @@ int gpd_hip_set_lenet_weights(gpd_hip_ctx *ctx, int channels, const float *conv1
       std::vector<float> *src;
     } tr[] = {{&ctx->lenet.c1wp, &t1}, {&ctx->lenet.c2wt, &t2}};
     for (auto &it : tr) {
-      if (*it.dst) (void)hipFree(*it.dst);
-      *it.dst = nullptr;
-      HIP_TRY(hipMalloc(it.dst, it.src->size() * sizeof(float)));
-      HIP_TRY(hipMemcpy(*it.dst, it.src->data(), it.src->size() * sizeof(float), hipMemcpyHostToDevice));
+      device_release(*it.dst);
+      HIP_RET(device_alloc(*it.dst, it.src->size()));
+      HIP_RET(hipMemcpy(*it.dst, it.src->data(), it.src->size() * sizeof(float), hipMemcpyHostToDevice));
     }
   }
-  HIP_TRY(lenet_fast_prepare(ctx->lenet.fast, channels, conv1_w, conv2_w, ip1_w));
+  HIP_RET(lenet_fast_prepare(ctx->lenet.fast, channels, conv1_w, conv2_w, ip1_w));
   ctx->lenet.channels = channels;
   return GPD_OK;
 }
@@ -462,9 +425,9 @@ int gpd_hip_set_lenet_mode(gpd_hip_ctx *ctx, int mode) {
     set_error("gpd_hip_set_lenet_mode: bad argument");
     return GPD_ERR_INVALID;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   for (auto &L : ctx->lane)
-    if (L.stream) HIP_TRY(hipStreamSynchronize(L.stream));  // the two modes lay pool1 out differently: no launch in flight
+    if (L.stream) HIP_RET(hipStreamSynchronize(L.stream));  // the two modes lay pool1 out differently: no launch in flight
   ctx->lenet.mode = mode;
   return GPD_OK;
 }
@@ -522,27 +485,27 @@ int gpd_hip_lenet_debug(gpd_hip_ctx *ctx, int which, int n, void *out) {
     set_error("gpd_hip_lenet_debug: bad argument");
     return GPD_ERR_INVALID;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   Lane &L = ctx->lane[0];
   LeNetScratch &s = L.lenet_scratch;
   if (n > s.capacity) {
     set_error("gpd_hip_lenet_debug: n = %d exceeds the scratch capacity %d", n, s.capacity);
     return GPD_ERR_STATE;
   }
-  HIP_TRY(hipStreamSynchronize(L.stream));
+  HIP_RET(hipStreamSynchronize(L.stream));
   if (which == 0) {
-    HIP_TRY(hipMemcpy(out, s.pool1, (size_t)n * 15680 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_RET(hipMemcpy(out, s.pool1, (size_t)n * 15680 * sizeof(float), hipMemcpyDeviceToHost));
   } else if (which == 1) {
     const size_t rows = ((size_t)n + 15) & ~(size_t)15;
     std::vector<unsigned short> blocked(3 * rows * kLenetXld);
-    HIP_TRY(hipMemcpy(blocked.data(), s.xs, blocked.size() * sizeof(unsigned short), hipMemcpyDeviceToHost));
+    HIP_RET(hipMemcpy(blocked.data(), s.xs, blocked.size() * sizeof(unsigned short), hipMemcpyDeviceToHost));
     lenet_fast_unblock_x(blocked.data(), n, static_cast<unsigned short *>(out));
   } else if (which == 2 && ctx->lenet.mode == GPD_LENET_SPLIT) {
     // the split path keeps ip1's output as four partial sums (they meet inside ip2's kernel): added here as there, in order
     const size_t rows = ((size_t)n + 31) & ~(size_t)31;
     std::vector<float> part(rows * 4 * kFc1Out), b1(kFc1Out);
-    HIP_TRY(hipMemcpy(part.data(), s.fc1p, part.size() * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b1.data(), ctx->lenet.f1b, b1.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_RET(hipMemcpy(part.data(), s.fc1p, part.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_RET(hipMemcpy(b1.data(), ctx->lenet.f1b, b1.size() * sizeof(float), hipMemcpyDeviceToHost));
     float *o = static_cast<float *>(out);
     for (int u = 0; u < kFc1Out; u++)
       for (int m = 0; m < n; m++) {
@@ -550,7 +513,7 @@ int gpd_hip_lenet_debug(gpd_hip_ctx *ctx, int which, int n, void *out) {
         o[(size_t)u * n + m] = v > 0.f ? v : 0.f;
       }
   } else if (which == 2) {
-    HIP_TRY(hipMemcpy2D(out, (size_t)n * sizeof(float), s.fc1t, (size_t)s.capacity * sizeof(float), (size_t)n * sizeof(float), kFc1Out,
+    HIP_RET(hipMemcpy2D(out, (size_t)n * sizeof(float), s.fc1t, (size_t)s.capacity * sizeof(float), (size_t)n * sizeof(float), kFc1Out,
                         hipMemcpyDeviceToHost));
   } else {
     set_error("gpd_hip_lenet_debug: which = %d", which);
@@ -570,23 +533,21 @@ int gpd_hip_score(gpd_hip_ctx *ctx, const uint8_t *images, int n, float *scores)
     return GPD_ERR_STATE;
   }
   if (n == 0) return GPD_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   Lane &L = ctx->lane[0];
   const size_t bytes = (size_t)n * kPix * ctx->lenet.channels;
   const uint8_t *d_img = nullptr;
   if (images) {
     if (bytes > L.d_img_in_bytes) {
-      if (L.d_img_in) (void)hipFree(L.d_img_in);
-      if (L.d_img_planar) (void)hipFree(L.d_img_planar);
-      L.d_img_in = nullptr;
-      L.d_img_planar = nullptr;
+      device_release(L.d_img_in);  // (never booked: note_alloc's comment in gpd_internal.h)
+      device_release(L.d_img_planar);
       L.d_img_in_bytes = 0;
-      HIP_TRY(hipMalloc(&L.d_img_in, bytes));
-      HIP_TRY(hipMalloc(&L.d_img_planar, bytes));
+      HIP_RET(device_alloc(L.d_img_in, bytes));
+      HIP_RET(device_alloc(L.d_img_planar, bytes));
       L.d_img_in_bytes = bytes;
     }
-    HIP_TRY(hipMemcpyAsync(L.d_img_in, images, bytes, hipMemcpyHostToDevice, L.stream));
-    HIP_TRY(hwc_to_planar(L.d_img_in, L.d_img_planar, n, ctx->lenet.channels, L.stream));
+    HIP_RET(hipMemcpyAsync(L.d_img_in, images, bytes, hipMemcpyHostToDevice, L.stream));
+    HIP_RET(hwc_to_planar(L.d_img_in, L.d_img_planar, n, ctx->lenet.channels, L.stream));
     d_img = L.d_img_planar;
   } else {
     if (n != L.images.num_candidates || !L.images.d_images) {
@@ -597,12 +558,12 @@ int gpd_hip_score(gpd_hip_ctx *ctx, const uint8_t *images, int n, float *scores)
   }
   int rc = reserve_scores(L, n);
   if (rc) return rc;
-  HIP_TRY(hipEventRecord(L.ev[2], L.stream));
-  HIP_TRY(lenet_forward(ctx->lenet, L.lenet_scratch, d_img, n, L.d_scores, L.stream));
-  HIP_TRY(hipEventRecord(L.ev[3], L.stream));
-  HIP_TRY(hipMemcpyAsync(scores, L.d_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, L.stream));
-  HIP_TRY(hipStreamSynchronize(L.stream));
-  HIP_TRY(hipEventElapsedTime(&L.stage_ms[2], L.ev[2], L.ev[3]));
+  HIP_RET(hipEventRecord(L.ev[2], L.stream));
+  HIP_RET(lenet_forward(ctx->lenet, L.lenet_scratch, d_img, n, L.d_scores, L.stream));
+  HIP_RET(hipEventRecord(L.ev[3], L.stream));
+  HIP_RET(hipMemcpyAsync(scores, L.d_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, L.stream));
+  HIP_RET(hipStreamSynchronize(L.stream));
+  HIP_RET(hipEventElapsedTime(&L.stage_ms[2], L.ev[2], L.ev[3]));
   return lenet_check(L.lenet_scratch);
 }
 
@@ -613,7 +574,7 @@ int gpd_hip_upload_cloud(gpd_hip_ctx *ctx, const float *xyz, const float *normal
     set_error("gpd_hip_upload_cloud: bad argument");
     return GPD_ERR_INVALID;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   Lane &L = ctx->lane[0];
   return cloud_upload(L.cloud, xyz, normals, num_points, cam_source, num_cams, view_points, L.stream, /*sync=*/true);
 }
@@ -624,11 +585,11 @@ int gpd_hip_upload_ground_truth(gpd_hip_ctx *ctx, const float *xyz, const float 
     set_error("gpd_hip_upload_ground_truth: bad argument");
     return GPD_ERR_INVALID;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   Lane &L = ctx->lane[0];
   LabelState &ls = ctx->label;
   if (num_points == 0) {  // cleared: the buffers stay, the next gpd_hip_label_view is refused
-    HIP_TRY(hipStreamSynchronize(L.stream));
+    HIP_RET(hipStreamSynchronize(L.stream));
     ls.gt.num_points = 0;
     ls.gt.generation++;
     return GPD_OK;
@@ -740,7 +701,7 @@ int gpd_hip_find_clusters(gpd_hip_ctx *ctx, const gpd_hand *hands, const double 
     set_error("gpd_hip_find_clusters: bad argument");
     return GPD_ERR_INVALID;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   return cluster_run(ctx->cluster, hands, scores, n, min_inliers, remove_inliers, out, out_scores, out_src, num_out, ctx->lane[0].stream);
 }
 
@@ -759,7 +720,7 @@ int gpd_hip_preprocess_cloud(gpd_hip_ctx *ctx, const float *xyz, const int32_t *
         set_error("gpd_hip_preprocess_cloud: the workspace holds a NaN");
         return GPD_ERR_INVALID;
       }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   return preprocess_run(ctx->pre, xyz, cam_source, num_points, num_cams, workspace, voxel_size, xyz_out, cam_out, src_out, num_out,
                         kernel_ms, ctx->lane[0].stream);
 }
@@ -775,7 +736,7 @@ int gpd_hip_estimate_normals(gpd_hip_ctx *ctx, double radius, float *normals) {
     set_error("gpd_hip_estimate_normals: no cloud uploaded");
     return GPD_ERR_STATE;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   return normals_run(L.cloud, radius, normals, L.stream);
 }
 
@@ -794,7 +755,7 @@ int gpd_hip_sample_above_plane(gpd_hip_ctx *ctx, double threshold, int max_itera
     set_error("gpd_hip_sample_above_plane: no cloud uploaded");
     return GPD_ERR_STATE;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   return plane_fit_run(ctx->plane, L.cloud, threshold, max_iterations, probability, optimize, indices_out, num_out, coeffs, num_inliers,
                        iterations, L.stream);
 }
@@ -830,7 +791,7 @@ int gpd_hip_refine_normals(gpd_hip_ctx *ctx, int k, int max_iterations, float co
     set_error("gpd_hip_refine_normals: bad argument: no cloud uploaded");
     return GPD_ERR_INVALID;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   return refine_run(ctx->refine, L.cloud, k, max_iterations, convergence_threshold, normals_out, iterations_out, ddot_out, num_nan_out, kernel_ms,
                     L.stream);
 }
@@ -851,14 +812,14 @@ static int search_any(gpd_hip_ctx *ctx, const char *who, const int32_t *sample_i
   if (num_samples == 0) return GPD_OK;
   int rc = check_samples(who, sample_indices, sample_xyz, num_samples, L.cloud.num_points);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(ctx->device));
-  HIP_TRY(hipEventRecord(L.ev[0], L.stream));
+  HIP_RET(hipSetDevice(ctx->device));
+  HIP_RET(hipEventRecord(L.ev[0], L.stream));
   rc = search_run(ctx->params, L.cloud, L.search, sample_indices, sample_xyz, num_samples, L.stream);
   if (rc) return rc;
-  HIP_TRY(hipEventRecord(L.ev[1], L.stream));
+  HIP_RET(hipEventRecord(L.ev[1], L.stream));
   rc = search_download(ctx->params, L.search, hands, num_sets, L.stream);
   if (rc) return rc;
-  HIP_TRY(hipEventElapsedTime(&L.stage_ms[0], L.ev[0], L.ev[1]));
+  HIP_RET(hipEventElapsedTime(&L.stage_ms[0], L.ev[0], L.ev[1]));
   return GPD_OK;
 }
 
@@ -897,7 +858,7 @@ int gpd_hip_reevaluate(gpd_hip_ctx *ctx, gpd_hand *hands, int num_hands, int32_t
         set_error("gpd_hip_reevaluate: hand %d has a non-finite sample", i);
         return GPD_ERR_INVALID;
       }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   L.images.num_candidates = 0;  // the search buffers the resident candidate list points into are reused
   return reevaluate_run(ctx->params, L.cloud, L.search, hands, num_hands, labels, L.stream);
 }
@@ -914,7 +875,7 @@ int gpd_hip_images(gpd_hip_ctx *ctx, const gpd_hand *hands, int num_sets, uint8_
     set_error("gpd_hip_images: no cloud uploaded");
     return GPD_ERR_STATE;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   SearchState &s = L.search;
   const int slots = ctx->params.num_hand_axes * ctx->params.num_orientations;
   *num_candidates = 0;
@@ -935,10 +896,10 @@ int gpd_hip_images(gpd_hip_ctx *ctx, const gpd_hand *hands, int num_sets, uint8_
     for (int j = 0; j < slots; j++) fv[(size_t)si * slots + j] = hands[(size_t)si * slots + j].valid ? 1 : 0;
     for (int r = 0; r < 3; r++) smp[3 * (size_t)si + r] = hands[(size_t)si * slots].sample[r];
   }
-  HIP_TRY(hipEventRecord(L.ev[0], L.stream));
+  HIP_RET(hipEventRecord(L.ev[0], L.stream));
   int rc = plan_build(ctx->params, L.cloud, s, L.plan, L.stream, fv.data(), smp.data(), num_sets);
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(L.stream));  // fv / smp are pageable: their copies have left them by now as well
+  HIP_RET(hipStreamSynchronize(L.stream));  // fv / smp are pageable: their copies have left them by now as well
   if (L.plan.h_summary->mismatch_set >= 0) {
     set_error("images: set %d does not match the last search (sample moved, or more sets than the search produced)",
               L.plan.h_summary->mismatch_set);
@@ -947,22 +908,22 @@ int gpd_hip_images(gpd_hip_ctx *ctx, const gpd_hand *hands, int num_sets, uint8_
   L.images.lcg_base = 0;  // gpd_hip_images: the cloud's stream of shadow draws from its start
   rc = images_run(ctx->params, L.cloud, s, L.plan, L.images, L.stream);
   if (rc) return rc;
-  HIP_TRY(hipEventRecord(L.ev[1], L.stream));
+  HIP_RET(hipEventRecord(L.ev[1], L.stream));
   const int n = L.images.num_candidates;
   *num_candidates = n;
   if (cand_index && n > 0)
-    HIP_TRY(hipMemcpyAsync(cand_index, L.plan.d_cand_out, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+    HIP_RET(hipMemcpyAsync(cand_index, L.plan.d_cand_out, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
   if (images && n > 0) {
     // the caller wants cv::Mat-layout pixels: planar -> HWC on the device, then one copy
     const size_t bytes = (size_t)L.images.capacity * kPix * ctx->params.image_num_channels;
-    if (!L.images.d_images_hwc) HIP_TRY(hipMalloc(&L.images.d_images_hwc, bytes));
-    HIP_TRY(planar_to_hwc(L.images.d_images, L.images.d_images_hwc, n, ctx->params.image_num_channels, L.stream));
-    HIP_TRY(hipMemcpyAsync(images, L.images.d_images_hwc, (size_t)n * kPix * ctx->params.image_num_channels, hipMemcpyDeviceToHost,
+    if (!L.images.d_images_hwc) HIP_RET(device_alloc(L.images.d_images_hwc, bytes));
+    HIP_RET(planar_to_hwc(L.images.d_images, L.images.d_images_hwc, n, ctx->params.image_num_channels, L.stream));
+    HIP_RET(hipMemcpyAsync(images, L.images.d_images_hwc, (size_t)n * kPix * ctx->params.image_num_channels, hipMemcpyDeviceToHost,
                            L.stream));
   }
-  HIP_TRY(hipMemcpyAsync(&L.h_flags->status, L.images.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
-  HIP_TRY(hipStreamSynchronize(L.stream));
-  HIP_TRY(hipEventElapsedTime(&L.stage_ms[1], L.ev[0], L.ev[1]));
+  HIP_RET(hipMemcpyAsync(&L.h_flags->status, L.images.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+  HIP_RET(hipStreamSynchronize(L.stream));
+  HIP_RET(hipEventElapsedTime(&L.stage_ms[1], L.ev[0], L.ev[1]));
   if (L.h_flags->status) {
     set_images_status_error(L.h_flags->status);
     return GPD_ERR_CAPACITY;

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "context.h"
+#include "buffers.h"
 #include "balance_model.h"
 #include "sis_model.h"
 
@@ -39,7 +40,7 @@ int job_begin(gpd_hip_ctx *ctx, Lane &L, Job &J) {
   J.live = false;
   J.num_sets = J.num_candidates = J.num_hands = 0;
   if (J.S == 0) return GPD_OK;
-  HIP_TRY(hipEventRecord(L.ev[0], L.stream));
+  HIP_RET(hipEventRecord(L.ev[0], L.stream));
   int rc;
   {
     StageRange r("gpd:search (neighbourhoods, frames, hand evaluation, workspace filter)");
@@ -47,13 +48,13 @@ int job_begin(gpd_hip_ctx *ctx, Lane &L, Job &J) {
                     J.resident ? &J.gather : nullptr);
   }
   if (rc) return rc;
-  HIP_TRY(hipEventRecord(L.ev[1], L.stream));
+  HIP_RET(hipEventRecord(L.ev[1], L.stream));
   {
     StageRange r("gpd:plan (hand sets, candidate list, shadow LCG offsets)");
     rc = plan_build(ctx->params, L.cloud, L.search, L.plan, L.stream);
   }
   if (rc) return rc;
-  HIP_TRY(hipEventRecord(L.ev_plan, L.stream));
+  HIP_RET(hipEventRecord(L.ev_plan, L.stream));
   J.live = true;
   return GPD_OK;
 }
@@ -63,7 +64,7 @@ int job_begin(gpd_hip_ctx *ctx, Lane &L, Job &J) {
 int job_wait_plan(gpd_hip_ctx *ctx, Lane &L, Job &J) {
   if (!J.live) return GPD_OK;
   J.live = false;  // set again once everything is enqueued
-  HIP_TRY(hipEventSynchronize(L.ev_plan));  // not the stream: in a batch the next cloud's search is already queued behind
+  HIP_RET(hipEventSynchronize(L.ev_plan));  // not the stream: in a batch the next cloud's search is already queued behind
   J.t_plan_ms = now_ms();
   if (L.plan.h_summary->worst_found > L.search.nn_cap) {
     // a neighbourhood overflowed the list capacity of the search kernel: once more with the large lists
@@ -81,7 +82,7 @@ int job_wait_plan(gpd_hip_ctx *ctx, Lane &L, Job &J) {
     rc = job_begin(ctx, L, J);
     if (rc) return rc;
     J.live = false;
-    HIP_TRY(hipStreamSynchronize(L.stream));
+    HIP_RET(hipStreamSynchronize(L.stream));
   }
   J.lcg_draws = L.plan.h_summary->total_draws;
   J.live = true;
@@ -113,7 +114,7 @@ int job_enqueue(gpd_hip_ctx *ctx, Lane &L, Job &J) {
     return GPD_ERR_INVALID;
   }
   (void)hipEventElapsedTime(&L.stage_ms[0], L.ev[0], L.ev[1]);  // here: the next job on this lane records them again
-  HIP_TRY(hipEventRecord(L.ev[4], L.stream));
+  HIP_RET(hipEventRecord(L.ev[4], L.stream));
   L.images.side_stream = !ctx->in_batch;
   L.images.lcg_base = J.lcg_base;
   int rc;
@@ -122,19 +123,19 @@ int job_enqueue(gpd_hip_ctx *ctx, Lane &L, Job &J) {
     rc = images_run(ctx->params, L.cloud, L.search, L.plan, L.images, L.stream);
   }
   if (rc) return rc;
-  HIP_TRY(hipEventRecord(L.ev[2], L.stream));
+  HIP_RET(hipEventRecord(L.ev[2], L.stream));
   if (n > 0) {
     rc = reserve_scores(L, n);
     if (rc) return rc;
     {
       StageRange r("gpd:lenet (conv1, conv2, ip1, ip2)");
-      HIP_TRY(lenet_forward(ctx->lenet, L.lenet_scratch, L.images.d_images, n, L.d_scores, L.stream));
+      HIP_RET(lenet_forward(ctx->lenet, L.lenet_scratch, L.images.d_images, n, L.d_scores, L.stream));
     }
-    HIP_TRY(hipMemcpyAsync(&L.h_flags->lenet, L.lenet_scratch.c1_stats + 2, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+    HIP_RET(hipMemcpyAsync(&L.h_flags->lenet, L.lenet_scratch.c1_stats + 2, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
   } else {
     L.h_flags->lenet = 0;
   }
-  HIP_TRY(hipEventRecord(L.ev[3], L.stream));
+  HIP_RET(hipEventRecord(L.ev[3], L.stream));
   rc = reserve_out(L, (size_t)J.out_records, k ? (size_t)n * sizeof(float) : 0);
   if (rc) return rc;
   L.h_flags->tie = 0;
@@ -153,12 +154,12 @@ int job_enqueue(gpd_hip_ctx *ctx, Lane &L, Job &J) {
       if (rc) return rc;
       rc = gather_records(L.d_all, L.d_sel, k, L.d_out, L.stream);
       if (rc) return rc;
-      HIP_TRY(hipMemcpyAsync(&L.h_flags->tie, L.d_sel + k, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+      HIP_RET(hipMemcpyAsync(&L.h_flags->tie, L.d_sel + k, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
     } else {
       L.h_flags->tie = 2;  // more winners than the device selection sorts: std::partial_sort on the host (job_end), no limit
     }
     // the scores (4 bytes per candidate) ride along: equal scores are settled with std::partial_sort on the host
-    HIP_TRY(hipMemcpyAsync(L.h_out + L.d_out_cap * sizeof(gpd_hand), L.d_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost,
+    HIP_RET(hipMemcpyAsync(L.h_out + L.d_out_cap * sizeof(gpd_hand), L.d_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost,
                            L.stream));
   } else {
     rc = plan_emit_hands(ctx->params, L.search, L.plan, L.d_scores, L.d_out, true, L.stream);
@@ -173,14 +174,14 @@ int job_enqueue(gpd_hip_ctx *ctx, Lane &L, Job &J) {
     for (int c = 0; c < J.chunks; c++) {
       const size_t r0 = std::min((size_t)c * per, (size_t)J.out_records), r1 = std::min(r0 + per, (size_t)J.out_records);
       if (r1 > r0)
-        HIP_TRY(hipMemcpyAsync(L.h_out + r0 * sizeof(gpd_hand), L.d_out + r0, (r1 - r0) * sizeof(gpd_hand), hipMemcpyDeviceToHost, L.stream));
-      HIP_TRY(hipEventRecord(L.ev_chunk[c], L.stream));
+        HIP_RET(hipMemcpyAsync(L.h_out + r0 * sizeof(gpd_hand), L.d_out + r0, (r1 - r0) * sizeof(gpd_hand), hipMemcpyDeviceToHost, L.stream));
+      HIP_RET(hipEventRecord(L.ev_chunk[c], L.stream));
     }
   } else if (J.out_records > 0) {
-    HIP_TRY(hipMemcpyAsync(L.h_out, L.d_out, (size_t)J.out_records * sizeof(gpd_hand), hipMemcpyDeviceToHost, L.stream));
+    HIP_RET(hipMemcpyAsync(L.h_out, L.d_out, (size_t)J.out_records * sizeof(gpd_hand), hipMemcpyDeviceToHost, L.stream));
   }
-  HIP_TRY(hipMemcpyAsync(&L.h_flags->status, L.images.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
-  HIP_TRY(hipEventRecord(L.ev_done, L.stream));
+  HIP_RET(hipMemcpyAsync(&L.h_flags->status, L.images.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+  HIP_RET(hipEventRecord(L.ev_done, L.stream));
   J.live = true;
   return GPD_OK;
 }
@@ -200,14 +201,14 @@ int job_end(gpd_hip_ctx *ctx, Lane &L, Job &J) {
     // (should a flag below turn out set, the caller's buffer holds records of a failed call: its content is unspecified then)
     const size_t per = ((size_t)J.out_records + J.chunks - 1) / J.chunks;
     for (int c = 0; c < J.chunks; c++) {
-      HIP_TRY(hipEventSynchronize(L.ev_chunk[c]));
+      HIP_RET(hipEventSynchronize(L.ev_chunk[c]));
       const auto t0 = std::chrono::steady_clock::now();
       const size_t r0 = std::min((size_t)c * per, (size_t)J.out_records), r1 = std::min(r0 + per, (size_t)J.out_records);
       if (r1 > r0) std::memcpy(J.hands + r0, L.h_out + r0 * sizeof(gpd_hand), (r1 - r0) * sizeof(gpd_hand));
       early_copy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
   }
-  HIP_TRY(hipEventSynchronize(L.ev_done));
+  HIP_RET(hipEventSynchronize(L.ev_done));
   const auto t_done = std::chrono::steady_clock::now();
   (void)hipEventElapsedTime(&L.stage_ms[1], L.ev[4], L.ev[2]);
   (void)hipEventElapsedTime(&L.stage_ms[2], L.ev[2], L.ev[3]);
@@ -231,11 +232,11 @@ int job_end(gpd_hip_ctx *ctx, Lane &L, Job &J) {
     std::partial_sort(v.begin(), v.begin() + k, v.end(), score_greater);
     std::vector<int32_t> sel((size_t)k);
     for (int i = 0; i < k; i++) sel[i] = v[i].second;
-    HIP_TRY(hipMemcpyAsync(L.d_sel, sel.data(), (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, L.stream));
+    HIP_RET(hipMemcpyAsync(L.d_sel, sel.data(), (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, L.stream));
     int rc = gather_records(L.d_all, L.d_sel, k, L.d_out, L.stream);  // not from L.search / L.plan: see job_middle
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(L.h_out, L.d_out, (size_t)k * sizeof(gpd_hand), hipMemcpyDeviceToHost, L.stream));
-    HIP_TRY(hipStreamSynchronize(L.stream));
+    HIP_RET(hipMemcpyAsync(L.h_out, L.d_out, (size_t)k * sizeof(gpd_hand), hipMemcpyDeviceToHost, L.stream));
+    HIP_RET(hipStreamSynchronize(L.stream));
   }
   if (J.out_records > 0 && !J.chunks) std::memcpy(J.hands, L.h_out, (size_t)J.out_records * sizeof(gpd_hand));
   J.copy_ms = early_copy_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_done).count();
@@ -277,7 +278,7 @@ int label_view_run(gpd_hip_ctx *ctx, gpd_label_view_job *job, const char *who, c
   }
   int rc = check_samples(who, j.sample_indices, nullptr, (int)total_samples, L.cloud.num_points);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   rc = label_init(ls);
   if (rc) return rc;
   if (j.round_counts) std::memset(j.round_counts, 0, (size_t)j.max_rounds * 2 * sizeof(int32_t));
@@ -308,7 +309,7 @@ int label_view_run(gpd_hip_ctx *ctx, gpd_label_view_job *job, const char *who, c
     j.stage_ms[0] += ms;
     int round_pos = 0;
     if (n > 0) {
-      HIP_TRY(hipEventRecord(L.ev[4], L.stream));
+      HIP_RET(hipEventRecord(L.ev[4], L.stream));
       L.images.side_stream = true;
       L.images.lcg_base = 0;  // every round is an ordinary call: its shadow stream starts at 0
       {
@@ -316,12 +317,12 @@ int label_view_run(gpd_hip_ctx *ctx, gpd_label_view_job *job, const char *who, c
         rc = images_run(p, L.cloud, L.search, L.plan, L.images, L.stream);
       }
       if (rc) return rc;
-      HIP_TRY(hipEventRecord(L.ev[2], L.stream));
+      HIP_RET(hipEventRecord(L.ev[2], L.stream));
       // the round joins the view's accumulator: images in the caller's layout, records as detect_select(0) returns them
-      HIP_TRY(hipEventRecord(ls.ev[0], L.stream));
+      HIP_RET(hipEventRecord(ls.ev[0], L.stream));
       rc = label_reserve(ls, acc + (size_t)n, acc, image_bytes, (size_t)n, L.stream);
       if (rc) return rc;
-      HIP_TRY(planar_to_hwc(L.images.d_images, ls.d_images + acc * image_bytes, n, C, L.stream));
+      HIP_RET(planar_to_hwc(L.images.d_images, ls.d_images + acc * image_bytes, n, C, L.stream));
       rc = plan_emit_hands(p, L.search, L.plan, nullptr, ls.d_hands + acc, true, L.stream);
       if (rc) return rc;
       // evalGroundTruth (grasp_detector.cpp:522-526) on the records where they are
@@ -333,8 +334,8 @@ int label_view_run(gpd_hip_ctx *ctx, gpd_label_view_job *job, const char *who, c
       }
       if (img_status) set_images_status_error(img_status);
       if (rc) return rc;
-      HIP_TRY(hipEventRecord(ls.ev[1], L.stream));
-      HIP_TRY(hipEventSynchronize(ls.ev[1]));
+      HIP_RET(hipEventRecord(ls.ev[1], L.stream));
+      HIP_RET(hipEventSynchronize(ls.ev[1]));
       (void)hipEventElapsedTime(&ms, L.ev[4], L.ev[2]);
       j.stage_ms[1] += ms;
       (void)hipEventElapsedTime(&ms, ls.ev[0], ls.ev[1]);
@@ -365,30 +366,23 @@ int label_view_run(gpd_hip_ctx *ctx, gpd_label_view_job *job, const char *who, c
   size_t off[4];
   const size_t out_bytes = sink ? 0 : label_out_layout(k, image_bytes, off);  // what the kept set takes in the pinned block
   if (k + all > 0) {
-    if (out_bytes + all > ls.h_out_bytes) {
-      note_alloc(__func__);
-      if (ls.h_out) (void)hipHostFree(ls.h_out);
-      ls.h_out = nullptr;
-      ls.h_out_bytes = 0;
-      const size_t cap = out_bytes + all + (out_bytes + all) / 8;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ls.h_out), cap, 0));
-      ls.h_out_bytes = cap;
-    }
-    HIP_TRY(hipEventRecord(ls.ev[2], L.stream));
+    rc = grow_pinned(ls.h_out, ls.h_out_bytes, out_bytes + all, slack_cap(out_bytes + all, 8), __func__);
+    if (rc) return rc;
+    HIP_RET(hipEventRecord(ls.ev[2], L.stream));
     if (sink && k > 0) {  // the kept set stays on the device: straight behind what the sink holds
       uint8_t *to_images = nullptr, *to_labels = nullptr;
       rc = sink->place(sink->self, k, &to_images, &to_labels);
       if (rc) return rc;
-      HIP_TRY(hipSetDevice(ctx->device));
+      HIP_RET(hipSetDevice(ctx->device));
       rc = label_select_gather(ls, (int)acc, end, L.stream, to_images, to_labels);
     } else {
       rc = label_select_gather(ls, (int)acc, end, L.stream);
     }
     if (rc) return rc;
-    if (k > 0 && !sink) HIP_TRY(hipMemcpyAsync(ls.h_out, ls.d_out, out_bytes, hipMemcpyDeviceToHost, L.stream));  // the kept set: one copy
-    if (all > 0) HIP_TRY(hipMemcpyAsync(ls.h_out + out_bytes, ls.d_labels, all, hipMemcpyDeviceToHost, L.stream));
-    HIP_TRY(hipEventRecord(ls.ev[3], L.stream));
-    HIP_TRY(hipEventSynchronize(ls.ev[3]));
+    if (k > 0 && !sink) HIP_RET(hipMemcpyAsync(ls.h_out, ls.d_out, out_bytes, hipMemcpyDeviceToHost, L.stream));  // the kept set: one copy
+    if (all > 0) HIP_RET(hipMemcpyAsync(ls.h_out + out_bytes, ls.d_labels, all, hipMemcpyDeviceToHost, L.stream));
+    HIP_RET(hipEventRecord(ls.ev[3], L.stream));
+    HIP_RET(hipEventSynchronize(ls.ev[3]));
     (void)hipEventElapsedTime(&j.stage_ms[3], ls.ev[2], ls.ev[3]);
     d2h += (long long)(k > 0 ? out_bytes : 0) + (long long)all;
     if (k > 0 && !sink) {
@@ -430,7 +424,7 @@ static int detect_any(gpd_hip_ctx *ctx, const char *who, const int32_t *sample_i
   if (num_hands) *num_hands = 0;
   int rc = check_samples(who, sample_indices, sample_xyz, num_samples, L.cloud.num_points);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   // GPD_DETECT_TIMING=1: wall time of the three steps, to stderr
   const bool timing = prof_env("GPD_DETECT_TIMING") != nullptr;
   const double t0 = now_ms();
@@ -529,7 +523,7 @@ int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job) {
   }
   int rc = check_samples("gpd_hip_detect_sis", j.sample_indices, nullptr, j.num_init_samples, L.cloud.num_points);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   rc = sis_init(ss);
   if (rc) return rc;
   const gpd_params &p = ctx->params;
@@ -552,8 +546,8 @@ int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job) {
                          rounds ? (size_t)block : 0);
   if (rc) return rc;
   if (rounds && j.num_init_samples > 0)
-    HIP_TRY(hipMemcpyAsync(ss.d_uniform, j.sample_indices, (size_t)j.num_init_samples * sizeof(int32_t), hipMemcpyHostToDevice, L.stream));
-  HIP_TRY(hipMemsetAsync(ss.d_meta, 0, sizeof(SisMeta), L.stream));
+    HIP_RET(hipMemcpyAsync(ss.d_uniform, j.sample_indices, (size_t)j.num_init_samples * sizeof(int32_t), hipMemcpyHostToDevice, L.stream));
+  HIP_RET(hipMemsetAsync(ss.d_meta, 0, sizeof(SisMeta), L.stream));
   *ss.h_meta = SisMeta();
   if (j.round_counts) std::memset(j.round_counts, 0, (size_t)(1 + j.num_iterations) * 4 * sizeof(int32_t));
   ss.grows = 0;
@@ -585,7 +579,7 @@ int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job) {
     sample::Stream sg(sis::stream_seed(j.seed, r < 0 ? 0 : r, 0)), su(sis::stream_seed(j.seed, r < 0 ? 0 : r, 1));
     for (bool first = true;; first = false) {  // the draw and the search; redone from the draw when the proposal blocks fell short
       if (pass > 0) {
-        if (first) HIP_TRY(hipMemsetAsync(ss.d_meta, 0, 4 * sizeof(int32_t), L.stream));  // the round's draw counts
+        if (first) HIP_RET(hipMemsetAsync(ss.d_meta, 0, 4 * sizeof(int32_t), L.stream));  // the round's draw counts
         const SisMeta left = first ? SisMeta() : *ss.h_meta;
         if (!first) {
           if (left.used_g > 0) rate_g = (double)left.acc_g / left.used_g;
@@ -607,10 +601,10 @@ int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job) {
         uint64_t *hu = reinterpret_cast<uint64_t *>(ss.h_block + ss.cap_block * sizeof(sis::Proposal));
         for (int i = 0; i < n_g; i++) hg[i] = sis::next_gauss(sg, j.sigma);
         for (int i = 0; i < n_u; i++) hu[i] = su.next();
-        HIP_TRY(hipEventRecord(ss.ev[0], L.stream));
+        HIP_RET(hipEventRecord(ss.ev[0], L.stream));
         rc = sis_draw(ss, L.cloud, centres, n_g, n_u, j.num_init_samples, j.workspace, j.sampling_method, num_gauss, num_rand, L.stream);
         if (rc) return rc;
-        HIP_TRY(hipEventRecord(ss.ev[1], L.stream));
+        HIP_RET(hipEventRecord(ss.ev[1], L.stream));
       }
       rc = job_begin(ctx, L, J);
       if (rc) return rc;
@@ -642,7 +636,7 @@ int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job) {
     const PlanSummary sm = *L.plan.h_summary;
     const int n = sm.num_candidates;
     if (n > 0) {
-      HIP_TRY(hipEventRecord(L.ev[4], L.stream));
+      HIP_RET(hipEventRecord(L.ev[4], L.stream));
       L.images.side_stream = true;
       L.images.lcg_base = lcg;
       {
@@ -650,22 +644,22 @@ int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job) {
         rc = images_run(p, L.cloud, L.search, L.plan, L.images, L.stream);
       }
       if (rc) return rc;
-      HIP_TRY(hipEventRecord(L.ev[2], L.stream));
+      HIP_RET(hipEventRecord(L.ev[2], L.stream));
       // the round joins the accumulators: images as the LeNet reads them, records as detect_select(0) returns them
       rc = sis_reserve(ss, acc + (size_t)n, acc, (size_t)centres + (size_t)sm.live_sets, (size_t)centres, image_bytes, L.stream);
       if (rc) return rc;
-      HIP_TRY(hipMemcpyAsync(ss.d_images + acc * image_bytes, L.images.d_images, (size_t)n * image_bytes, hipMemcpyDeviceToDevice, L.stream));
+      HIP_RET(hipMemcpyAsync(ss.d_images + acc * image_bytes, L.images.d_images, (size_t)n * image_bytes, hipMemcpyDeviceToDevice, L.stream));
       rc = plan_emit_hands(p, L.search, L.plan, nullptr, ss.d_hands + acc, true, L.stream);
       if (rc) return rc;
       rc = sis_accumulate(ss, acc, n, centres, L.images.d_status, L.stream);
       if (rc) return rc;
-      HIP_TRY(hipEventRecord(ss.ev[2], L.stream));
+      HIP_RET(hipEventRecord(ss.ev[2], L.stream));
       img_pending = true;
     } else {
       L.images.num_candidates = 0;  // no candidate list of this round is resident
     }
     if (pass > 0 && j.samples_out)
-      HIP_TRY(hipMemcpyAsync(ss.d_samples + (size_t)r * j.num_samples * 3, ss.d_round_xyz, (size_t)j.num_samples * 3 * sizeof(double),
+      HIP_RET(hipMemcpyAsync(ss.d_samples + (size_t)r * j.num_samples * 3, ss.d_round_xyz, (size_t)j.num_samples * 3 * sizeof(double),
                              hipMemcpyDeviceToDevice, L.stream));
     if (j.round_counts) {
       int32_t *rcnt = j.round_counts + 4 * (size_t)pass;
@@ -685,22 +679,22 @@ int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job) {
   const int rounds_run = pass > 0 ? pass - 1 : 0;
   const int N = (int)acc;
   // classify everything at once (:164-167), cut at min_score, cluster (:175-181)
-  HIP_TRY(hipEventRecord(ss.ev[3], L.stream));
+  HIP_RET(hipEventRecord(ss.ev[3], L.stream));
   L.h_flags->lenet = 0;
   if (N > 0) {
     rc = reserve_scores(L, N);
     if (rc) return rc;
     {
       StageRange r_("gpd:lenet (detect_sis: every accumulated image)");
-      HIP_TRY(lenet_forward(ctx->lenet, L.lenet_scratch, ss.d_images, N, L.d_scores, L.stream));
+      HIP_RET(lenet_forward(ctx->lenet, L.lenet_scratch, ss.d_images, N, L.d_scores, L.stream));
     }
-    HIP_TRY(hipMemcpyAsync(&L.h_flags->lenet, L.lenet_scratch.c1_stats + 2, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+    HIP_RET(hipMemcpyAsync(&L.h_flags->lenet, L.lenet_scratch.c1_stats + 2, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
     rc = sis_select(ss, L.d_scores, N, j.min_score, L.stream);
     if (rc) return rc;
   }
-  HIP_TRY(hipMemcpyAsync(ss.h_meta, ss.d_meta, sizeof(SisMeta), hipMemcpyDeviceToHost, L.stream));
-  HIP_TRY(hipEventRecord(ss.ev[5], L.stream));
-  HIP_TRY(hipEventSynchronize(ss.ev[5]));
+  HIP_RET(hipMemcpyAsync(ss.h_meta, ss.d_meta, sizeof(SisMeta), hipMemcpyDeviceToHost, L.stream));
+  HIP_RET(hipEventRecord(ss.ev[5], L.stream));
+  HIP_RET(hipEventSynchronize(ss.ev[5]));
   d2h += (long long)sizeof(SisMeta) + (N > 0 ? 4 : 0);
   book_images();
   if (ss.h_meta->img_status) {
@@ -722,8 +716,8 @@ int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job) {
     StageRange r_("gpd:find_clusters (detect_sis)");
     rc = cluster_run_resident(ctx->cluster, ss.d_keep, k, j.min_inliers, j.remove_inliers, L.stream);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(&ss.h_meta->kept, ctx->cluster.d_num, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
-    HIP_TRY(hipStreamSynchronize(L.stream));
+    HIP_RET(hipMemcpyAsync(&ss.h_meta->kept, ctx->cluster.d_num, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+    HIP_RET(hipStreamSynchronize(L.stream));
     d2h += 4;
     k = ss.h_meta->kept;
     d_res = ctx->cluster.d_out;
@@ -744,21 +738,14 @@ int gpd_hip_detect_sis(gpd_hip_ctx *ctx, gpd_sis_job *job) {
   const size_t b_smp = j.samples_out ? (size_t)rounds_run * j.num_samples * 3 * sizeof(double) : 0;
   const size_t b_cen = j.centres_out ? (size_t)centres * 3 * sizeof(double) : 0;
   if (b_rec + b_smp + b_cen > 0) {
-    if (b_rec + b_smp + b_cen > ss.h_out_bytes) {
-      note_alloc(__func__);
-      if (ss.h_out) (void)hipHostFree(ss.h_out);
-      ss.h_out = nullptr;
-      ss.h_out_bytes = 0;
-      const size_t cap = b_rec + b_smp + b_cen + (b_rec + b_smp + b_cen) / 8;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ss.h_out), cap, 0));
-      ss.h_out_bytes = cap;
-    }
-    if (b_rec) HIP_TRY(hipMemcpyAsync(ss.h_out, d_res, b_rec, hipMemcpyDeviceToHost, L.stream));  // the result: one copy
-    if (b_smp) HIP_TRY(hipMemcpyAsync(ss.h_out + b_rec, ss.d_samples, b_smp, hipMemcpyDeviceToHost, L.stream));
-    if (b_cen) HIP_TRY(hipMemcpyAsync(ss.h_out + b_rec + b_smp, ss.d_centres, b_cen, hipMemcpyDeviceToHost, L.stream));
+    rc = grow_pinned(ss.h_out, ss.h_out_bytes, b_rec + b_smp + b_cen, slack_cap(b_rec + b_smp + b_cen, 8), __func__);
+    if (rc) return rc;
+    if (b_rec) HIP_RET(hipMemcpyAsync(ss.h_out, d_res, b_rec, hipMemcpyDeviceToHost, L.stream));  // the result: one copy
+    if (b_smp) HIP_RET(hipMemcpyAsync(ss.h_out + b_rec, ss.d_samples, b_smp, hipMemcpyDeviceToHost, L.stream));
+    if (b_cen) HIP_RET(hipMemcpyAsync(ss.h_out + b_rec + b_smp, ss.d_centres, b_cen, hipMemcpyDeviceToHost, L.stream));
   }
-  HIP_TRY(hipEventRecord(ss.ev[4], L.stream));
-  HIP_TRY(hipEventSynchronize(ss.ev[4]));
+  HIP_RET(hipEventRecord(ss.ev[4], L.stream));
+  HIP_RET(hipEventSynchronize(ss.ev[4]));
   (void)hipEventElapsedTime(&j.stage_ms[3], ss.ev[3], ss.ev[4]);
   d2h += (long long)(b_rec + b_smp + b_cen);
   if (b_rec) std::memcpy(j.hands, ss.h_out, b_rec);

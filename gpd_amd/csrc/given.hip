@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "context.h"
+#include "buffers.h"
 #include "given_model.h"
 
 namespace gpd {
@@ -69,7 +70,7 @@ static int given_run(gpd_hip_ctx *ctx, const char *who, const gpd_hand *hands, i
   }
   *num_candidates = 0;
   if (lcg_draws) *lcg_draws = 0;
-  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_RET(hipSetDevice(ctx->device));
   SearchState &s = L.search;
   const gpd_params &p = ctx->params;
   const int slots = p.num_hand_axes * p.num_orientations;
@@ -79,7 +80,7 @@ static int given_run(gpd_hip_ctx *ctx, const char *who, const gpd_hand *hands, i
   std::vector<double> xyz((size_t)num_sets * 3);
   for (int i = 0; i < num_sets; i++)
     for (int r = 0; r < 3; r++) xyz[3 * (size_t)i + r] = hands[(size_t)i * slots].sample[r];
-  HIP_TRY(hipEventRecord(L.ev[0], L.stream));
+  HIP_RET(hipEventRecord(L.ev[0], L.stream));
   int rc = given_lists_run(p, L.cloud, s, xyz.data(), num_sets, L.stream);
   if (rc) return rc;
   rc = given_ingest(s, hands, num_sets, slots, L.stream);
@@ -88,32 +89,32 @@ static int given_run(gpd_hip_ctx *ctx, const char *who, const gpd_hand *hands, i
   rc = plan_build(p, L.cloud, s, L.plan, L.stream);
   s.num_samples = 0;         // ... these lists have no search behind them (gpd_hip_images, gpd_hip_replay refuse)
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(L.stream));  // `hands` is pageable: its copy has left it by now as well
+  HIP_RET(hipStreamSynchronize(L.stream));  // `hands` is pageable: its copy has left it by now as well
   L.images.lcg_base = lcg_base;
   rc = images_run(p, L.cloud, s, L.plan, L.images, L.stream);
   if (rc) return rc;
-  HIP_TRY(hipEventRecord(L.ev[1], L.stream));
+  HIP_RET(hipEventRecord(L.ev[1], L.stream));
   const int n = L.images.num_candidates;
   if (cand_index && n > 0)
-    HIP_TRY(hipMemcpyAsync(cand_index, L.plan.d_cand_out, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+    HIP_RET(hipMemcpyAsync(cand_index, L.plan.d_cand_out, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
   if (images && n > 0) {
     const size_t bytes = (size_t)L.images.capacity * kPix * p.image_num_channels;
-    if (!L.images.d_images_hwc) HIP_TRY(hipMalloc(&L.images.d_images_hwc, bytes));
-    HIP_TRY(planar_to_hwc(L.images.d_images, L.images.d_images_hwc, n, p.image_num_channels, L.stream));
-    HIP_TRY(hipMemcpyAsync(images, L.images.d_images_hwc, (size_t)n * kPix * p.image_num_channels, hipMemcpyDeviceToHost, L.stream));
+    if (!L.images.d_images_hwc) HIP_RET(device_alloc(L.images.d_images_hwc, bytes));
+    HIP_RET(planar_to_hwc(L.images.d_images, L.images.d_images_hwc, n, p.image_num_channels, L.stream));
+    HIP_RET(hipMemcpyAsync(images, L.images.d_images_hwc, (size_t)n * kPix * p.image_num_channels, hipMemcpyDeviceToHost, L.stream));
   }
   if (scores && n > 0) {
     rc = reserve_scores(L, n);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(L.ev[2], L.stream));
-    HIP_TRY(lenet_forward(ctx->lenet, L.lenet_scratch, L.images.d_images, n, L.d_scores, L.stream));
-    HIP_TRY(hipEventRecord(L.ev[3], L.stream));
-    HIP_TRY(hipMemcpyAsync(scores, L.d_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, L.stream));
+    HIP_RET(hipEventRecord(L.ev[2], L.stream));
+    HIP_RET(lenet_forward(ctx->lenet, L.lenet_scratch, L.images.d_images, n, L.d_scores, L.stream));
+    HIP_RET(hipEventRecord(L.ev[3], L.stream));
+    HIP_RET(hipMemcpyAsync(scores, L.d_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, L.stream));
   }
-  HIP_TRY(hipMemcpyAsync(&L.h_flags->status, L.images.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
-  HIP_TRY(hipStreamSynchronize(L.stream));
-  HIP_TRY(hipEventElapsedTime(&L.stage_ms[1], L.ev[0], L.ev[1]));
-  if (scores && n > 0) HIP_TRY(hipEventElapsedTime(&L.stage_ms[2], L.ev[2], L.ev[3]));
+  HIP_RET(hipMemcpyAsync(&L.h_flags->status, L.images.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+  HIP_RET(hipStreamSynchronize(L.stream));
+  HIP_RET(hipEventElapsedTime(&L.stage_ms[1], L.ev[0], L.ev[1]));
+  if (scores && n > 0) HIP_RET(hipEventElapsedTime(&L.stage_ms[2], L.ev[2], L.ev[3]));
   if (L.h_flags->status) {
     set_images_status_error(L.h_flags->status);
     return GPD_ERR_CAPACITY;

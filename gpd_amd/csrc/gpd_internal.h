@@ -85,9 +85,15 @@ void set_error(const char *fmt, ...);
   } while (0)
 // the device and the first lane's stream of a context (context.hip): what a trainer (train.hip) runs on
 void ctx_device_stream(gpd_hip_ctx *ctx, int *device, hipStream_t *stream);
-// every growth of a device / pinned buffer (hipFree + hipMalloc: a device stall) is counted per host thread; the batch
-// entry reports the count per cloud (gpd_detect_job::allocs) so that a pass that was supposed to run on pre-sized lanes
-// can be seen to have done so
+// Growths of device / pinned buffers (hipFree + hipMalloc: a device stall) are counted per host thread; the batch entry
+// reports the count per cloud (gpd_detect_job::allocs) so that a pass that was supposed to run on pre-sized lanes can be
+// seen to have done so.  The rule of a growth has one text, buffers.h; its helpers book on the `who` they are handed, and
+// a group site books once itself.  BOOKED: everything a lane, a cloud, a search, a plan, the image and LeNet buffers, the
+// normals, plane, refine, label and SIS states grow by size.  NOT booked (as found; the helpers take a null `who`, these
+// sites use the typed allocate / release alone): gpd_hip_score's staging pair (d_img_in, d_img_planar), the HWC copy of a
+// download (d_images_hwc), plan_build's given-set tables, cluster_reserve, the LeNet weight tables, everything of a
+// trainer and a trainer group (their pools included), the replay pipe's second buffer, and the fixed-size words a state
+// allocates once (h_flags, d_status / d_pts_scratch, the d_meta / h_meta pairs, d_nan / h_nan).  DESIGN §3 has the list.
 void note_alloc(const char *where);
 
 // roctx range around a stage of the path (host side: what the stage enqueues); `rocprofv3 --marker-trace --kernel-trace`

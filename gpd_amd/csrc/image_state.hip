@@ -7,14 +7,13 @@
 #include <vector>
 
 #include "gpd_internal.h"
+#include "buffers.h"
 #include "image_model.h"
 
 namespace gpd {
 
 void images_free(ImageState &im) {
-  void *ptrs[] = {im.d_images, im.d_images_hwc, im.d_status, im.d_set_bits, im.d_overflow, im.d_overflow2, im.d_pts_overflow, im.d_pts_scratch, im.d_huge_scratch};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
+  device_release(im.d_images, im.d_images_hwc, im.d_status, im.d_set_bits, im.d_overflow, im.d_overflow2, im.d_pts_overflow, im.d_pts_scratch, im.d_huge_scratch);
   if (im.ev_fork) (void)hipEventDestroy(im.ev_fork);
   if (im.ev_join) (void)hipEventDestroy(im.ev_join);
   if (im.aux) (void)hipStreamDestroy(im.aux);
@@ -26,26 +25,19 @@ void images_free(ImageState &im) {
 int images_reserve(const gpd_params &p, ImageState &im, int n, int shadow_sets) {
   const int C = p.image_num_channels;
   if (!im.d_status) {
-    HIP_RET(hipMalloc(&im.d_status, 4 * sizeof(int32_t)));  // [0] flags, [1..3] the counters of the three overflow lists: ONE memset per launch
+    HIP_RET(device_alloc(im.d_status, 4));  // [0] flags, [1..3] the counters of the three overflow lists: ONE memset per launch
     HIP_RET(hipMemset(im.d_status, 0, 4 * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&im.d_pts_scratch, (size_t)LGRID * PTS_SCRATCH_BYTES));
+    HIP_RET(device_alloc(im.d_pts_scratch, (size_t)LGRID * PTS_SCRATCH_BYTES));
   }
   if (n > im.capacity) {
     note_alloc(__func__);
-    void *ptrs[] = {im.d_images, im.d_images_hwc, im.d_overflow, im.d_overflow2, im.d_pts_overflow};
-    for (void *q : ptrs)
-      if (q) (void)hipFree(q);
-    im.d_overflow = nullptr;
-    im.d_overflow2 = nullptr;
-    im.d_pts_overflow = nullptr;
-    im.d_images = nullptr;
-    im.d_images_hwc = nullptr;
+    device_release(im.d_images, im.d_images_hwc, im.d_overflow, im.d_overflow2, im.d_pts_overflow);
     im.capacity = 0;
-    const int cap = n + n / 4;  // slack: the clouds of a batch differ a little
-    HIP_RET(hipMalloc(&im.d_images, (size_t)cap * kPix * C));
-    HIP_RET(hipMalloc(&im.d_overflow, (size_t)cap * sizeof(int32_t)));  // list (its counter: d_status[1])
-    HIP_RET(hipMalloc(&im.d_overflow2, (size_t)cap * sizeof(int32_t)));  // ... of the large instantiation, for the general kernel
-    HIP_RET(hipMalloc(&im.d_pts_overflow, (size_t)cap * sizeof(int32_t)));
+    const int cap = slack_cap(n, 4);  // slack: the clouds of a batch differ a little
+    HIP_RET(device_alloc(im.d_images, (size_t)cap * kPix * C));
+    HIP_RET(device_alloc(im.d_overflow, (size_t)cap));  // list (its counter: d_status[1])
+    HIP_RET(device_alloc(im.d_overflow2, (size_t)cap));  // ... of the large instantiation, for the general kernel
+    HIP_RET(device_alloc(im.d_pts_overflow, (size_t)cap));
     im.capacity = cap;
   }
   {
@@ -65,13 +57,12 @@ int images_reserve(const gpd_params &p, ImageState &im, int n, int shadow_sets) 
   const size_t setwords = (size_t)(((long long)im.set_sd * im.set_sd * im.set_sd + 31) / 32);
   if (C == 15 && (shadow_sets > im.cap_shadow_sets || setwords > im.cap_setwords)) {
     note_alloc(__func__);
-    if (im.d_set_bits) (void)hipFree(im.d_set_bits);
-    im.d_set_bits = nullptr;
+    device_release(im.d_set_bits);
     im.cap_shadow_sets = 0;
     const int want = shadow_sets > im.cap_shadow_sets ? shadow_sets : im.cap_shadow_sets;
-    const int cap = want + want / 4;
+    const int cap = slack_cap(want, 4);
     const size_t words = setwords > im.cap_setwords ? setwords : im.cap_setwords;
-    HIP_RET(hipMalloc(&im.d_set_bits, (size_t)cap * words * sizeof(uint32_t)));
+    HIP_RET(device_alloc(im.d_set_bits, (size_t)cap * words));
     // defined contents from the first launch on: shadow_set_kernel<0> writes only the rows its candidates' windows cover, and
     // the words around them keep what is there (zero, or an earlier launch's voxels — see the reader's note in shadow_image_kernel)
     HIP_RET(hipMemset(im.d_set_bits, 0, (size_t)cap * words * sizeof(uint32_t)));
@@ -82,7 +73,7 @@ int images_reserve(const gpd_params &p, ImageState &im, int n, int shadow_sets) 
     // the general shadow kernel's list rows, one per workgroup of its persistent grid; the default geometry cannot reach it
     // (its box holds fewer voxel cells than the large instantiation lists)
     note_alloc(__func__);
-    HIP_RET(hipMalloc(&im.d_huge_scratch, (size_t)LGRID * HUGE_SCRATCH_BYTES));
+    HIP_RET(device_alloc(im.d_huge_scratch, (size_t)LGRID * HUGE_SCRATCH_BYTES));
   }
   return GPD_OK;
 }

@@ -4,6 +4,7 @@
 // end of a view is the kept set in one copy.  The ground-truth check itself (reevaluateHypotheses per hand set) is search.hip's
 // label_round; the definition of the selection is balance_model.h.
 #include "gpd_internal.h"
+#include "buffers.h"
 
 #include <algorithm>
 
@@ -96,11 +97,8 @@ __global__ __launch_bounds__(256) void label_gather_sink_kernel(const uint4 *__r
 void label_free(LabelState &ls) {
   cloud_free(ls.gt);
   search_free(ls.gt_search);
-  void *dev[] = {ls.d_images, ls.d_hands, ls.d_labels, ls.d_cand_list, ls.d_meta, ls.d_sel, ls.d_out};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
-  if (ls.h_meta) (void)hipHostFree(ls.h_meta);
-  if (ls.h_out) (void)hipHostFree(ls.h_out);
+  device_release(ls.d_images, ls.d_hands, ls.d_labels, ls.d_cand_list, ls.d_meta, ls.d_sel, ls.d_out);
+  pinned_release(ls.h_meta, ls.h_out);
   for (auto &e : ls.ev)
     if (e) (void)hipEventDestroy(e);
   ls = LabelState();
@@ -108,22 +106,15 @@ void label_free(LabelState &ls) {
 
 int label_init(LabelState &ls) {
   if (ls.d_meta) return GPD_OK;
-  HIP_RET(hipMalloc(&ls.d_meta, 4 * sizeof(int32_t)));
-  HIP_RET(hipHostMalloc(reinterpret_cast<void **>(&ls.h_meta), 4 * sizeof(int32_t), 0));
+  HIP_RET(device_alloc(ls.d_meta, 4));
+  HIP_RET(pinned_alloc(ls.h_meta, 4));
   for (auto &e : ls.ev) HIP_RET(hipEventCreate(&e));
   return GPD_OK;
 }
 
 int label_reserve(LabelState &ls, size_t need, size_t used, size_t image_bytes, size_t round_candidates, hipStream_t stream) {
-  if (round_candidates > ls.cap_round) {
-    note_alloc(__func__);
-    if (ls.d_cand_list) (void)hipFree(ls.d_cand_list);
-    ls.d_cand_list = nullptr;
-    ls.cap_round = 0;
-    const size_t cap = round_candidates + round_candidates / 4;
-    HIP_RET(hipMalloc(&ls.d_cand_list, cap * sizeof(int32_t)));
-    ls.cap_round = cap;
-  }
+  int rc = grow_device(ls.d_cand_list, ls.cap_round, round_candidates, slack_cap(round_candidates, 4), __func__);
+  if (rc) return rc;
   if (image_bytes != ls.image_bytes) {  // (a context has one channel count: only the first call comes here)
     used = 0;
     ls.cap = 0;
@@ -135,24 +126,12 @@ int label_reserve(LabelState &ls, size_t need, size_t used, size_t image_bytes, 
     return GPD_ERR_CAPACITY;
   }
   note_alloc(__func__);
-  const size_t cap = std::min(std::max(need + need / 2, (size_t)64), kLabelAccBudget / per);
-  uint8_t *img = nullptr, *lab = nullptr;
-  gpd_hand *hands = nullptr;
-  HIP_RET(hipMalloc(&img, cap * image_bytes));
-  HIP_RET(hipMalloc(&hands, cap * sizeof(gpd_hand)));
-  HIP_RET(hipMalloc(&lab, cap));
-  if (used > 0) {  // the rounds so far move over
-    HIP_RET(hipMemcpyAsync(img, ls.d_images, used * image_bytes, hipMemcpyDeviceToDevice, stream));
-    HIP_RET(hipMemcpyAsync(hands, ls.d_hands, used * sizeof(gpd_hand), hipMemcpyDeviceToDevice, stream));
-    HIP_RET(hipMemcpyAsync(lab, ls.d_labels, used, hipMemcpyDeviceToDevice, stream));
-    HIP_RET(hipStreamSynchronize(stream));
-  }
-  void *old[] = {ls.d_images, ls.d_hands, ls.d_labels};
-  for (void *p : old)
-    if (p) (void)hipFree(p);
-  ls.d_images = img;
-  ls.d_hands = hands;
-  ls.d_labels = lab;
+  const size_t cap = std::min(std::max(slack_cap(need, 2), (size_t)64), kLabelAccBudget / per);
+  // the rounds so far move over
+  rc = grow_group_keep({group_buffer(ls.d_images, image_bytes, true), group_buffer(ls.d_hands, sizeof(gpd_hand), true),
+                        group_buffer(ls.d_labels, 1, true)},
+                       cap, used, stream);
+  if (rc) return rc;
   ls.cap = cap;
   ls.image_bytes = image_bytes;
   ls.grows++;
@@ -171,23 +150,13 @@ size_t label_out_layout(size_t k, size_t image_bytes, size_t off[4]) {
 int label_select_gather(LabelState &ls, int n, int end, hipStream_t stream, uint8_t *sink_images, uint8_t *sink_labels) {
   const size_t k = (size_t)2 * end;
   if (k == 0) return GPD_OK;
-  if (k > ls.cap_sel) {
-    note_alloc(__func__);
-    if (ls.d_sel) (void)hipFree(ls.d_sel);
-    ls.d_sel = nullptr;
-    ls.cap_sel = 0;
-    HIP_RET(hipMalloc(&ls.d_sel, (k + k / 4) * sizeof(int32_t)));
-    ls.cap_sel = k + k / 4;
-  }
+  int rc = grow_device(ls.d_sel, ls.cap_sel, k, slack_cap(k, 4), __func__);
+  if (rc) return rc;
   size_t off[4];
   const size_t bytes = label_out_layout(k, ls.image_bytes, off);
-  if (!sink_images && bytes > ls.d_out_bytes) {
-    note_alloc(__func__);
-    if (ls.d_out) (void)hipFree(ls.d_out);
-    ls.d_out = nullptr;
-    ls.d_out_bytes = 0;
-    HIP_RET(hipMalloc(&ls.d_out, bytes + bytes / 4));
-    ls.d_out_bytes = bytes + bytes / 4;
+  if (!sink_images) {
+    rc = grow_device(ls.d_out, ls.d_out_bytes, bytes, slack_cap(bytes, 4), __func__);
+    if (rc) return rc;
   }
   balance_select_kernel<<<1, SEL_T, 0, stream>>>(ls.d_labels, n, end, ls.d_sel);
   HIP_RET(hipGetLastError());

@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "gpd_internal.h"
+#include "buffers.h"
 #include <type_traits>
 
 namespace gpd {
@@ -829,17 +830,17 @@ hipError_t lenet_scratch_reserve(LeNetScratch &s, int n) {
   note_alloc(__func__);
   lenet_scratch_free(s);
   s.num_cus = num_cus;
-  n = (n + n / 4 + 3) & ~3;  // slack: the clouds of a batch differ a little, every growth stalls the device; a multiple of 4: the row length of the transposed ip1 buffers (16-byte accesses)
+  n = (slack_cap(n, 4) + 3) & ~3;  // slack: the clouds of a batch differ a little, every growth stalls the device; a multiple of 4: the row length of the transposed ip1 buffers (16-byte accesses)
   hipError_t e;
-  if ((e = hipMalloc(&s.pool1, (size_t)n * P1_IMG * sizeof(float))) != hipSuccess) return e;
-  if ((e = hipMalloc(&s.flat, (size_t)n * kFc1In * sizeof(float))) != hipSuccess) return e;
+  if ((e = device_alloc(s.pool1, (size_t)n * P1_IMG)) != hipSuccess) return e;
+  if ((e = device_alloc(s.flat, (size_t)n * kFc1In)) != hipSuccess) return e;
   constexpr size_t kXld = kLenetXld;  // 7200 + 96 zeros, which no kernel ever writes
   const size_t xs_rows = ((size_t)n + 15) & ~(size_t)15;  // whole 16-image blocks (lenet_fast.hip f3_blocked)
-  if ((e = hipMalloc(&s.xs, 3 * xs_rows * kXld * sizeof(unsigned short))) != hipSuccess) return e;
+  if ((e = device_alloc(s.xs, 3 * xs_rows * kXld)) != hipSuccess) return e;
   if ((e = hipMemset(s.xs, 0, 3 * xs_rows * kXld * sizeof(unsigned short))) != hipSuccess) return e;
-  if ((e = hipMalloc(&s.fc1t, (size_t)n * kFc1Out * sizeof(float))) != hipSuccess) return e;
-  if ((e = hipMalloc(&s.fc1p, (((size_t)n + 31) & ~(size_t)31) * 4 * kFc1Out * sizeof(float))) != hipSuccess) return e;  // whole 32-image blocks (fc1p_index)
-  if ((e = hipMalloc(&s.c1_stats, 4 * sizeof(unsigned long long))) != hipSuccess) return e;
+  if ((e = device_alloc(s.fc1t, (size_t)n * kFc1Out)) != hipSuccess) return e;
+  if ((e = device_alloc(s.fc1p, (((size_t)n + 31) & ~(size_t)31) * 4 * kFc1Out)) != hipSuccess) return e;  // whole 32-image blocks (fc1p_index)
+  if ((e = device_alloc(s.c1_stats, 4)) != hipSuccess) return e;
   if ((e = hipMemset(s.c1_stats, 0, 4 * sizeof(unsigned long long))) != hipSuccess) return e;
   s.capacity = n;
   return hipSuccess;
@@ -859,12 +860,7 @@ int lenet_check(LeNetScratch &s) {
 }
 
 void lenet_scratch_free(LeNetScratch &s) {
-  if (s.pool1) (void)hipFree(s.pool1);
-  if (s.flat) (void)hipFree(s.flat);
-  if (s.xs) (void)hipFree(s.xs);
-  if (s.fc1t) (void)hipFree(s.fc1t);
-  if (s.fc1p) (void)hipFree(s.fc1p);
-  if (s.c1_stats) (void)hipFree(s.c1_stats);
+  device_release(s.pool1, s.flat, s.xs, s.fc1t, s.fc1p, s.c1_stats);
   s = LeNetScratch();
 }
 

@@ -19,6 +19,7 @@
 // Measured against float64 on the reference pins the scores of this path are closer than the f32 chain's
 // (tests/test_gpu_lenet_fast.py), and within 1e-4 of the reference's plain-float Eigen path on every pin.
 #include "gpd_internal.h"
+#include "buffers.h"
 
 #include <cstring>
 
@@ -835,9 +836,7 @@ __global__ __launch_bounds__(F3_THREADS) void fc1_bf16_kernel(const unsigned sho
 // Host side: the operand tables (built once per gpd_hip_set_lenet_weights) and the launch sequence.
 // ---------------------------------------------------------------------------------------------------------------------
 void lenet_fast_free(LeNetFast &f) {
-  void *ps[] = {f.c1a, f.c1corr, f.c1shift, f.c2b, f.f1wt};
-  for (void *p : ps)
-    if (p) (void)hipFree(p);
+  device_release(f.c1a, f.c1corr, f.c1shift, f.c2b, f.f1wt);
   f = LeNetFast();
 }
 
@@ -993,15 +992,15 @@ hipError_t lenet_fast_prepare(LeNetFast &f, int channels, const float *c1w, cons
   lenet_fast_conv2_tables(c2w, btab);
   lenet_fast_ip1_tables(f1w, wt);
   hipError_t e;
-  auto up = [&](auto **dst, const void *src, size_t bytes) -> hipError_t {
-    if ((e = hipMalloc(reinterpret_cast<void **>(dst), bytes)) != hipSuccess) return e;
-    return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+  auto up = [&](auto *&dst, const void *src, size_t bytes) -> hipError_t {  // (every table is a whole number of dst's elements)
+    if ((e = device_alloc(dst, (bytes + sizeof(*dst) - 1) / sizeof(*dst))) != hipSuccess) return e;
+    return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
   };
-  if ((e = up(&f.c1a, atab.data(), atab.size())) != hipSuccess) return e;
-  if ((e = up(&f.c1corr, corr.data(), corr.size() * sizeof(double))) != hipSuccess) return e;
-  if ((e = up(&f.c1shift, shift.data(), shift.size() * sizeof(int))) != hipSuccess) return e;
-  if ((e = up(&f.c2b, btab.data(), btab.size() * sizeof(unsigned short))) != hipSuccess) return e;
-  if ((e = up(&f.f1wt, wt.data(), wt.size() * sizeof(unsigned short))) != hipSuccess) return e;
+  if ((e = up(f.c1a, atab.data(), atab.size())) != hipSuccess) return e;
+  if ((e = up(f.c1corr, corr.data(), corr.size() * sizeof(double))) != hipSuccess) return e;
+  if ((e = up(f.c1shift, shift.data(), shift.size() * sizeof(int))) != hipSuccess) return e;
+  if ((e = up(f.c2b, btab.data(), btab.size() * sizeof(unsigned short))) != hipSuccess) return e;
+  if ((e = up(f.f1wt, wt.data(), wt.size() * sizeof(unsigned short))) != hipSuccess) return e;
   return hipSuccess;
 }
 

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "buffers.h"
 #include "eigen3.h"
 #include "gpd_internal.h"
 #include "grid_sort.h"
@@ -462,9 +463,7 @@ __global__ __launch_bounds__(64) void normals_finish_kernel(NormalsParams P) {
 }
 
 void normals_free(NormalsScratch &s) {
-  void *ptrs[] = {s.d_count, s.d_lists, s.d_big, s.d_big_off, s.d_arena, s.d_ctl, s.d_out, s.d_cent};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
+  device_release(s.d_count, s.d_lists, s.d_big, s.d_big_off, s.d_arena, s.d_ctl, s.d_out, s.d_cent);
   s = NormalsScratch();
 }
 
@@ -484,24 +483,24 @@ int normals_run(Cloud &c, double radius, float *normals_out, hipStream_t stream)
     normals_free(s);
     s.d_arena = arena;
     s.arena_cap = arena_cap;
-    const int cap = P + P / 4;
-    HIP_RET(hipMalloc(&s.d_count, (size_t)cap * sizeof(int32_t)));
+    const int cap = slack_cap(P, 4);
+    HIP_RET(device_alloc(s.d_count, (size_t)cap));
     // the transposed lists take 16 KB per point (1024 entries of 16 bytes; a point touches 16 B per neighbour): a tile of at
     // most kNormalsTile points at a time shares ONE such array (1 GB), whatever the size of the cloud — sized per point of
     // the whole cloud it was 10 GB for a 500k-point raw scan
     const size_t tile_pts = std::min<size_t>(((size_t)cap + 63) / 64 * 64, kNormalsTile);
-    HIP_RET(hipMalloc(&s.d_lists, tile_pts * NL_CAP * sizeof(float4)));
-    HIP_RET(hipMalloc(&s.d_big, ((size_t)cap + 1) * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_big_off, (size_t)cap * sizeof(long long)));
-    HIP_RET(hipMalloc(&s.d_ctl, 4 * sizeof(unsigned long long)));  // [0] arena top, [1] status
-    HIP_RET(hipMalloc(&s.d_out, (size_t)cap * 3 * sizeof(float)));
-    HIP_RET(hipMalloc(&s.d_cent, (size_t)cap * 3 * sizeof(double)));
+    HIP_RET(device_alloc(s.d_lists, tile_pts * NL_CAP));
+    HIP_RET(device_alloc(s.d_big, (size_t)cap + 1));
+    HIP_RET(device_alloc(s.d_big_off, (size_t)cap));
+    HIP_RET(device_alloc(s.d_ctl, 4));  // [0] arena top, [1] status
+    HIP_RET(device_alloc(s.d_out, (size_t)cap * 3));
+    HIP_RET(device_alloc(s.d_cent, (size_t)cap * 3));
     s.cap_points = cap;
   }
   if (!s.d_arena) {
     note_alloc(__func__);
     const long long want = 1ll << 20;  // 8 MB: a voxelised cloud needs none of it
-    HIP_RET(hipMalloc(&s.d_arena, (size_t)want * sizeof(unsigned long long)));
+    HIP_RET(device_alloc(s.d_arena, (size_t)want));
     s.arena_cap = want;
   }
   NormalsParams np;
@@ -566,11 +565,10 @@ int normals_run(Cloud &c, double radius, float *normals_out, hipStream_t stream)
     if (!(h.status & 1)) break;
     // more / larger neighbourhoods beyond a wave's reach than the arena holds: grow it to what this run asked for
     note_alloc(__func__);
-    (void)hipFree(s.d_arena);
-    s.d_arena = nullptr;
+    device_release(s.d_arena);
     s.arena_cap = 0;
-    const long long want = (long long)h.top + (long long)h.top / 8;
-    if (attempt == 1 || hipMalloc(&s.d_arena, (size_t)want * sizeof(unsigned long long)) != hipSuccess) {
+    const long long want = slack_cap((long long)h.top, 8);
+    if (attempt == 1 || device_alloc(s.d_arena, (size_t)want) != hipSuccess) {
       (void)hipGetLastError();
       set_error("normals: the neighbour lists of this cloud (%llu sort slots within %.3f m) do not fit the device memory", h.top, radius);
       return GPD_ERR_CAPACITY;

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "gpd_internal.h"
+#include "buffers.h"
 
 namespace gpd {
 
@@ -328,11 +329,9 @@ __global__ __launch_bounds__(PLAN_THREADS) void plan_kernel(PlanParams P) {
 }
 
 void plan_free(Plan &pl) {
-  void *ptrs[] = {pl.d_sample_of_set, pl.d_hand_cand, pl.d_cand_hand, pl.d_cand_out, pl.d_cand_meta, pl.d_set_meta, pl.d_summary,
-                  pl.d_set_flags, pl.d_set_samples, pl.d_parts, pl.d_ticket};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  if (pl.h_summary) (void)hipHostFree(pl.h_summary);
+  device_release(pl.d_sample_of_set, pl.d_hand_cand, pl.d_cand_hand, pl.d_cand_out, pl.d_cand_meta, pl.d_set_meta, pl.d_summary, pl.d_set_flags,
+                 pl.d_set_samples, pl.d_parts, pl.d_ticket);
+  pinned_release(pl.h_summary);
   pl = Plan();
 }
 
@@ -345,21 +344,21 @@ int plan_reserve(Plan &pl, int want_samples, int slots, int cams, hipStream_t st
   const int capL = slots > pl.cap_slots ? slots : pl.cap_slots;
   plan_free(pl);
   const size_t H = (size_t)capS * capL;
-  HIP_RET(hipMalloc(&pl.d_sample_of_set, (size_t)capS * sizeof(int32_t)));
-  HIP_RET(hipMalloc(&pl.d_hand_cand, H * sizeof(int32_t)));
-  HIP_RET(hipMalloc(&pl.d_cand_hand, H * sizeof(int32_t)));
-  HIP_RET(hipMalloc(&pl.d_cand_out, H * sizeof(int32_t)));
-  HIP_RET(hipMalloc(&pl.d_cand_meta, H * 4 * sizeof(int32_t)));
-  HIP_RET(hipMalloc(&pl.d_set_meta, (size_t)capS * capC * 8 * sizeof(int32_t)));
-  HIP_RET(hipMalloc(&pl.d_summary, sizeof(PlanSummary)));
+  HIP_RET(device_alloc(pl.d_sample_of_set, (size_t)capS));
+  HIP_RET(device_alloc(pl.d_hand_cand, H));
+  HIP_RET(device_alloc(pl.d_cand_hand, H));
+  HIP_RET(device_alloc(pl.d_cand_out, H));
+  HIP_RET(device_alloc(pl.d_cand_meta, H * 4));
+  HIP_RET(device_alloc(pl.d_set_meta, (size_t)capS * capC * 8));
+  HIP_RET(device_alloc(pl.d_summary, 1));
   // look-back state of plan_kernel: zeroed once (stamps are compared with a launch number that starts at 1)
   const size_t nparts = (size_t)(capS + PLAN_THREADS - 1) / PLAN_THREADS + 1;
-  HIP_RET(hipMalloc(&pl.d_parts, nparts * sizeof(PlanPart)));
-  HIP_RET(hipMalloc(&pl.d_ticket, sizeof(unsigned)));
+  HIP_RET(device_alloc(pl.d_parts, nparts));
+  HIP_RET(device_alloc(pl.d_ticket, 1));
   HIP_RET(hipMemsetAsync(pl.d_parts, 0, nparts * sizeof(PlanPart), stream));
   HIP_RET(hipMemsetAsync(pl.d_ticket, 0, sizeof(unsigned), stream));
   pl.epoch = 0;
-  HIP_RET(hipHostMalloc(reinterpret_cast<void **>(&pl.h_summary), sizeof(PlanSummary), 0));
+  HIP_RET(pinned_alloc(pl.h_summary, 1));
   pl.cap_samples = capS;
   pl.cap_slots = capL;
   pl.cap_cams = capC;
@@ -380,14 +379,11 @@ int plan_build(const gpd_params &p, const Cloud &c, const SearchState &s, Plan &
   pp.num_sets_given = 0;
   if (set_flags) {
     if (num_sets_given > pl.cap_set_flags || !pl.d_set_flags) {
-      if (pl.d_set_flags) (void)hipFree(pl.d_set_flags);
-      if (pl.d_set_samples) (void)hipFree(pl.d_set_samples);
-      pl.d_set_flags = nullptr;
-      pl.d_set_samples = nullptr;
+      device_release(pl.d_set_flags, pl.d_set_samples);  // (never booked: note_alloc's comment in gpd_internal.h)
       pl.cap_set_flags = 0;
       const int cap = num_sets_given > pl.cap_samples ? num_sets_given : pl.cap_samples;
-      HIP_RET(hipMalloc(&pl.d_set_flags, (size_t)cap * pl.cap_slots + 16));
-      HIP_RET(hipMalloc(&pl.d_set_samples, ((size_t)cap * 3 + 1) * sizeof(double)));
+      HIP_RET(device_alloc(pl.d_set_flags, (size_t)cap * pl.cap_slots + 16));
+      HIP_RET(device_alloc(pl.d_set_samples, (size_t)cap * 3 + 1));
       pl.cap_set_flags = cap;
     }
     if (num_sets_given > 0) {

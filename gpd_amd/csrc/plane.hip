@@ -15,6 +15,7 @@
 // The distance test `(double)fabsf(dist) < threshold` runs as `fabsf(dist) <= threshold_f32(threshold)`, the same
 // decision for every float (plane_model.h).  -ffp-contract=off (Makefile): every expression is evaluated unfused.
 #include "gpd_internal.h"
+#include "buffers.h"
 #include "plane_model.h"
 #include "wave_ops.h"
 
@@ -306,27 +307,22 @@ hipError_t compact(PlaneState &s, const Cloud &c, float4 plane, float thr, int w
 
 int plane_reserve(PlaneState &s, int n) {
   if (!s.d_meta) {
-    HIP_RET(hipMalloc(&s.d_meta, sizeof(PlaneMeta)));
-    HIP_RET(hipMalloc(&s.d_coef, kPlaneMaxHyp * sizeof(float4)));
-    HIP_RET(hipMalloc(&s.d_counts, kPlaneMaxHyp * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_accu, 9 * sizeof(float)));
-    HIP_RET(hipHostMalloc(&s.h_pin, sizeof(PlaneMeta) + kPlaneMaxHyp * (sizeof(float4) + sizeof(int32_t)) + 16 * sizeof(float), hipHostMallocDefault));
+    HIP_RET(device_alloc(s.d_meta, sizeof(PlaneMeta)));
+    HIP_RET(device_alloc(s.d_coef, kPlaneMaxHyp));
+    HIP_RET(device_alloc(s.d_counts, kPlaneMaxHyp));
+    HIP_RET(device_alloc(s.d_accu, 9));
+    HIP_RET(pinned_alloc(s.h_pin, sizeof(PlaneMeta) + kPlaneMaxHyp * (sizeof(float4) + sizeof(int32_t)) + 16 * sizeof(float)));
     note_alloc("plane: fixed buffers");
   }
   if (n > s.capacity) {
-    const int cap = n + n / 4 + 1024;
+    const int cap = slack_cap(n, 4) + 1024;
     const int nb = (cap + kFlagThreads - 1) / kFlagThreads;
-    (void)hipFree(s.d_block_count);
-    (void)hipFree(s.d_block_off);
-    (void)hipFree(s.d_xyz);
-    (void)hipFree(s.d_idx);
-    s.d_block_count = s.d_block_off = s.d_idx = nullptr;
-    s.d_xyz = nullptr;
+    device_release(s.d_block_count, s.d_block_off, s.d_xyz, s.d_idx);
     s.capacity = 0;
-    HIP_RET(hipMalloc(&s.d_block_count, (size_t)nb * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_block_off, (size_t)nb * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_xyz, (size_t)cap * 3 * sizeof(float)));
-    HIP_RET(hipMalloc(&s.d_idx, (size_t)cap * sizeof(int32_t)));
+    HIP_RET(device_alloc(s.d_block_count, (size_t)nb));
+    HIP_RET(device_alloc(s.d_block_off, (size_t)nb));
+    HIP_RET(device_alloc(s.d_xyz, (size_t)cap * 3));
+    HIP_RET(device_alloc(s.d_idx, (size_t)cap));
     note_alloc("plane: compaction buffers");
     s.capacity = cap;
   }
@@ -334,15 +330,8 @@ int plane_reserve(PlaneState &s, int n) {
 }
 
 void plane_free(PlaneState &s) {
-  (void)hipFree(s.d_meta);
-  (void)hipFree(s.d_coef);
-  (void)hipFree(s.d_counts);
-  (void)hipFree(s.d_accu);
-  (void)hipFree(s.d_block_count);
-  (void)hipFree(s.d_block_off);
-  (void)hipFree(s.d_xyz);
-  (void)hipFree(s.d_idx);
-  if (s.h_pin) (void)hipHostFree(s.h_pin);
+  device_release(s.d_meta, s.d_coef, s.d_counts, s.d_accu, s.d_block_count, s.d_block_off, s.d_xyz, s.d_idx);
+  pinned_release(s.h_pin);
   s = PlaneState();
 }
 

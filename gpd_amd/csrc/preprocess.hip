@@ -22,6 +22,7 @@
 // against 1.5 ms this way and 7.9 ms for the std::set itself — DESIGN §8.)  Everything around it (keys, minimum, gather
 // of the kept voxels) is data parallel and stays on the device.
 #include "gpd_internal.h"
+#include "buffers.h"
 #include "wave_ops.h"
 #include <cfloat>
 #include <cmath>
@@ -279,10 +280,8 @@ static int voxel_accept_host(const int4 *keys, int n, const int8_t *ops, int32_t
 }
 
 void preprocess_free(PreState &s) {
-  void *dev[] = {s.d_xyz, s.d_cam, s.d_block_count, s.d_block_off, s.d_block_lo, s.d_src, s.d_keys, s.d_rank, s.d_out_xyz, s.d_out_cam, s.d_out_src, s.d_meta};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
-  if (s.h_pin) (void)hipHostFree(s.h_pin);
+  device_release(s.d_xyz, s.d_cam, s.d_block_count, s.d_block_off, s.d_block_lo, s.d_src, s.d_keys, s.d_rank, s.d_out_xyz, s.d_out_cam, s.d_out_src, s.d_meta);
+  pinned_release(s.h_pin);
   hipEvent_t e0 = s.ev[0], e1 = s.ev[1], e2 = s.ev_keys;  // the events outlive a re-allocation
   s = PreState();
   s.ev[0] = e0;
@@ -322,27 +321,27 @@ int preprocess_begin(PreState &s, const float *xyz, const int32_t *cam_source, i
   s.M = 0;
   if (n == 0) return GPD_OK;
   if (n > s.capacity || num_cams > s.cap_cams) {
-    const int cap = n > s.capacity ? n + n / 4 : s.capacity, cams = num_cams > s.cap_cams ? num_cams : s.cap_cams;
+    const int cap = n > s.capacity ? slack_cap(n, 4) : s.capacity, cams = num_cams > s.cap_cams ? num_cams : s.cap_cams;
     note_alloc(__func__);
     preprocess_free(s);
     s.n = n;
     s.num_cams = num_cams;
     s.cell = cell;
     const int blocks = (cap + PP_THREADS - 1) / PP_THREADS;
-    HIP_RET(hipMalloc(&s.d_xyz, (size_t)cap * 3 * sizeof(float)));
-    HIP_RET(hipMalloc(&s.d_cam, (size_t)cap * (cams > 0 ? cams : 1) * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_block_count, (size_t)blocks * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_block_off, (size_t)blocks * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_block_lo, (size_t)blocks * 3 * sizeof(float)));
-    HIP_RET(hipMalloc(&s.d_src, (size_t)cap * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_keys, (size_t)cap * sizeof(int4)));
-    HIP_RET(hipMalloc(&s.d_rank, (size_t)cap * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_out_xyz, (size_t)cap * 3 * sizeof(float)));
-    HIP_RET(hipMalloc(&s.d_out_cam, (size_t)cap * (cams > 0 ? cams : 1) * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_out_src, (size_t)cap * sizeof(int32_t)));
-    HIP_RET(hipMalloc(&s.d_meta, sizeof(PreMeta)));
+    HIP_RET(device_alloc(s.d_xyz, (size_t)cap * 3));
+    HIP_RET(device_alloc(s.d_cam, (size_t)cap * (cams > 0 ? cams : 1)));
+    HIP_RET(device_alloc(s.d_block_count, (size_t)blocks));
+    HIP_RET(device_alloc(s.d_block_off, (size_t)blocks));
+    HIP_RET(device_alloc(s.d_block_lo, (size_t)blocks * 3));
+    HIP_RET(device_alloc(s.d_src, (size_t)cap));
+    HIP_RET(device_alloc(s.d_keys, (size_t)cap));
+    HIP_RET(device_alloc(s.d_rank, (size_t)cap));
+    HIP_RET(device_alloc(s.d_out_xyz, (size_t)cap * 3));
+    HIP_RET(device_alloc(s.d_out_cam, (size_t)cap * (cams > 0 ? cams : 1)));
+    HIP_RET(device_alloc(s.d_out_src, (size_t)cap));
+    HIP_RET(device_alloc(s.d_meta, sizeof(PreMeta)));
     // pinned: [keys 16 B x cap][ranks 4 B x cap][PreMeta][bounds 6 floats]
-    HIP_RET(hipHostMalloc(reinterpret_cast<void **>(&s.h_pin), (size_t)cap * 20 + 256, 0));
+    HIP_RET(pinned_alloc(s.h_pin, (size_t)cap * 20 + 256));
     s.capacity = cap;
     s.cap_cams = cams;
   }

@@ -15,6 +15,7 @@
 //      stop discards it.
 //   4. the result replaces the cloud's normals (planes nx, ny, nz and pnrm); the cloud's generation moves on.
 #include "gpd_internal.h"
+#include "buffers.h"
 #include "grid_sort.h"
 #include "refine_model.h"
 
@@ -222,47 +223,35 @@ int refine_reserve(RefineState &s, int n, int k) {
   const size_t lists = ((size_t)n + 63) / 64 * 64 * (size_t)k;
   if (n > s.cap_points) {
     note_alloc(__func__);
-    for (float4 *&b : s.d_buf) {
-      (void)hipFree(b);
-      b = nullptr;
-    }
-    (void)hipFree(s.d_dots);
-    (void)hipFree(s.d_aos);
-    if (s.h_dots) (void)hipHostFree(s.h_dots);
-    s.d_dots = s.d_aos = s.h_dots = nullptr;
+    for (float4 *&b : s.d_buf) device_release(b);
+    device_release(s.d_dots, s.d_aos);
+    pinned_release(s.h_dots);
     s.cap_points = 0;
-    const int cap = n + n / 4;
-    for (float4 *&b : s.d_buf) HIP_RET(hipMalloc(&b, (size_t)cap * sizeof(float4)));
-    HIP_RET(hipMalloc(&s.d_dots, (size_t)cap * sizeof(float)));
-    HIP_RET(hipMalloc(&s.d_aos, (size_t)cap * 3 * sizeof(float)));
-    HIP_RET(hipHostMalloc(reinterpret_cast<void **>(&s.h_dots), (size_t)cap * 2 * sizeof(float), 0));
+    const int cap = slack_cap(n, 4);
+    for (float4 *&b : s.d_buf) HIP_RET(device_alloc(b, (size_t)cap));
+    HIP_RET(device_alloc(s.d_dots, (size_t)cap));
+    HIP_RET(device_alloc(s.d_aos, (size_t)cap * 3));
+    HIP_RET(pinned_alloc(s.h_dots, (size_t)cap * 2));
     s.cap_points = cap;
   }
-  if (lists > s.cap_lists) {
-    note_alloc(__func__);
-    (void)hipFree(s.d_lists);
-    s.d_lists = nullptr;
-    s.cap_lists = 0;
-    HIP_RET(hipMalloc(&s.d_lists, (lists + lists / 4) * sizeof(int32_t)));
-    s.cap_lists = lists + lists / 4;
-  }
+  const int rc = grow_device(s.d_lists, s.cap_lists, lists, slack_cap(lists, 4), __func__);
+  if (rc) return rc;
   if (!s.ev_dots[0])
     for (hipEvent_t &e : s.ev_dots) HIP_RET(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   if (!s.d_nan) {
-    HIP_RET(hipMalloc(&s.d_nan, sizeof(int32_t)));
-    HIP_RET(hipHostMalloc(reinterpret_cast<void **>(&s.h_nan), sizeof(int32_t), 0));
+    HIP_RET(device_alloc(s.d_nan, 1));
+    HIP_RET(pinned_alloc(s.h_nan, 1));
   }
   return GPD_OK;
 }
 
 void refine_free(RefineState &s) {
-  (void)hipFree(s.d_lists);
-  for (float4 *b : s.d_buf) (void)hipFree(b);
-  (void)hipFree(s.d_dots);
-  (void)hipFree(s.d_aos);
-  if (s.h_dots) (void)hipHostFree(s.h_dots);
-  (void)hipFree(s.d_nan);
-  if (s.h_nan) (void)hipHostFree(s.h_nan);
+  device_release(s.d_lists);
+  for (float4 *&b : s.d_buf) device_release(b);
+  device_release(s.d_dots, s.d_aos);
+  pinned_release(s.h_dots);
+  device_release(s.d_nan);
+  pinned_release(s.h_nan);
   for (hipEvent_t e : s.ev_dots)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : s.ev)

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstdio>
 
+#include "buffers.h"
 #include "eigen3.h"
 #include "gpd_internal.h"
 #include "grid_sort.h"
@@ -953,10 +954,8 @@ __global__ __launch_bounds__(256) void sample_gather_kernel(const int32_t *__res
 // Host side
 // ---------------------------------------------------------------------------
 void search_free(SearchState &s) {
-  void *ptrs[] = {s.d_sample_idx, s.d_sample_xyz, s.d_counts, s.d_nn_idx, s.d_nn, s.d_frames, s.d_centers, s.d_hands, s.d_fvalid, s.d_hl,
-                  s.d_labels};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);  // hipFree waits for the device: the side stream is idle as well
+  // hipFree waits for the device: the side stream is idle as well
+  device_release(s.d_sample_idx, s.d_sample_xyz, s.d_counts, s.d_nn_idx, s.d_nn, s.d_frames, s.d_centers, s.d_hands, s.d_fvalid, s.d_hl, s.d_labels);
   if (s.ev_fork) (void)hipEventDestroy(s.ev_fork);
   if (s.ev_join) (void)hipEventDestroy(s.ev_join);
   if (s.aux) (void)hipStreamDestroy(s.aux);
@@ -985,17 +984,17 @@ static int search_reserve(SearchState &s, int S, int cap, int slots) {
   const uint64_t seen = s.seen_generation;
   search_free(s);
   s.seen_generation = seen;  // (search_free resets the whole state; the cloud the lists belong to is still the same)
-  HIP_RET(hipMalloc(&s.d_sample_idx, (size_t)newS * sizeof(int32_t)));
-  HIP_RET(hipMalloc(&s.d_sample_xyz, (size_t)newS * 3 * sizeof(double)));
-  HIP_RET(hipMalloc(&s.d_counts, (size_t)newS * 8 * sizeof(int32_t)));
-  HIP_RET(hipMalloc(&s.d_nn_idx, (size_t)newS * cap * sizeof(int32_t)));
-  HIP_RET(hipMalloc(&s.d_nn, (size_t)newS * 6 * cap * sizeof(float)));
-  HIP_RET(hipMalloc(&s.d_frames, (size_t)newS * 12 * sizeof(double)));
-  HIP_RET(hipMalloc(&s.d_centers, (size_t)newS * 3 * sizeof(double)));
-  HIP_RET(hipMalloc(&s.d_hands, (size_t)newS * slots * sizeof(gpd_hand)));
-  HIP_RET(hipMalloc(&s.d_fvalid, (size_t)newS * slots));
-  HIP_RET(hipMalloc(&s.d_hl, (size_t)newS * cap * sizeof(float4)));
-  HIP_RET(hipMalloc(&s.d_labels, (size_t)newS * sizeof(int32_t)));
+  HIP_RET(device_alloc(s.d_sample_idx, (size_t)newS));
+  HIP_RET(device_alloc(s.d_sample_xyz, (size_t)newS * 3));
+  HIP_RET(device_alloc(s.d_counts, (size_t)newS * 8));
+  HIP_RET(device_alloc(s.d_nn_idx, (size_t)newS * cap));
+  HIP_RET(device_alloc(s.d_nn, (size_t)newS * 6 * cap));
+  HIP_RET(device_alloc(s.d_frames, (size_t)newS * 12));
+  HIP_RET(device_alloc(s.d_centers, (size_t)newS * 3));
+  HIP_RET(device_alloc(s.d_hands, (size_t)newS * slots));
+  HIP_RET(device_alloc(s.d_fvalid, (size_t)newS * slots));
+  HIP_RET(device_alloc(s.d_hl, (size_t)newS * cap));
+  HIP_RET(device_alloc(s.d_labels, (size_t)newS));
   s.capacity_samples = newS;
   s.nn_cap = cap;
   return GPD_OK;

@@ -4,6 +4,7 @@
 // and images (sis_accumulate_kernel), and the cut at min_score over the accumulated records (sis_select_kernel).  The round loop
 // itself is gpd_hip_detect_sis in detect.hip.
 #include "gpd_internal.h"
+#include "buffers.h"
 
 #include <algorithm>
 
@@ -215,32 +216,15 @@ __global__ __launch_bounds__(1024) void sis_select_kernel(gpd_hand *__restrict__
   if (tid == 0) meta->kept = running;
 }
 
-template <typename T>
-int grow(T *&p, size_t &cap, size_t need, size_t keep, hipStream_t stream, const char *who) {
-  if (need <= cap) return GPD_OK;
-  note_alloc(who);
-  const size_t ncap = std::max(need + need / 2, (size_t)64);
-  T *q = nullptr;
-  HIP_RET(hipMalloc(reinterpret_cast<void **>(&q), ncap * sizeof(T)));
-  if (keep > 0 && p) {
-    HIP_RET(hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, stream));
-    HIP_RET(hipStreamSynchronize(stream));
-  }
-  if (p) (void)hipFree(p);
-  p = q;
-  cap = ncap;
-  return GPD_OK;
-}
+// the draw's buffers and the accumulators grow by half, to 64 elements at the least
+size_t half_more(size_t need) { return std::max(slack_cap(need, 2), (size_t)64); }
 
 }  // namespace
 
 void sis_free(SisState &ss) {
-  void *dev[] = {ss.d_images, ss.d_hands, ss.d_keep, ss.d_centres, ss.d_round_xyz, ss.d_samples, ss.d_uniform, ss.d_gauss, ss.d_unif, ss.d_meta};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
-  if (ss.h_block) (void)hipHostFree(ss.h_block);
-  if (ss.h_meta) (void)hipHostFree(ss.h_meta);
-  if (ss.h_out) (void)hipHostFree(ss.h_out);
+  device_release(ss.d_images, ss.d_hands, ss.d_keep, ss.d_centres, ss.d_round_xyz, ss.d_samples, ss.d_uniform, ss.d_gauss, ss.d_unif,
+                 ss.d_meta);
+  pinned_release(ss.h_block, ss.h_meta, ss.h_out);
   for (auto &e : ss.ev)
     if (e) (void)hipEventDestroy(e);
   ss = SisState();
@@ -248,14 +232,14 @@ void sis_free(SisState &ss) {
 
 int sis_init(SisState &ss) {
   if (ss.d_meta) return GPD_OK;
-  HIP_RET(hipMalloc(reinterpret_cast<void **>(&ss.d_meta), sizeof(SisMeta)));
-  HIP_RET(hipHostMalloc(reinterpret_cast<void **>(&ss.h_meta), sizeof(SisMeta), 0));
+  HIP_RET(device_alloc(ss.d_meta, 1));
+  HIP_RET(pinned_alloc(ss.h_meta, 1));
   for (auto &e : ss.ev) HIP_RET(hipEventCreate(&e));
   return GPD_OK;
 }
 
 int sis_reserve(SisState &ss, size_t need, size_t used, size_t centres, size_t used_centres, size_t image_bytes, hipStream_t stream) {
-  int rc = grow(ss.d_centres, ss.cap_centres, centres * 3, used_centres * 3, stream, __func__);
+  int rc = grow_device_keep(ss.d_centres, ss.cap_centres, centres * 3, half_more(centres * 3), used_centres * 3, stream, __func__);
   if (rc) return rc;
   if (image_bytes != ss.image_bytes) {  // (a context has one channel count: only the first call comes here)
     used = 0;
@@ -268,23 +252,12 @@ int sis_reserve(SisState &ss, size_t need, size_t used, size_t centres, size_t u
     return GPD_ERR_CAPACITY;
   }
   note_alloc(__func__);
-  const size_t cap = std::min(std::max(need + need / 2, (size_t)64), kSisAccBudget / per);
-  uint8_t *img = nullptr;
-  gpd_hand *hands = nullptr, *keep = nullptr;
-  HIP_RET(hipMalloc(reinterpret_cast<void **>(&img), cap * image_bytes));
-  HIP_RET(hipMalloc(reinterpret_cast<void **>(&hands), cap * sizeof(gpd_hand)));
-  HIP_RET(hipMalloc(reinterpret_cast<void **>(&keep), cap * sizeof(gpd_hand)));
-  if (used > 0) {  // the rounds so far move over
-    HIP_RET(hipMemcpyAsync(img, ss.d_images, used * image_bytes, hipMemcpyDeviceToDevice, stream));
-    HIP_RET(hipMemcpyAsync(hands, ss.d_hands, used * sizeof(gpd_hand), hipMemcpyDeviceToDevice, stream));
-    HIP_RET(hipStreamSynchronize(stream));
-  }
-  void *old[] = {ss.d_images, ss.d_hands, ss.d_keep};
-  for (void *p : old)
-    if (p) (void)hipFree(p);
-  ss.d_images = img;
-  ss.d_hands = hands;
-  ss.d_keep = keep;
+  const size_t cap = std::min(half_more(need), kSisAccBudget / per);
+  // the rounds so far move over (d_keep is rewritten by every selection)
+  rc = grow_group_keep({group_buffer(ss.d_images, image_bytes, true), group_buffer(ss.d_hands, sizeof(gpd_hand), true),
+                        group_buffer(ss.d_keep, sizeof(gpd_hand), false)},
+                       cap, used, stream);
+  if (rc) return rc;
   ss.cap = cap;
   ss.image_bytes = image_bytes;
   ss.grows++;
@@ -293,29 +266,25 @@ int sis_reserve(SisState &ss, size_t need, size_t used, size_t centres, size_t u
 
 int sis_reserve_round(SisState &ss, size_t round_samples, size_t all_samples, size_t uniform, size_t block) {
   const size_t had_round = ss.cap_round;
-  int rc = grow(ss.d_round_xyz, ss.cap_round, round_samples * 3, 0, nullptr, __func__);
+  int rc = grow_device_keep(ss.d_round_xyz, ss.cap_round, round_samples * 3, half_more(round_samples * 3), 0, nullptr, __func__);
   if (rc) return rc;
   // a round whose draw falls short is searched as far as it is filled and then redone: the rest must be finite coordinates
   if (ss.cap_round != had_round) {
     HIP_RET(hipMemset(ss.d_round_xyz, 0, ss.cap_round * sizeof(double)));
     HIP_RET(hipDeviceSynchronize());  // (a growth: as rare as the hipMalloc before it)
   }
-  rc = grow(ss.d_samples, ss.cap_samples, all_samples * 3, 0, nullptr, __func__);
+  rc = grow_device_keep(ss.d_samples, ss.cap_samples, all_samples * 3, half_more(all_samples * 3), 0, nullptr, __func__);
   if (rc) return rc;
-  rc = grow(ss.d_uniform, ss.cap_uniform, uniform, 0, nullptr, __func__);
+  rc = grow_device_keep(ss.d_uniform, ss.cap_uniform, uniform, half_more(uniform), 0, nullptr, __func__);
   if (rc) return rc;
   if (block > ss.cap_block) {
     note_alloc(__func__);
-    if (ss.d_gauss) (void)hipFree(ss.d_gauss);
-    if (ss.d_unif) (void)hipFree(ss.d_unif);
-    if (ss.h_block) (void)hipHostFree(ss.h_block);
-    ss.d_gauss = nullptr;
-    ss.d_unif = nullptr;
-    ss.h_block = nullptr;
+    device_release(ss.d_gauss, ss.d_unif);
+    pinned_release(ss.h_block);
     ss.cap_block = 0;
-    HIP_RET(hipMalloc(&ss.d_gauss, block * sizeof(sis::Proposal)));
-    HIP_RET(hipMalloc(reinterpret_cast<void **>(&ss.d_unif), block * sizeof(unsigned long long)));
-    HIP_RET(hipHostMalloc(reinterpret_cast<void **>(&ss.h_block), block * (sizeof(sis::Proposal) + sizeof(unsigned long long)), 0));
+    HIP_RET(device_alloc(ss.d_gauss, block * sizeof(sis::Proposal)));
+    HIP_RET(device_alloc(ss.d_unif, block));
+    HIP_RET(pinned_alloc(ss.h_block, block * (sizeof(sis::Proposal) + sizeof(unsigned long long))));
     ss.cap_block = block;
   }
   return GPD_OK;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "context.h"
+#include "buffers.h"
 #include "sample_model.h"
 #include "train.h"
 
@@ -664,11 +665,6 @@ bool all_finite(const float *v, size_t n) {
   return true;
 }
 
-template <class T>
-hipError_t dev_alloc(T **p, size_t count) {
-  return hipMalloc(reinterpret_cast<void **>(p), (count ? count : 1) * sizeof(T));
-}
-
 size_t image_bytes(const gpd_hip_trainer *t) { return (size_t)kPix * t->C; }
 
 // pool `which` holds exactly `capacity` (>= n) images afterwards, its first n kept.  The stream is synchronised before a pool is
@@ -676,15 +672,15 @@ size_t image_bytes(const gpd_hip_trainer *t) { return (size_t)kPix * t->C; }
 int pool_resize(const char *who, gpd_hip_trainer *t, int which, int capacity) {
   if (capacity == t->cap[which]) return GPD_OK;
   const size_t ib = image_bytes(t);
-  HIP_TRY(hipSetDevice(t->device));
-  HIP_TRY(hipStreamSynchronize(t->stream));
+  HIP_RET(hipSetDevice(t->device));
+  HIP_RET(hipStreamSynchronize(t->stream));
   uint8_t *img = nullptr, *lab = nullptr;
   if (capacity > 0) {
-    hipError_t e = dev_alloc(&img, (size_t)capacity * ib);
-    if (e == hipSuccess) e = dev_alloc(&lab, (size_t)capacity);
+    hipError_t e = device_alloc(img, (size_t)capacity * ib);
+    if (e == hipSuccess) e = device_alloc(lab, (size_t)capacity);
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      if (img) (void)hipFree(img);
+      device_release(img);
       set_error("%s: no room for %d images of %d channels (%zu bytes): %s", who, capacity, t->C, (size_t)capacity * (ib + 1), hipGetErrorString(e));
       return GPD_ERR_CAPACITY;
     }
@@ -693,15 +689,13 @@ int pool_resize(const char *who, gpd_hip_trainer *t, int which, int capacity) {
       if (c == hipSuccess) c = hipMemcpyAsync(lab, t->d_lab[which], (size_t)t->n[which], hipMemcpyDeviceToDevice, t->stream);
       if (c == hipSuccess) c = hipStreamSynchronize(t->stream);
       if (c != hipSuccess) {
-        (void)hipFree(img);
-        (void)hipFree(lab);
+        device_release(img, lab);
         set_error("%s: moving the pool failed: %s", who, hipGetErrorString(c));
         return GPD_ERR_HIP;
       }
     }
   }
-  if (t->d_img[which]) (void)hipFree(t->d_img[which]);
-  if (t->d_lab[which]) (void)hipFree(t->d_lab[which]);
+  device_release(t->d_img[which], t->d_lab[which]);
   t->d_img[which] = img;
   t->d_lab[which] = lab;
   t->cap[which] = capacity;
@@ -828,24 +822,24 @@ int gpd_hip_train_create_recipe(gpd_hip_ctx *ctx, const gpd_train_params *params
   const size_t total = t->off[8], B = (size_t)t->maxb;
   const size_t part = B * (size_t)std::max(std::max(kF2 * kF1 * kTaps, 4 * kF1 * kTaps * t->C), kFc1Splits * kFc1Out);
   hipError_t e = hipSetDevice(t->device);
-  if (e == hipSuccess) e = dev_alloc(&t->d_p, total);
-  if (e == hipSuccess) e = dev_alloc(&t->d_g, total);
-  if (e == hipSuccess) e = dev_alloc(&t->d_m, total);
-  if (e == hipSuccess && r.solver == GPD_TRAIN_SOLVER_ADAM) e = dev_alloc(&t->d_v, total);
-  if (e == hipSuccess) e = dev_alloc(&t->d_idx, (size_t)kIdxCap);
-  if (e == hipSuccess) e = dev_alloc(&t->d_loss, (size_t)kIdxCap);
-  if (e == hipSuccess) e = dev_alloc(&t->d_pool1, B * kF1 * kP1);
-  if (e == hipSuccess) e = dev_alloc(&t->d_dpool1, B * kF1 * kP1);
-  if (e == hipSuccess) e = dev_alloc(&t->d_arg1, B * kF1 * kP1);
-  if (e == hipSuccess) e = dev_alloc(&t->d_pool2, B * kFc1In);
-  if (e == hipSuccess) e = dev_alloc(&t->d_dpool2, B * kFc1In);
-  if (e == hipSuccess) e = dev_alloc(&t->d_arg2, B * kFc1In);
-  if (e == hipSuccess) e = dev_alloc(&t->d_a1, B * kFc1Out);
-  if (e == hipSuccess) e = dev_alloc(&t->d_dz1, B * kFc1Out);
-  if (e == hipSuccess) e = dev_alloc(&t->d_logits, B * 2);
-  if (e == hipSuccess) e = dev_alloc(&t->d_dl, B * 2);
-  if (e == hipSuccess) e = dev_alloc(&t->d_loss_b, B);
-  if (e == hipSuccess) e = dev_alloc(&t->d_part, part);
+  if (e == hipSuccess) e = device_alloc(t->d_p, total);
+  if (e == hipSuccess) e = device_alloc(t->d_g, total);
+  if (e == hipSuccess) e = device_alloc(t->d_m, total);
+  if (e == hipSuccess && r.solver == GPD_TRAIN_SOLVER_ADAM) e = device_alloc(t->d_v, total);
+  if (e == hipSuccess) e = device_alloc(t->d_idx, (size_t)kIdxCap);
+  if (e == hipSuccess) e = device_alloc(t->d_loss, (size_t)kIdxCap);
+  if (e == hipSuccess) e = device_alloc(t->d_pool1, B * kF1 * kP1);
+  if (e == hipSuccess) e = device_alloc(t->d_dpool1, B * kF1 * kP1);
+  if (e == hipSuccess) e = device_alloc(t->d_arg1, B * kF1 * kP1);
+  if (e == hipSuccess) e = device_alloc(t->d_pool2, B * kFc1In);
+  if (e == hipSuccess) e = device_alloc(t->d_dpool2, B * kFc1In);
+  if (e == hipSuccess) e = device_alloc(t->d_arg2, B * kFc1In);
+  if (e == hipSuccess) e = device_alloc(t->d_a1, B * kFc1Out);
+  if (e == hipSuccess) e = device_alloc(t->d_dz1, B * kFc1Out);
+  if (e == hipSuccess) e = device_alloc(t->d_logits, B * 2);
+  if (e == hipSuccess) e = device_alloc(t->d_dl, B * 2);
+  if (e == hipSuccess) e = device_alloc(t->d_loss_b, B);
+  if (e == hipSuccess) e = device_alloc(t->d_part, part);
   for (int i = 0; i < kMaxKernels && e == hipSuccess; i++) e = hipEventCreate(&t->ev[i]);
   if (e == hipSuccess) e = hipMemsetAsync(t->d_p, 0, total * sizeof(float), t->stream);
   if (e == hipSuccess) e = hipMemsetAsync(t->d_m, 0, total * sizeof(float), t->stream);
@@ -865,10 +859,9 @@ void gpd_hip_train_destroy(gpd_hip_trainer *t) {
   if (!t) return;
   (void)hipSetDevice(t->device);
   if (t->stream) (void)hipStreamSynchronize(t->stream);
-  void *dev[] = {t->d_p,     t->d_g,      t->d_m,      t->d_v,    t->d_img[0], t->d_img[1], t->d_lab[0], t->d_lab[1], t->d_idx, t->d_loss, t->d_pool1,
-                 t->d_pool2, t->d_dpool1, t->d_dpool2, t->d_arg1, t->d_arg2,   t->d_a1,     t->d_dz1,    t->d_logits, t->d_dl,  t->d_loss_b, t->d_part};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
+  device_release(t->d_p, t->d_g, t->d_m, t->d_v, t->d_img[0], t->d_img[1], t->d_lab[0], t->d_lab[1], t->d_idx, t->d_loss, t->d_pool1,
+                 t->d_pool2, t->d_dpool1, t->d_dpool2, t->d_arg1, t->d_arg2, t->d_a1, t->d_dz1, t->d_logits, t->d_dl, t->d_loss_b,
+                 t->d_part);
   for (hipEvent_t e : t->ev)
     if (e) (void)hipEventDestroy(e);
   delete t;
@@ -908,12 +901,12 @@ int gpd_hip_train_set_state(gpd_hip_trainer *t, const float *const tensors[8]) {
       return GPD_ERR_INVALID;
     }
   for (int i = 0; i < 8; i++) std::memcpy(t->h_all.data() + t->off[i], tensors[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
-  HIP_TRY(hipSetDevice(t->device));
+  HIP_RET(hipSetDevice(t->device));
   const size_t bytes = t->off[8] * sizeof(float);
-  HIP_TRY(hipMemcpyAsync(t->d_p, t->h_all.data(), bytes, hipMemcpyHostToDevice, t->stream));
-  HIP_TRY(hipMemsetAsync(t->d_m, 0, bytes, t->stream));
-  if (t->d_v) HIP_TRY(hipMemsetAsync(t->d_v, 0, bytes, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
+  HIP_RET(hipMemcpyAsync(t->d_p, t->h_all.data(), bytes, hipMemcpyHostToDevice, t->stream));
+  HIP_RET(hipMemsetAsync(t->d_m, 0, bytes, t->stream));
+  if (t->d_v) HIP_RET(hipMemsetAsync(t->d_v, 0, bytes, t->stream));
+  HIP_RET(hipStreamSynchronize(t->stream));
   t->step = 0;
   return GPD_OK;
 }
@@ -928,9 +921,9 @@ int gpd_hip_train_get_state(gpd_hip_trainer *t, float *const tensors[8]) {
       set_error("gpd_hip_train_get_state: tensor %d is null", i);
       return GPD_ERR_INVALID;
     }
-  HIP_TRY(hipSetDevice(t->device));
-  HIP_TRY(hipMemcpyAsync(t->h_all.data(), t->d_p, t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
+  HIP_RET(hipSetDevice(t->device));
+  HIP_RET(hipMemcpyAsync(t->h_all.data(), t->d_p, t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  HIP_RET(hipStreamSynchronize(t->stream));
   for (int i = 0; i < 8; i++) std::memcpy(tensors[i], t->h_all.data() + t->off[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
   return GPD_OK;
 }
@@ -975,13 +968,13 @@ int gpd_hip_train_get_solver_state(gpd_hip_trainer *t, float *const m[8], float 
       set_error("gpd_hip_train_get_solver_state: tensor %d is null", i);
       return GPD_ERR_INVALID;
     }
-  HIP_TRY(hipSetDevice(t->device));
+  HIP_RET(hipSetDevice(t->device));
   const float *src[2] = {t->d_m, t->d_v};
   float *const *dst[2] = {m, v};
   for (int b = 0; b < 2; b++) {
     if (!src[b]) continue;
-    HIP_TRY(hipMemcpyAsync(t->h_all.data(), src[b], t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
+    HIP_RET(hipMemcpyAsync(t->h_all.data(), src[b], t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    HIP_RET(hipStreamSynchronize(t->stream));
     for (int i = 0; i < 8; i++) std::memcpy(dst[b][i], t->h_all.data() + t->off[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
   }
   *count = t->step;
@@ -1000,13 +993,13 @@ int gpd_hip_train_set_solver_state(gpd_hip_trainer *t, const float *const m[8], 
         set_error("gpd_hip_train_set_solver_state: buffer %d, tensor %d is null or holds a non-finite value", b, i);
         return GPD_ERR_INVALID;
       }
-  HIP_TRY(hipSetDevice(t->device));
+  HIP_RET(hipSetDevice(t->device));
   float *dst[2] = {t->d_m, t->d_v};
   for (int b = 0; b < 2; b++) {
     if (!src[b]) continue;
     for (int i = 0; i < 8; i++) std::memcpy(t->h_all.data() + t->off[i], src[b][i], (t->off[i + 1] - t->off[i]) * sizeof(float));
-    HIP_TRY(hipMemcpyAsync(dst[b], t->h_all.data(), t->off[8] * sizeof(float), hipMemcpyHostToDevice, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
+    HIP_RET(hipMemcpyAsync(dst[b], t->h_all.data(), t->off[8] * sizeof(float), hipMemcpyHostToDevice, t->stream));
+    HIP_RET(hipStreamSynchronize(t->stream));
   }
   t->step = count;
   return GPD_OK;
@@ -1027,18 +1020,16 @@ int gpd_hip_train_set_data(gpd_hip_trainer *t, int which, const uint8_t *images_
     set_error("gpd_hip_train_set_data: %d images of %d channels are %zu bytes; a resident set holds 4 GiB", n, t->C, bytes);
     return GPD_ERR_CAPACITY;
   }
-  HIP_TRY(hipSetDevice(t->device));
-  HIP_TRY(hipStreamSynchronize(t->stream));
-  if (t->d_img[which]) HIP_TRY(hipFree(t->d_img[which]));
-  if (t->d_lab[which]) HIP_TRY(hipFree(t->d_lab[which]));
-  t->d_img[which] = t->d_lab[which] = nullptr;
+  HIP_RET(hipSetDevice(t->device));
+  HIP_RET(hipStreamSynchronize(t->stream));
+  device_release(t->d_img[which], t->d_lab[which]);
   t->n[which] = t->cap[which] = 0;
   if (n == 0) return GPD_OK;
-  HIP_TRY(dev_alloc(&t->d_img[which], bytes));
-  HIP_TRY(dev_alloc(&t->d_lab[which], (size_t)n));
-  HIP_TRY(hipMemcpyAsync(t->d_img[which], images_hwc, bytes, hipMemcpyHostToDevice, t->stream));
-  HIP_TRY(hipMemcpyAsync(t->d_lab[which], labels, (size_t)n, hipMemcpyHostToDevice, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
+  HIP_RET(device_alloc(t->d_img[which], bytes));
+  HIP_RET(device_alloc(t->d_lab[which], (size_t)n));
+  HIP_RET(hipMemcpyAsync(t->d_img[which], images_hwc, bytes, hipMemcpyHostToDevice, t->stream));
+  HIP_RET(hipMemcpyAsync(t->d_lab[which], labels, (size_t)n, hipMemcpyHostToDevice, t->stream));
+  HIP_RET(hipStreamSynchronize(t->stream));
   t->n[which] = t->cap[which] = n;
   return GPD_OK;
 }
@@ -1069,13 +1060,13 @@ int gpd_hip_train_append_data(gpd_hip_trainer *t, int which, const uint8_t *imag
   int rc = check_labels("gpd_hip_train_append_data", labels, n);
   if (rc) return rc;
   if (n == 0) return GPD_OK;
-  HIP_TRY(hipSetDevice(t->device));
+  HIP_RET(hipSetDevice(t->device));
   rc = pool_grow("gpd_hip_train_append_data", t, which, n);
   if (rc) return rc;
   const size_t ib = image_bytes(t), at = (size_t)t->n[which];
-  HIP_TRY(hipMemcpyAsync(t->d_img[which] + at * ib, images_hwc, (size_t)n * ib, hipMemcpyHostToDevice, t->stream));
-  HIP_TRY(hipMemcpyAsync(t->d_lab[which] + at, labels, (size_t)n, hipMemcpyHostToDevice, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
+  HIP_RET(hipMemcpyAsync(t->d_img[which] + at * ib, images_hwc, (size_t)n * ib, hipMemcpyHostToDevice, t->stream));
+  HIP_RET(hipMemcpyAsync(t->d_lab[which] + at, labels, (size_t)n, hipMemcpyHostToDevice, t->stream));
+  HIP_RET(hipStreamSynchronize(t->stream));
   t->n[which] += n;
   return GPD_OK;
 }
@@ -1088,10 +1079,10 @@ int gpd_hip_train_get_data(gpd_hip_trainer *t, int which, int first, int count, 
   }
   if (count == 0) return GPD_OK;
   const size_t ib = image_bytes(t);
-  HIP_TRY(hipSetDevice(t->device));
-  HIP_TRY(hipMemcpyAsync(images_hwc, t->d_img[which] + (size_t)first * ib, (size_t)count * ib, hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipMemcpyAsync(labels, t->d_lab[which] + (size_t)first, (size_t)count, hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
+  HIP_RET(hipSetDevice(t->device));
+  HIP_RET(hipMemcpyAsync(images_hwc, t->d_img[which] + (size_t)first * ib, (size_t)count * ib, hipMemcpyDeviceToHost, t->stream));
+  HIP_RET(hipMemcpyAsync(labels, t->d_lab[which] + (size_t)first, (size_t)count, hipMemcpyDeviceToHost, t->stream));
+  HIP_RET(hipStreamSynchronize(t->stream));
   return GPD_OK;
 }
 
@@ -1117,11 +1108,11 @@ int gpd_hip_train_reorder(gpd_hip_trainer *t, int which, int first, int count, c
     set_error("gpd_hip_train_reorder: %d images are more than one launch takes", count);
     return GPD_ERR_CAPACITY;
   }
-  HIP_TRY(hipSetDevice(t->device));
+  HIP_RET(hipSetDevice(t->device));
   // the scratch block: the range's images | its order | its labels
   const size_t off_order = (size_t)count * ib, off_lab = off_order + ((size_t)count * sizeof(int32_t) + 15) / 16 * 16;
   uint8_t *scratch = nullptr;
-  if (dev_alloc(&scratch, off_lab + (size_t)count) != hipSuccess) {
+  if (device_alloc(scratch, off_lab + (size_t)count) != hipSuccess) {
     (void)hipGetLastError();
     set_error("gpd_hip_train_reorder: no room for a scratch block of %zu bytes", off_lab + (size_t)count);
     return GPD_ERR_CAPACITY;
@@ -1136,7 +1127,7 @@ int gpd_hip_train_reorder(gpd_hip_trainer *t, int which, int first, int count, c
     e = hipGetLastError();
   }
   const hipError_t e2 = hipStreamSynchronize(t->stream);
-  (void)hipFree(scratch);
+  device_release(scratch);
   if (e != hipSuccess || e2 != hipSuccess) {
     set_error("gpd_hip_train_reorder: %s", hipGetErrorString(e != hipSuccess ? e : e2));
     return GPD_ERR_HIP;
@@ -1171,11 +1162,11 @@ int gpd_hip_train_steps(gpd_hip_trainer *t, const int32_t *indices, int num_step
   }
   rc = check_indices("gpd_hip_train_steps", indices, (long long)num_steps * batch, t->n[0]);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(t->device));
+  HIP_RET(hipSetDevice(t->device));
   const int per = kIdxCap / batch;
   for (int s0 = 0; s0 < num_steps; s0 += per) {
     const int ns = std::min(per, num_steps - s0);
-    HIP_TRY(hipMemcpyAsync(t->d_idx, indices + (size_t)s0 * batch, (size_t)ns * batch * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
+    HIP_RET(hipMemcpyAsync(t->d_idx, indices + (size_t)s0 * batch, (size_t)ns * batch * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
     for (int s = 0; s < ns; s++) {
       int k = 0;
       const int *idx = t->d_idx + (size_t)s * batch;
@@ -1183,9 +1174,9 @@ int gpd_hip_train_steps(gpd_hip_trainer *t, const int32_t *indices, int num_step
       enqueue_backward(t, idx, batch, false, k);
       enqueue_update(t, false, k);
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(losses + s0, t->d_loss, (size_t)ns * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
+    HIP_RET(hipGetLastError());
+    HIP_RET(hipMemcpyAsync(losses + s0, t->d_loss, (size_t)ns * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    HIP_RET(hipStreamSynchronize(t->stream));
   }
   return GPD_OK;
 }
@@ -1204,15 +1195,15 @@ int gpd_hip_train_gradients(gpd_hip_trainer *t, const int32_t *indices, int batc
     }
   rc = check_indices("gpd_hip_train_gradients", indices, batch, t->n[0]);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(t->device));
-  HIP_TRY(hipMemcpyAsync(t->d_idx, indices, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
+  HIP_RET(hipSetDevice(t->device));
+  HIP_RET(hipMemcpyAsync(t->d_idx, indices, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
   int k = 0;
   enqueue_forward(t, 0, t->d_idx, batch, true, t->d_loss, false, k);
   enqueue_backward(t, t->d_idx, batch, false, k);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(t->h_all.data(), t->d_g, t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipMemcpyAsync(loss, t->d_loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
+  HIP_RET(hipGetLastError());
+  HIP_RET(hipMemcpyAsync(t->h_all.data(), t->d_g, t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  HIP_RET(hipMemcpyAsync(loss, t->d_loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  HIP_RET(hipStreamSynchronize(t->stream));
   for (int i = 0; i < 8; i++) std::memcpy(grads[i], t->h_all.data() + t->off[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
   return GPD_OK;
 }
@@ -1228,12 +1219,12 @@ int gpd_hip_train_apply(gpd_hip_trainer *t, const float *const grads[8]) {
       return GPD_ERR_INVALID;
     }
   for (int i = 0; i < 8; i++) std::memcpy(t->h_all.data() + t->off[i], grads[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
-  HIP_TRY(hipSetDevice(t->device));
-  HIP_TRY(hipMemcpyAsync(t->d_g, t->h_all.data(), t->off[8] * sizeof(float), hipMemcpyHostToDevice, t->stream));
+  HIP_RET(hipSetDevice(t->device));
+  HIP_RET(hipMemcpyAsync(t->d_g, t->h_all.data(), t->off[8] * sizeof(float), hipMemcpyHostToDevice, t->stream));
   int k = 0;
   enqueue_update(t, false, k);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(t->stream));
+  HIP_RET(hipGetLastError());
+  HIP_RET(hipStreamSynchronize(t->stream));
   return GPD_OK;
 }
 
@@ -1253,22 +1244,22 @@ int gpd_hip_train_eval(gpd_hip_trainer *t, int which, const int32_t *indices, in
     set_error("gpd_hip_train_eval: %d images asked for, set %d holds %d", n, which, t->n[which]);
     return GPD_ERR_INVALID;
   }
-  HIP_TRY(hipSetDevice(t->device));
+  HIP_RET(hipSetDevice(t->device));
   std::vector<int32_t> idx((size_t)n);
   std::vector<uint8_t> lab((size_t)n);
   for (int i = 0; i < n; i++) idx[(size_t)i] = indices ? indices[i] : i;
   for (int i0 = 0; i0 < n; i0 += t->maxb) {
     const int B = std::min(t->maxb, n - i0);
-    HIP_TRY(hipMemcpyAsync(t->d_idx, idx.data() + i0, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
+    HIP_RET(hipMemcpyAsync(t->d_idx, idx.data() + i0, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
     int k = 0;
     enqueue_forward(t, which, t->d_idx, B, false, nullptr, false, k);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(logits + 2 * (size_t)i0, t->d_logits, (size_t)B * 2 * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
+    HIP_RET(hipGetLastError());
+    HIP_RET(hipMemcpyAsync(logits + 2 * (size_t)i0, t->d_logits, (size_t)B * 2 * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    HIP_RET(hipStreamSynchronize(t->stream));
   }
   // the labels of the set come back once; argmax as torch.max: the first maximum
   std::vector<uint8_t> all((size_t)std::max(t->n[which], 1));
-  if (n > 0) HIP_TRY(hipMemcpy(all.data(), t->d_lab[which], (size_t)t->n[which], hipMemcpyDeviceToHost));
+  if (n > 0) HIP_RET(hipMemcpy(all.data(), t->d_lab[which], (size_t)t->n[which], hipMemcpyDeviceToHost));
   int correct = 0;
   for (int i = 0; i < n; i++) correct += (logits[2 * i + 1] > logits[2 * i] ? 1 : 0) == all[(size_t)idx[(size_t)i]];
   *num_correct = correct;
@@ -1284,16 +1275,16 @@ int gpd_hip_train_step_timed(gpd_hip_trainer *t, const int32_t *indices, int bat
   }
   rc = check_indices("gpd_hip_train_step_timed", indices, batch, t->n[0]);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(t->device));
-  HIP_TRY(hipMemcpyAsync(t->d_idx, indices, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
+  HIP_RET(hipSetDevice(t->device));
+  HIP_RET(hipMemcpyAsync(t->d_idx, indices, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
   int k = 0;
   mark(t, true, k);
   enqueue_forward(t, 0, t->d_idx, batch, true, t->d_loss, true, k);
   enqueue_backward(t, t->d_idx, batch, true, k);
   enqueue_update(t, true, k);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(t->stream));
-  for (int i = 0; i + 1 < k; i++) HIP_TRY(hipEventElapsedTime(&ms[i], t->ev[i], t->ev[i + 1]));
+  HIP_RET(hipGetLastError());
+  HIP_RET(hipStreamSynchronize(t->stream));
+  for (int i = 0; i + 1 < k; i++) HIP_RET(hipEventElapsedTime(&ms[i], t->ev[i], t->ev[i + 1]));
   *num = k - 1;
   return GPD_OK;
 }

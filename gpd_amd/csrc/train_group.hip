@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "context.h"
+#include "buffers.h"
 #include "group_model.h"
 #include "train.h"
 
@@ -265,8 +266,8 @@ int gpd_hip_train_group_create(gpd_hip_trainer *const *trainers, int num, gpd_hi
   hipError_t e = hipSuccess;
   for (int r = 0; r < num && e == hipSuccess; r++) {
     e = use_device(g, r);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&g->gather[(size_t)r]), std::max<size_t>((size_t)(num - 1) * g->row, 4) * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&g->d_count[(size_t)r]), sizeof(unsigned long long));
+    if (e == hipSuccess) e = device_alloc(g->gather[(size_t)r], std::max<size_t>((size_t)(num - 1) * g->row, 4));
+    if (e == hipSuccess) e = device_alloc(g->d_count[(size_t)r], 1);
     for (int j = 0; j < 3 && e == hipSuccess; j++) e = hipEventCreateWithFlags(&g->ev[(size_t)(j * num + r)], hipEventDisableTiming);
   }
   if (e != hipSuccess) {
@@ -285,8 +286,7 @@ void gpd_hip_train_group_destroy(gpd_hip_train_group *g) {
   (void)sync_all(g);
   for (int r = 0; r < g->G; r++) {
     (void)use_device(g, r);
-    if (g->gather[(size_t)r]) (void)hipFree(g->gather[(size_t)r]);
-    if (g->d_count[(size_t)r]) (void)hipFree(g->d_count[(size_t)r]);
+    device_release(g->gather[(size_t)r], g->d_count[(size_t)r]);
     for (int j = 0; j < 3; j++)
       if (g->ev[(size_t)(j * g->G + r)]) (void)hipEventDestroy(g->ev[(size_t)(j * g->G + r)]);
   }
