@@ -707,8 +707,12 @@ __global__ __launch_bounds__(IMG_THREADS) void shadow_image_any_kernel(ImgParams
 // grasp_image_kernel: normals (3) and depth (1) channels per projection of one candidate
 // (createNormalsImage / createDepthImage, image_strategy.cpp:124-190).
 // ---------------------------------------------------------------------------
+// The small instantiation runs every projection of its candidate.  The large one is entered once per (candidate,
+// projection) item of the overflow queue: `item_pr` is the one projection it runs; the points are collected per item
+// (the projections are independent behind that), and what happens once per CANDIDATE — the capacity report, the flag —
+// is left to the item of projection 0.
 template <bool BIG>
-__device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG> &S, const int cand) {
+__device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG> &S, const int cand, const int item_pr = 0) {
   constexpr int CAP = BIG ? PT_CAP_BIG : PT_CAP;
   unsigned long long t_last = __builtin_readcyclecounter();
   const ImgConsts &K = c_img;
@@ -822,7 +826,7 @@ __device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG
     // indices do not fit the 16-bit segment table the small instantiation lists them in (the reference has no limit,
     // hand_search.cpp:178; the large one keeps them 32 bits wide): queue the candidate for the large one
     // (nothing has been written yet), or report it when this already is the large one
-    if (tid == 0) {
+    if (tid == 0 && (!BIG || item_pr == 0)) {
       if (!BIG && P.pts_overflow_list)
         P.pts_overflow_list[atomicAdd(P.pts_overflow_count, 1)] = cand;
       else
@@ -873,7 +877,8 @@ __device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG
   // moved to the kernel's entry): a thread counts and places exactly the entries it has written itself (e = tid + k *
   // IMG_THREADS in all three loops), and the index list in `place`, which other threads read above, is rewritten only
   // behind the barrier of the count.
-  for (int pr = 0; pr < K.nproj; pr++) {
+  const int pr_first = BIG ? item_pr : 0, pr_end = BIG ? item_pr + 1 : K.nproj;
+  for (int pr = pr_first; pr < pr_end; pr++) {
     // Nine barriers per projection (fifteen before): count | scan (2) | place and list | walk | listing of the live
     // groups | min / max | staging | copy-out.
     // (the cell counters are zero: cleared at the entry, then by the copy-out of the previous projection)
@@ -1106,17 +1111,22 @@ __device__ __forceinline__ void grasp_image_body(const ImgParams &P, SmemPts<BIG
     __syncthreads();
     TICK(8);
   }
-  if (tid == 0 && S.flag) atomicOr(P.status, S.flag);
+  if (tid == 0 && S.flag && (!BIG || item_pr == 0)) atomicOr(P.status, S.flag);
 }
 
 template <bool BIG>
 __global__ __launch_bounds__(IMG_THREADS, BIG ? 2 : 4) void grasp_image_kernel(ImgParams P) {
   __shared__ SmemPts<BIG> S;
   if constexpr (BIG) {
-    const int count = *P.cand_count;
-    for (int q = blockIdx.x; q < count; q += gridDim.x) {
-      __syncthreads();  // the previous candidate's LDS is dead
-      grasp_image_body<true>(P, S, P.cand_list[q]);
+    // the unit of the walk is one projection of one queued candidate: a queue of ten is thirty workgroups' work, not ten
+    // workgroups' of three projections in a row (59 -> 30 us alone on the chip for the benchmark's ten; beside the shadow
+    // kernel a workgroup waits for a CU with this much LDS free, whichever way the queue is cut: profiles/NOTES.md N)
+    const int np = c_img.nproj;
+    const int items = *P.cand_count * np;
+    for (int it = blockIdx.x; it < items; it += gridDim.x) {
+      __syncthreads();  // the previous item's LDS is dead
+      const int q = it / np;
+      grasp_image_body<true>(P, S, P.cand_list[q], it - q * np);
     }
   } else {
     const int cand = xcd_candidate(P.num_cand);
@@ -1150,13 +1160,15 @@ struct SetParams {
 // MODE 0: the default region (86^3 bits, built in LDS, written out once); 1: WIDE (128^3 bits = 256 KB: straight into the
 // set's global row, which the host has cleared); 2: a region of run-time size (c_img.set_sd), also straight into global memory —
 // image volumes of any size the general shadow kernel below takes
+// (MODE 0 is held to the 64 registers at which two workgroups — their bitsets fill the LDS between them — share a CU: eight waves per SIMD)
 template <int MODE>
-__global__ __launch_bounds__(SET_THREADS) void shadow_set_kernel(SetParams P) {
+__global__ __launch_bounds__(SET_THREADS, MODE == 0 ? 8 : 1) void shadow_set_kernel(SetParams P) {
   constexpr bool WIDE = MODE != 0;
   const ImgConsts &K = c_img;
   const int SD = MODE == 2 ? K.set_sd : Vox<MODE == 1>::SD, SR = MODE == 2 ? K.set_sr : Vox<MODE == 1>::SR;
   const int SETWORDS = MODE == 2 ? (int)(((long long)SD * SD * SD + 31) / 32) : Vox<MODE == 1>::SETWORDS;
   __shared__ uint32_t lds_bits[WIDE ? 1 : Vox<false>::SETWORDS];
+  __shared__ int s_bb[6];  // MODE 0: x0, x1, y0, y1, z0, z1 of the candidates' windows, in region voxels
   const int set = blockIdx.x;
   const int tid = threadIdx.x;
   const int slot_s = P.set_meta[8 * set + 0];
@@ -1170,14 +1182,41 @@ __global__ __launch_bounds__(SET_THREADS) void shadow_set_kernel(SetParams P) {
   uint32_t *out = P.set_bits + (size_t)set * SETWORDS;
   uint32_t *bits = WIDE ? out : lds_bits;
   if (!WIDE) {
+    if (tid == 0) {
+      s_bb[0] = s_bb[2] = s_bb[4] = SD;
+      s_bb[1] = s_bb[3] = s_bb[5] = -1;
+    }
     for (int w = tid; w < SETWORDS; w += SET_THREADS) lds_bits[w] = 0u;
     __syncthreads();
   }
   const double *smp = P.frames + 12 * (size_t)slot_s;
-  int ox = (int)floor(smp[0] * K.voxel_mult) - SR, oy = (int)floor(smp[1] * K.voxel_mult) - SR,
-      oz = (int)floor(smp[2] * K.voxel_mult) - SR;
-  // opaque to the optimiser: it re-associated v - (floor - SR) into (v - floor) + SR, two operations per coordinate and draw
-  asm volatile("" : "+v"(ox), "+v"(oy), "+v"(oz));
+  const int org[3] = {(int)floor(smp[0] * K.voxel_mult) - SR, (int)floor(smp[1] * K.voxel_mult) - SR,
+                      (int)floor(smp[2] * K.voxel_mult) - SR};
+  if (!WIDE) {
+    // The voxel bounding box of the windows shadow_image_kernel opens for the set's candidates, floor(min) - 1 ..
+    // floor(max) + 1 per axis (the arithmetic of shadow_image_body's S.vorg / v1), here relative to the region.  Nothing
+    // outside it is ever read with effect: only its rows are written out below, and a bit survives a reader only through
+    // the exact box test of its voxel.  So the rays are tested against it BEFORE they are drawn.
+    if (tid < P.slots && P.hand_cand[(size_t)slot_s * P.slots + tid] >= 0) {
+      const gpd_hand &H = P.hands[(size_t)slot_s * P.slots + tid];
+      const double lo[3] = {H.bottom, H.center - K.half_od, -1.0 * K.vol_height};
+      const double hi[3] = {H.bottom + K.vol_depth, H.center + K.half_od, K.vol_height};
+      double wmin[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, wmax[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+      for (int k = 0; k < 8; k++) {
+        const double bx = (k & 1) ? hi[0] : lo[0], by = (k & 2) ? hi[1] : lo[1], bz = (k & 4) ? hi[2] : lo[2];
+        for (int a = 0; a < 3; a++) {
+          const double w = H.sample[a] + H.frame[3 * a] * bx + H.frame[3 * a + 1] * by + H.frame[3 * a + 2] * bz;
+          wmin[a] = fmin(wmin[a], w);
+          wmax[a] = fmax(wmax[a], w);
+        }
+      }
+      for (int a = 0; a < 3; a++) {
+        atomicMin(&s_bb[2 * a], (int)floor(wmin[a] * K.voxel_mult) - 1 - org[a]);
+        atomicMax(&s_bb[2 * a + 1], (int)floor(wmax[a] * K.voxel_mult) + 1 - org[a]);
+      }
+    }
+    __syncthreads();
+  }
   // shadow_vec = shadow_length * (center - view_point) / norm (hand_set.cpp:147-150)
   const double *cen = P.centers + 3 * (size_t)slot_s;
   double vec[3];
@@ -1185,9 +1224,11 @@ __global__ __launch_bounds__(SET_THREADS) void shadow_set_kernel(SetParams P) {
   const double nrm = sqrt(vec[0] * vec[0] + vec[1] * vec[1] + vec[2] * vec[2]);
   for (int r = 0; r < 3; r++) vec[r] = K.shadow_length * vec[r] / nrm;
   uint32_t state = lcg_jump(0u, off + (unsigned long long)tid * (unsigned)K.num_shadow);
-  for (int i = tid; i < N; i += SET_THREADS) {
-    const double p0 = (double)nn[0 * P.cap + i], p1 = (double)nn[1 * P.cap + i], p2 = (double)nn[2 * P.cap + i];
-    uint32_t st = state;
+  int ox = org[0], oy = org[1], oz = org[2];
+  // opaque to the optimiser: it re-associated v - (floor - SR) into (v - floor) + SR, two operations per coordinate and draw
+  asm volatile("" : "+v"(ox), "+v"(oy), "+v"(oz));
+  // the num_shadow draws of one ray: point p, LCG state st at the ray's first draw
+  auto draw_ray = [&](const double p0, const double p1, const double p2, uint32_t st) {
     for (int k = 0; k < K.num_shadow; k++) {
       const double t = (double)(int)lcg_step(st) * K.rand_inv;
       const int vx = (int)((p0 + t * vec[0]) * K.voxel_mult) - ox;
@@ -1201,38 +1242,96 @@ __global__ __launch_bounds__(SET_THREADS) void shadow_set_kernel(SetParams P) {
         atomicOr(&bits[bit >> 5], 1u << (bit & 31));
       }
     }
-    state = K.stride_a * state + K.stride_c;  // advance by SET_THREADS * num_shadow draws
-  }
-  if (!WIDE) {
-    // Written out: only the rows (lines along z) inside the voxel bounding box of the set's candidate boxes, one voxel of margin
-    // around each — shadow_image_kernel reads the rows of a candidate's window and keeps the bits its box test passes, and no bit
-    // outside a box passes it, so whatever an earlier launch left in the rest of the row is never seen (129 MB of bitsets per
-    // 5000 candidates were written in full before: half of the image stage's excess HBM traffic).
-    __shared__ int s_bb[4];  // x0, x1, y0, y1 in region voxels
-    if (tid == 0) {
-      s_bb[0] = s_bb[2] = SD;
-      s_bb[1] = s_bb[3] = -1;
+  };
+  if constexpr (MODE == 0) {
+    // ---- Rays that cannot reach the candidates' windows are dropped, the others packed 64 to a wave before they are drawn.
+    // A draw sets voxel trunc(y_a) - org_a per axis, y_a = (p_a + t * vec_a) * voxel_mult, and is seen only if that index is
+    // in [b0_a, b1_a] (s_bb clamped to the region), for which y_a must lie in (b0_a + org_a - 1, b1_a + org_a + 1) whichever
+    // way the conversion truncates.  The test takes one voxel more on either side, W_a = [b0_a + org_a - 2, b1_a + org_a + 2],
+    // against q_a + t * d_a with q = p * voxel_mult, d = vec * voxel_mult: that differs from y_a by rounding alone, ~1e-13
+    // voxels for coordinates of metres, and so do the ends of the parameter interval (an error e in t moves the point by
+    // e * d_a = ~1e-16 * |W_a - q_a|) — the spare voxel is 1e13 times that, no rounding question arises.
+    // The parameter: lcg_step returns ((int32)s >> 16) & 0x7fff, an integer 0 .. 32767; rand_inv = RN(1 / 32767), so
+    // t = (int)lcg_step(st) * rand_inv takes 32768 values from 0 to RN(32767 * RN(1 / 32767)), which is 1 to within an ulp:
+    // the range tested is [0, 1], the ulp again ~1e-15 voxels.
+    // An axis whose |d_a| < 1e-9 voxels (a ray parallel to the slab; d_a == 0 exactly when the view point lies on a coordinate
+    // axis through the centre) is not divided by: the point moves < 1e-9 voxels along it, so it is in the slab W_a or not.
+    double wlo[3], whi[3], dinv[3];
+    bool par[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      // s_bb clamped to the region (no candidate: b0 > b1 + 4, every ray misses)
+      const int b0 = max(s_bb[2 * a], 0), b1 = min(s_bb[2 * a + 1], SD - 1);
+      wlo[a] = (double)(b0 + org[a] - 2);
+      whi[a] = (double)(b1 + org[a] + 2);
+      const double d = vec[a] * K.voxel_mult;
+      par[a] = !(fabs(d) >= 1e-9);
+      dinv[a] = par[a] ? 0.0 : 1.0 / d;
     }
-    __syncthreads();
-    if (tid < P.slots && P.hand_cand[(size_t)slot_s * P.slots + tid] >= 0) {
-      const gpd_hand &H = P.hands[(size_t)slot_s * P.slots + tid];
-      const double lo[3] = {H.bottom, H.center - K.half_od, -1.0 * K.vol_height};
-      const double hi[3] = {H.bottom + K.vol_depth, H.center + K.half_od, K.vol_height};
-      double wmin[2] = {DBL_MAX, DBL_MAX}, wmax[2] = {-DBL_MAX, -DBL_MAX};
-      for (int k = 0; k < 8; k++) {
-        const double bx = (k & 1) ? hi[0] : lo[0], by = (k & 2) ? hi[1] : lo[1], bz = (k & 4) ? hi[2] : lo[2];
-        for (int a = 0; a < 2; a++) {
-          const double w = H.sample[a] + H.frame[3 * a] * bx + H.frame[3 * a + 1] * by + H.frame[3 * a + 2] * bz;
-          wmin[a] = fmin(wmin[a], w);
-          wmax[a] = fmax(wmax[a], w);
+    // The survivors of successive rounds gather in registers: `pend` of them wait in lanes 0 .. pend - 1 of the wave (pend
+    // < 64, the same in every lane).  A round's lanes are permuted as a whole — its k survivors, in lane order, to lanes
+    // pend, pend + 1, ... (mod 64), the others behind them — so that one ds_permute per register moves them (no LDS memory:
+    // the two resident workgroups leave none).  When 64 have gathered they are drawn with every lane live; what is left
+    // at the end is drawn once more.  The draws are OR-ed into the bitset, so their order is free, and a ray's LCG state
+    // depends on its index alone: a dropped ray costs nothing else.
+    const int lane = tid & 63;
+    double g0 = 0.0, g1 = 0.0, g2 = 0.0;  // the gathered rays
+    uint32_t gs = 0u;
+    int pend = 0;
+    for (int base = 0; base < N; base += SET_THREADS) {
+      const int i = base + tid, ic = i < N ? i : N - 1;
+      const double p0 = (double)nn[0 * P.cap + ic], p1 = (double)nn[1 * P.cap + ic], p2 = (double)nn[2 * P.cap + ic];
+      const double pp[3] = {p0, p1, p2};
+      bool keep = i < N;
+      double t0 = 0.0, t1 = 1.0;
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        const double q = pp[a] * K.voxel_mult;
+        if (par[a]) {
+          keep = keep && q >= wlo[a] && q <= whi[a];
+        } else {
+          const double ta = (wlo[a] - q) * dinv[a], tb = (whi[a] - q) * dinv[a];
+          t0 = fmax(t0, fmin(ta, tb));
+          t1 = fmin(t1, fmax(ta, tb));
         }
       }
-      // the window shadow_image_kernel opens for this box: floor(min) - 1 .. floor(max) + 1, here relative to the region
-      atomicMin(&s_bb[0], (int)floor(wmin[0] * K.voxel_mult) - 1 - ox);
-      atomicMax(&s_bb[1], (int)floor(wmax[0] * K.voxel_mult) + 1 - ox);
-      atomicMin(&s_bb[2], (int)floor(wmin[1] * K.voxel_mult) - 1 - oy);
-      atomicMax(&s_bb[3], (int)floor(wmax[1] * K.voxel_mult) + 1 - oy);
+      keep = keep && t0 <= t1;
+      const unsigned long long ballot = __ballot(keep);
+      const int k = __popcll(ballot);
+      if (k) {  // (the same in every lane of the wave)
+        const int below = __popcll(ballot & ((1ull << lane) - 1ull));
+        const int dest = ((keep ? pend + below : pend + k + (lane - below)) & 63) << 2;
+        auto move = [dest](const double x) {
+          return __hiloint2double(__builtin_amdgcn_ds_permute(dest, __double2hiint(x)),
+                                  __builtin_amdgcn_ds_permute(dest, __double2loint(x)));
+        };
+        const double a0 = move(p0), a1 = move(p1), a2 = move(p2);
+        const uint32_t as = (uint32_t)__builtin_amdgcn_ds_permute(dest, (int)state);
+        const bool arrived = ((lane - pend) & 63) < k;  // this lane received one of the round's survivors
+        if (pend + k < 64) {
+          if (arrived) g0 = a0, g1 = a1, g2 = a2, gs = as;
+          pend += k;
+        } else {
+          if (lane >= pend) g0 = a0, g1 = a1, g2 = a2, gs = as;  // (all of them have: k >= 64 - pend)
+          draw_ray(g0, g1, g2, gs);
+          pend += k - 64;
+          if (lane < pend) g0 = a0, g1 = a1, g2 = a2, gs = as;  // the survivors that wrapped round
+        }
+      }
+      state = K.stride_a * state + K.stride_c;  // advance by SET_THREADS * num_shadow draws
     }
+    if (lane < pend) draw_ray(g0, g1, g2, gs);
+  } else {
+    for (int i = tid; i < N; i += SET_THREADS) {
+      draw_ray((double)nn[0 * P.cap + i], (double)nn[1 * P.cap + i], (double)nn[2 * P.cap + i], state);
+      state = K.stride_a * state + K.stride_c;  // advance by SET_THREADS * num_shadow draws
+    }
+  }
+  if (!WIDE) {
+    // Written out: only the rows (lines along z) inside the x-y footprint of that bounding box — shadow_image_kernel reads
+    // the rows of a candidate's window and keeps the bits its box test passes, and no bit outside a box passes it, so
+    // whatever an earlier launch left in the rest of the row is never seen (129 MB of bitsets per 5000 candidates were
+    // written in full before: half of the image stage's excess HBM traffic).
     __syncthreads();
     const int x0 = max(s_bb[0], 0), x1 = min(s_bb[1], SD - 1), y0 = max(s_bb[2], 0), y1 = min(s_bb[3], SD - 1);
     if (x1 >= x0 && y1 >= y0) {
