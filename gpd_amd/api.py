@@ -246,6 +246,81 @@ def lenet_from_torch(state, channels, input_scale=1.0 / 256):
                 f1w=f1w, f1b=t["fc1.bias"].ravel().copy(), f2w=f2w, f2b=t["fc2.bias"].ravel().copy())
 
 
+class LenetShape(C.Structure):
+    """gpd_lenet_shape (include/gpd_hip.h): C -> conv1_out -> conv2_out -> fc1_out [-> fc2_out] -> 2; fc2_out = 0: no third
+    dense layer (pytorch/network.py::Net), > 0: NetCCFFF."""
+    _fields_ = [("channels", C.c_int32), ("conv1_out", C.c_int32), ("conv2_out", C.c_int32), ("fc1_out", C.c_int32), ("fc2_out", C.c_int32)]
+
+    def as_tuple(self):
+        return (self.channels, self.conv1_out, self.conv2_out, self.fc1_out, self.fc2_out)
+
+    def __repr__(self):
+        return "LenetShape(channels=%d, conv1_out=%d, conv2_out=%d, fc1_out=%d, fc2_out=%d)" % self.as_tuple()
+
+
+TORCH_NET_KEYS = TORCH_KEYS + ("fc3.weight", "fc3.bias")
+
+
+def lenet_shape_check(shape):
+    """gpd_hip_lenet_shape_check -> True when the shape is within the limits of the general route."""
+    return lib().gpd_hip_lenet_shape_check(C.byref(shape)) == 0
+
+
+def torch_net_arrays(state):
+    """A state dict of pytorch/network.py::Net or ::NetCCFFF of any widths -> (LenetShape, [8 or 10 contiguous f32 arrays in
+    torch layout, conv1.weight .. fc2.bias (.. fc3.bias)]).  The shape is read off the tensors; fc3.* keys select NetCCFFF.
+    Values and the `module.` prefix as in torch_state_arrays.  ValueError when the tensors do not fit one another."""
+    plain = {}
+    for k, v in state.items():
+        k = str(k)
+        plain[k[len("module."):] if k.startswith("module.") else k] = v
+    has3 = "fc3.weight" in plain or "fc3.bias" in plain
+    arrs = []
+    for k in (TORCH_NET_KEYS if has3 else TORCH_KEYS):
+        if k not in plain:
+            raise KeyError("state dict has no %r (keys: %s)" % (k, sorted(plain)))
+        v = plain[k]
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        arrs.append(np.ascontiguousarray(v, np.float32))
+    c1, c2, f1, f2 = arrs[0], arrs[2], arrs[4], arrs[6]
+    if c1.ndim != 4 or c1.shape[2:] != (5, 5) or c2.ndim != 4 or c2.shape[2:] != (5, 5) or f1.ndim != 2 or f2.ndim != 2:
+        raise ValueError("conv weights must be [out][in][5][5] and dense weights [out][in]: got %s"
+                         % [tuple(a.shape) for a in (c1, c2, f1, f2)])
+    F1, Cn = c1.shape[:2]
+    F2, H1 = c2.shape[0], f1.shape[0]
+    want = [(F1, Cn, 5, 5), (F1,), (F2, F1, 5, 5), (F2,), (H1, F2 * 144), (H1,)]
+    if has3:
+        H2 = f2.shape[0]
+        want += [(H2, H1), (H2,), (2, H2), (2,)]
+    else:
+        H2 = 0
+        want += [(2, H1), (2,)]
+    for k, a, w in zip(TORCH_NET_KEYS, arrs, want):
+        if tuple(a.shape) != w:
+            raise ValueError("%s has shape %s, %s expected from the other tensors" % (k, tuple(a.shape), w))
+    return LenetShape(int(Cn), int(F1), int(F2), int(H1), int(H2)), arrs
+
+
+def _pointer_table(arrs):
+    t = (C.c_void_p * 10)()
+    for i, a in enumerate(arrs):
+        t[i] = a.ctypes.data
+    return t
+
+
+def lenet_net_from_torch(state, input_scale=1.0 / 256):
+    """gpd_hip_lenet_net_from_torch: a state dict of Net / NetCCFFF (see torch_net_arrays) -> (LenetShape, the 8 or 10 tensors
+    in the layouts gpd_hip_set_lenet_net takes).  Host only."""
+    shape, arrs = torch_net_arrays(state)
+    outs = [np.zeros(a.size, np.float32) for a in arrs]
+    L = lib()
+    rc = L.gpd_hip_lenet_net_from_torch(C.byref(shape), float(input_scale), _pointer_table(arrs), _pointer_table(outs))
+    if rc != 0:
+        raise GpdHipError("libgpd_hip error %d: %s" % (rc, L.gpd_hip_last_error().decode()))
+    return shape, outs
+
+
 def bind_host_thread(device):
     """gpd_hip_bind_host_thread: the calling thread onto the CPUs of the device's NUMA node -> (node or -1, cpus)."""
     n = C.c_int(0)
@@ -261,6 +336,8 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_set_lenet_mode", "gpd_hip_lenet_debug", "gpd_hip_lenet_fast_tables", "gpd_hip_detect_sharded",
            "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals", "gpd_hip_sample_positions",
            "gpd_hip_set_lenet_conv_relu", "gpd_hip_lenet_from_torch",
+           "gpd_hip_lenet_shape_check", "gpd_hip_lenet_net_from_torch", "gpd_hip_set_lenet_net", "gpd_hip_lenet_net_debug",
+           "gpd_hip_lenet_net_info",
            "gpd_hip_upload_ground_truth", "gpd_hip_label_view", "gpd_hip_balance_view", "gpd_hip_sizeof_label_view_job",
            "gpd_hip_shuffle_orders", "gpd_hip_sis_proposals", "gpd_hip_sis_select", "gpd_hip_detect_sis", "gpd_hip_sizeof_sis_job",
            "gpd_hip_image_model", "gpd_hip_given_check", "gpd_hip_images_given", "gpd_hip_score_given",
@@ -334,6 +411,11 @@ def lib():
         L.gpd_hip_set_lenet_conv_relu.argtypes = [C.c_void_p, C.c_int]
         L.gpd_hip_lenet_from_torch.argtypes = [C.c_int, C.c_double] + [C.c_void_p] * 6
         L.gpd_hip_lenet_debug.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.gpd_hip_lenet_shape_check.argtypes = [C.POINTER(LenetShape)]
+        L.gpd_hip_lenet_net_from_torch.argtypes = [C.POINTER(LenetShape), C.c_double, C.c_void_p, C.c_void_p]
+        L.gpd_hip_set_lenet_net.argtypes = [C.c_void_p, C.POINTER(LenetShape), C.c_void_p]
+        L.gpd_hip_lenet_net_debug.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.gpd_hip_lenet_net_info.argtypes = [C.c_void_p, C.c_void_p]
         L.gpd_hip_replay_times.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
         L.gpd_hip_upload_ground_truth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.gpd_hip_label_view.argtypes = [C.c_void_p, C.POINTER(LabelViewJob)]
@@ -465,6 +547,34 @@ class Context:
         """A state dict of pytorch/network.py::Net (see lenet_from_torch) as the context's scoring network: weights + conv ReLUs."""
         self.set_lenet_weights(lenet_from_torch(state, self.params.image_num_channels, input_scale))
         self.set_lenet_conv_relu(True)
+
+    def set_lenet_net(self, state, input_scale=1.0 / 256, conv_relu=True):
+        """A state dict of pytorch/network.py::Net or ::NetCCFFF of any widths within the limits (LenetShape) as the context's
+        scoring network, on the shape-general route (exact f32 chains; set_lenet_mode is ignored by it).  set_lenet_weights /
+        set_lenet_torch return the context to the stock route.  -> the LenetShape"""
+        shape, arrs = lenet_net_from_torch(state, input_scale)
+        self._lenet_shape = shape
+        self._check(lib().gpd_hip_set_lenet_net(self._h, C.byref(shape), _pointer_table(arrs)))
+        self.set_lenet_conv_relu(conv_relu)
+        return shape
+
+    def lenet_net_debug(self, which, n):
+        """gpd_hip_lenet_net_debug: pool1 [n,F1,28,28] (0), pool2 [n,F2,12,12] (1), fc1 [n,H1] (2), fc2 [n,H2] (3) or the logits
+        [n,2] (4) of the last scoring call, which must have taken the general route (GpdHipError otherwise)."""
+        sh = getattr(self, "_lenet_shape", None)
+        if sh is None:
+            raise GpdHipError("lenet_net_debug: no network set by set_lenet_net")
+        n = int(n)
+        out = np.zeros({0: (n, sh.conv1_out, 28, 28), 1: (n, sh.conv2_out, 12, 12), 2: (n, sh.fc1_out), 3: (n, max(sh.fc2_out, 1)),
+                        4: (n, 2)}[int(which)], np.float32)
+        self._check(lib().gpd_hip_lenet_net_debug(self._h, int(which), n, _ptr(out)))
+        return out
+
+    def lenet_net_info(self):
+        """gpd_hip_lenet_net_info -> dict(chunk_images, scratch_bytes_per_image, lds_bytes, macs_per_image)"""
+        out = np.zeros(4, np.int64)
+        self._check(lib().gpd_hip_lenet_net_info(self._h, _ptr(out)))
+        return dict(chunk_images=int(out[0]), scratch_bytes_per_image=int(out[1]), lds_bytes=int(out[2]), macs_per_image=int(out[3]))
 
     def lenet_debug(self, which, n):
         """Test hook: pool1 (0), the flattened pool2 as bf16 planes (1) or ip1 transposed (2) of the last score() pass."""

@@ -312,6 +312,7 @@ void gpd_hip_destroy(gpd_hip_ctx *ctx) {
                   &ctx->lenet.f1w, &ctx->lenet.f1b, &ctx->lenet.f2w, &ctx->lenet.f2b, &ctx->lenet.c1wp, &ctx->lenet.c2wt};
   for (float **p : ws) device_release(*p);
   lenet_fast_free(ctx->lenet.fast);
+  lenet_net_free(ctx->lenet.net);
   for (auto &e : ctx->replay_events) (void)hipEventDestroy(e);
   if (ctx->pipe_stream) {
     (void)hipStreamSynchronize(ctx->pipe_stream);
@@ -390,6 +391,7 @@ int gpd_hip_set_lenet_weights(gpd_hip_ctx *ctx, int channels, const float *conv1
   // from here until every upload has succeeded the context holds NO weights: an update that fails half way (out of memory in
   // lenet_fast_prepare, say) leaves scoring calls refused with "LeNet weights not set" instead of launching on freed tables
   ctx->lenet.channels = 0;
+  lenet_net_free(ctx->lenet.net);  // back to the stock route (gpd_hip_set_lenet_net)
   for (auto &it : items) {
     device_release(*it.dst);
     HIP_RET(device_alloc(*it.dst, it.n));

@@ -38,10 +38,41 @@ void lenet_fast_free(LeNetFast &f);
 void lenet_fast_unblock_x(const unsigned short *blocked, int n, unsigned short *planes);  // test hook: [3][n][7200] from the blocked X
 hipError_t lenet_fast_prepare(LeNetFast &f, int channels, const float *c1w, const float *c2w, const float *f1w);
 
+// ---- the shape-general route (lenet_net.hip): any gpd_lenet_shape within the limits of gpd_hip_lenet_shape_check ----
+// A network installed by gpd_hip_set_lenet_net, in the kernels' layouts: conv weights k-major with the filters padded to
+// whole tiles of 32 and the k padded to an even count ([K + K % 2][Fpad], zeros in the padding: the tail of a chain);
+// dense weights k-major with the k padded to whole steps of 32 and the units to whole tiles of 128.
+struct LeNetNet {
+  bool active = false;  // every scoring call of the context takes this route (lenet_forward's first branch)
+  gpd_lenet_shape shape = {0, 0, 0, 0, 0};
+  float *c1wt = nullptr, *c1b = nullptr, *c2wt = nullptr, *c2b = nullptr;
+  float *f1w = nullptr, *f1b = nullptr, *f2w = nullptr, *f2b = nullptr;  // f2*: null when shape.fc2_out == 0
+  float *lw = nullptr, *lb = nullptr;                                    // the 2-logit layer [H][2], [2]
+  int f1pad = 0, f2pad = 0;          // conv filters in whole tiles of 32
+  int u1pad = 0, u2pad = 0;          // dense units in whole tiles of 128
+  int cb1 = 0, cb2 = 0;              // input channels a workgroup stages at a time (at most 8; even when there are several chunks)
+  int aoff1 = 0, aoff2 = 0;          // where the weight tile starts in a conv launch's dynamic LDS (behind the input rows)
+  int lds1 = 0, lds2 = 0, lds_max = 0;  // dynamic LDS of the two conv launches; the largest LDS of any kernel of the route
+  long long scratch_per_image = 0;   // bytes
+  long long macs_per_image = 0;
+  int chunk = 0;                     // images per pass
+};
+struct LeNetNetScratch {
+  int capacity = 0;  // images
+  bool ran = false;  // the lane's last scoring call took the general route (gpd_hip_lenet_net_debug)
+  float *pool1 = nullptr;  // [cap][F1][28][28]
+  float *pool2 = nullptr;  // [cap][144][F2]: pixel-major, fc1's k order
+  float *h1 = nullptr, *h2 = nullptr;  // [cap][ld]: ld = the units rounded up to a multiple of 4 (16-byte row reads)
+  float *logits = nullptr;             // [cap][2]
+};
+void lenet_net_free(LeNetNet &net);
+void lenet_net_scratch_free(LeNetNetScratch &s);
+
 struct LeNetWeights {
   int channels = 0;
   int mode = GPD_LENET_SPLIT;  // gpd_hip_set_lenet_mode
   bool conv_relu = false;      // gpd_hip_set_lenet_conv_relu: ReLU on pool1 and pool2 (the network of the reference's PyTorch scripts)
+  LeNetNet net;                // gpd_hip_set_lenet_net
   LeNetFast fast;
   float *c1w = nullptr, *c1b = nullptr, *c2w = nullptr, *c2b = nullptr;
   float *c1wp = nullptr;  // conv1 weights padded to [20][C][28] (25 taps + 3 zeros): 16-byte rows for the LDS table
@@ -61,7 +92,11 @@ struct LeNetScratch {
   unsigned long long *c1_stats = nullptr;  // device: [0] (chunk, channel) pairs conv1 executed, [1] pairs it looked at — summed
                                            // over its launches since the last gpd_hip_conv1_stats(reset); [2] != 0: a launch gave up
                                            // waiting for an image slot (its scores are invalid: lenet_check)
+  LeNetNetScratch net;     // the general route's own buffers (lenet_net.hip)
 };
+// lenet_forward's branch for a context whose network came through gpd_hip_set_lenet_net
+hipError_t lenet_net_forward(const LeNetWeights &w, LeNetScratch &s, const uint8_t *d_images, int n, float *d_scores,
+                             hipStream_t stream, hipEvent_t *kernel_events);
 
 // Scores n images (device pointer, planar u8 [n][C][3600]) into d_scores (device). Async on stream.
 hipError_t lenet_forward(const LeNetWeights &w, LeNetScratch &s, const uint8_t *d_images, int n, float *d_scores,

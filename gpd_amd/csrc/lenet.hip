@@ -861,6 +861,7 @@ int lenet_check(LeNetScratch &s) {
 
 void lenet_scratch_free(LeNetScratch &s) {
   device_release(s.pool1, s.flat, s.xs, s.fc1t, s.fc1p, s.c1_stats);
+  lenet_net_scratch_free(s.net);
   s = LeNetScratch();
 }
 
@@ -869,6 +870,8 @@ void lenet_scratch_free(LeNetScratch &s) {
 hipError_t lenet_forward(const LeNetWeights &w, LeNetScratch &s, const uint8_t *d_images, int n, float *d_scores,
                          hipStream_t stream, hipEvent_t *kernel_events) {
   if (n <= 0) return hipSuccess;
+  if (w.net.active) return lenet_net_forward(w, s, d_images, n, d_scores, stream, kernel_events);  // gpd_hip_set_lenet_net: the shape-general route (lenet_net.hip)
+  s.net.ran = false;
   const int kChunk = 65536;  // images per pass: 6.1 GB of scratch (pool1 + flat + fc1) at the full chunk — sized for 288 GB of HBM
   if (!s.num_cus) {  // persistent conv2 workgroups: one per CU (256 on MI355X)
     int dev = 0;

@@ -63,6 +63,14 @@ class HipClassifier : public Classifier {
   // on the fused path's context as well.  Without the file: the reference's Eigen network, as ever.
   bool convRelu() const { return conv_relu_; }
   const std::vector<float> &parameter(int i) const { return params_[i]; }
+  // A network.cfg that also names conv1_out, conv2_out, fc1_out [and fc2_out > 0: NetCCFFF, with fc3.weight.bin / fc3.bias.bin]
+  // describes another member of the reference's network family; it is loaded through gpd_hip_lenet_net_from_torch and
+  // scored on the shape-general route (gpd_hip_set_lenet_net).  parameter(i) is empty then.
+  bool general() const { return general_; }
+  const gpd_lenet_shape &shape() const { return shape_; }
+  // The loaded network and its conv ReLU flag into a context (the classifier's own, and GraspDetector's fused path's):
+  // gpd_hip_set_lenet_weights or gpd_hip_set_lenet_net, then gpd_hip_set_lenet_conv_relu -> GPD_OK or the first error
+  int installOn(gpd_hip_ctx *ctx) const;
 
  private:
   gpd_hip_ctx *ctx_ = nullptr;
@@ -71,6 +79,10 @@ class HipClassifier : public Classifier {
   bool conv_relu_ = false;
   int batch_size_ = 1;
   std::vector<float> params_[8];
+  void loadGeneral(const std::string &dir, const int widths[4], double input_scale);
+  bool general_ = false;
+  gpd_lenet_shape shape_ = {0, 0, 0, 0, 0};
+  std::vector<float> net_[10];  // the general route's layouts
 };
 
 }  // namespace net

@@ -549,6 +549,7 @@ HipClassifier::HipClassifier(const std::string &, const std::string &weights_fil
                                        "fc1.weight.bin",   "fc1.bias.bin",   "fc2.weight.bin",   "fc2.bias.bin"};
   bool torch_layout = false;
   double input_scale = 1.0;
+  int net_shape[4] = {-1, -1, -1, -1};  // conv1_out, conv2_out, fc1_out, fc2_out of network.cfg, when it has them
   if (std::ifstream((dir + "network.cfg").c_str()).good()) {
     util::ConfigFile net_cfg(dir + "network.cfg");
     net_cfg.ExtractKeys();
@@ -569,6 +570,18 @@ HipClassifier::HipClassifier(const std::string &, const std::string &weights_fil
       printf("ERROR: %snetwork.cfg: input_scale needs layout = torch\n", dir.c_str());
       return;
     }
+    static const char *shape_keys[4] = {"conv1_out", "conv2_out", "fc1_out", "fc2_out"};
+    for (int i = 0; i < 4; i++) net_shape[i] = net_cfg.getValueOfKey<int>(shape_keys[i], -1);
+  }
+  // network.cfg with conv1_out / conv2_out / fc1_out [/ fc2_out]: another member of the reference's network family
+  // (pytorch/network.py: other widths, NetCCFFF), which the shape-general route scores (gpd_hip_set_lenet_net)
+  if (net_shape[0] != -1 || net_shape[1] != -1 || net_shape[2] != -1 || net_shape[3] != -1) {
+    if (!torch_layout) {
+      printf("ERROR: %snetwork.cfg: conv1_out / conv2_out / fc1_out / fc2_out need layout = torch\n", dir.c_str());
+      return;
+    }
+    loadGeneral(dir, net_shape, input_scale);
+    return;
   }
   for (int i = 0; i < 8; i++) params_[i] = readBinaryFileIntoVector(dir + (torch_layout ? torch_files[i] : files[i]));
   const auto &c1w = params_[0];
@@ -608,6 +621,70 @@ HipClassifier::HipClassifier(const std::string &, const std::string &weights_fil
     return;
   }
   loaded_ = true;
+}
+
+// A torch directory of another shape: the 8 (Net) or 10 (NetCCFFF) tensors as torch stores them, converted once by
+// gpd_hip_lenet_net_from_torch into the general route's layouts (net_), and installed in the classifier's own context.
+void HipClassifier::loadGeneral(const std::string &dir, const int widths[4], double input_scale) {
+  static const char *names[10] = {"conv1.weight.bin", "conv1.bias.bin", "conv2.weight.bin", "conv2.bias.bin", "fc1.weight.bin",
+                                  "fc1.bias.bin",     "fc2.weight.bin", "fc2.bias.bin",   "fc3.weight.bin", "fc3.bias.bin"};
+  const int F1 = widths[0], F2 = widths[1], H1 = widths[2], H2 = widths[3] == -1 ? 0 : widths[3];
+  const int files = H2 > 0 ? 10 : 8;
+  std::vector<float> raw[10];
+  for (int i = 0; i < files; i++) raw[i] = readBinaryFileIntoVector(dir + names[i]);
+  const size_t per_channel = F1 > 0 ? (size_t)F1 * 25 : 1;
+  shape_ = {(int32_t)(raw[0].size() / per_channel), F1, F2, H1, H2};
+  if (gpd_hip_lenet_shape_check(&shape_) != GPD_OK) {
+    printf("ERROR: %snetwork.cfg: %s\n", dir.c_str(), gpd_hip_last_error());
+    return;
+  }
+  const size_t N = H2 > 0 ? (size_t)H2 : 2;
+  const size_t want[10] = {(size_t)F1 * shape_.channels * 25, (size_t)F1, (size_t)F2 * F1 * 25, (size_t)F2, (size_t)H1 * F2 * 144, (size_t)H1,
+                           N * H1, N, (size_t)2 * H2, (size_t)(H2 > 0 ? 2 : 0)};
+  for (int i = 0; i < files; i++)
+    if (raw[i].size() != want[i]) {
+      printf("ERROR: LeNet parameter files in %s are missing or have unexpected sizes\n", dir.c_str());
+      return;
+    }
+  const float *in[10];
+  float *out[10];
+  for (int i = 0; i < 10; i++) {
+    net_[i].assign(i < files ? want[i] : 0, 0.f);
+    in[i] = i < files ? raw[i].data() : nullptr;
+    out[i] = i < files ? net_[i].data() : nullptr;
+  }
+  if (gpd_hip_lenet_net_from_torch(&shape_, input_scale, in, out) != GPD_OK) {
+    printf("ERROR: %snetwork.cfg: %s\n", dir.c_str(), gpd_hip_last_error());
+    return;
+  }
+  general_ = true;
+  channels_ = shape_.channels;
+  gpd_params p;
+  gpd_hip_default_params(&p);
+  p.image_num_channels = channels_;
+  if (gpd_hip_create(0, &p, &ctx_) != GPD_OK) {
+    printf("ERROR: %s\n", gpd_hip_last_error());
+    ctx_ = nullptr;
+    return;
+  }
+  if (installOn(ctx_) != GPD_OK) {
+    printf("ERROR: %s\n", gpd_hip_last_error());
+    return;
+  }
+  loaded_ = true;
+}
+
+int HipClassifier::installOn(gpd_hip_ctx *ctx) const {
+  int rc;
+  if (general_) {
+    const float *t[10];
+    for (int i = 0; i < 10; i++) t[i] = net_[i].empty() ? nullptr : net_[i].data();
+    rc = gpd_hip_set_lenet_net(ctx, &shape_, t);
+  } else {
+    rc = gpd_hip_set_lenet_weights(ctx, channels_, params_[0].data(), params_[1].data(), params_[2].data(), params_[3].data(), params_[4].data(),
+                                   params_[5].data(), params_[6].data(), params_[7].data());
+  }
+  return rc != GPD_OK ? rc : gpd_hip_set_lenet_conv_relu(ctx, conv_relu_ ? 1 : 0);
 }
 
 HipClassifier::~HipClassifier() {
@@ -776,10 +853,7 @@ GraspDetector::GraspDetector(const std::string &config_filename) {
     } else if (hc->channels() != params_.image_num_channels) {
       printf("ERROR: the classifier's %d channels do not match image_num_channels = %d\n", hc->channels(), params_.image_num_channels);
       classifier_.reset();
-    } else if (gpd_hip_set_lenet_weights(ctx_, hc->channels(), hc->parameter(0).data(), hc->parameter(1).data(),
-                                         hc->parameter(2).data(), hc->parameter(3).data(), hc->parameter(4).data(),
-                                         hc->parameter(5).data(), hc->parameter(6).data(), hc->parameter(7).data()) == GPD_OK &&
-               gpd_hip_set_lenet_conv_relu(ctx_, hc->convRelu() ? 1 : 0) == GPD_OK) {  // (the directory's network.cfg, if any)
+    } else if (hc->installOn(ctx_) == GPD_OK) {  // the weights (either route) and the conv ReLU flag of the directory's network.cfg, if any
       has_classifier_ = true;
       fused_classifier_ = true;
       // hip_lenet_mode (not a reference key): 0 = split operands on the int8 / bf16 matrix pipes (default), 1 = the f32

@@ -154,6 +154,62 @@ int gpd_hip_set_lenet_conv_relu(gpd_hip_ctx *ctx, int on);
 int gpd_hip_lenet_from_torch(int channels, double input_scale, const float *conv1_weight, const float *fc1_weight,
                              const float *fc2_weight, float *conv1_w_out, float *ip1_w_out, float *ip2_w_out);
 
+/* ---- the shape-general scoring route -------------------------------------------------------------------------------
+ * The family of networks the reference's pytorch/network.py describes (its CHANNELS lists; Net and NetCCFFF) on 60x60
+ * images:
+ *   conv1  channels -> conv1_out, 5x5, valid;  2x2 max-pool;  ReLU when gpd_hip_set_lenet_conv_relu is on
+ *   conv2  conv1_out -> conv2_out, 5x5, valid; 2x2 max-pool;  ReLU when gpd_hip_set_lenet_conv_relu is on
+ *   fc1    conv2_out * 144 -> fc1_out, ReLU
+ *   fc2    fc1_out -> fc2_out, ReLU           only when fc2_out > 0 (NetCCFFF)
+ *   last   -> 2 logits;  score = logit1 - logit0
+ * Limits (gpd_hip_lenet_shape_check is their one statement): channels in {1, 3, 12, 15}, 1 <= conv1_out <= 64,
+ * 1 <= conv2_out <= 128, 1 <= fc1_out <= 1024, 0 <= fc2_out <= 1024.
+ * Arithmetic: every multiply-add layer is one f32 chain per output — acc = 0, acc = fmaf(w, x, acc) with k ascending, then
+ * acc + bias — with k = (input channel, kh, kw) in the convolutions, k = pixel * conv2_out + channel in fc1 (the project's
+ * pixel-major flatten) and k = the hidden index in fc2 and the last layer.  No split-K, no atomics: a score does not depend on
+ * the batch it is computed in.  The kernels run the chains on the f32-input matrix instructions of gfx950, which are bit for
+ * bit such chains.  The stock shape (C, 20, 50, 500, 0) is legal here; gpd_hip_set_lenet_weights serves it with tuned kernels. */
+typedef struct gpd_lenet_shape {
+  int32_t channels, conv1_out, conv2_out, fc1_out, fc2_out;
+} gpd_lenet_shape;
+
+/* GPD_OK when the shape is within the limits above, GPD_ERR_INVALID (and an error text) otherwise or for a null pointer.  Host only. */
+int gpd_hip_lenet_shape_check(const gpd_lenet_shape *shape);
+
+/* A state dict of pytorch/network.py::Net / NetCCFFF -> the layouts gpd_hip_set_lenet_net takes.  Host only, no context.
+ * torch_tensors, row-major as torch stores them (F1 = conv1_out, F2 = conv2_out, H1 = fc1_out, H2 = fc2_out):
+ *   [0] conv1.weight [F1][C][5][5]   [1] conv1.bias [F1]   [2] conv2.weight [F2][F1][5][5]   [3] conv2.bias [F2]
+ *   [4] fc1.weight [H1][F2*144] over the channel-major flatten (k = channel * 144 + pixel)     [5] fc1.bias [H1]
+ *   H2 > 0:  [6] fc2.weight [H2][H1]  [7] fc2.bias [H2]  [8] fc3.weight [2][H2]  [9] fc3.bias [2]
+ *   H2 == 0: [6] fc2.weight [2][H1]   [7] fc2.bias [2]   [8], [9] unused (may be null)
+ * out, caller-allocated with the same element counts (the route's layouts):
+ *   [0] [F1][C*25] = (float)((double)w * input_scale)      [2] [F2][F1*25] unchanged      biases [1] [3] [5] [7] [9] unchanged
+ *   [4] [F2*144][H1]: out[(p * F2 + c) * H1 + u] = fc1[u][c * 144 + p]
+ *   [6] [H1][N]:      out[j * N + u] = fc2[u][j], N = H2 (or 2 when H2 == 0)
+ *   [8] [H2][2]:      out[j * 2 + u] = fc3[u][j]           (H2 > 0 only)
+ * GPD_ERR_INVALID: a null pointer among the used ones, a shape outside the limits, a non-finite or non-positive input_scale. */
+int gpd_hip_lenet_net_from_torch(const gpd_lenet_shape *shape, double input_scale, const float *const torch_tensors[10],
+                                 float *const out[10]);
+
+/* Installs a network of `shape` (tensors in the layouts gpd_hip_lenet_net_from_torch writes).  Every later scoring call of
+ * the context — gpd_hip_score, gpd_hip_detect*, gpd_hip_detect_batch[_multi], gpd_hip_detect_sharded (each context its own),
+ * gpd_hip_detect_sis, gpd_hip_score_given, gpd_hip_replay — takes the general route, until gpd_hip_set_lenet_weights
+ * returns the context to the stock one.  gpd_hip_set_lenet_conv_relu is honoured as on the stock route;
+ * gpd_hip_set_lenet_mode is accepted and IGNORED: this route is always the exact f32 chain.  shape->channels must equal the
+ * context's image_num_channels; every weight and bias must be finite; the LDS the shape needs is checked here, not at
+ * launch (GPD_ERR_INVALID each). */
+int gpd_hip_set_lenet_net(gpd_hip_ctx *ctx, const gpd_lenet_shape *shape, const float *const tensors[10]);
+
+/* Activations of the last scoring call that took the general route (lane 0; n images, at most the first chunk), plain
+ * row-major f32: which = 0: pool1 [n][F1][28][28], 1: pool2 [n][F2][12][12], 2: fc1 [n][H1], 3: fc2 [n][H2] (H2 > 0 only),
+ * 4: logits [n][2] — pool tensors after the ReLU when it is on.  GPD_ERR_INVALID when the last scoring call did not take
+ * the general route (how a caller learns which route ran). */
+int gpd_hip_lenet_net_debug(gpd_hip_ctx *ctx, int which, int n, float *out);
+
+/* info[0] images per chunk, [1] scratch bytes per image, [2] the largest static + dynamic LDS of the route's kernels
+ * (bytes), [3] multiply-adds per image.  GPD_ERR_STATE without an installed network. */
+int gpd_hip_lenet_net_info(gpd_hip_ctx *ctx, long long info[4]);
+
 /* Replaces Classifier::classifyImages (net/classifier.h:70-71,
  * eigen_classifier.cpp:59-79).  images: n contiguous 60x60xC u8 HWC images
  * (cv::Mat CV_8UC(C) layout); scores[i] = logit1 - logit0.
