@@ -119,7 +119,7 @@ struct BatchRun {
         const int rcf = search_force_capacity(L.search, 8192);
         if (rcf) return rcf;
       }
-      const int cand = candidate_bound(ctx->params, maxS, maxC, budget);
+      const int cand = candidate_bound(ctx->params, maxS, maxC, budget, &ctx->lenet.net);
       int rc = GPD_OK;
       if (!all_selected) rc = lane_reserve(ctx, L, maxP, maxC, maxS, cand, 0);
       if (!rc && maxSel > 0) rc = lane_reserve(ctx, L, maxP, maxC, maxS, cand, maxSel);

@@ -119,7 +119,7 @@ int lane_init(Lane &L, hipStream_t shared = nullptr);
 // growing a buffer is hipFree + hipMalloc, which waits for the whole device — in a batch that is a hole in BOTH
 // lanes' queues.  gpd_hip_reserve and gpd_hip_detect_batch call this ahead of the first cloud.
 int lane_reserve(gpd_hip_ctx *ctx, Lane &L, int points, int cams, int samples, int candidates, int selected);
-int candidate_bound(const gpd_params &p, int samples, int cams = 1, size_t budget = kReserveBudget);
+int candidate_bound(const gpd_params &p, int samples, int cams = 1, size_t budget = kReserveBudget, const LeNetNet *net = nullptr);
 int reserve_scores(Lane &L, int n);
 int reserve_out(Lane &L, size_t records, size_t extra_bytes);
 int reserve_draws(Lane &L, int n);

@@ -123,11 +123,14 @@ int reserve_selection(Lane &L, int k, int n) {
 // the most candidates `samples` samples can give (every slot a valid hand), cut to what `budget` bytes hold: per candidate
 // its image, the LeNet scratch of both scoring modes (pool1, the f32 and the three-plane bf16 flatten, ip1 and its four K
 // quarters), score and records; per (hand set, camera) a shadow voxel bitset of the 86^3-bit default window (wider image
-// volumes take more: images_reserve grows them on demand)
-int candidate_bound(const gpd_params &p, int samples, int cams, size_t budget) {
+// volumes take more: images_reserve grows them on demand).  With a network of the general route installed (`net`) a candidate
+// costs that network's scratch (LeNetNet::scratch_per_image) and its score instead of the stock scratch, which lane_reserve
+// then sizes for one image.
+int candidate_bound(const gpd_params &p, int samples, int cams, size_t budget, const LeNetNet *net) {
   const long long upper = (long long)samples * p.num_hand_axes * p.num_orientations;
-  const size_t per = (size_t)kPix * p.image_num_channels + (20 * 784 + kFc1In + 5 * kFc1Out + 1) * sizeof(float) + 3 * (size_t)kLenetXld * 2 +
-                     2 * sizeof(gpd_hand);
+  const size_t scratch = net && net->active ? (size_t)net->scratch_per_image + sizeof(float)
+                                            : (20 * 784 + kFc1In + 5 * kFc1Out + 1) * sizeof(float) + 3 * (size_t)kLenetXld * 2;
+  const size_t per = (size_t)kPix * p.image_num_channels + scratch + 2 * sizeof(gpd_hand);
   const size_t bitsets = p.image_num_channels == 15 ? (size_t)std::max(samples, 1) * std::max(cams, 1) * ((86 * 86 * 86 + 31) / 32 * 4) : 0;
   const long long fit = budget > bitsets ? (long long)((budget - bitsets) / per) : 0;
   return (int)std::max(1ll, std::min(upper, fit));
@@ -144,7 +147,15 @@ int lane_reserve(gpd_hip_ctx *ctx, Lane &L, int points, int cams, int samples, i
   const long long sets = std::min((long long)samples, (long long)candidates) * cams;  // (live hand set, camera) voxel bitsets
   rc = images_reserve(p, L.images, candidates, p.image_num_channels == 15 ? (int)sets : 0);
   if (rc) return rc;
-  HIP_RET(lenet_scratch_reserve(L.lenet_scratch, std::min(candidates, kLeNetChunk)));
+  const LeNetNet &net = ctx->lenet.net;
+  if (net.active) {
+    // the general route scores in its own scratch; of the stock one it needs the launch error word alone (lenet_net_forward).
+    // The stock scratch first: when it grows it releases the general one with it (lenet_scratch_free)
+    HIP_RET(lenet_scratch_reserve(L.lenet_scratch, 1));
+    HIP_RET(lenet_net_scratch_reserve(net, L.lenet_scratch.net, std::min(candidates, net.chunk)));
+  } else {
+    HIP_RET(lenet_scratch_reserve(L.lenet_scratch, std::min(candidates, kLeNetChunk)));
+  }
   rc = reserve_scores(L, candidates);
   if (rc) return rc;
   if (selected >= 0) {
@@ -332,7 +343,7 @@ int gpd_hip_reserve(gpd_hip_ctx *ctx, int max_points, int max_cams, int max_samp
     return GPD_ERR_INVALID;
   }
   HIP_RET(hipSetDevice(ctx->device));
-  const int cand = max_candidates > 0 ? max_candidates : candidate_bound(ctx->params, max_samples, max_cams);
+  const int cand = max_candidates > 0 ? max_candidates : candidate_bound(ctx->params, max_samples, max_cams, kReserveBudget, &ctx->lenet.net);
   for (int l = 0; l < kLanes; l++) {
     int rc = lane_init(ctx->lane[l]);
     if (rc) return rc;

@@ -67,6 +67,10 @@ struct LeNetNetScratch {
 };
 void lenet_net_free(LeNetNet &net);
 void lenet_net_scratch_free(LeNetNetScratch &s);
+// the scratch of `net` for passes of up to n images (cut to net.chunk, a quarter of slack); a growth is booked (note_alloc).
+// lenet_net_forward calls it per pass, lane_reserve ahead of the first cloud.  gpd_hip_set_lenet_net frees the scratch of every
+// lane when it installs a network: a reservation made before the install does not outlive it.
+hipError_t lenet_net_scratch_reserve(const LeNetNet &net, LeNetNetScratch &s, int n);
 
 struct LeNetWeights {
   int channels = 0;

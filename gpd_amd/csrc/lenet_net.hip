@@ -7,6 +7,9 @@
 // holds the lower k of a step, half 1 the higher — so the kernels below keep ONE accumulator set per output tile and walk k
 // in order; zero steps (a k padded to an even count, a dense K padded to whole steps of 32) sit at the END of a chain, where
 // fmaf(0, x, acc) leaves acc as it is.  Tiling by batch size changes which lanes work, never the order inside a chain.
+// That holds for every finite weight, subnormal ones included: the kernels' f32 denormal mode is IEEE (the Makefile passes no
+// denormal flag), and on the device the MFMA, the epilogues and the logit chains return subnormal operands, products, sums and
+// planes bit for bit as the CPU chain does, beside values above 2^90 (tests/test_gpu_lenet_net_edges.py, the hostile set).
 //
 //   net_conv_pool_kernel   implicit GEMM of a 5x5 valid convolution, M = 32 filters, N = 32 POOLED pixels per wave: the four
 //                          accumulators of a wave are the four pixels of the 2x2 pool windows, so the pool is a per-register
@@ -279,7 +282,19 @@ void dense(const float *X, int ldx, const float *W, int upad, const float *bias,
     dense_launch<4>(X, ldx, W, upad, bias, out, ldo, n, K, U, stream);
 }
 
-hipError_t net_scratch_reserve(const LeNetNet &net, LeNetNetScratch &s, int n) {
+}  // namespace
+
+void lenet_net_free(LeNetNet &net) {
+  device_release(net.c1wt, net.c1b, net.c2wt, net.c2b, net.f1w, net.f1b, net.f2w, net.f2b, net.lw, net.lb);
+  net = LeNetNet();
+}
+
+void lenet_net_scratch_free(LeNetNetScratch &s) {
+  device_release(s.pool1, s.pool2, s.h1, s.h2, s.logits);
+  s = LeNetNetScratch();
+}
+
+hipError_t lenet_net_scratch_reserve(const LeNetNet &net, LeNetNetScratch &s, int n) {
   if (n <= s.capacity) return hipSuccess;
   note_alloc(__func__);
   lenet_net_scratch_free(s);
@@ -295,18 +310,6 @@ hipError_t net_scratch_reserve(const LeNetNet &net, LeNetNetScratch &s, int n) {
   return hipSuccess;
 }
 
-}  // namespace
-
-void lenet_net_free(LeNetNet &net) {
-  device_release(net.c1wt, net.c1b, net.c2wt, net.c2b, net.f1w, net.f1b, net.f2w, net.f2b, net.lw, net.lb);
-  net = LeNetNet();
-}
-
-void lenet_net_scratch_free(LeNetNetScratch &s) {
-  device_release(s.pool1, s.pool2, s.h1, s.h2, s.logits);
-  s = LeNetNetScratch();
-}
-
 hipError_t lenet_net_forward(const LeNetWeights &w, LeNetScratch &s, const uint8_t *d_images, int n, float *d_scores, hipStream_t stream,
                              hipEvent_t *kernel_events) {
   const LeNetNet &net = w.net;
@@ -315,7 +318,7 @@ hipError_t lenet_net_forward(const LeNetWeights &w, LeNetScratch &s, const uint8
   // the fused entries copy the stock route's launch error word behind every scoring pass (lenet_check): it has to exist
   if (!s.c1_stats && (e = lenet_scratch_reserve(s, 1)) != hipSuccess) return e;
   LeNetNetScratch &t = s.net;
-  if ((e = net_scratch_reserve(net, t, std::min(n, net.chunk))) != hipSuccess) return e;
+  if ((e = lenet_net_scratch_reserve(net, t, std::min(n, net.chunk))) != hipSuccess) return e;
   const int chunk = std::min(net.chunk, t.capacity);
   const int C = sh.channels, F1 = sh.conv1_out, F2 = sh.conv2_out, H1 = sh.fc1_out, H2 = sh.fc2_out;
   const int ld1 = round_up(H1, 4), ld2 = round_up(H2, 4);

@@ -196,8 +196,10 @@ int gpd_hip_lenet_net_from_torch(const gpd_lenet_shape *shape, double input_scal
  * gpd_hip_detect_sis, gpd_hip_score_given, gpd_hip_replay — takes the general route, until gpd_hip_set_lenet_weights
  * returns the context to the stock one.  gpd_hip_set_lenet_conv_relu is honoured as on the stock route;
  * gpd_hip_set_lenet_mode is accepted and IGNORED: this route is always the exact f32 chain.  shape->channels must equal the
- * context's image_num_channels; every weight and bias must be finite; the LDS the shape needs is checked here, not at
- * launch (GPD_ERR_INVALID each). */
+ * context's image_num_channels; every weight and bias must be finite (subnormal ones are kept and computed with: the
+ * route does not flush); the LDS the shape needs is checked here, not at launch (GPD_ERR_INVALID each).
+ * Order: install, THEN gpd_hip_reserve.  The route's scratch depends on the shape, so an install frees the scratch of every
+ * lane; a reservation made before it is void for the scoring buffers, which then grow (booked) in the first pass of each lane. */
 int gpd_hip_set_lenet_net(gpd_hip_ctx *ctx, const gpd_lenet_shape *shape, const float *const tensors[10]);
 
 /* Activations of the last scoring call that took the general route (lane 0; n images, at most the first chunk), plain
@@ -550,8 +552,11 @@ int gpd_hip_detect_select(gpd_hip_ctx *ctx, const int32_t *sample_indices, int n
  * a hipFree + hipMalloc, which waits for the whole device).  max_candidates: scored hands per cloud, 0 = the upper
  * bound max_samples x slots (cut to 16 GB of candidate-sized buffers per lane); max_selected: the largest
  * num_selected that will be asked for (0: none).  Optional: gpd_hip_detect_batch sizes its lanes itself from the
- * jobs it is given; the single-cloud entries grow their buffers on demand (25 % slack, never shrinking).  No
- * reference counterpart: the reference allocates per call. */
+ * jobs it is given; the single-cloud entries grow their buffers on demand (25 % slack, never shrinking).  The scoring
+ * scratch is that of the network the context holds NOW: with one installed by gpd_hip_set_lenet_net, the general route's
+ * (a candidate priced at its scratch bytes per image, gpd_hip_lenet_net_info) and one image's worth of the stock one; call
+ * this after the install, a later install frees that scratch again.  No reference counterpart: the reference allocates per
+ * call. */
 int gpd_hip_reserve(gpd_hip_ctx *ctx, int max_points, int max_cams, int max_samples, int max_candidates, int max_selected);
 
 /* One independent cloud of a batch: the arguments of gpd_hip_upload_cloud + gpd_hip_detect_select.

@@ -30,9 +30,11 @@ def _ctx(C):
     return api.Context(api.default_params(C))
 
 
-def _check_against_chain(ctx, name, want, n, label):
+def _check_against_chain(ctx, name, want, n, label, imgs=None):
+    """Scores, then the debug tensors in layer order: the first tensor that differs is the assertion that fails.  imgs: other
+    images than R.images(name) (at most 35: image i of the batch is image i % 35 of them, as want is indexed)"""
     idx = np.arange(n) % ltr.N_IMAGES
-    sc = ctx.score(R.images(name, n))
+    sc = ctx.score(R.images(name, n) if imgs is None else imgs[idx % len(imgs)])
     bad = np.flatnonzero(sc != want["score"][idx])
     print("%s n = %d: %d scores differ from the chain%s" % (label, n, len(bad), "" if not len(bad) else
                                                              ", max |diff| = %.3g" % float(np.abs(sc - want["score"][idx]).max())))

@@ -13,12 +13,13 @@ from gpd_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = sorted(R.SHAPES)
+EDGE_NAMES = sorted(R.EDGE_SHAPES)
 
 
 def test_shape_limits():
     L = api.lib()
-    for name in NAMES:
-        assert api.lenet_shape_check(api.LenetShape(*R.SHAPES[name])), name
+    for name in NAMES + EDGE_NAMES:
+        assert api.lenet_shape_check(api.LenetShape(*R.ALL_SHAPES[name])), name
     ok = (15, 20, 50, 500, 0)
     assert api.lenet_shape_check(api.LenetShape(*ok))
     for C in (1, 3, 12, 15):
@@ -153,13 +154,13 @@ def _gamma(m):
     return u / (1.0 - u)
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + EDGE_NAMES)
 def test_chain_layers_are_within_the_chain_bound_of_float64(name, oracle_mod):
     """Per layer, on the chain network's OWN f32 inputs: |chain - float64| <= gamma_{K+1} (sum |w x| + |b|), the standard bound of
     a K-term fmaf chain plus the bias add (K + 1 roundings, u = 2^-24) — derived, not measured."""
     import torch
     import torch.nn.functional as F
-    shape = R.SHAPES[name]
+    shape = R.ALL_SHAPES[name]
     C, F1, F2, H1, H2 = shape
     _, arrs = R.route_arrays(name)
     o = R.chain_image(oracle_mod, shape, arrs, R.images(name, 1)[0], keep_conv=True)
@@ -219,3 +220,59 @@ def test_chain_scores_against_float64_and_the_relus_clamp(name):
     assert 0.3 <= float(np.abs(t["score"]).max()) <= 30  # O(1)
     # the chain's clamps are zeros, and the truth's clear negatives are among them
     assert (c["pool1"][t["pre1"] < -1e-3] == 0).all() and (c["pool2"][t["pre2"] < -1e-3] == 0).all() and (c["fc1"][t["z1"] < -1e-3] == 0).all()
+
+
+@pytest.mark.parametrize("name", EDGE_NAMES)
+def test_edge_shape_weights_tell_the_images_apart(name):
+    """Conditions on the WEIGHTS of the edge shapes (change EDGE_SEEDS, not the conditions): one-unit networks cannot have O(1)
+    scores or a fair clamp share, but a test on them says something only if the 35 images get (nearly) 35 different scores and no
+    layer is dead — in either conv_relu setting the device tests use."""
+    assert not set(R.EDGE_SHAPES) & set(R.SHAPES)
+    for relu in (True, False) if name in "FG" else (True,):
+        c = R.chain(name, False, relu)
+        distinct = len(np.unique(c["score"]))
+        live = {k: float((v != 0).mean()) for k, v in c.items() if v is not None}
+        print("%s conv_relu = %d: %d distinct scores of %d, non-zero share %s" % (name, relu, distinct, len(c["score"]), live))
+        assert len(c["score"]) == 35 and distinct >= 30
+        for k, v in c.items():
+            assert (v is None) == (k == "fc2" and R.EDGE_SHAPES[name][4] == 0)
+            if v is not None:
+                assert np.isfinite(v).all() and np.any(v != 0), k
+    st, arrs = R.state(name), R.route_arrays(name)[1]
+    shape, got = api.lenet_net_from_torch(st, R.INPUT_SCALE)
+    assert shape.as_tuple() == R.EDGE_SHAPES[name] and all(np.array_equal(g, w) for g, w in zip(got, arrs))
+
+
+def test_hostile_set_has_what_it_is_for():
+    """Conditions on lenet_net_ref.hostile_state("F") and its images, on the chain reference: everything is finite (NaN is left
+    out on purpose: fmaxf and numpy.maximum treat it differently, a question of definition and not of kernels); non-zero
+    subnormal values in every layer — at least 100 in pool1, at least 10 in pool2, fc1 and fc2 — with the conv ReLUs on and off;
+    a largest magnitude above 2^90; subnormal conv1 weights after the input scale; an image of 255s, one of zeros, one without a
+    zero pixel."""
+    name = "F"
+    st = R.hostile_state(name)
+    arrs = R.numpy_route_arrays(st)
+    shape, got = api.lenet_net_from_torch(st, R.INPUT_SCALE)  # the library's conversion keeps the subnormal weights
+    assert shape.as_tuple() == R.EDGE_SHAPES[name] and all(np.array_equal(g, w) for g, w in zip(got, arrs))
+    assert all(np.isfinite(a).all() for a in arrs)
+    assert R.subnormals(arrs[0]) >= 250 and all(R.subnormals(arrs[i]) >= 100 for i in (2, 4, 6))
+    rows = R.HOSTILE_ROWS[name]
+    c1 = arrs[0].reshape(7, 300)
+    assert not c1[rows["c1_zero"]].any() and c1[rows["c1_lone"]].max() == np.float32(1e4) * np.float32(2.0 ** -8)
+    assert np.abs(c1[rows["c1_big"]]).max() > 2.0 ** 85
+    span = np.abs(c1[rows["c1_span"]])
+    assert span.max() / span[span > 0].min() > 1e5
+    img = R.hostile_images(name)
+    assert 12 <= len(img) <= R.ltr.N_IMAGES
+    assert (img[-3] == 255).all() and not img[-2].any() and img[-1].min() >= 1
+    for relu in (True, False):
+        c = R.hostile_chain(name, relu)
+        counts = {k: R.subnormals(c[k]) for k in ("pool1", "pool2", "fc1", "fc2")}
+        biggest = max(float(np.abs(v).max()) for v in c.values())
+        print("hostile F conv_relu = %d: subnormals %s, largest magnitude %.3g, %d distinct scores" % (relu, counts, biggest,
+                                                                                                      len(np.unique(c["score"]))))
+        for k, v in c.items():
+            assert np.isfinite(v).all(), k
+        assert counts["pool1"] >= 100 and min(counts["pool2"], counts["fc1"], counts["fc2"]) >= 10
+        assert biggest > 2.0 ** 90
+        assert len(np.unique(c["score"])) == len(img)
