@@ -364,17 +364,11 @@ extern "C" {
 
 int gpd_hip_detect_batch(gpd_hip_ctx *ctx, gpd_detect_job *jobs, int num_jobs) {
   StageRange range_("gpd:detect_batch");
-  if (!ctx || num_jobs < 0 || (num_jobs > 0 && !jobs)) {
-    set_error("gpd_hip_detect_batch: bad argument");
-    return GPD_ERR_INVALID;
-  }
-  if (!ctx->lenet.channels) {
-    set_error("gpd_hip_detect_batch: LeNet weights not set");
-    return GPD_ERR_STATE;
-  }
+  int rc = refuse("gpd_hip_detect_batch", ctx, num_jobs >= 0 && (num_jobs == 0 || jobs), {Need::LeNet});
+  if (rc) return rc;
   HIP_RET(hipSetDevice(ctx->device));
   BatchRun b(ctx, jobs, num_jobs);
-  int rc = b.validate();
+  rc = b.validate();
   if (rc) return rc;
   for (int l = 1; l < kLanes; l++) {
     rc = lane_init(ctx->lane[l]);

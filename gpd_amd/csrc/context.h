@@ -1,7 +1,8 @@
-// What the host-side translation units of the C-ABI share (context.hip, detect.hip, batch.hip, replay.hip; no kernel
+// What the host-side translation units of the C-ABI share (context.hip, detect.hip, rounds.hip, given.hip, batch.hip, replay.hip; no kernel
 // includes this): the context and its lanes, one fused detect in flight, the error text and the allocation counter.
 #pragma once
 
+#include <initializer_list>
 #include <vector>
 
 #include "gpd_internal.h"
@@ -125,6 +126,24 @@ int reserve_out(Lane &L, size_t records, size_t extra_bytes);
 int reserve_draws(Lane &L, int n);
 int reserve_selection(Lane &L, int k, int n);
 int check_samples(const char *who, const int32_t *sample_indices, const double *sample_xyz, int num_samples, int num_points);
+
+// The refusals an entry opens with, in the order it names them: "<who>: bad argument" (GPD_ERR_INVALID) without a context or
+// with args_ok false, then per need the text and GPD_ERR_STATE.  GPD_OK: the entry may go on.
+enum class Need { Cloud, LeNet, NoBatch };  // lane 0 holds a cloud; LeNet weights are set; gpd_hip_detect_batch is not driving the lanes
+int refuse(const char *who, const gpd_hip_ctx *ctx, bool args_ok, std::initializer_list<Need> needs = {});
+
+// ---- one stage on a lane (context.hip); the callers record the events that time a stage around these ----
+// The image kernels over the lane's plan (its summary is on the host), under a StageRange `range`, between ev_start and ev_end;
+// ev_start null: the caller recorded it ahead of the lists and the plan it times with the images.
+int lane_images(gpd_hip_ctx *ctx, Lane &L, bool side_stream, unsigned long long lcg_base, const char *range, hipEvent_t ev_start,
+                hipEvent_t ev_end);
+// A LeNet pass over n planar images into L.d_scores, and the pass's launch error word on its way to h_flags->lenet; n == 0
+// enqueues nothing and clears the flag on the host.
+int lane_lenet(gpd_hip_ctx *ctx, Lane &L, const uint8_t *d_images, int n, const char *range);
+// After the wait: the capacity flags of the image kernels (GPD_ERR_CAPACITY), then, for a call that scored, h_flags->lenet.
+int lane_check(Lane &L, int32_t image_status, bool scored);
+// The lane's n images in the caller's layout (HWC) and their candidates' indices, enqueued towards the caller's memory.
+int lane_download_images(const gpd_params &p, Lane &L, int n, uint8_t *images, int32_t *cand_index);
 
 // ---- detect.hip: the three steps of a fused detect ----
 int job_begin(gpd_hip_ctx *ctx, Lane &L, Job &J);

@@ -1,6 +1,6 @@
-// C-ABI of libgpd_hip.so (include/gpd_hip.h): the context and its lanes, the LeNet setters, uploads and the single-stage
-// entries.  The fused detect is detect.hip, the batch / multi-context / sharded entries batch.hip, bench.py's
-// measurement hooks replay.hip; context.h is what the four share.
+// C-ABI of libgpd_hip.so (include/gpd_hip.h): the context and its lanes, the refusals and the lane stages every entry is built
+// from, the LeNet setters, uploads and the single-stage entries.  The fused detect is detect.hip, the round-loop entries rounds.hip,
+// the batch / multi-context / sharded entries batch.hip, bench.py's measurement hooks replay.hip; context.h is what they share.
 //
 // A context owns two LANES — each a HIP stream with its own cloud, search buffers, candidate plan,
 // image buffers and LeNet scratch.  Every single-cloud entry point runs on lane 0.
@@ -185,6 +185,80 @@ int check_samples(const char *who, const int32_t *sample_indices, const double *
   return GPD_OK;
 }
 
+int refuse(const char *who, const gpd_hip_ctx *ctx, bool args_ok, std::initializer_list<Need> needs) {
+  if (!ctx || !args_ok) {
+    set_error("%s: bad argument", who);
+    return GPD_ERR_INVALID;
+  }
+  for (Need need : needs) {
+    if (need == Need::Cloud && !ctx->lane[0].cloud.num_points)
+      set_error("%s: no cloud uploaded", who);
+    else if (need == Need::LeNet && !ctx->lenet.channels)
+      set_error("%s: LeNet weights not set", who);
+    else if (need == Need::NoBatch && ctx->in_batch)
+      set_error("%s: gpd_hip_detect_batch is driving the lanes", who);
+    else
+      continue;
+    return GPD_ERR_STATE;
+  }
+  return GPD_OK;
+}
+
+int lane_images(gpd_hip_ctx *ctx, Lane &L, bool side_stream, unsigned long long lcg_base, const char *range, hipEvent_t ev_start,
+                hipEvent_t ev_end) {
+  if (ev_start) HIP_RET(hipEventRecord(ev_start, L.stream));
+  L.images.side_stream = side_stream;
+  L.images.lcg_base = lcg_base;
+  {
+    StageRange r(range);
+    const int rc = images_run(ctx->params, L.cloud, L.search, L.plan, L.images, L.stream);
+    if (rc) return rc;
+  }
+  HIP_RET(hipEventRecord(ev_end, L.stream));
+  return GPD_OK;
+}
+
+int lane_lenet(gpd_hip_ctx *ctx, Lane &L, const uint8_t *d_images, int n, const char *range) {
+  if (n <= 0) {
+    L.h_flags->lenet = 0;
+    return GPD_OK;
+  }
+  const int rc = reserve_scores(L, n);
+  if (rc) return rc;
+  {
+    StageRange r(range);
+    HIP_RET(lenet_forward(ctx->lenet, L.lenet_scratch, d_images, n, L.d_scores, L.stream));
+  }
+  // the word rides with the call's results: it is read (lane_check) after the wait the call makes for them anyway
+  HIP_RET(hipMemcpyAsync(&L.h_flags->lenet, lenet_fault_word(L.lenet_scratch), sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+  return GPD_OK;
+}
+
+int lane_check(Lane &L, int32_t image_status, bool scored) {
+  if (image_status) {
+    set_images_status_error(image_status);
+    return GPD_ERR_CAPACITY;
+  }
+  if (scored && L.h_flags->lenet) {
+    const int rc = lenet_check(L.lenet_scratch);  // clears the device word, sets the error text
+    return rc ? rc : GPD_ERR_HIP;
+  }
+  return GPD_OK;
+}
+
+int lane_download_images(const gpd_params &p, Lane &L, int n, uint8_t *images, int32_t *cand_index) {
+  if (cand_index && n > 0)
+    HIP_RET(hipMemcpyAsync(cand_index, L.plan.d_cand_out, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+  if (images && n > 0) {
+    // the caller wants cv::Mat-layout pixels: planar -> HWC on the device, then one copy
+    const size_t bytes = (size_t)L.images.capacity * kPix * p.image_num_channels;
+    if (!L.images.d_images_hwc) HIP_RET(device_alloc(L.images.d_images_hwc, bytes));
+    HIP_RET(planar_to_hwc(L.images.d_images, L.images.d_images_hwc, n, p.image_num_channels, L.stream));
+    HIP_RET(hipMemcpyAsync(images, L.images.d_images_hwc, (size_t)n * kPix * p.image_num_channels, hipMemcpyDeviceToHost, L.stream));
+  }
+  return GPD_OK;
+}
+
 }  // namespace gpd
 
 using namespace gpd;
@@ -338,10 +412,9 @@ void gpd_hip_destroy(gpd_hip_ctx *ctx) {
 }
 
 int gpd_hip_reserve(gpd_hip_ctx *ctx, int max_points, int max_cams, int max_samples, int max_candidates, int max_selected) {
-  if (!ctx || max_points < 1 || max_cams < 1 || max_cams > kMaxCams || max_samples < 0 || max_candidates < 0 || max_selected < 0) {
-    set_error("gpd_hip_reserve: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_reserve", ctx, max_points >= 1 && max_cams >= 1 && max_cams <= kMaxCams && max_samples >= 0 && max_candidates >= 0 &&
+                                                   max_selected >= 0))
+    return rc;
   HIP_RET(hipSetDevice(ctx->device));
   const int cand = max_candidates > 0 ? max_candidates : candidate_bound(ctx->params, max_samples, max_cams, kReserveBudget, &ctx->lenet.net);
   for (int l = 0; l < kLanes; l++) {
@@ -434,10 +507,7 @@ int gpd_hip_set_lenet_weights(gpd_hip_ctx *ctx, int channels, const float *conv1
 }
 
 int gpd_hip_set_lenet_mode(gpd_hip_ctx *ctx, int mode) {
-  if (!ctx || (mode != GPD_LENET_SPLIT && mode != GPD_LENET_F32_CHAIN)) {
-    set_error("gpd_hip_set_lenet_mode: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_set_lenet_mode", ctx, mode == GPD_LENET_SPLIT || mode == GPD_LENET_F32_CHAIN)) return rc;
   HIP_RET(hipSetDevice(ctx->device));
   for (auto &L : ctx->lane)
     if (L.stream) HIP_RET(hipStreamSynchronize(L.stream));  // the two modes lay pool1 out differently: no launch in flight
@@ -449,10 +519,7 @@ int gpd_hip_set_lenet_mode(gpd_hip_ctx *ctx, int mode) {
 // Caffe / OpenVINO network has none).  Context state like the mode: every scoring entry goes through lenet_forward with
 // ctx->lenet, which picks the kernels' RELU instantiations at enqueue time; gpd_hip_set_lenet_weights leaves it alone.
 int gpd_hip_set_lenet_conv_relu(gpd_hip_ctx *ctx, int on) {
-  if (!ctx || (on != 0 && on != 1)) {
-    set_error("gpd_hip_set_lenet_conv_relu: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_set_lenet_conv_relu", ctx, on == 0 || on == 1)) return rc;
   ctx->lenet.conv_relu = on != 0;
   return GPD_OK;
 }
@@ -494,10 +561,7 @@ int gpd_hip_lenet_from_torch(int channels, double input_scale, const float *conv
 // test hook: the intermediate tensors of lane 0's last LeNet pass (which = 0: pool1 as f32 [n][15680], 1: the three bf16
 // planes of the flattened pool2 [3][n][7200] (split path), 2: fc1 transposed f32 [500][n])
 int gpd_hip_lenet_debug(gpd_hip_ctx *ctx, int which, int n, void *out) {
-  if (!ctx || !out || n < 1) {
-    set_error("gpd_hip_lenet_debug: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_lenet_debug", ctx, out && n >= 1)) return rc;
   HIP_RET(hipSetDevice(ctx->device));
   Lane &L = ctx->lane[0];
   LeNetScratch &s = L.lenet_scratch;
@@ -537,15 +601,8 @@ int gpd_hip_lenet_debug(gpd_hip_ctx *ctx, int which, int n, void *out) {
 
 int gpd_hip_score(gpd_hip_ctx *ctx, const uint8_t *images, int n, float *scores) {
   StageRange range_("gpd:score (classifyImages)");
-  if (!ctx || !scores || n < 0) {
-    set_error("gpd_hip_score: bad argument");
-    return GPD_ERR_INVALID;
-  }
-  if (!ctx->lenet.channels) {
-    set_error("gpd_hip_score: LeNet weights not set");
-    return GPD_ERR_STATE;
-  }
-  if (n == 0) return GPD_OK;
+  int rc = refuse("gpd_hip_score", ctx, scores && n >= 0, {Need::LeNet});
+  if (rc || n == 0) return rc;
   HIP_RET(hipSetDevice(ctx->device));
   Lane &L = ctx->lane[0];
   const size_t bytes = (size_t)n * kPix * ctx->lenet.channels;
@@ -569,24 +626,20 @@ int gpd_hip_score(gpd_hip_ctx *ctx, const uint8_t *images, int n, float *scores)
     }
     d_img = L.images.d_images;
   }
-  int rc = reserve_scores(L, n);
-  if (rc) return rc;
   HIP_RET(hipEventRecord(L.ev[2], L.stream));
-  HIP_RET(lenet_forward(ctx->lenet, L.lenet_scratch, d_img, n, L.d_scores, L.stream));
+  rc = lane_lenet(ctx, L, d_img, n, "gpd:lenet (gpd_hip_score)");
+  if (rc) return rc;
   HIP_RET(hipEventRecord(L.ev[3], L.stream));
   HIP_RET(hipMemcpyAsync(scores, L.d_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, L.stream));
   HIP_RET(hipStreamSynchronize(L.stream));
   HIP_RET(hipEventElapsedTime(&L.stage_ms[2], L.ev[2], L.ev[3]));
-  return lenet_check(L.lenet_scratch);
+  return lane_check(L, 0, /*scored=*/true);
 }
 
 int gpd_hip_upload_cloud(gpd_hip_ctx *ctx, const float *xyz, const float *normals, int num_points, const int32_t *cam_source,
                          int num_cams, const double *view_points) {
   StageRange range_("gpd:upload_cloud (+ uniform grid)");
-  if (!ctx || !xyz || !normals || num_points <= 0 || !cam_source || num_cams < 1 || !view_points) {
-    set_error("gpd_hip_upload_cloud: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_upload_cloud", ctx, xyz && normals && num_points > 0 && cam_source && num_cams >= 1 && view_points)) return rc;
   HIP_RET(hipSetDevice(ctx->device));
   Lane &L = ctx->lane[0];
   return cloud_upload(L.cloud, xyz, normals, num_points, cam_source, num_cams, view_points, L.stream, /*sync=*/true);
@@ -594,10 +647,7 @@ int gpd_hip_upload_cloud(gpd_hip_ctx *ctx, const float *xyz, const float *normal
 
 int gpd_hip_upload_ground_truth(gpd_hip_ctx *ctx, const float *xyz, const float *normals, int num_points) {
   StageRange range_("gpd:upload_ground_truth (+ uniform grid)");
-  if (!ctx || num_points < 0 || (num_points > 0 && (!xyz || !normals))) {
-    set_error("gpd_hip_upload_ground_truth: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_upload_ground_truth", ctx, num_points >= 0 && (num_points == 0 || (xyz && normals)))) return rc;
   HIP_RET(hipSetDevice(ctx->device));
   Lane &L = ctx->lane[0];
   LabelState &ls = ctx->label;
@@ -710,10 +760,7 @@ int gpd_hip_shuffle_orders(uint32_t seed, const int32_t *sizes, int num_sets, in
 int gpd_hip_find_clusters(gpd_hip_ctx *ctx, const gpd_hand *hands, const double *scores, int n, int min_inliers, int remove_inliers,
                           gpd_hand *out, double *out_scores, int32_t *out_src, int *num_out) {
   StageRange range_("gpd:find_clusters");
-  if (!ctx || !num_out || n < 0 || (n > 0 && (!hands || !scores || !out || !out_scores || !out_src))) {
-    set_error("gpd_hip_find_clusters: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_find_clusters", ctx, num_out && n >= 0 && (n == 0 || (hands && scores && out && out_scores && out_src)))) return rc;
   HIP_RET(hipSetDevice(ctx->device));
   return cluster_run(ctx->cluster, hands, scores, n, min_inliers, remove_inliers, out, out_scores, out_src, num_out, ctx->lane[0].stream);
 }
@@ -722,11 +769,9 @@ int gpd_hip_preprocess_cloud(gpd_hip_ctx *ctx, const float *xyz, const int32_t *
                              const double *workspace, float voxel_size, float *xyz_out, int32_t *cam_out, int32_t *src_out,
                              int *num_out, float *kernel_ms) {
   StageRange range_("gpd:preprocess_cloud (workspace cut, voxeliser)");
-  if (!ctx || !num_out || num_points < 0 || num_cams < 0 || (num_points > 0 && (!xyz || !xyz_out)) ||
-      (num_points > 0 && num_cams > 0 && (!cam_source || !cam_out)) || !(voxel_size == voxel_size)) {
-    set_error("gpd_hip_preprocess_cloud: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  const bool bad = !num_out || num_points < 0 || num_cams < 0 || (num_points > 0 && (!xyz || !xyz_out)) ||
+                   (num_points > 0 && num_cams > 0 && (!cam_source || !cam_out)) || !(voxel_size == voxel_size);
+  if (int rc = refuse("gpd_hip_preprocess_cloud", ctx, !bad)) return rc;
   if (workspace)
     for (int a = 0; a < 6; a++)
       if (workspace[a] != workspace[a]) {
@@ -740,34 +785,22 @@ int gpd_hip_preprocess_cloud(gpd_hip_ctx *ctx, const float *xyz, const int32_t *
 
 int gpd_hip_estimate_normals(gpd_hip_ctx *ctx, double radius, float *normals) {
   StageRange range_("gpd:estimate_normals");
-  if (!ctx || !normals || !(radius > 0.0)) {
-    set_error("gpd_hip_estimate_normals: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_estimate_normals", ctx, normals && radius > 0.0, {Need::Cloud})) return rc;
   Lane &L = ctx->lane[0];
-  if (!L.cloud.num_points) {
-    set_error("gpd_hip_estimate_normals: no cloud uploaded");
-    return GPD_ERR_STATE;
-  }
   HIP_RET(hipSetDevice(ctx->device));
   return normals_run(L.cloud, radius, normals, L.stream);
 }
 
 int gpd_hip_sample_above_plane(gpd_hip_ctx *ctx, double threshold, int max_iterations, double probability, int optimize,
                                 int32_t *indices_out, int *num_out, float coeffs[4], int *num_inliers, int *iterations) {
-  if (!ctx || !indices_out || !num_out || !coeffs || !num_inliers || !iterations || max_iterations < 0) {
-    set_error("gpd_hip_sample_above_plane: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_sample_above_plane", ctx, indices_out && num_out && coeffs && num_inliers && iterations && max_iterations >= 0))
+    return rc;
   if (max_iterations >= kPlaneMaxHyp) {
     set_error("gpd_hip_sample_above_plane: max_iterations = %d, the capacity is %d", max_iterations, kPlaneMaxHyp - 1);
     return GPD_ERR_CAPACITY;
   }
+  if (int rc = refuse("gpd_hip_sample_above_plane", ctx, true, {Need::Cloud})) return rc;
   Lane &L = ctx->lane[0];
-  if (!L.cloud.num_points) {
-    set_error("gpd_hip_sample_above_plane: no cloud uploaded");
-    return GPD_ERR_STATE;
-  }
   HIP_RET(hipSetDevice(ctx->device));
   return plane_fit_run(ctx->plane, L.cloud, threshold, max_iterations, probability, optimize, indices_out, num_out, coeffs, num_inliers,
                        iterations, L.stream);
@@ -790,11 +823,9 @@ int gpd_hip_sample_positions(int n, int num_draws, uint32_t seed, int with_repet
 
 int gpd_hip_refine_normals(gpd_hip_ctx *ctx, int k, int max_iterations, float convergence_threshold, float *normals_out, int *iterations_out,
                            float *ddot_out, int *num_nan_out, float kernel_ms[3]) {
-  if (!ctx || !normals_out || !iterations_out || !num_nan_out || k < 1 || max_iterations < 0 || !std::isfinite(convergence_threshold) ||
-      convergence_threshold < 0.f) {
-    set_error("gpd_hip_refine_normals: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_refine_normals", ctx, normals_out && iterations_out && num_nan_out && k >= 1 && max_iterations >= 0 &&
+                                                          std::isfinite(convergence_threshold) && convergence_threshold >= 0.f))
+    return rc;
   if (k > kRefineKCap) {
     set_error("gpd_hip_refine_normals: k = %d, the capacity is %d", k, kRefineKCap);
     return GPD_ERR_CAPACITY;
@@ -812,18 +843,12 @@ int gpd_hip_refine_normals(gpd_hip_ctx *ctx, int k, int max_iterations, float co
 // samples by index (sample_xyz == nullptr) or by coordinates (sample_indices == nullptr)
 static int search_any(gpd_hip_ctx *ctx, const char *who, const int32_t *sample_indices, const double *sample_xyz, int num_samples,
                       gpd_hand *hands, int *num_sets) {
-  if (!ctx || (!sample_indices && !sample_xyz) || num_samples < 0 || !hands || !num_sets) {
-    set_error("%s: bad argument", who);
-    return GPD_ERR_INVALID;
-  }
+  int rc = refuse(who, ctx, (sample_indices || sample_xyz) && num_samples >= 0 && hands && num_sets, {Need::Cloud});
+  if (rc) return rc;
   Lane &L = ctx->lane[0];
-  if (!L.cloud.num_points) {
-    set_error("%s: no cloud uploaded", who);
-    return GPD_ERR_STATE;
-  }
   *num_sets = 0;
   if (num_samples == 0) return GPD_OK;
-  int rc = check_samples(who, sample_indices, sample_xyz, num_samples, L.cloud.num_points);
+  rc = check_samples(who, sample_indices, sample_xyz, num_samples, L.cloud.num_points);
   if (rc) return rc;
   HIP_RET(hipSetDevice(ctx->device));
   HIP_RET(hipEventRecord(L.ev[0], L.stream));
@@ -838,33 +863,20 @@ static int search_any(gpd_hip_ctx *ctx, const char *who, const int32_t *sample_i
 
 int gpd_hip_search(gpd_hip_ctx *ctx, const int32_t *sample_indices, int num_samples, gpd_hand *hands, int *num_sets) {
   StageRange range_("gpd:search (unfused entry)");
-  if (!sample_indices) {
-    set_error("gpd_hip_search: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_search", ctx, sample_indices)) return rc;
   return search_any(ctx, "gpd_hip_search", sample_indices, nullptr, num_samples, hands, num_sets);
 }
 
 int gpd_hip_search_samples(gpd_hip_ctx *ctx, const double *samples_xyz, int num_samples, gpd_hand *hands, int *num_sets) {
-  if (!samples_xyz) {
-    set_error("gpd_hip_search_samples: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_search_samples", ctx, samples_xyz)) return rc;
   return search_any(ctx, "gpd_hip_search_samples", nullptr, samples_xyz, num_samples, hands, num_sets);
 }
 
 int gpd_hip_reevaluate(gpd_hip_ctx *ctx, gpd_hand *hands, int num_hands, int32_t *labels) {
   StageRange range_("gpd:reevaluate");
-  if (!ctx || num_hands < 0 || (num_hands > 0 && (!hands || !labels))) {
-    set_error("gpd_hip_reevaluate: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  int rc = refuse("gpd_hip_reevaluate", ctx, num_hands >= 0 && (num_hands == 0 || (hands && labels)), {Need::Cloud});
+  if (rc || num_hands == 0) return rc;
   Lane &L = ctx->lane[0];
-  if (!L.cloud.num_points) {
-    set_error("gpd_hip_reevaluate: no cloud uploaded");
-    return GPD_ERR_STATE;
-  }
-  if (num_hands == 0) return GPD_OK;
   for (int i = 0; i < num_hands; i++)
     for (int r = 0; r < 3; r++)
       if (!std::isfinite(hands[i].sample[r])) {
@@ -879,15 +891,9 @@ int gpd_hip_reevaluate(gpd_hip_ctx *ctx, gpd_hand *hands, int num_hands, int32_t
 int gpd_hip_images(gpd_hip_ctx *ctx, const gpd_hand *hands, int num_sets, uint8_t *images, int32_t *cand_index,
                    int *num_candidates) {
   StageRange range_("gpd:images (unfused entry)");
-  if (!ctx || !hands || num_sets < 0 || !num_candidates) {
-    set_error("gpd_hip_images: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  int rc = refuse("gpd_hip_images", ctx, hands && num_sets >= 0 && num_candidates, {Need::Cloud});
+  if (rc) return rc;
   Lane &L = ctx->lane[0];
-  if (!L.cloud.num_points) {
-    set_error("gpd_hip_images: no cloud uploaded");
-    return GPD_ERR_STATE;
-  }
   HIP_RET(hipSetDevice(ctx->device));
   SearchState &s = L.search;
   const int slots = ctx->params.num_hand_axes * ctx->params.num_orientations;
@@ -910,7 +916,7 @@ int gpd_hip_images(gpd_hip_ctx *ctx, const gpd_hand *hands, int num_sets, uint8_
     for (int r = 0; r < 3; r++) smp[3 * (size_t)si + r] = hands[(size_t)si * slots].sample[r];
   }
   HIP_RET(hipEventRecord(L.ev[0], L.stream));
-  int rc = plan_build(ctx->params, L.cloud, s, L.plan, L.stream, fv.data(), smp.data(), num_sets);
+  rc = plan_build(ctx->params, L.cloud, s, L.plan, L.stream, fv.data(), smp.data(), num_sets);
   if (rc) return rc;
   HIP_RET(hipStreamSynchronize(L.stream));  // fv / smp are pageable: their copies have left them by now as well
   if (L.plan.h_summary->mismatch_set >= 0) {
@@ -918,30 +924,17 @@ int gpd_hip_images(gpd_hip_ctx *ctx, const gpd_hand *hands, int num_sets, uint8_
               L.plan.h_summary->mismatch_set);
     return GPD_ERR_STATE;
   }
-  L.images.lcg_base = 0;  // gpd_hip_images: the cloud's stream of shadow draws from its start
-  rc = images_run(ctx->params, L.cloud, s, L.plan, L.images, L.stream);
+  // the cloud's stream of shadow draws from its start; ev[0] stands ahead of the plan: stage_ms[1] is plan + images
+  rc = lane_images(ctx, L, /*side_stream=*/true, 0, "gpd:images (gpd_hip_images)", nullptr, L.ev[1]);
   if (rc) return rc;
-  HIP_RET(hipEventRecord(L.ev[1], L.stream));
   const int n = L.images.num_candidates;
   *num_candidates = n;
-  if (cand_index && n > 0)
-    HIP_RET(hipMemcpyAsync(cand_index, L.plan.d_cand_out, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
-  if (images && n > 0) {
-    // the caller wants cv::Mat-layout pixels: planar -> HWC on the device, then one copy
-    const size_t bytes = (size_t)L.images.capacity * kPix * ctx->params.image_num_channels;
-    if (!L.images.d_images_hwc) HIP_RET(device_alloc(L.images.d_images_hwc, bytes));
-    HIP_RET(planar_to_hwc(L.images.d_images, L.images.d_images_hwc, n, ctx->params.image_num_channels, L.stream));
-    HIP_RET(hipMemcpyAsync(images, L.images.d_images_hwc, (size_t)n * kPix * ctx->params.image_num_channels, hipMemcpyDeviceToHost,
-                           L.stream));
-  }
+  rc = lane_download_images(ctx->params, L, n, images, cand_index);
+  if (rc) return rc;
   HIP_RET(hipMemcpyAsync(&L.h_flags->status, L.images.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
   HIP_RET(hipStreamSynchronize(L.stream));
   HIP_RET(hipEventElapsedTime(&L.stage_ms[1], L.ev[0], L.ev[1]));
-  if (L.h_flags->status) {
-    set_images_status_error(L.h_flags->status);
-    return GPD_ERR_CAPACITY;
-  }
-  return GPD_OK;
+  return lane_check(L, L.h_flags->status, /*scored=*/false);
 }
 
 }  // extern "C"

@@ -47,19 +47,10 @@ int given_ingest(SearchState &s, const gpd_hand *hands, int S, int slots, hipStr
 // the body of both entries; with_scores: the LeNet pass behind the images, scores [n] and cand [n] on the host
 static int given_run(gpd_hip_ctx *ctx, const char *who, const gpd_hand *hands, int num_sets, uint64_t lcg_base, uint8_t *images,
                      int32_t *cand_index, int *num_candidates, uint64_t *lcg_draws, float *scores) {
-  if (!ctx || num_sets < 0 || (num_sets > 0 && !hands) || !num_candidates) {
-    set_error("%s: bad argument", who);
-    return GPD_ERR_INVALID;
-  }
+  const bool args_ok = num_sets >= 0 && (num_sets == 0 || hands) && num_candidates;
+  int rc = scores ? refuse(who, ctx, args_ok, {Need::Cloud, Need::LeNet}) : refuse(who, ctx, args_ok, {Need::Cloud});
+  if (rc) return rc;
   Lane &L = ctx->lane[0];
-  if (!L.cloud.num_points) {
-    set_error("%s: no cloud uploaded", who);
-    return GPD_ERR_STATE;
-  }
-  if (scores && !ctx->lenet.channels) {
-    set_error("%s: LeNet weights not set", who);
-    return GPD_ERR_STATE;
-  }
   {
     int bad_set = -1, bad_slot = -1;
     char msg[256];
@@ -81,7 +72,7 @@ static int given_run(gpd_hip_ctx *ctx, const char *who, const gpd_hand *hands, i
   for (int i = 0; i < num_sets; i++)
     for (int r = 0; r < 3; r++) xyz[3 * (size_t)i + r] = hands[(size_t)i * slots].sample[r];
   HIP_RET(hipEventRecord(L.ev[0], L.stream));
-  int rc = given_lists_run(p, L.cloud, s, xyz.data(), num_sets, L.stream);
+  rc = given_lists_run(p, L.cloud, s, xyz.data(), num_sets, L.stream);
   if (rc) return rc;
   rc = given_ingest(s, hands, num_sets, slots, L.stream);
   if (rc) return rc;
@@ -90,38 +81,28 @@ static int given_run(gpd_hip_ctx *ctx, const char *who, const gpd_hand *hands, i
   s.num_samples = 0;         // ... these lists have no search behind them (gpd_hip_images, gpd_hip_replay refuse)
   if (rc) return rc;
   HIP_RET(hipStreamSynchronize(L.stream));  // `hands` is pageable: its copy has left it by now as well
-  L.images.lcg_base = lcg_base;
-  rc = images_run(p, L.cloud, s, L.plan, L.images, L.stream);
+  // ev[0] stands ahead of the lists: stage_ms[1] is lists + plan + images
+  rc = lane_images(ctx, L, /*side_stream=*/true, lcg_base, "gpd:images (given hand sets)", nullptr, L.ev[1]);
   if (rc) return rc;
-  HIP_RET(hipEventRecord(L.ev[1], L.stream));
   const int n = L.images.num_candidates;
-  if (cand_index && n > 0)
-    HIP_RET(hipMemcpyAsync(cand_index, L.plan.d_cand_out, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
-  if (images && n > 0) {
-    const size_t bytes = (size_t)L.images.capacity * kPix * p.image_num_channels;
-    if (!L.images.d_images_hwc) HIP_RET(device_alloc(L.images.d_images_hwc, bytes));
-    HIP_RET(planar_to_hwc(L.images.d_images, L.images.d_images_hwc, n, p.image_num_channels, L.stream));
-    HIP_RET(hipMemcpyAsync(images, L.images.d_images_hwc, (size_t)n * kPix * p.image_num_channels, hipMemcpyDeviceToHost, L.stream));
-  }
-  if (scores && n > 0) {
-    rc = reserve_scores(L, n);
-    if (rc) return rc;
+  rc = lane_download_images(p, L, n, images, cand_index);
+  if (rc) return rc;
+  const bool scored = scores && n > 0;
+  if (scored) {
     HIP_RET(hipEventRecord(L.ev[2], L.stream));
-    HIP_RET(lenet_forward(ctx->lenet, L.lenet_scratch, L.images.d_images, n, L.d_scores, L.stream));
+    rc = lane_lenet(ctx, L, L.images.d_images, n, "gpd:lenet (given hand sets)");
+    if (rc) return rc;
     HIP_RET(hipEventRecord(L.ev[3], L.stream));
     HIP_RET(hipMemcpyAsync(scores, L.d_scores, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, L.stream));
   }
   HIP_RET(hipMemcpyAsync(&L.h_flags->status, L.images.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
   HIP_RET(hipStreamSynchronize(L.stream));
   HIP_RET(hipEventElapsedTime(&L.stage_ms[1], L.ev[0], L.ev[1]));
-  if (scores && n > 0) HIP_RET(hipEventElapsedTime(&L.stage_ms[2], L.ev[2], L.ev[3]));
-  if (L.h_flags->status) {
-    set_images_status_error(L.h_flags->status);
-    return GPD_ERR_CAPACITY;
-  }
+  if (scored) HIP_RET(hipEventElapsedTime(&L.stage_ms[2], L.ev[2], L.ev[3]));
+  rc = lane_check(L, L.h_flags->status, scored);
+  if (rc) return rc;
   *num_candidates = n;
   if (lcg_draws) *lcg_draws = L.plan.h_summary->total_draws;
-  if (scores && n > 0) return lenet_check(L.lenet_scratch);
   return GPD_OK;
 }
 
@@ -156,10 +137,7 @@ int gpd_hip_images_given(gpd_hip_ctx *ctx, const gpd_hand *hands, int num_sets, 
 int gpd_hip_score_given(gpd_hip_ctx *ctx, gpd_hand *hands, int num_sets, uint64_t lcg_base, float *scores, int32_t *cand_index,
                         int *num_candidates, uint64_t *lcg_draws) {
   StageRange range_("gpd:score_given");
-  if (!ctx || num_sets < 0 || !num_candidates) {
-    set_error("gpd_hip_score_given: bad argument");
-    return GPD_ERR_INVALID;
-  }
+  if (int rc = refuse("gpd_hip_score_given", ctx, num_sets >= 0 && num_candidates)) return rc;
   // one score and one index per candidate come back (the caller holds the records): room for every valid hand
   const int slots = ctx->params.num_hand_axes * ctx->params.num_orientations;
   size_t nv = 0;

@@ -111,6 +111,8 @@ hipError_t lenet_forward_fast(const LeNetWeights &w, LeNetScratch &s, const uint
 hipError_t lenet_scratch_reserve(LeNetScratch &s, int n);
 // after the stream was synchronised: GPD_ERR_HIP (and the error word cleared) when a conv1 launch gave up on its slot protocol
 int lenet_check(LeNetScratch &s);
+// the launch error word lenet_check reads, for a caller that copies its low four bytes out behind a pass (non-zero: call lenet_check)
+inline const void *lenet_fault_word(const LeNetScratch &s) { return s.c1_stats + 2; }
 void lenet_scratch_free(LeNetScratch &s);
 
 void set_error(const char *fmt, ...);
@@ -379,7 +381,7 @@ struct LabelSink {
   void *self;
   int (*place)(void *self, size_t k, uint8_t **images, uint8_t **labels);
 };
-// the body of gpd_hip_label_view (detect.hip); sink != null: the kept images and labels go to the sink, and job->images, labels,
+// the body of gpd_hip_label_view (rounds.hip); sink != null: the kept images and labels go to the sink, and job->images, labels,
 // hands, src_index and capacity are not read
 int label_view_run(gpd_hip_ctx *ctx, gpd_label_view_job *job, const char *who, const LabelSink *sink);
 

@@ -105,3 +105,56 @@ def test_image_routes_refuses_null_arguments():
     assert L.gpd_hip_last_image_routes(not_a_context, route, 4, None) == -1
     assert L.gpd_hip_last_image_routes(not_a_context, route, -1, info) == -1
     assert b"bad argument" in L.gpd_hip_last_error()
+
+
+def test_context_entries_refuse_null_arguments():
+    """Every entry of context.hip, detect.hip, rounds.hip and given.hip that takes a context, and gpd_hip_detect_batch, refuses a
+    null context, and a null in place of its first required pointer, with GPD_ERR_INVALID and the text "<entry>: bad argument" (gpd_hip_set_lenet_weights has
+    said "null argument" from its first day), before it touches the context or the device (no GPU needed)."""
+    from gpd_amd import api
+    L = api.lib()
+    ctx = ctypes.create_string_buffer(1 << 20)  # not a context, and never read: the null beside it is refused first
+    buf = ctypes.create_string_buffer(4096)
+    i = [ctypes.byref(ctypes.c_int()) for _ in range(4)]
+    u64, f32 = ctypes.byref(ctypes.c_uint64()), ctypes.byref(ctypes.c_float())
+    # entry -> the arguments behind the context, the first required pointer None
+    cases = {
+        "gpd_hip_reserve": None,
+        "gpd_hip_set_lenet_weights": (15, None, buf, buf, buf, buf, buf, buf, buf),
+        "gpd_hip_set_lenet_mode": None,
+        "gpd_hip_set_lenet_conv_relu": None,
+        "gpd_hip_lenet_debug": (0, 1, None),
+        "gpd_hip_score": (buf, 1, None),
+        "gpd_hip_upload_cloud": (None, buf, 1, buf, 1, buf),
+        "gpd_hip_upload_ground_truth": (None, buf, 1),
+        "gpd_hip_find_clusters": (buf, buf, 0, 0, 0, buf, buf, buf, None),
+        "gpd_hip_preprocess_cloud": (buf, buf, 1, 1, buf, 0.01, buf, buf, buf, None, f32),
+        "gpd_hip_estimate_normals": (0.01, None),
+        "gpd_hip_sample_above_plane": (0.01, 10, 0.99, 0, None, i[0], buf, i[1], i[2]),
+        "gpd_hip_refine_normals": (4, 1, 0.0, None, i[0], buf, i[1], buf),
+        "gpd_hip_search": (None, 1, buf, i[0]),
+        "gpd_hip_search_samples": (None, 1, buf, i[0]),
+        "gpd_hip_reevaluate": (None, 1, buf),
+        "gpd_hip_images": (None, 1, buf, buf, i[0]),
+        "gpd_hip_detect": (None, 1, buf, i[0], i[1]),
+        "gpd_hip_detect_samples": (None, 1, buf, i[0], i[1]),
+        "gpd_hip_detect_select": (None, 1, 0, buf, 8, i[0], i[1], i[2]),
+        "gpd_hip_label_view": (None,),
+        "gpd_hip_detect_sis": (None,),
+        "gpd_hip_images_given": (None, 1, 0, buf, buf, i[0], u64),
+        "gpd_hip_score_given": (buf, 1, 0, buf, buf, None, u64),
+        "gpd_hip_detect_batch": (None, 1),  # batch.hip: the one entry there that opens with the same helper
+    }
+    valid = {"gpd_hip_reserve": (1, 1, 0, 0, 0), "gpd_hip_set_lenet_mode": (0,), "gpd_hip_set_lenet_conv_relu": (0,),
+             "gpd_hip_label_view": (ctypes.byref(api.LabelViewJob()),), "gpd_hip_detect_sis": (ctypes.byref(api.SisJob()),),
+             "gpd_hip_detect_batch": (ctypes.byref(api.DetectJob()), 1)}
+    for name, args in sorted(cases.items()):
+        text = name.encode() + (b": null argument" if name == "gpd_hip_set_lenet_weights" else b": bad argument")
+        fn = getattr(L, name)
+        # a null context: the other arguments as good as they get without a device
+        good = valid.get(name) or tuple(ctypes.cast(buf, ctypes.POINTER(ctypes.c_int)) if a is None else a for a in args)
+        assert fn(None, *good) == -1, name
+        assert L.gpd_hip_last_error() == text, (name, L.gpd_hip_last_error())
+        if args is not None:
+            assert fn(ctx, *args) == -1, name
+            assert L.gpd_hip_last_error() == text, (name, L.gpd_hip_last_error())
