@@ -351,7 +351,11 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_train_reorder", "gpd_hip_train_append_view",
            "gpd_hip_train_group_mean", "gpd_hip_train_group_slices", "gpd_hip_train_group_schedule", "gpd_hip_train_group_create",
            "gpd_hip_train_group_destroy", "gpd_hip_train_group_broadcast", "gpd_hip_train_group_steps", "gpd_hip_train_group_verify",
-           "gpd_hip_train_group_last_bytes"]
+           "gpd_hip_train_group_last_bytes",
+           "gpd_hip_train_create_net", "gpd_hip_train_shape", "gpd_hip_train_net_set_state", "gpd_hip_train_net_get_state",
+           "gpd_hip_train_net_gradients", "gpd_hip_train_net_apply", "gpd_hip_train_net_get_solver_state",
+           "gpd_hip_train_net_set_solver_state", "gpd_hip_train_net_sizes", "gpd_hip_train_net_init_state",
+           "gpd_hip_train_net_init_xavier"]
 
 
 def build(prof=True):
@@ -471,6 +475,18 @@ def lib():
         L.gpd_hip_train_group_steps.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.gpd_hip_train_group_verify.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
         L.gpd_hip_train_group_last_bytes.argtypes = [C.c_void_p, C.c_void_p]
+        L.gpd_hip_train_create_net.argtypes = [C.c_void_p, C.POINTER(TrainParams), C.POINTER(TrainRecipe), C.POINTER(LenetShape),
+                                               C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_shape.argtypes = [C.c_void_p, C.POINTER(LenetShape)]
+        L.gpd_hip_train_net_set_state.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_net_get_state.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_net_gradients.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_float)]
+        L.gpd_hip_train_net_apply.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_net_get_solver_state.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
+        L.gpd_hip_train_net_set_solver_state.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_longlong]
+        L.gpd_hip_train_net_sizes.argtypes = [C.POINTER(LenetShape), C.c_void_p]
+        L.gpd_hip_train_net_init_state.argtypes = [C.POINTER(LenetShape), C.c_uint32, C.POINTER(C.c_void_p)]
+        L.gpd_hip_train_net_init_xavier.argtypes = [C.POINTER(LenetShape), C.c_uint32, C.POINTER(C.c_void_p)]
         assert L.gpd_hip_sizeof_train_recipe() == C.sizeof(TrainRecipe)
         assert L.gpd_hip_sizeof_label_view_job() == C.sizeof(LabelViewJob)
         assert L.gpd_hip_sizeof_sis_job() == C.sizeof(SisJob)
@@ -1022,6 +1038,58 @@ def _state_pointers(state, channels):
     return arrs, (C.c_void_p * 8)(*[a.ctypes.data for a in arrs])
 
 
+def net_shape(channels, shape):
+    """(F1, F2, H1) or (F1, F2, H1, H2) or a LenetShape -> the LenetShape at `channels` channels"""
+    if isinstance(shape, LenetShape):
+        if shape.channels != int(channels):
+            raise ValueError("the shape has %d channels, %d expected" % (shape.channels, int(channels)))
+        return shape
+    w = [int(x) for x in shape]
+    if len(w) not in (3, 4):
+        raise ValueError("a network shape is (F1, F2, H1) or (F1, F2, H1, H2), not %r" % (shape,))
+    return LenetShape(int(channels), w[0], w[1], w[2], w[3] if len(w) == 4 else 0)
+
+
+def net_keys(shape):
+    """The keys of the state of a network of `shape`: TORCH_KEYS, or TORCH_NET_KEYS with a third dense layer."""
+    return TORCH_NET_KEYS if shape.fc2_out > 0 else TORCH_KEYS
+
+
+def net_state_shapes(shape):
+    """The shapes of the 8 or 10 tensors of a network of `shape` (a LenetShape), in net_keys order."""
+    Cn, F1, F2, H1, H2 = shape.as_tuple()
+    out = [(F1, Cn, 5, 5), (F1,), (F2, F1, 5, 5), (F2,), (H1, F2 * 144), (H1,)]
+    return tuple(out + ([(H2, H1), (H2,), (2, H2), (2,)] if H2 > 0 else [(2, H1), (2,)]))
+
+
+def net_sizes(shape):
+    """gpd_hip_train_net_sizes: the element counts of the ten tensors (the last two 0 without a third dense layer; host only)."""
+    n = (C.c_size_t * 10)()
+    _lib_check(lib().gpd_hip_train_net_sizes(C.byref(shape), n))
+    return [int(x) for x in n]
+
+
+def _net_buffers(shape):
+    arrs = [np.zeros(s, np.float32) for s in net_state_shapes(shape)]
+    return arrs, _pointer_table(arrs)
+
+
+def _net_pointers(state, shape):
+    plain = {(str(k)[len("module."):] if str(k).startswith("module.") else str(k)): v for k, v in state.items()}
+    arrs = []
+    for k, want in zip(net_keys(shape), net_state_shapes(shape)):
+        if k not in plain:
+            raise KeyError("state dict has no %r (keys: %s)" % (k, sorted(plain)))
+        v = plain[k]
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        a = np.ascontiguousarray(v, np.float32)
+        if a.size != int(np.prod(want)):
+            raise ValueError("%s has %d elements, %d expected for %r" % (k, a.size, int(np.prod(want)), shape))
+        arrs.append(a)
+    return arrs, _pointer_table(arrs)
+
+
 def train_default_params(channels=15, max_batch=64):
     p = TrainParams()
     lib().gpd_hip_train_default_params(C.byref(p))
@@ -1029,9 +1097,15 @@ def train_default_params(channels=15, max_batch=64):
     return p
 
 
-def init_state(channels, seed=0):
+def init_state(channels, seed=0, shape=None):
     """gpd_hip_train_init_state: a seeded initial state of Net, every tensor U(-1/sqrt(fan_in), 1/sqrt(fan_in)) (host only)
-    -> {key: f32 array in torch layout}."""
+    -> {key: f32 array in torch layout}.  shape (net_shape): gpd_hip_train_net_init_state for a network of those widths, 8 or
+    10 tensors."""
+    if shape is not None:
+        shape = net_shape(channels, shape)
+        arrs, ptrs = _net_buffers(shape)
+        _lib_check(lib().gpd_hip_train_net_init_state(C.byref(shape), int(seed) & 0xFFFFFFFF, ptrs))
+        return dict(zip(net_keys(shape), arrs))
     if int(channels) not in (1, 3, 12, 15):
         raise GpdHipError("libgpd_hip error -1: init_state: %d channels (1, 3, 12 or 15)" % int(channels))
     arrs, ptrs = _state_buffers(channels)
@@ -1069,9 +1143,14 @@ def train_default_recipe(which=0, **kw):
     return r
 
 
-def init_xavier(channels, seed=0):
+def init_xavier(channels, seed=0, shape=None):
     """gpd_hip_train_init_xavier: Caffe's xavier filler from the project's seeded stream — weights U(-sqrt(3 / fan_in),
-    sqrt(3 / fan_in)), biases 0 (host only) -> {key: f32 array in torch layout}."""
+    sqrt(3 / fan_in)), biases 0 (host only) -> {key: f32 array in torch layout}.  shape: as in init_state."""
+    if shape is not None:
+        shape = net_shape(channels, shape)
+        arrs, ptrs = _net_buffers(shape)
+        _lib_check(lib().gpd_hip_train_net_init_xavier(C.byref(shape), int(seed) & 0xFFFFFFFF, ptrs))
+        return dict(zip(net_keys(shape), arrs))
     if int(channels) not in (1, 3, 12, 15):
         raise GpdHipError("libgpd_hip error -1: init_xavier: %d channels (1, 3, 12 or 15)" % int(channels))
     arrs, ptrs = _state_buffers(channels)
@@ -1089,10 +1168,12 @@ def learning_rate(recipe, base_lr, it):
 class Trainer:
     """One gpd_hip_trainer on a Context's device and stream.  Without a recipe: Net (pytorch/network.py) under softmax
     cross-entropy and Adam, as pytorch/train_net3.py trains it.  recipe (train_default_recipe): the network with or without conv
-    ReLUs, Adam or Caffe's SGD, a learning-rate policy.  The state travels as a dict of numpy arrays in torch layout, both ways.
-    Close it before its context."""
+    ReLUs, Adam or Caffe's SGD, a learning-rate policy.  shape = (F1, F2, H1) or (F1, F2, H1, H2): a network of those widths
+    (gpd_hip_train_create_net; H2 > 0: NetCCFFF, whose state has the ten TORCH_NET_KEYS) at the params' channel count; None: the
+    stock widths through the stock entries.  The state travels as a dict of numpy arrays in torch layout, both ways.  Close it
+    before its context."""
 
-    def __init__(self, ctx, params=None, recipe=None, **kw):
+    def __init__(self, ctx, params=None, recipe=None, shape=None, **kw):
         self.params = params if params is not None else train_default_params(ctx.params.image_num_channels)
         self.recipe = recipe
         for k, v in kw.items():
@@ -1102,7 +1183,13 @@ class Trainer:
         self.channels = int(self.params.channels)
         self._ctx = ctx  # keeps the context (the stream) alive
         self._h = C.c_void_p()
-        if recipe is None:
+        self._net = shape is not None  # the entries with tables of 10
+        self.shape = net_shape(self.channels, shape) if self._net else LenetShape(self.channels, 20, 50, 500, 0)
+        self.keys = net_keys(self.shape)
+        if self._net:
+            self._check(lib().gpd_hip_train_create_net(ctx._h, C.byref(self.params), C.byref(recipe) if recipe is not None else None,
+                                                       C.byref(self.shape), C.byref(self._h)))
+        elif recipe is None:
             self._check(lib().gpd_hip_train_create(ctx._h, C.byref(self.params), C.byref(self._h)))
         else:
             self._check(lib().gpd_hip_train_create_recipe(ctx._h, C.byref(self.params), C.byref(recipe), C.byref(self._h)))
@@ -1122,29 +1209,39 @@ class Trainer:
         except Exception:
             pass
 
+    def _buffers(self):
+        return _net_buffers(self.shape) if self._net else _state_buffers(self.channels)
+
+    def _pointers(self, state):
+        return _net_pointers(state, self.shape) if self._net else _state_pointers(state, self.channels)
+
+    def _entry(self, name):
+        """gpd_hip_train_<name>, or gpd_hip_train_net_<name> for a trainer made with a shape"""
+        return getattr(lib(), ("gpd_hip_train_net_" if self._net else "gpd_hip_train_") + name)
+
     def set_state(self, state):
-        """The eight tensors; the solver's buffers (Adam's moments, SGD's history) and the update count start again."""
-        arrs, ptrs = _state_pointers(state, self.channels)
-        self._check(lib().gpd_hip_train_set_state(self._h, ptrs))
+        """The tensors of self.keys; the solver's buffers (Adam's moments, SGD's history) and the update count start again."""
+        arrs, ptrs = self._pointers(state)
+        self._check(self._entry("set_state")(self._h, ptrs))
 
     def get_state(self):
-        arrs, ptrs = _state_buffers(self.channels)
-        self._check(lib().gpd_hip_train_get_state(self._h, ptrs))
-        return dict(zip(TORCH_KEYS, arrs))
+        arrs, ptrs = self._buffers()
+        self._check(self._entry("get_state")(self._h, ptrs))
+        return dict(zip(self.keys, arrs))
 
     def get_solver_state(self):
         """-> dict(count = updates since set_state, m = {key: array}: Adam's exp_avg or SGD's history, v = Adam's exp_avg_sq or None)"""
-        m, mp = _state_buffers(self.channels)
-        v, vp = _state_buffers(self.channels) if not self.sgd else (None, None)
+        m, mp = self._buffers()
+        v, vp = self._buffers() if not self.sgd else (None, None)
         n = C.c_longlong(0)
-        self._check(lib().gpd_hip_train_get_solver_state(self._h, mp, vp, C.byref(n)))
-        return dict(count=int(n.value), m=dict(zip(TORCH_KEYS, m)), v=dict(zip(TORCH_KEYS, v)) if v is not None else None)
+        self._check(self._entry("get_solver_state")(self._h, mp, vp, C.byref(n)))
+        return dict(count=int(n.value), m=dict(zip(self.keys, m)), v=dict(zip(self.keys, v)) if v is not None else None)
 
     def set_solver_state(self, solver_state):
         """What get_solver_state returned, after set_state: the run continues byte for byte."""
-        m, mp = _state_pointers(solver_state["m"], self.channels)
-        v, vp = (None, None) if self.sgd or solver_state.get("v") is None else _state_pointers(solver_state["v"], self.channels)
-        self._check(lib().gpd_hip_train_set_solver_state(self._h, mp, vp, int(solver_state["count"])))
+        m, mp = self._pointers(solver_state["m"])
+        v, vp = (None, None) if self.sgd or solver_state.get("v") is None else self._pointers(solver_state["v"])
+        self._check(self._entry("set_solver_state")(self._h, mp, vp, int(solver_state["count"])))
 
     def set_data(self, images, labels, which=0):
         """The resident set `which` (0: training, 1: test): images u8 [n,60,60,C], labels u8 [n] of 0 / 1."""
@@ -1231,15 +1328,15 @@ class Trainer:
     def gradients(self, indices):
         """Forward and backward of one batch, no update -> ({key: gradient}, loss)."""
         idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
-        arrs, ptrs = _state_buffers(self.channels)
+        arrs, ptrs = self._buffers()
         loss = C.c_float(0)
-        self._check(lib().gpd_hip_train_gradients(self._h, _ptr(idx), len(idx), ptrs, C.byref(loss)))
-        return dict(zip(TORCH_KEYS, arrs)), float(loss.value)
+        self._check(self._entry("gradients")(self._h, _ptr(idx), len(idx), ptrs, C.byref(loss)))
+        return dict(zip(self.keys, arrs)), float(loss.value)
 
     def apply(self, grads):
         """One step of the solver from the host's gradients (a dict like gradients() returns)."""
-        arrs, ptrs = _state_pointers(grads, self.channels)
-        self._check(lib().gpd_hip_train_apply(self._h, ptrs))
+        arrs, ptrs = self._pointers(grads)
+        self._check(self._entry("apply")(self._h, ptrs))
 
     def eval(self, indices=None, n=None, which=0):
         """Forward only over set `which`: the images `indices`, or the first n (default: all given by n) -> (logits f32 [n,2], num_correct)."""
@@ -1260,8 +1357,13 @@ class Trainer:
 
     def install(self, ctx=None, input_scale=None):
         """get_state followed by Context.set_lenet_torch: the trained network becomes `ctx`'s (default: the trainer's own) scoring
-        network, with the conv ReLUs on for Net and off for the Caffe network."""
+        network, with the conv ReLUs on for Net and off for the Caffe network.  A network of other widths than the stock ones
+        goes through Context.set_lenet_net onto the general route."""
         ctx = self._ctx if ctx is None else ctx
+        if self.shape.as_tuple()[1:] != (20, 50, 500, 0):
+            ctx.set_lenet_net(self.get_state(), float(self.params.input_scale) if input_scale is None else input_scale,
+                              conv_relu=not self.caffe_network)
+            return
         ctx.set_lenet_torch(self.get_state(), float(self.params.input_scale) if input_scale is None else input_scale)
         if self.caffe_network:
             ctx.set_lenet_conv_relu(False)

@@ -19,7 +19,11 @@ struct gpd_hip_trainer {
   gpd_train_params p;
   gpd_train_recipe r;
   int C = 0, maxb = 0;
-  size_t off[9] = {0};                                                // the eight tensors inside the four parameter-sized buffers
+  gpd_lenet_shape shape = {0, 0, 0, 0, 0};                            // the widths are the trainer's: F1 -> F2 -> H1 [-> H2] -> 2
+  int F1 = 0, F2 = 0, H1 = 0, H2 = 0;
+  int nt = 8;                                                         // tensors of the state: 8, or 10 with a third dense layer (H2 > 0)
+  size_t off[11] = {0};                                               // the tensors inside the four parameter-sized buffers
+  size_t total = 0;                                                   // off[nt]: floats of a parameter-sized buffer
   float *d_p = nullptr, *d_g = nullptr, *d_m = nullptr, *d_v = nullptr;  // SGD: d_m is the history, d_v stays null
   long long step = 0;                                                 // updates since the last set_state
   uint8_t *d_img[2] = {nullptr, nullptr}, *d_lab[2] = {nullptr, nullptr};
@@ -27,13 +31,15 @@ struct gpd_hip_trainer {
   int cap[2] = {0, 0};         // images the pools hold: n <= cap
   int *d_idx = nullptr;        // [kIdxCap]
   float *d_loss = nullptr;     // [kIdxCap] one per step of an enqueue
-  float *d_pool1 = nullptr, *d_pool2 = nullptr, *d_dpool1 = nullptr, *d_dpool2 = nullptr;  // [maxb][20][784], [maxb][7200]
+  float *d_pool1 = nullptr, *d_pool2 = nullptr, *d_dpool1 = nullptr, *d_dpool2 = nullptr;  // [maxb][F1][784], [maxb][F2 * 144]
   uint8_t *d_arg1 = nullptr, *d_arg2 = nullptr;
-  float *d_a1 = nullptr, *d_dz1 = nullptr;  // [maxb][500]
+  float *d_a1 = nullptr, *d_dz1 = nullptr;  // [maxb][H1]
+  float *d_a2 = nullptr, *d_dz2 = nullptr;  // [maxb][H2], H2 > 0 only
   float *d_logits = nullptr, *d_dl = nullptr, *d_loss_b = nullptr;
-  float *d_part = nullptr;     // split-K partials of fc1 forward, conv2 dW, conv1 dW
+  float *d_part = nullptr;     // split-K partials of fc1 forward, conv2 dW, conv1 dW: room for the largest of the three
   hipEvent_t ev[gpd::kMaxKernels] = {nullptr};
   std::vector<float> h_all;    // host staging of a parameter-sized buffer
+  std::vector<const char *> names;  // of the launches of one timed step, in launch order
 };
 
 namespace gpd {
@@ -42,7 +48,7 @@ namespace gpd {
 // every kernel; k counts the kernels ----
 // forward over batch B of set `which` on the indices at d_idx; train: the loss of the batch into *d_loss_out and dlogits
 void enqueue_forward(gpd_hip_trainer *t, int which, const int *d_idx, int B, bool train, float *d_loss_out, bool timed, int &k);
-// the eight gradients of the batch into t->d_g (every element is written)
+// the gradients of the batch (all nt tensors) into t->d_g (every element is written)
 void enqueue_backward(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, int &k);
 // the recipe's solver from t->d_g; counts the update (t->step)
 void enqueue_update(gpd_hip_trainer *t, bool timed, int &k);

@@ -1,5 +1,6 @@
 // Training of pytorch/network.py::Net and of the Caffe LeNet (the same network without the ReLUs behind the convolutions) on
-// the device: forward with pooling argmax, backward, Adam or Caffe's SGD.
+// the device: forward with pooling argmax, backward, Adam or Caffe's SGD.  The layer widths are the trainer's
+// (gpd_hip_train_create_net: any gpd_lenet_shape, NetCCFFF's third dense layer included); the spatial sizes are constants.
 //
 // Every GEMM-shaped pass is one instantiation of gemm32: a wave owns a 32 x 32 tile of the result and walks its K range with
 // v_mfma_f32_32x32x2_f32, whose result is a k-ascending f32 fmaf chain.  The operands are never materialised: an operand type
@@ -26,13 +27,13 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kF1 = 20, kF2 = 50, kTaps = 25;
+constexpr int kF1 = 20, kF2 = 50, kTaps = 25;  // kF1, kF2, kFc1Out: the stock widths, what the entries without a shape create
 constexpr int kP1 = 784, kP1W = 28;    // pool1: 28 x 28
 constexpr int kP2 = 144, kP2W = 12;    // pool2: 12 x 12
 constexpr int kO1 = 3136, kO1W = 56;   // conv1 output: 56 x 56
 constexpr int kO2 = 576, kO2W = 24;    // conv2 output: 24 x 24
 constexpr int kMasked = 4;             // argmax byte of a pooled value the ReLU clamped (value <= 0)
-constexpr int kFc1Splits = 16;         // fc1 forward: K = 7200 in 16 ranges of 450
+constexpr int kFc1Splits = 16;         // fc1 forward: K = 144 F2 in 16 ranges of 9 F2 (7200 in ranges of 450 at F2 = 50)
 constexpr int kMaxBatch = 1024;
 
 // ---- operands: ctx(i) once per lane, at(ctx, k) once per k step --------------------------------------------------------------
@@ -237,6 +238,43 @@ struct MaskStore {
   }
 };
 
+// a dense layer whose K fits one range: out[m][n] = relu(acc + bias[n]), row-major [M][N]
+struct BiasReluStore {
+  const float *bias;
+  float *out;
+  int M, N;
+  __device__ void store(const f32x16 &acc, int m0, int n0, int lane, int) const {
+    const int n = n0 + (lane & 31);
+    if (n >= N) return;
+    const float bv = bias[n];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      const int m = m0 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+      if (m >= M) continue;
+      const float v = acc[r] + bv;
+      out[(long long)m * N + n] = v > 0.f ? v : 0.f;
+    }
+  }
+};
+
+// the gradient in front of a dense layer's ReLU, row-major [M][N]: zero where the activation act[m][n] was clamped
+struct ActMaskStore {
+  float *out;
+  const float *act;
+  int M, N;
+  __device__ void store(const f32x16 &acc, int m0, int n0, int lane, int) const {
+    const int n = n0 + (lane & 31);
+    if (n >= N) return;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      const int m = m0 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+      if (m >= M) continue;
+      const long long o = (long long)m * N + n;
+      out[o] = act[o] > 0.f ? acc[r] : 0.f;
+    }
+  }
+};
+
 template <class A, class B, class E>
 __global__ void __launch_bounds__(256) gemm32(A a, B b, E e, int tiles_m, int tiles_n, int K, int k_chunk) {
   const int lane = threadIdx.x & 63;
@@ -287,19 +325,23 @@ __global__ void sum_partials(const float *part, int S, int E, const float *bias,
 // sqrt(8) times more than torch's blocked float32 sums do, and it showed in the loss and in fc2.bias at B = 257 (NOTES §L)
 __device__ inline float join8(const float c[8]) { return ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7])); }
 
-// fc2, softmax cross-entropy and its gradient, one image per thread
-__global__ void head_kernel(const float *a1, const float *w, const float *bias, const uint8_t *labels, const int *idx, int B, float *logits,
-                            float *loss_b, float *dl) {
+// the last dense layer (W inputs: H1, or H2 behind a third dense layer), softmax cross-entropy and its gradient, one image per
+// thread.  WC: the width as a constant (the stock 500: the loop's trip count is then known, which is worth 0.015 ms of a step at
+// batch 64), 0: the argument
+template <int WC>
+__global__ void head_kernel(const float *a1, const float *w, const float *bias, const uint8_t *labels, const int *idx, int B, int W_arg,
+                            float *logits, float *loss_b, float *dl) {
+  const int W = WC ? WC : W_arg;
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   float c0[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, c1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int u0 = 0; u0 < kFc1Out; u0 += 8) {
+  for (int u0 = 0; u0 < W; u0 += 8) {
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-      if (u0 + j < kFc1Out) {
-        const float a = a1[(size_t)b * kFc1Out + u0 + j];
+      if (u0 + j < W) {
+        const float a = a1[(size_t)b * W + u0 + j];
         c0[j] = fmaf(a, w[u0 + j], c0[j]);
-        c1[j] = fmaf(a, w[kFc1Out + u0 + j], c1[j]);
+        c1[j] = fmaf(a, w[W + u0 + j], c1[j]);
       }
     }
   }
@@ -343,20 +385,21 @@ __global__ void __launch_bounds__(256) loss_kernel(const float *loss_b, int B, f
   if (threadIdx.x == 0) *out = s / (float)B;
 }
 
-// dZ1 = (dlogits W2) where fc1's ReLU passed
-__global__ void fc2_back_kernel(const float *dl, const float *w, const float *a1, int B, float *dz1) {
+// dZ = (dlogits W_last) where the ReLU of the layer in front of the logits (W wide) passed
+__global__ void fc2_back_kernel(const float *dl, const float *w, const float *a1, int B, int W, float *dz1) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= B * kFc1Out) return;
-  const int b = e / kFc1Out, u = e % kFc1Out;
-  dz1[e] = a1[e] > 0.f ? fmaf(dl[2 * b + 1], w[kFc1Out + u], dl[2 * b] * w[u]) : 0.f;
+  if (e >= B * W) return;
+  const int b = e / W, u = e % W;
+  dz1[e] = a1[e] > 0.f ? fmaf(dl[2 * b + 1], w[W + u], dl[2 * b] * w[u]) : 0.f;
 }
 
-// fc2.weight [2][500], fc2.bias [2], fc1.bias [500]: sums over the batch, image b on chain b mod 8
-__global__ void head_grads_kernel(const float *dl, const float *a1, const float *dz1, int B, float *g_f2w, float *g_f2b, float *g_f1b) {
+// the last layer's weight [2][W] and bias [2], and the bias [W] of the layer in front of it: sums over the batch, image b on
+// chain b mod 8
+__global__ void head_grads_kernel(const float *dl, const float *a1, const float *dz1, int B, int W, float *g_f2w, float *g_f2b, float *g_f1b) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 3 * kFc1Out + 2) return;
-  const int kind = t < 2 * kFc1Out ? 0 : t < 2 * kFc1Out + 2 ? 1 : 2;
-  const int j = kind == 0 ? t / kFc1Out : t - 2 * kFc1Out, u = kind == 0 ? t % kFc1Out : t - 2 * kFc1Out - 2;
+  if (t >= 3 * W + 2) return;
+  const int kind = t < 2 * W ? 0 : t < 2 * W + 2 ? 1 : 2;
+  const int j = kind == 0 ? t / W : t - 2 * W, u = kind == 0 ? t % W : t - 2 * W - 2;
   float c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int b0 = 0; b0 < B; b0 += 8) {
 #pragma unroll
@@ -364,11 +407,11 @@ __global__ void head_grads_kernel(const float *dl, const float *a1, const float 
       const int b = b0 + i;
       if (b >= B) continue;
       if (kind == 0)
-        c[i] = fmaf(dl[2 * b + j], a1[(size_t)b * kFc1Out + u], c[i]);
+        c[i] = fmaf(dl[2 * b + j], a1[(size_t)b * W + u], c[i]);
       else if (kind == 1)
         c[i] += dl[2 * b + j];
       else
-        c[i] += dz1[(size_t)b * kFc1Out + u];
+        c[i] += dz1[(size_t)b * W + u];
     }
   }
   const float s = join8(c);
@@ -378,6 +421,19 @@ __global__ void head_grads_kernel(const float *dl, const float *a1, const float 
     g_f2b[j] = s;
   else
     g_f1b[u] = s;
+}
+
+// out[u] = the sum over the batch of dz[b][u], image b on chain b mod 8 as in head_grads_kernel: fc1.bias behind a third dense layer
+__global__ void batch_sum_kernel(const float *dz, int B, int W, float *out) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= W) return;
+  float c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int b0 = 0; b0 < B; b0 += 8) {
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+      if (b0 + i < B) c[i] += dz[(size_t)(b0 + i) * W + u];
+  }
+  out[u] = join8(c);
 }
 
 // a convolution's bias gradient: block f sums g[b][f][0 .. pp) image by image, the images' sums joined in image order
@@ -451,12 +507,39 @@ const char *const kKernelNames[] = {"conv1_forward", "conv2_forward", "fc1_forwa
 constexpr int kNumKernels = sizeof(kKernelNames) / sizeof(kKernelNames[0]) - 1;  // of one step: it ends in adam or in sgd
 static_assert(kNumKernels + 1 <= kMaxKernels, "events");
 
+// the launches of one timed step of a trainer with (third) or without a third dense layer, in launch order
+std::vector<const char *> step_names(bool third, bool sgd) {
+  std::vector<const char *> n = {"conv1_forward", "conv2_forward", "fc1_forward", "fc1_sum_relu"};
+  if (third) n.push_back("fc2_forward");
+  n.insert(n.end(), {"head", "loss", third ? "fc3_backward" : "fc2_backward", "head_grads"});
+  if (third) n.insert(n.end(), {"fc2_dw", "fc2_dx", "fc1_db"});
+  n.insert(n.end(), {"fc1_dw", "fc1_dx", "conv2_db", "conv2_dw", "conv2_dw_sum", "conv2_dx", "conv1_db", "conv1_dw", "conv1_dw_sum", sgd ? "sgd" : "adam"});
+  return n;
+}
+constexpr int kNumKernelsThird = kNumKernels + 4;
+static_assert(kNumKernelsThird + 1 <= kMaxKernels, "events");
+
 bool channels_ok(int c) { return c == 1 || c == 3 || c == 12 || c == 15; }
 
-void tensor_sizes(int C, size_t n[8]) {
-  n[0] = (size_t)kF1 * C * kTaps, n[1] = kF1, n[2] = (size_t)kF2 * kF1 * kTaps, n[3] = kF2;
-  n[4] = (size_t)kFc1Out * kFc1In, n[5] = kFc1Out, n[6] = 2 * kFc1Out, n[7] = 2;
+gpd_lenet_shape stock_shape(int C) { return {C, kF1, kF2, kFc1Out, 0}; }
+
+int num_tensors(const gpd_lenet_shape &s) { return s.fc2_out > 0 ? 10 : 8; }
+
+// element counts of the state's tensors in state order: eight, or ten with a third dense layer (n[8] = n[9] = 0 without)
+void tensor_sizes(const gpd_lenet_shape &s, size_t n[10]) {
+  const size_t F1 = (size_t)s.conv1_out, F2 = (size_t)s.conv2_out, H1 = (size_t)s.fc1_out, H2 = (size_t)s.fc2_out, N = H2 ? H2 : 2;
+  n[0] = F1 * (size_t)s.channels * kTaps, n[1] = F1, n[2] = F2 * F1 * kTaps, n[3] = F2;
+  n[4] = H1 * F2 * kP2, n[5] = H1, n[6] = N * H1, n[7] = N;
+  n[8] = H2 ? 2 * H2 : 0, n[9] = H2 ? 2 : 0;
 }
+
+// fan_in of layer l = tensor / 2
+void fan_ins(const gpd_lenet_shape &s, int f[5]) {
+  f[0] = s.channels * kTaps, f[1] = s.conv1_out * kTaps, f[2] = s.conv2_out * kP2, f[3] = s.fc1_out, f[4] = s.fc2_out;
+}
+
+const char *const kTensorNames[10] = {"conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight",
+                                      "fc1.bias",     "fc2.weight", "fc2.bias",   "fc3.weight", "fc3.bias"};
 
 }  // namespace
 
@@ -471,24 +554,32 @@ void mark(gpd_hip_trainer *t, bool timed, int &k) {
 template <bool RELU>
 void forward_passes(gpd_hip_trainer *t, int which, const int *d_idx, int B, bool train, float *d_loss_out, bool timed, int &k) {
   hipStream_t st = t->stream;
-  const int C = t->C;
+  const int C = t->C, F1 = t->F1, F2 = t->F2, H1 = t->H1, H2 = t->H2, fc1_in = F2 * kP2;
   const float *p = t->d_p;
   const Input<uint8_t> img{t->d_img[which], d_idx, (long long)kPix * C, 1, kImg * C, C, (float)t->p.input_scale};
-  launch_gemm(st, PatchByPos<uint8_t>{img, kP1W, kP1, B * kO1}, Plain{p + t->off[0], (long long)C * kTaps, 1, kF1},
-              PoolStore<RELU>{p + t->off[1], t->d_pool1, t->d_arg1, kF1, kP1, B * kP1}, B * kO1, kF1, C * kTaps, (C * kTaps + 1) & ~1);
+  launch_gemm(st, PatchByPos<uint8_t>{img, kP1W, kP1, B * kO1}, Plain{p + t->off[0], (long long)C * kTaps, 1, F1},
+              PoolStore<RELU>{p + t->off[1], t->d_pool1, t->d_arg1, F1, kP1, B * kP1}, B * kO1, F1, C * kTaps, (C * kTaps + 1) & ~1);
   mark(t, timed, k);
-  const Input<float> p1{t->d_pool1, nullptr, (long long)kF1 * kP1, kP1, kP1W, 1, 1.f};
-  launch_gemm(st, PatchByPos<float>{p1, kP2W, kP2, B * kO2}, Plain{p + t->off[2], (long long)kF1 * kTaps, 1, kF2},
-              PoolStore<RELU>{p + t->off[3], t->d_pool2, t->d_arg2, kF2, kP2, B * kP2}, B * kO2, kF2, kF1 * kTaps, kF1 * kTaps);
+  const Input<float> p1{t->d_pool1, nullptr, (long long)F1 * kP1, kP1, kP1W, 1, 1.f};
+  launch_gemm(st, PatchByPos<float>{p1, kP2W, kP2, B * kO2}, Plain{p + t->off[2], (long long)F1 * kTaps, 1, F2},
+              PoolStore<RELU>{p + t->off[3], t->d_pool2, t->d_arg2, F2, kP2, B * kP2}, B * kO2, F2, F1 * kTaps, F1 * kTaps);
   mark(t, timed, k);
-  launch_gemm(st, Plain{t->d_pool2, kFc1In, 1, B}, Plain{p + t->off[4], kFc1In, 1, kFc1Out}, RawStore{t->d_part, B, kFc1Out}, B, kFc1Out,
-              kFc1In, kFc1In / kFc1Splits);
+  // K = 144 F2 in kFc1Splits ranges of 9 F2 (an odd range is legal: the k loop pads its last pair)
+  launch_gemm(st, Plain{t->d_pool2, fc1_in, 1, B}, Plain{p + t->off[4], fc1_in, 1, H1}, RawStore{t->d_part, B, H1}, B, H1, fc1_in,
+              fc1_in / kFc1Splits);
   mark(t, timed, k);
-  hipLaunchKernelGGL(sum_partials<true>, dim3((B * kFc1Out + 255) / 256), dim3(256), 0, st, t->d_part, kFc1Splits, B * kFc1Out,
-                     p + t->off[5], kFc1Out, t->d_a1);
+  hipLaunchKernelGGL(sum_partials<true>, dim3((B * H1 + 255) / 256), dim3(256), 0, st, t->d_part, kFc1Splits, B * H1, p + t->off[5], H1,
+                     t->d_a1);
   mark(t, timed, k);
-  hipLaunchKernelGGL(head_kernel, dim3((B + 63) / 64), dim3(64), 0, st, t->d_a1, p + t->off[6], p + t->off[7], t->d_lab[which], d_idx, B,
-                     t->d_logits, t->d_loss_b, train ? t->d_dl : nullptr);
+  if (H2 > 0) {
+    // A2 [B][H2] = relu(A1 W2^T + b2), K = H1: one chain per output, no split
+    launch_gemm(st, Plain{t->d_a1, H1, 1, B}, Plain{p + t->off[6], H1, 1, H2}, BiasReluStore{p + t->off[7], t->d_a2, B, H2}, B, H2, H1, H1);
+    mark(t, timed, k);
+  }
+  const int last = H2 > 0 ? 8 : 6;  // the tensor of the layer that makes the logits
+  const int W = H2 > 0 ? H2 : H1;
+  hipLaunchKernelGGL(W == kFc1Out ? head_kernel<kFc1Out> : head_kernel<0>, dim3((B + 63) / 64), dim3(64), 0, st, H2 > 0 ? t->d_a2 : t->d_a1,
+                     p + t->off[last], p + t->off[last + 1], t->d_lab[which], d_idx, B, W, t->d_logits, t->d_loss_b, train ? t->d_dl : nullptr);
   mark(t, timed, k);
   if (!train) return;
   hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(256), 0, st, t->d_loss_b, B, d_loss_out);
@@ -498,46 +589,62 @@ void forward_passes(gpd_hip_trainer *t, int which, const int *d_idx, int B, bool
 template <bool RELU>
 void backward_passes(gpd_hip_trainer *t, const int *d_idx, int B, bool timed, int &k) {
   hipStream_t st = t->stream;
-  const int C = t->C;
+  const int C = t->C, F1 = t->F1, F2 = t->F2, H1 = t->H1, H2 = t->H2, fc1_in = F2 * kP2;
   const float *p = t->d_p;
   float *g = t->d_g;
-  hipLaunchKernelGGL(fc2_back_kernel, dim3((B * kFc1Out + 255) / 256), dim3(256), 0, st, t->d_dl, p + t->off[6], t->d_a1, B, t->d_dz1);
+  if (H2 > 0) {
+    hipLaunchKernelGGL(fc2_back_kernel, dim3((B * H2 + 255) / 256), dim3(256), 0, st, t->d_dl, p + t->off[8], t->d_a2, B, H2, t->d_dz2);
+    mark(t, timed, k);
+    hipLaunchKernelGGL(head_grads_kernel, dim3((3 * H2 + 2 + 255) / 256), dim3(256), 0, st, t->d_dl, t->d_a2, t->d_dz2, B, H2, g + t->off[8],
+                       g + t->off[9], g + t->off[7]);
+    mark(t, timed, k);
+    // fc2.weight [H2][H1] = dZ2^T A1, K = B
+    launch_gemm(st, Plain{t->d_dz2, 1, H2, H2}, Plain{t->d_a1, 1, H1, H1}, RawStore{g + t->off[6], H2, H1}, H2, H1, B, (B + 1) & ~1);
+    mark(t, timed, k);
+    // dZ1 [B][H1] = dZ2 W2, K = H2, zero where fc1's ReLU clamped
+    launch_gemm(st, Plain{t->d_dz2, H2, 1, B}, Plain{p + t->off[6], 1, H1, H1}, ActMaskStore{t->d_dz1, t->d_a1, B, H1}, B, H1, H2, H2);
+    mark(t, timed, k);
+    hipLaunchKernelGGL(batch_sum_kernel, dim3((H1 + 255) / 256), dim3(256), 0, st, t->d_dz1, B, H1, g + t->off[5]);
+    mark(t, timed, k);
+  } else {
+    hipLaunchKernelGGL(fc2_back_kernel, dim3((B * H1 + 255) / 256), dim3(256), 0, st, t->d_dl, p + t->off[6], t->d_a1, B, H1, t->d_dz1);
+    mark(t, timed, k);
+    hipLaunchKernelGGL(head_grads_kernel, dim3((3 * H1 + 2 + 255) / 256), dim3(256), 0, st, t->d_dl, t->d_a1, t->d_dz1, B, H1, g + t->off[6],
+                       g + t->off[7], g + t->off[5]);
+    mark(t, timed, k);
+  }
+  // fc1.weight [H1][144 F2] = dZ1^T P2, K = B
+  launch_gemm(st, Plain{t->d_dz1, 1, H1, H1}, Plain{t->d_pool2, 1, fc1_in, fc1_in}, RawStore{g + t->off[4], H1, fc1_in}, H1, fc1_in, B,
+              (B + 1) & ~1);
   mark(t, timed, k);
-  hipLaunchKernelGGL(head_grads_kernel, dim3((3 * kFc1Out + 2 + 255) / 256), dim3(256), 0, st, t->d_dl, t->d_a1, t->d_dz1, B, g + t->off[6],
-                     g + t->off[7], g + t->off[5]);
+  // dPool2 [B][144 F2] = dZ1 W1, K = H1, zero where conv2's ReLU (Net) clamped
+  launch_gemm(st, Plain{t->d_dz1, H1, 1, B}, Plain{p + t->off[4], 1, fc1_in, fc1_in}, MaskStore<RELU>{t->d_dpool2, t->d_arg2, B, fc1_in, 1}, B,
+              fc1_in, H1, H1);
   mark(t, timed, k);
-  // fc1.weight [500][7200] = dZ1^T P2, K = B
-  launch_gemm(st, Plain{t->d_dz1, 1, kFc1Out, kFc1Out}, Plain{t->d_pool2, 1, kFc1In, kFc1In}, RawStore{g + t->off[4], kFc1Out, kFc1In},
-              kFc1Out, kFc1In, B, (B + 1) & ~1);
+  hipLaunchKernelGGL(bias_grad_kernel, dim3(F2), dim3(256), 0, st, t->d_dpool2, B, F2, kP2, g + t->off[3]);
   mark(t, timed, k);
-  // dPool2 [B][7200] = dZ1 W1, K = 500, zero where conv2's ReLU (Net) clamped
-  launch_gemm(st, Plain{t->d_dz1, kFc1Out, 1, B}, Plain{p + t->off[4], 1, kFc1In, kFc1In}, MaskStore<RELU>{t->d_dpool2, t->d_arg2, B, kFc1In, 1},
-              B, kFc1In, kFc1Out, kFc1Out);
+  // conv2.weight [F2][25 F1], K = B * 576: one partial per image
+  const PoolGrad pg2{t->d_dpool2, t->d_arg2, F2, kP2W, kP2};
+  const Input<float> p1{t->d_pool1, nullptr, (long long)F1 * kP1, kP1, kP1W, 1, 1.f};
+  launch_gemm(st, GradByFilter<kO2W, kO2>{pg2}, PatchByTap<float, kO2W, kO2>{p1, F1 * kTaps}, RawStore{t->d_part, F2, F1 * kTaps}, F2,
+              F1 * kTaps, B * kO2, kO2);
   mark(t, timed, k);
-  hipLaunchKernelGGL(bias_grad_kernel, dim3(kF2), dim3(256), 0, st, t->d_dpool2, B, kF2, kP2, g + t->off[3]);
-  mark(t, timed, k);
-  // conv2.weight [50][500], K = B * 576: one partial per image
-  const PoolGrad pg2{t->d_dpool2, t->d_arg2, kF2, kP2W, kP2};
-  const Input<float> p1{t->d_pool1, nullptr, (long long)kF1 * kP1, kP1, kP1W, 1, 1.f};
-  launch_gemm(st, GradByFilter<kO2W, kO2>{pg2}, PatchByTap<float, kO2W, kO2>{p1, kF1 * kTaps}, RawStore{t->d_part, kF2, kF1 * kTaps}, kF2,
-              kF1 * kTaps, B * kO2, kO2);
-  mark(t, timed, k);
-  hipLaunchKernelGGL(sum_partials<false>, dim3((kF2 * kF1 * kTaps + 255) / 256), dim3(256), 0, st, t->d_part, B, kF2 * kF1 * kTaps, nullptr, 1,
+  hipLaunchKernelGGL(sum_partials<false>, dim3((F2 * F1 * kTaps + 255) / 256), dim3(256), 0, st, t->d_part, B, F2 * F1 * kTaps, nullptr, 1,
                      g + t->off[2]);
   mark(t, timed, k);
-  // dPool1 [B][20][784] = transposed convolution of the expanded dPool2, K = 1250, zero where conv1's ReLU (Net) clamped
-  launch_gemm(st, GradByPos{pg2, kP1W, kP1, kO2W, B * kP1}, WeightByChannel{p + t->off[2], kF1}, MaskStore<RELU>{t->d_dpool1, t->d_arg1, B * kP1, kF1, kP1},
-              B * kP1, kF1, kF2 * kTaps, kF2 * kTaps);
+  // dPool1 [B][F1][784] = transposed convolution of the expanded dPool2, K = 25 F2, zero where conv1's ReLU (Net) clamped
+  launch_gemm(st, GradByPos{pg2, kP1W, kP1, kO2W, B * kP1}, WeightByChannel{p + t->off[2], F1}, MaskStore<RELU>{t->d_dpool1, t->d_arg1, B * kP1, F1, kP1},
+              B * kP1, F1, F2 * kTaps, F2 * kTaps);
   mark(t, timed, k);
-  hipLaunchKernelGGL(bias_grad_kernel, dim3(kF1), dim3(256), 0, st, t->d_dpool1, B, kF1, kP1, g + t->off[1]);
+  hipLaunchKernelGGL(bias_grad_kernel, dim3(F1), dim3(256), 0, st, t->d_dpool1, B, F1, kP1, g + t->off[1]);
   mark(t, timed, k);
-  // conv1.weight [20][25 C], K = B * 3136: four partials per image
-  const PoolGrad pg1{t->d_dpool1, t->d_arg1, kF1, kP1W, kP1};
+  // conv1.weight [F1][25 C], K = B * 3136: four partials per image
+  const PoolGrad pg1{t->d_dpool1, t->d_arg1, F1, kP1W, kP1};
   const Input<uint8_t> img{t->d_img[0], d_idx, (long long)kPix * C, 1, kImg * C, C, (float)t->p.input_scale};
-  launch_gemm(st, GradByFilter<kO1W, kO1>{pg1}, PatchByTap<uint8_t, kO1W, kO1>{img, C * kTaps}, RawStore{t->d_part, kF1, C * kTaps}, kF1,
+  launch_gemm(st, GradByFilter<kO1W, kO1>{pg1}, PatchByTap<uint8_t, kO1W, kO1>{img, C * kTaps}, RawStore{t->d_part, F1, C * kTaps}, F1,
               C * kTaps, B * kO1, kO1 / 4);
   mark(t, timed, k);
-  hipLaunchKernelGGL(sum_partials<false>, dim3((kF1 * C * kTaps + 255) / 256), dim3(256), 0, st, t->d_part, 4 * B, kF1 * C * kTaps, nullptr, 1,
+  hipLaunchKernelGGL(sum_partials<false>, dim3((F1 * C * kTaps + 255) / 256), dim3(256), 0, st, t->d_part, 4 * B, F1 * C * kTaps, nullptr, 1,
                      g + t->off[0]);
   mark(t, timed, k);
 }
@@ -601,13 +708,15 @@ int check_recipe(const char *who, const gpd_train_recipe &r) {
 void enqueue_sgd(gpd_hip_trainer *t, bool timed, int &k) {
   const float lr = (float)learning_rate(t->r, t->p.lr, t->step);
   t->step++;
+  // ten tensors (a third dense layer): every multiplier is 1 (checked at creation), so the eight slots serve: whichever slot an
+  // element of the last two tensors lands in holds their rate and decay
   SgdTensors ts;
   for (int i = 0; i < 8; i++) {
     ts.end[i] = (int)t->off[i + 1];
     ts.rate[i] = lr * (float)t->r.lr_mult[i];
     ts.decay[i] = (float)t->p.weight_decay * (float)t->r.decay_mult[i];
   }
-  const int n = (int)t->off[8];
+  const int n = (int)t->total;
   hipLaunchKernelGGL(sgd_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, t->d_p, t->d_g, t->d_m, n, ts, (float)t->r.momentum);
   mark(t, timed, k);
 }
@@ -617,7 +726,7 @@ void enqueue_adam(gpd_hip_trainer *t, bool timed, int &k) {
   t->step++;
   const gpd_train_params &q = t->p;
   const double bc1 = 1.0 - std::pow(q.beta1, (double)t->step), bc2 = 1.0 - std::pow(q.beta2, (double)t->step);
-  const int n = (int)t->off[8];
+  const int n = (int)t->total;
   hipLaunchKernelGGL(adam_kernel, dim3((n + 255) / 256), dim3(256), 0, t->stream, t->d_p, t->d_g, t->d_m, t->d_v, n, (float)q.weight_decay,
                      (float)q.beta1, (float)(1.0 - q.beta1), (float)q.beta2, (float)(1.0 - q.beta2), (float)(lr / bc1), (float)std::sqrt(bc2), (float)q.eps);
   mark(t, timed, k);
@@ -737,6 +846,279 @@ struct ViewSink {
   }
 };
 
+// a table of 8 on a trainer of ten tensors: refused, nothing changed (a null trainer is the callee's to refuse)
+int eight_only(const char *who, const gpd_hip_trainer *t) {
+  if (!t || t->nt == 8) return GPD_OK;
+  set_error("%s: the trainer's network has a third dense layer and ten tensors; use the gpd_hip_train_net_ entry", who);
+  return GPD_ERR_STATE;
+}
+
+size_t tensor_size(const gpd_hip_trainer *t, int i) { return t->off[i + 1] - t->off[i]; }
+
+// U(-bound, bound) per tensor from one xorshift64 stream, the tensors in order.  xavier: Caffe's filler, bound sqrt(3 / fan_in),
+// biases 0 without a draw, no weight outside its bound; otherwise torch's default, bound 1 / sqrt(fan_in), biases drawn too
+int init_tensors(const char *who, const gpd_lenet_shape *shape, uint32_t seed, float *const tensors[10], bool xavier) {
+  if (!shape || !tensors) {
+    set_error("%s: null argument", who);
+    return GPD_ERR_INVALID;
+  }
+  if (gpd_hip_lenet_shape_check(shape) != GPD_OK) return GPD_ERR_INVALID;
+  size_t sz[10];
+  tensor_sizes(*shape, sz);
+  const int nt = num_tensors(*shape);
+  for (int i = 0; i < nt; i++)
+    if (!tensors[i]) {
+      set_error("%s: tensor %d is null", who, i);
+      return GPD_ERR_INVALID;
+    }
+  int fan_in[5];
+  fan_ins(*shape, fan_in);
+  sample::Stream st(seed);
+  for (int i = 0; i < nt; i++) {
+    if (xavier && (i & 1)) {  // a bias: constant filler 0, no draw
+      std::fill(tensors[i], tensors[i] + sz[i], 0.f);
+      continue;
+    }
+    const double bound = xavier ? std::sqrt(3.0 / (double)fan_in[i / 2]) : (double)(float)(1.0 / std::sqrt((double)fan_in[i / 2]));
+    // 24 bits of the draw -> the centres of 2^24 equal cells of (-bound, bound); xavier: the rounding to float never leaves the bound
+    for (size_t j = 0; j < sz[i]; j++) {
+      float w = (float)((2.0 * ((double)(st.next() >> 40) + 0.5) / 16777216.0 - 1.0) * bound);
+      if (xavier && std::fabs((double)w) > bound) w = std::nextafterf(w, 0.f);
+      tensors[i][j] = w;
+    }
+  }
+  return GPD_OK;
+}
+
+int set_state(const char *who, gpd_hip_trainer *t, const float *const *tensors) {
+  if (!t || !tensors) {
+    set_error("%s: null argument", who);
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < t->nt; i++)
+    if (!tensors[i] || !all_finite(tensors[i], tensor_size(t, i))) {
+      set_error("%s: %s is null or holds a non-finite value", who, kTensorNames[i]);
+      return GPD_ERR_INVALID;
+    }
+  for (int i = 0; i < t->nt; i++) std::memcpy(t->h_all.data() + t->off[i], tensors[i], tensor_size(t, i) * sizeof(float));
+  HIP_RET(hipSetDevice(t->device));
+  const size_t bytes = t->total * sizeof(float);
+  HIP_RET(hipMemcpyAsync(t->d_p, t->h_all.data(), bytes, hipMemcpyHostToDevice, t->stream));
+  HIP_RET(hipMemsetAsync(t->d_m, 0, bytes, t->stream));
+  if (t->d_v) HIP_RET(hipMemsetAsync(t->d_v, 0, bytes, t->stream));
+  HIP_RET(hipStreamSynchronize(t->stream));
+  t->step = 0;
+  return GPD_OK;
+}
+
+int get_state(const char *who, gpd_hip_trainer *t, float *const *tensors) {
+  if (!t || !tensors) {
+    set_error("%s: null argument", who);
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < t->nt; i++)
+    if (!tensors[i]) {
+      set_error("%s: tensor %d is null", who, i);
+      return GPD_ERR_INVALID;
+    }
+  HIP_RET(hipSetDevice(t->device));
+  HIP_RET(hipMemcpyAsync(t->h_all.data(), t->d_p, t->total * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  HIP_RET(hipStreamSynchronize(t->stream));
+  for (int i = 0; i < t->nt; i++) std::memcpy(tensors[i], t->h_all.data() + t->off[i], tensor_size(t, i) * sizeof(float));
+  return GPD_OK;
+}
+
+int get_solver_state(const char *who, gpd_hip_trainer *t, float *const *m, float *const *v, long long *count) {
+  if (!t || !m || !count || (t->d_v && !v)) {
+    set_error("%s: null argument", who);
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < t->nt; i++)
+    if (!m[i] || (t->d_v && !v[i])) {
+      set_error("%s: tensor %d is null", who, i);
+      return GPD_ERR_INVALID;
+    }
+  HIP_RET(hipSetDevice(t->device));
+  const float *src[2] = {t->d_m, t->d_v};
+  float *const *dst[2] = {m, v};
+  for (int b = 0; b < 2; b++) {
+    if (!src[b]) continue;
+    HIP_RET(hipMemcpyAsync(t->h_all.data(), src[b], t->total * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    HIP_RET(hipStreamSynchronize(t->stream));
+    for (int i = 0; i < t->nt; i++) std::memcpy(dst[b][i], t->h_all.data() + t->off[i], tensor_size(t, i) * sizeof(float));
+  }
+  *count = t->step;
+  return GPD_OK;
+}
+
+int set_solver_state(const char *who, gpd_hip_trainer *t, const float *const *m, const float *const *v, long long count) {
+  if (!t || !m || (t->d_v && !v) || count < 0) {
+    set_error("%s: null argument or a negative count", who);
+    return GPD_ERR_INVALID;
+  }
+  const float *const *src[2] = {m, t->d_v ? v : nullptr};
+  for (int b = 0; b < 2; b++)
+    for (int i = 0; i < t->nt && src[b]; i++)
+      if (!src[b][i] || !all_finite(src[b][i], tensor_size(t, i))) {
+        set_error("%s: buffer %d, tensor %d is null or holds a non-finite value", who, b, i);
+        return GPD_ERR_INVALID;
+      }
+  HIP_RET(hipSetDevice(t->device));
+  float *dst[2] = {t->d_m, t->d_v};
+  for (int b = 0; b < 2; b++) {
+    if (!src[b]) continue;
+    for (int i = 0; i < t->nt; i++) std::memcpy(t->h_all.data() + t->off[i], src[b][i], tensor_size(t, i) * sizeof(float));
+    HIP_RET(hipMemcpyAsync(dst[b], t->h_all.data(), t->total * sizeof(float), hipMemcpyHostToDevice, t->stream));
+    HIP_RET(hipStreamSynchronize(t->stream));
+  }
+  t->step = count;
+  return GPD_OK;
+}
+
+int gradients(const char *who, gpd_hip_trainer *t, const int32_t *indices, int batch, float *const *grads, float *loss) {
+  int rc = check_batch(who, t, indices, batch);
+  if (rc) return rc;
+  if (!grads || !loss) {
+    set_error("%s: null argument", who);
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < t->nt; i++)
+    if (!grads[i]) {
+      set_error("%s: tensor %d is null", who, i);
+      return GPD_ERR_INVALID;
+    }
+  rc = check_indices(who, indices, batch, t->n[0]);
+  if (rc) return rc;
+  HIP_RET(hipSetDevice(t->device));
+  HIP_RET(hipMemcpyAsync(t->d_idx, indices, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
+  int k = 0;
+  enqueue_forward(t, 0, t->d_idx, batch, true, t->d_loss, false, k);
+  enqueue_backward(t, t->d_idx, batch, false, k);
+  HIP_RET(hipGetLastError());
+  HIP_RET(hipMemcpyAsync(t->h_all.data(), t->d_g, t->total * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  HIP_RET(hipMemcpyAsync(loss, t->d_loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  HIP_RET(hipStreamSynchronize(t->stream));
+  for (int i = 0; i < t->nt; i++) std::memcpy(grads[i], t->h_all.data() + t->off[i], tensor_size(t, i) * sizeof(float));
+  return GPD_OK;
+}
+
+int apply(const char *who, gpd_hip_trainer *t, const float *const *grads) {
+  if (!t || !grads) {
+    set_error("%s: null argument", who);
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < t->nt; i++)
+    if (!grads[i] || !all_finite(grads[i], tensor_size(t, i))) {
+      set_error("%s: tensor %d is null or holds a non-finite value", who, i);
+      return GPD_ERR_INVALID;
+    }
+  for (int i = 0; i < t->nt; i++) std::memcpy(t->h_all.data() + t->off[i], grads[i], tensor_size(t, i) * sizeof(float));
+  HIP_RET(hipSetDevice(t->device));
+  HIP_RET(hipMemcpyAsync(t->d_g, t->h_all.data(), t->total * sizeof(float), hipMemcpyHostToDevice, t->stream));
+  int k = 0;
+  enqueue_update(t, false, k);
+  HIP_RET(hipGetLastError());
+  HIP_RET(hipStreamSynchronize(t->stream));
+  return GPD_OK;
+}
+
+// every creation entry; shape == null: the stock widths at the parameters' channel count.  Everything is checked before anything is allocated
+int create_trainer(gpd_hip_ctx *ctx, const gpd_train_params *params, const gpd_train_recipe *recipe, const gpd_lenet_shape *shape,
+                   gpd_hip_trainer **out) {
+  if (!ctx || !params || !out) {
+    set_error("gpd_hip_train_create: null argument");
+    return GPD_ERR_INVALID;
+  }
+  gpd_train_recipe r;
+  (void)gpd_hip_train_default_recipe(&r, 0);
+  if (recipe) {
+    r = *recipe;
+    const int rc = check_recipe("gpd_hip_train_create_recipe", r);
+    if (rc) return rc;
+  }
+  const gpd_train_params &q = *params;
+  if (shape) {
+    if (gpd_hip_lenet_shape_check(shape) != GPD_OK) return GPD_ERR_INVALID;
+    if (shape->channels != q.channels) {
+      set_error("gpd_hip_train_create_net: the shape has %d channels, the parameters %d", shape->channels, q.channels);
+      return GPD_ERR_INVALID;
+    }
+    for (int i = 0; i < 8 && shape->fc2_out > 0; i++)
+      if (r.lr_mult[i] != 1.0 || r.decay_mult[i] != 1.0) {
+        set_error("gpd_hip_train_create_net: a network with a third dense layer has ten tensors, the recipe eight multiplier slots: every multiplier must be 1");
+        return GPD_ERR_INVALID;
+      }
+  }
+  if (!channels_ok(q.channels)) {
+    set_error("gpd_hip_train_create: %d channels (1, 3, 12 or 15)", q.channels);
+    return GPD_ERR_INVALID;
+  }
+  if (q.max_batch < 1 || q.max_batch > kMaxBatch) {
+    set_error("gpd_hip_train_create: max_batch %d is outside 1 .. %d", q.max_batch, kMaxBatch);
+    return GPD_ERR_INVALID;
+  }
+  if (!(q.lr >= 0 && std::isfinite(q.lr)) || !(q.beta1 >= 0 && q.beta1 < 1) || !(q.beta2 >= 0 && q.beta2 < 1) ||
+      !(q.eps >= 0 && std::isfinite(q.eps)) || !(q.weight_decay >= 0 && std::isfinite(q.weight_decay)) ||
+      !(q.input_scale > 0 && std::isfinite(q.input_scale))) {
+    set_error("gpd_hip_train_create: a hyper-parameter is out of range");
+    return GPD_ERR_INVALID;
+  }
+  gpd_hip_trainer *t = new gpd_hip_trainer();
+  ctx_device_stream(ctx, &t->device, &t->stream);
+  t->p = q;
+  t->r = r;
+  t->C = q.channels;
+  t->maxb = q.max_batch;
+  t->shape = shape ? *shape : stock_shape(q.channels);
+  t->F1 = t->shape.conv1_out, t->F2 = t->shape.conv2_out, t->H1 = t->shape.fc1_out, t->H2 = t->shape.fc2_out;
+  t->nt = num_tensors(t->shape);
+  t->names = step_names(t->H2 > 0, r.solver == GPD_TRAIN_SOLVER_SGD);
+  size_t sz[10];
+  tensor_sizes(t->shape, sz);
+  for (int i = 0; i < t->nt; i++) t->off[i + 1] = t->off[i] + sz[i];
+  t->total = t->off[t->nt];
+  // every count below in size_t: at the limits (64, 128, 1024, 1024; batch 1024) conv2's partials alone are 0.8 GB
+  const size_t total = t->total, B = (size_t)t->maxb, F1 = (size_t)t->F1, F2 = (size_t)t->F2, H1 = (size_t)t->H1, H2 = (size_t)t->H2;
+  const size_t fc1_in = F2 * kP2;
+  // d_part: fc1's forward partials, conv2's dW partials (one per image), conv1's dW partials (four per image)
+  const size_t part = B * std::max(std::max(F2 * F1 * kTaps, 4 * F1 * kTaps * (size_t)t->C), kFc1Splits * H1);
+  hipError_t e = hipSetDevice(t->device);
+  if (e == hipSuccess) e = device_alloc(t->d_p, total);
+  if (e == hipSuccess) e = device_alloc(t->d_g, total);
+  if (e == hipSuccess) e = device_alloc(t->d_m, total);
+  if (e == hipSuccess && r.solver == GPD_TRAIN_SOLVER_ADAM) e = device_alloc(t->d_v, total);
+  if (e == hipSuccess) e = device_alloc(t->d_idx, (size_t)kIdxCap);
+  if (e == hipSuccess) e = device_alloc(t->d_loss, (size_t)kIdxCap);
+  if (e == hipSuccess) e = device_alloc(t->d_pool1, B * F1 * kP1);
+  if (e == hipSuccess) e = device_alloc(t->d_dpool1, B * F1 * kP1);
+  if (e == hipSuccess) e = device_alloc(t->d_arg1, B * F1 * kP1);
+  if (e == hipSuccess) e = device_alloc(t->d_pool2, B * fc1_in);
+  if (e == hipSuccess) e = device_alloc(t->d_dpool2, B * fc1_in);
+  if (e == hipSuccess) e = device_alloc(t->d_arg2, B * fc1_in);
+  if (e == hipSuccess) e = device_alloc(t->d_a1, B * H1);
+  if (e == hipSuccess) e = device_alloc(t->d_dz1, B * H1);
+  if (e == hipSuccess && H2) e = device_alloc(t->d_a2, B * H2);
+  if (e == hipSuccess && H2) e = device_alloc(t->d_dz2, B * H2);
+  if (e == hipSuccess) e = device_alloc(t->d_logits, B * 2);
+  if (e == hipSuccess) e = device_alloc(t->d_dl, B * 2);
+  if (e == hipSuccess) e = device_alloc(t->d_loss_b, B);
+  if (e == hipSuccess) e = device_alloc(t->d_part, part);
+  for (int i = 0; i < kMaxKernels && e == hipSuccess; i++) e = hipEventCreate(&t->ev[i]);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_p, 0, total * sizeof(float), t->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_m, 0, total * sizeof(float), t->stream);
+  if (e == hipSuccess && t->d_v) e = hipMemsetAsync(t->d_v, 0, total * sizeof(float), t->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("gpd_hip_train_create: %s", hipGetErrorString(e));
+    gpd_hip_train_destroy(t);
+    return GPD_ERR_HIP;
+  }
+  t->h_all.resize(total);
+  *out = t;
+  return GPD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -784,74 +1166,24 @@ int gpd_hip_train_create(gpd_hip_ctx *ctx, const gpd_train_params *params, gpd_h
 }
 
 int gpd_hip_train_create_recipe(gpd_hip_ctx *ctx, const gpd_train_params *params, const gpd_train_recipe *recipe, gpd_hip_trainer **out) {
-  if (!ctx || !params || !out) {
-    set_error("gpd_hip_train_create: null argument");
+  return create_trainer(ctx, params, recipe, nullptr, out);
+}
+
+int gpd_hip_train_create_net(gpd_hip_ctx *ctx, const gpd_train_params *params, const gpd_train_recipe *recipe, const gpd_lenet_shape *shape,
+                             gpd_hip_trainer **out) {
+  if (!shape) {
+    set_error("gpd_hip_train_create_net: null argument");
     return GPD_ERR_INVALID;
   }
-  gpd_train_recipe r;
-  (void)gpd_hip_train_default_recipe(&r, 0);
-  if (recipe) {
-    r = *recipe;
-    const int rc = check_recipe("gpd_hip_train_create_recipe", r);
-    if (rc) return rc;
-  }
-  const gpd_train_params &q = *params;
-  if (!channels_ok(q.channels)) {
-    set_error("gpd_hip_train_create: %d channels (1, 3, 12 or 15)", q.channels);
+  return create_trainer(ctx, params, recipe, shape, out);
+}
+
+int gpd_hip_train_shape(const gpd_hip_trainer *t, gpd_lenet_shape *out) {
+  if (!t || !out) {
+    set_error("gpd_hip_train_shape: null argument");
     return GPD_ERR_INVALID;
   }
-  if (q.max_batch < 1 || q.max_batch > kMaxBatch) {
-    set_error("gpd_hip_train_create: max_batch %d is outside 1 .. %d", q.max_batch, kMaxBatch);
-    return GPD_ERR_INVALID;
-  }
-  if (!(q.lr >= 0 && std::isfinite(q.lr)) || !(q.beta1 >= 0 && q.beta1 < 1) || !(q.beta2 >= 0 && q.beta2 < 1) ||
-      !(q.eps >= 0 && std::isfinite(q.eps)) || !(q.weight_decay >= 0 && std::isfinite(q.weight_decay)) ||
-      !(q.input_scale > 0 && std::isfinite(q.input_scale))) {
-    set_error("gpd_hip_train_create: a hyper-parameter is out of range");
-    return GPD_ERR_INVALID;
-  }
-  gpd_hip_trainer *t = new gpd_hip_trainer();
-  ctx_device_stream(ctx, &t->device, &t->stream);
-  t->p = q;
-  t->r = r;
-  t->C = q.channels;
-  t->maxb = q.max_batch;
-  size_t sz[8];
-  tensor_sizes(t->C, sz);
-  for (int i = 0; i < 8; i++) t->off[i + 1] = t->off[i] + sz[i];
-  const size_t total = t->off[8], B = (size_t)t->maxb;
-  const size_t part = B * (size_t)std::max(std::max(kF2 * kF1 * kTaps, 4 * kF1 * kTaps * t->C), kFc1Splits * kFc1Out);
-  hipError_t e = hipSetDevice(t->device);
-  if (e == hipSuccess) e = device_alloc(t->d_p, total);
-  if (e == hipSuccess) e = device_alloc(t->d_g, total);
-  if (e == hipSuccess) e = device_alloc(t->d_m, total);
-  if (e == hipSuccess && r.solver == GPD_TRAIN_SOLVER_ADAM) e = device_alloc(t->d_v, total);
-  if (e == hipSuccess) e = device_alloc(t->d_idx, (size_t)kIdxCap);
-  if (e == hipSuccess) e = device_alloc(t->d_loss, (size_t)kIdxCap);
-  if (e == hipSuccess) e = device_alloc(t->d_pool1, B * kF1 * kP1);
-  if (e == hipSuccess) e = device_alloc(t->d_dpool1, B * kF1 * kP1);
-  if (e == hipSuccess) e = device_alloc(t->d_arg1, B * kF1 * kP1);
-  if (e == hipSuccess) e = device_alloc(t->d_pool2, B * kFc1In);
-  if (e == hipSuccess) e = device_alloc(t->d_dpool2, B * kFc1In);
-  if (e == hipSuccess) e = device_alloc(t->d_arg2, B * kFc1In);
-  if (e == hipSuccess) e = device_alloc(t->d_a1, B * kFc1Out);
-  if (e == hipSuccess) e = device_alloc(t->d_dz1, B * kFc1Out);
-  if (e == hipSuccess) e = device_alloc(t->d_logits, B * 2);
-  if (e == hipSuccess) e = device_alloc(t->d_dl, B * 2);
-  if (e == hipSuccess) e = device_alloc(t->d_loss_b, B);
-  if (e == hipSuccess) e = device_alloc(t->d_part, part);
-  for (int i = 0; i < kMaxKernels && e == hipSuccess; i++) e = hipEventCreate(&t->ev[i]);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_p, 0, total * sizeof(float), t->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_m, 0, total * sizeof(float), t->stream);
-  if (e == hipSuccess && t->d_v) e = hipMemsetAsync(t->d_v, 0, total * sizeof(float), t->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  if (e != hipSuccess) {
-    set_error("gpd_hip_train_create: %s", hipGetErrorString(e));
-    gpd_hip_train_destroy(t);
-    return GPD_ERR_HIP;
-  }
-  t->h_all.resize(total);
-  *out = t;
+  *out = t->shape;
   return GPD_OK;
 }
 
@@ -860,11 +1192,29 @@ void gpd_hip_train_destroy(gpd_hip_trainer *t) {
   (void)hipSetDevice(t->device);
   if (t->stream) (void)hipStreamSynchronize(t->stream);
   device_release(t->d_p, t->d_g, t->d_m, t->d_v, t->d_img[0], t->d_img[1], t->d_lab[0], t->d_lab[1], t->d_idx, t->d_loss, t->d_pool1,
-                 t->d_pool2, t->d_dpool1, t->d_dpool2, t->d_arg1, t->d_arg2, t->d_a1, t->d_dz1, t->d_logits, t->d_dl, t->d_loss_b,
-                 t->d_part);
+                 t->d_pool2, t->d_dpool1, t->d_dpool2, t->d_arg1, t->d_arg2, t->d_a1, t->d_dz1, t->d_a2, t->d_dz2, t->d_logits, t->d_dl,
+                 t->d_loss_b, t->d_part);
   for (hipEvent_t e : t->ev)
     if (e) (void)hipEventDestroy(e);
   delete t;
+}
+
+int gpd_hip_train_net_sizes(const gpd_lenet_shape *shape, size_t n[10]) {
+  if (!shape || !n) {
+    set_error("gpd_hip_train_net_sizes: null argument");
+    return GPD_ERR_INVALID;
+  }
+  if (gpd_hip_lenet_shape_check(shape) != GPD_OK) return GPD_ERR_INVALID;
+  tensor_sizes(*shape, n);
+  return GPD_OK;
+}
+
+int gpd_hip_train_net_init_state(const gpd_lenet_shape *shape, uint32_t seed, float *const tensors[10]) {
+  return init_tensors("gpd_hip_train_net_init_state", shape, seed, tensors, false);
+}
+
+int gpd_hip_train_net_init_xavier(const gpd_lenet_shape *shape, uint32_t seed, float *const tensors[10]) {
+  return init_tensors("gpd_hip_train_net_init_xavier", shape, seed, tensors, true);
 }
 
 int gpd_hip_train_init_state(int channels, uint32_t seed, float *const tensors[8]) {
@@ -872,60 +1222,8 @@ int gpd_hip_train_init_state(int channels, uint32_t seed, float *const tensors[8
     set_error("gpd_hip_train_init_state: %d channels (1, 3, 12 or 15) or a null argument", channels);
     return GPD_ERR_INVALID;
   }
-  size_t sz[8];
-  tensor_sizes(channels, sz);
-  for (int i = 0; i < 8; i++)
-    if (!tensors[i]) {
-      set_error("gpd_hip_train_init_state: tensor %d is null", i);
-      return GPD_ERR_INVALID;
-    }
-  const int fan_in[4] = {channels * kTaps, kF1 * kTaps, kFc1In, kFc1Out};
-  sample::Stream st(seed);
-  for (int i = 0; i < 8; i++) {
-    const double bound = (double)(float)(1.0 / std::sqrt((double)fan_in[i / 2]));
-    // 24 bits of the draw -> the centres of 2^24 equal cells of (-bound, bound)
-    for (size_t j = 0; j < sz[i]; j++) tensors[i][j] = (float)((2.0 * ((double)(st.next() >> 40) + 0.5) / 16777216.0 - 1.0) * bound);
-  }
-  return GPD_OK;
-}
-
-int gpd_hip_train_set_state(gpd_hip_trainer *t, const float *const tensors[8]) {
-  if (!t || !tensors) {
-    set_error("gpd_hip_train_set_state: null argument");
-    return GPD_ERR_INVALID;
-  }
-  static const char *const names[8] = {"conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"};
-  for (int i = 0; i < 8; i++)
-    if (!tensors[i] || !all_finite(tensors[i], t->off[i + 1] - t->off[i])) {
-      set_error("gpd_hip_train_set_state: %s is null or holds a non-finite value", names[i]);
-      return GPD_ERR_INVALID;
-    }
-  for (int i = 0; i < 8; i++) std::memcpy(t->h_all.data() + t->off[i], tensors[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
-  HIP_RET(hipSetDevice(t->device));
-  const size_t bytes = t->off[8] * sizeof(float);
-  HIP_RET(hipMemcpyAsync(t->d_p, t->h_all.data(), bytes, hipMemcpyHostToDevice, t->stream));
-  HIP_RET(hipMemsetAsync(t->d_m, 0, bytes, t->stream));
-  if (t->d_v) HIP_RET(hipMemsetAsync(t->d_v, 0, bytes, t->stream));
-  HIP_RET(hipStreamSynchronize(t->stream));
-  t->step = 0;
-  return GPD_OK;
-}
-
-int gpd_hip_train_get_state(gpd_hip_trainer *t, float *const tensors[8]) {
-  if (!t || !tensors) {
-    set_error("gpd_hip_train_get_state: null argument");
-    return GPD_ERR_INVALID;
-  }
-  for (int i = 0; i < 8; i++)
-    if (!tensors[i]) {
-      set_error("gpd_hip_train_get_state: tensor %d is null", i);
-      return GPD_ERR_INVALID;
-    }
-  HIP_RET(hipSetDevice(t->device));
-  HIP_RET(hipMemcpyAsync(t->h_all.data(), t->d_p, t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-  HIP_RET(hipStreamSynchronize(t->stream));
-  for (int i = 0; i < 8; i++) std::memcpy(tensors[i], t->h_all.data() + t->off[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
-  return GPD_OK;
+  const gpd_lenet_shape stock = stock_shape(channels);
+  return init_tensors("gpd_hip_train_init_state", &stock, seed, tensors, false);
 }
 
 int gpd_hip_train_init_xavier(int channels, uint32_t seed, float *const tensors[8]) {
@@ -933,76 +1231,38 @@ int gpd_hip_train_init_xavier(int channels, uint32_t seed, float *const tensors[
     set_error("gpd_hip_train_init_xavier: %d channels (1, 3, 12 or 15) or a null argument", channels);
     return GPD_ERR_INVALID;
   }
-  size_t sz[8];
-  tensor_sizes(channels, sz);
-  for (int i = 0; i < 8; i++)
-    if (!tensors[i]) {
-      set_error("gpd_hip_train_init_xavier: tensor %d is null", i);
-      return GPD_ERR_INVALID;
-    }
-  const int fan_in[4] = {channels * kTaps, kF1 * kTaps, kFc1In, kFc1Out};
-  sample::Stream st(seed);
-  for (int i = 0; i < 8; i++) {
-    if (i & 1) {  // a bias: constant filler 0, no draw
-      std::fill(tensors[i], tensors[i] + sz[i], 0.f);
-      continue;
-    }
-    const double bound = std::sqrt(3.0 / (double)fan_in[i / 2]);
-    // 24 bits of the draw -> the centres of 2^24 equal cells of (-bound, bound); the rounding to float never leaves the bound
-    for (size_t j = 0; j < sz[i]; j++) {
-      float w = (float)((2.0 * ((double)(st.next() >> 40) + 0.5) / 16777216.0 - 1.0) * bound);
-      if (std::fabs((double)w) > bound) w = std::nextafterf(w, 0.f);
-      tensors[i][j] = w;
-    }
-  }
-  return GPD_OK;
+  const gpd_lenet_shape stock = stock_shape(channels);
+  return init_tensors("gpd_hip_train_init_xavier", &stock, seed, tensors, true);
 }
 
+// The entries with tables of 8 serve every trainer without a third dense layer; the _net_ entries, with tables of 10 whose
+// slots [8] and [9] are not read for such a trainer, serve every trainer.
+int gpd_hip_train_set_state(gpd_hip_trainer *t, const float *const tensors[8]) {
+  const int rc = eight_only("gpd_hip_train_set_state", t);
+  return rc ? rc : set_state("gpd_hip_train_set_state", t, tensors);
+}
+int gpd_hip_train_net_set_state(gpd_hip_trainer *t, const float *const tensors[10]) { return set_state("gpd_hip_train_net_set_state", t, tensors); }
+
+int gpd_hip_train_get_state(gpd_hip_trainer *t, float *const tensors[8]) {
+  const int rc = eight_only("gpd_hip_train_get_state", t);
+  return rc ? rc : get_state("gpd_hip_train_get_state", t, tensors);
+}
+int gpd_hip_train_net_get_state(gpd_hip_trainer *t, float *const tensors[10]) { return get_state("gpd_hip_train_net_get_state", t, tensors); }
+
 int gpd_hip_train_get_solver_state(gpd_hip_trainer *t, float *const m[8], float *const v[8], long long *count) {
-  if (!t || !m || !count || (t->d_v && !v)) {
-    set_error("gpd_hip_train_get_solver_state: null argument");
-    return GPD_ERR_INVALID;
-  }
-  for (int i = 0; i < 8; i++)
-    if (!m[i] || (t->d_v && !v[i])) {
-      set_error("gpd_hip_train_get_solver_state: tensor %d is null", i);
-      return GPD_ERR_INVALID;
-    }
-  HIP_RET(hipSetDevice(t->device));
-  const float *src[2] = {t->d_m, t->d_v};
-  float *const *dst[2] = {m, v};
-  for (int b = 0; b < 2; b++) {
-    if (!src[b]) continue;
-    HIP_RET(hipMemcpyAsync(t->h_all.data(), src[b], t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-    HIP_RET(hipStreamSynchronize(t->stream));
-    for (int i = 0; i < 8; i++) std::memcpy(dst[b][i], t->h_all.data() + t->off[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
-  }
-  *count = t->step;
-  return GPD_OK;
+  const int rc = eight_only("gpd_hip_train_get_solver_state", t);
+  return rc ? rc : get_solver_state("gpd_hip_train_get_solver_state", t, m, v, count);
+}
+int gpd_hip_train_net_get_solver_state(gpd_hip_trainer *t, float *const m[10], float *const v[10], long long *count) {
+  return get_solver_state("gpd_hip_train_net_get_solver_state", t, m, v, count);
 }
 
 int gpd_hip_train_set_solver_state(gpd_hip_trainer *t, const float *const m[8], const float *const v[8], long long count) {
-  if (!t || !m || (t->d_v && !v) || count < 0) {
-    set_error("gpd_hip_train_set_solver_state: null argument or a negative count");
-    return GPD_ERR_INVALID;
-  }
-  const float *const *src[2] = {m, t->d_v ? v : nullptr};
-  for (int b = 0; b < 2; b++)
-    for (int i = 0; i < 8 && src[b]; i++)
-      if (!src[b][i] || !all_finite(src[b][i], t->off[i + 1] - t->off[i])) {
-        set_error("gpd_hip_train_set_solver_state: buffer %d, tensor %d is null or holds a non-finite value", b, i);
-        return GPD_ERR_INVALID;
-      }
-  HIP_RET(hipSetDevice(t->device));
-  float *dst[2] = {t->d_m, t->d_v};
-  for (int b = 0; b < 2; b++) {
-    if (!src[b]) continue;
-    for (int i = 0; i < 8; i++) std::memcpy(t->h_all.data() + t->off[i], src[b][i], (t->off[i + 1] - t->off[i]) * sizeof(float));
-    HIP_RET(hipMemcpyAsync(dst[b], t->h_all.data(), t->off[8] * sizeof(float), hipMemcpyHostToDevice, t->stream));
-    HIP_RET(hipStreamSynchronize(t->stream));
-  }
-  t->step = count;
-  return GPD_OK;
+  const int rc = eight_only("gpd_hip_train_set_solver_state", t);
+  return rc ? rc : set_solver_state("gpd_hip_train_set_solver_state", t, m, v, count);
+}
+int gpd_hip_train_net_set_solver_state(gpd_hip_trainer *t, const float *const m[10], const float *const v[10], long long count) {
+  return set_solver_state("gpd_hip_train_net_set_solver_state", t, m, v, count);
 }
 
 int gpd_hip_train_set_data(gpd_hip_trainer *t, int which, const uint8_t *images_hwc, const uint8_t *labels, int n) {
@@ -1182,51 +1442,18 @@ int gpd_hip_train_steps(gpd_hip_trainer *t, const int32_t *indices, int num_step
 }
 
 int gpd_hip_train_gradients(gpd_hip_trainer *t, const int32_t *indices, int batch, float *const grads[8], float *loss) {
-  int rc = check_batch("gpd_hip_train_gradients", t, indices, batch);
-  if (rc) return rc;
-  if (!grads || !loss) {
-    set_error("gpd_hip_train_gradients: null argument");
-    return GPD_ERR_INVALID;
-  }
-  for (int i = 0; i < 8; i++)
-    if (!grads[i]) {
-      set_error("gpd_hip_train_gradients: tensor %d is null", i);
-      return GPD_ERR_INVALID;
-    }
-  rc = check_indices("gpd_hip_train_gradients", indices, batch, t->n[0]);
-  if (rc) return rc;
-  HIP_RET(hipSetDevice(t->device));
-  HIP_RET(hipMemcpyAsync(t->d_idx, indices, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
-  int k = 0;
-  enqueue_forward(t, 0, t->d_idx, batch, true, t->d_loss, false, k);
-  enqueue_backward(t, t->d_idx, batch, false, k);
-  HIP_RET(hipGetLastError());
-  HIP_RET(hipMemcpyAsync(t->h_all.data(), t->d_g, t->off[8] * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-  HIP_RET(hipMemcpyAsync(loss, t->d_loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
-  HIP_RET(hipStreamSynchronize(t->stream));
-  for (int i = 0; i < 8; i++) std::memcpy(grads[i], t->h_all.data() + t->off[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
-  return GPD_OK;
+  const int rc = eight_only("gpd_hip_train_gradients", t);
+  return rc ? rc : gradients("gpd_hip_train_gradients", t, indices, batch, grads, loss);
+}
+int gpd_hip_train_net_gradients(gpd_hip_trainer *t, const int32_t *indices, int batch, float *const grads[10], float *loss) {
+  return gradients("gpd_hip_train_net_gradients", t, indices, batch, grads, loss);
 }
 
 int gpd_hip_train_apply(gpd_hip_trainer *t, const float *const grads[8]) {
-  if (!t || !grads) {
-    set_error("gpd_hip_train_apply: null argument");
-    return GPD_ERR_INVALID;
-  }
-  for (int i = 0; i < 8; i++)
-    if (!grads[i] || !all_finite(grads[i], t->off[i + 1] - t->off[i])) {
-      set_error("gpd_hip_train_apply: tensor %d is null or holds a non-finite value", i);
-      return GPD_ERR_INVALID;
-    }
-  for (int i = 0; i < 8; i++) std::memcpy(t->h_all.data() + t->off[i], grads[i], (t->off[i + 1] - t->off[i]) * sizeof(float));
-  HIP_RET(hipSetDevice(t->device));
-  HIP_RET(hipMemcpyAsync(t->d_g, t->h_all.data(), t->off[8] * sizeof(float), hipMemcpyHostToDevice, t->stream));
-  int k = 0;
-  enqueue_update(t, false, k);
-  HIP_RET(hipGetLastError());
-  HIP_RET(hipStreamSynchronize(t->stream));
-  return GPD_OK;
+  const int rc = eight_only("gpd_hip_train_apply", t);
+  return rc ? rc : apply("gpd_hip_train_apply", t, grads);
 }
+int gpd_hip_train_net_apply(gpd_hip_trainer *t, const float *const grads[10]) { return apply("gpd_hip_train_net_apply", t, grads); }
 
 int gpd_hip_train_eval(gpd_hip_trainer *t, int which, const int32_t *indices, int n, float *logits, int *num_correct) {
   if (!t || which < 0 || which > 1 || n < 0 || (n > 0 && !logits) || !num_correct) {
@@ -1269,8 +1496,9 @@ int gpd_hip_train_eval(gpd_hip_trainer *t, int which, const int32_t *indices, in
 int gpd_hip_train_step_timed(gpd_hip_trainer *t, const int32_t *indices, int batch, float *ms, int capacity, int *num) {
   int rc = check_batch("gpd_hip_train_step_timed", t, indices, batch);
   if (rc) return rc;
-  if (!ms || !num || capacity < kNumKernels) {
-    set_error("gpd_hip_train_step_timed: ms must hold %d values", kNumKernels);
+  const int launches = (int)t->names.size();  // kNumKernels, or kNumKernelsThird behind a third dense layer
+  if (!ms || !num || capacity < launches) {
+    set_error("gpd_hip_train_step_timed: ms must hold %d values", launches);
     return GPD_ERR_INVALID;
   }
   rc = check_indices("gpd_hip_train_step_timed", indices, batch, t->n[0]);
@@ -1292,7 +1520,8 @@ int gpd_hip_train_step_timed(gpd_hip_trainer *t, const int32_t *indices, int bat
 const char *gpd_hip_train_kernel_name(int i) { return i >= 0 && i < kNumKernels ? kKernelNames[i] : ""; }
 
 const char *gpd_hip_train_kernel_name_of(const gpd_hip_trainer *t, int i) {
-  return t && t->r.solver == GPD_TRAIN_SOLVER_SGD && i == kNumKernels - 1 ? kKernelNames[kNumKernels] : gpd_hip_train_kernel_name(i);
+  if (!t) return gpd_hip_train_kernel_name(i);
+  return i >= 0 && i < (int)t->names.size() ? t->names[(size_t)i] : "";
 }
 
 }  // extern "C"

@@ -245,6 +245,12 @@ int gpd_hip_train_group_create(gpd_hip_trainer *const *trainers, int num, gpd_hi
       set_error("gpd_hip_train_group_create: trainer %d has %d channels, trainer 0 has %d", r, trainers[r]->C, trainers[0]->C);
       return GPD_ERR_INVALID;
     }
+    const gpd_lenet_shape &sr = trainers[r]->shape, &s0 = trainers[0]->shape;
+    if (sr.conv1_out != s0.conv1_out || sr.conv2_out != s0.conv2_out || sr.fc1_out != s0.fc1_out || sr.fc2_out != s0.fc2_out) {
+      set_error("gpd_hip_train_group_create: trainer %d trains a network of widths %d, %d, %d, %d, trainer 0 one of %d, %d, %d, %d", r, sr.conv1_out,
+                sr.conv2_out, sr.fc1_out, sr.fc2_out, s0.conv1_out, s0.conv2_out, s0.fc1_out, s0.fc2_out);
+      return GPD_ERR_INVALID;
+    }
     if (!same_params(trainers[r]->p, trainers[0]->p)) {
       set_error("gpd_hip_train_group_create: the gpd_train_params of trainer %d differ from trainer 0's in more than max_batch", r);
       return GPD_ERR_INVALID;
@@ -257,7 +263,7 @@ int gpd_hip_train_group_create(gpd_hip_trainer *const *trainers, int num, gpd_hi
   gpd_hip_train_group *g = new gpd_hip_train_group();
   g->G = num;
   g->t.assign(trainers, trainers + num);
-  g->n = trainers[0]->off[8];
+  g->n = trainers[0]->total;
   group::slices(g->n, num, g->first);
   for (int o = 0; o < num; o++) g->row = std::max(g->row, (slice_size(g, o) + 3) / 4 * 4);
   g->gather.assign((size_t)num, nullptr);

@@ -34,7 +34,7 @@ def _general_net(state):
     return api.torch_net_arrays(state)
 
 
-def _export_general(shape, arrs, out_dir, input_scale):
+def _export_general(shape, arrs, out_dir, input_scale, conv_relu=True):
     """The 8 or 10 tensors in torch layout and a network.cfg that also names the widths; the host layer converts them with
     gpd_hip_lenet_net_from_torch and scores on the shape-general route (gpd_hip_set_lenet_net)."""
     if not api.lenet_shape_check(shape):
@@ -45,19 +45,20 @@ def _export_general(shape, arrs, out_dir, input_scale):
         a.astype("<f4").tofile(os.path.join(out_dir, name))
     with open(os.path.join(out_dir, "network.cfg"), "w") as f:
         f.write("# written by gpd_amd.torch_export: pytorch/network.py::%s, tensors as torch stores them\n"
-                "layout = torch\nconv_relu = 1\ninput_scale = %s\nconv1_out = %d\nconv2_out = %d\nfc1_out = %d\nfc2_out = %d\n"
-                % ("NetCCFFF" if shape.fc2_out else "Net", repr(float(input_scale)), shape.conv1_out, shape.conv2_out, shape.fc1_out, shape.fc2_out))
+                "layout = torch\nconv_relu = %d\ninput_scale = %s\nconv1_out = %d\nconv2_out = %d\nfc1_out = %d\nfc2_out = %d\n"
+                % ("NetCCFFF" if shape.fc2_out else "Net", int(bool(conv_relu)), repr(float(input_scale)), shape.conv1_out, shape.conv2_out, shape.fc1_out, shape.fc2_out))
     return sorted(names) + ["network.cfg"]
 
 
-def export(state, out_dir, input_scale=1.0 / 256):
+def export(state, out_dir, input_scale=1.0 / 256, conv_relu=True):
     """Write the tensors of `state` and network.cfg into out_dir -> the file names.  The stock network (api.torch_state_arrays):
-    eight tensors; any other shape of the family, or NetCCFFF (api.torch_net_arrays): eight or ten, and the widths in network.cfg."""
+    eight tensors; any other shape of the family, or NetCCFFF (api.torch_net_arrays): eight or ten, and the widths in network.cfg.
+    conv_relu = False: the network was trained without the ReLUs behind the convolutions (the trainer's Caffe variant)."""
     general = _general_net(state)
     if general is not None:
         if not (np.isfinite(input_scale) and input_scale > 0):
             raise ValueError("input_scale must be finite and positive")
-        return _export_general(general[0], general[1], out_dir, input_scale)
+        return _export_general(general[0], general[1], out_dir, input_scale, conv_relu)
     t = api.torch_state_arrays(state)
     if not (np.isfinite(input_scale) and input_scale > 0):
         raise ValueError("input_scale must be finite and positive")
@@ -68,7 +69,7 @@ def export(state, out_dir, input_scale=1.0 / 256):
         t[k].astype("<f4").tofile(os.path.join(out_dir, name))
     with open(os.path.join(out_dir, "network.cfg"), "w") as f:
         f.write("# written by gpd_amd.torch_export: pytorch/network.py::Net, tensors as torch stores them\n"
-                "layout = torch\nconv_relu = 1\ninput_scale = %s\n" % repr(float(input_scale)))
+                "layout = torch\nconv_relu = %d\ninput_scale = %s\n" % (int(bool(conv_relu)), repr(float(input_scale))))
     return sorted(FILES.values()) + ["network.cfg"]
 
 

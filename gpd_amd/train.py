@@ -43,6 +43,16 @@ its shard; an epoch (a pass, under the Caffe recipe) is min_r(n_r) // (batch / G
 route: the TAILS ARE DROPPED — no short last batch, and the images a larger shard has beyond the smallest sit the epoch out.
 The test set, eval, snapshots and the export live on replica 0; --resume and --init set replica 0 and broadcast.  --generate
 with --devices is refused.  Without --devices the tool behaves to the byte as before.
+
+python -m gpd_amd.train TRAIN_DIR ... --net F1,F2,H1[,H2]
+
+trains a network of other widths — pytorch/network.py::Net with conv1_out F1, conv2_out F2 and fc1_out H1, or ::NetCCFFF with a
+third dense layer of H2 outputs (train_net3.py's commented-out alternative) — with either recipe and with --devices; under
+--recipe caffe it is that network without the ReLUs behind the convolutions.  The initial state is the seeded filler of the
+recipe for those widths.  DIR receives what gpd_amd.torch_export writes for such a network — the 8 or 10 tensors in torch
+layout and a network.cfg that names the widths (and conv_relu = 0 under the Caffe recipe) — and model.pwf holds the same
+tensors; snapshots and --resume carry them all.  --init is refused (an Eigen-layout directory has the stock widths), and so is
+--freeze with a third dense layer (the recipe has multipliers for eight tensors).  Without --net nothing changes.
 """
 import argparse
 import os
@@ -133,6 +143,11 @@ def batch_rows(seed, n, batch, first, count, per=None):
     return rows[first - e0 * per:first - e0 * per + count]
 
 
+def trainer_kw(a):
+    """The Trainer arguments --net asks for"""
+    return dict(shape=a.net) if a.net else {}
+
+
 def write_snapshot(trainer, directory):
     os.makedirs(directory, exist_ok=True)
     s = trainer.get_solver_state()
@@ -143,10 +158,10 @@ def write_snapshot(trainer, directory):
 def read_snapshot(trainer, directory):
     """-> the iteration the snapshot was taken at"""
     with np.load(os.path.join(directory, "state.npz")) as z:
-        trainer.set_state({k: z[k] for k in api.TORCH_KEYS})
+        trainer.set_state({k: z[k] for k in trainer.keys})
     with np.load(os.path.join(directory, "solver.npz")) as z:
         count = int(z["count"])
-        trainer.set_solver_state(dict(count=count, m={k: z["m." + k] for k in api.TORCH_KEYS}, v=None))
+        trainer.set_solver_state(dict(count=count, m={k: z["m." + k] for k in trainer.keys}, v=None))
     return count
 
 
@@ -261,12 +276,12 @@ class Replicas:
 def main_caffe(a):
     C, device, train_set = open_sets(a)
     recipe = api.train_default_recipe(1, lr_mult={k: 0.0 for k in frozen_names(a.freeze or "")})
-    reps = Replicas(a, train_set, recipe=recipe, lr=api.CAFFE_BASE_LR) if a.devices else None
+    reps = Replicas(a, train_set, recipe=recipe, lr=api.CAFFE_BASE_LR, **trainer_kw(a)) if a.devices else None
     if reps:
         ctx, trainer = None, reps.trainers[0]
     else:
         ctx = api.Context(api.default_params(C), device=device)
-        trainer = api.Trainer(ctx, recipe=recipe, max_batch=a.batch, lr=api.CAFFE_BASE_LR)
+        trainer = api.Trainer(ctx, recipe=recipe, max_batch=a.batch, lr=api.CAFFE_BASE_LR, **trainer_kw(a))
     try:
         scale = float(trainer.params.input_scale)
         start = 0
@@ -277,7 +292,7 @@ def main_caffe(a):
             fill = api.lenet_from_torch(api.init_xavier(C, a.seed), C, scale)
             trainer.set_state(eigen_export.to_torch(eigen_export.load(a.init, fill), scale))
         else:
-            trainer.set_state(api.init_xavier(C, a.seed))
+            trainer.set_state(api.init_xavier(C, a.seed, shape=a.net))
         if reps:
             reps.group.broadcast(0)
             n, n_test = sum(reps.shards), reps.n_test
@@ -288,15 +303,30 @@ def main_caffe(a):
             n, n_test = fill_sets(trainer, a, train_set)
             print("training on %d images of %d channels from iteration %d to %d%s" % (n, C, start, a.max_iter, ", testing on %d" % min(TEST_IMAGES, n_test) if n_test else ""))
             state = train_caffe(trainer, n, a.max_iter, a.batch, a.seed, n_test, start, a.snapshot, a.out)
-        names = eigen_export.export(state, a.out, scale)
+        if a.net:  # the Eigen layout has the stock widths only
+            names = torch_export.export(state, a.out, scale, conv_relu=False)
+        else:
+            names = eigen_export.export(state, a.out, scale)
     finally:
         if reps:
             reps.close()
         else:
             trainer.close()
             ctx.close()
+    if a.net:
+        names += save_pwf(state, a.out)
     print("wrote %s: %s" % (a.out, " ".join(names)))
     return 0
+
+
+def save_pwf(state, out):
+    """model.pwf, torch.save of the state dict as pytorch/train_net3.py saves it, where torch imports -> the names written"""
+    try:
+        import torch
+    except ImportError:
+        return []
+    torch.save({k: torch.from_numpy(v.copy()) for k, v in state.items()}, os.path.join(out, "model.pwf"))
+    return ["model.pwf"]
 
 
 def parse_args(argv=None):
@@ -316,7 +346,19 @@ def parse_args(argv=None):
     ap.add_argument("--resume", help="caffe: a snapshot directory to continue from")
     ap.add_argument("--init", help="caffe: an Eigen-layout parameter directory to start from")
     ap.add_argument("--freeze", help="caffe: tensors or layers whose lr_mult is 0, comma-separated")
+    ap.add_argument("--net", metavar="F1,F2,H1[,H2]", help="other widths: conv1_out, conv2_out, fc1_out and, for NetCCFFF, fc2_out")
     a = ap.parse_args(argv)
+    if a.net is not None:
+        try:
+            a.net = tuple(int(x) for x in a.net.split(","))
+        except ValueError:
+            ap.error("--net takes three or four comma-separated widths")
+        if len(a.net) not in (3, 4) or min(a.net) < 1:
+            ap.error("--net takes three or four positive widths: F1,F2,H1[,H2]")
+        if a.init:
+            ap.error("--init reads an Eigen-layout directory, which has the stock widths: it goes without --net")
+        if a.freeze and len(a.net) == 4:
+            ap.error("--freeze with a third dense layer: the recipe has multipliers for eight tensors")
     if a.generate and (a.train_dir or a.test):
         ap.error("--generate fills both sets itself: it goes without TRAIN_DIR and --test")
     if not a.generate and not a.train_dir:
@@ -342,14 +384,14 @@ def main(argv=None):
     if a.recipe == "caffe":
         return main_caffe(a)
     C, device, train_set = open_sets(a)
-    reps = Replicas(a, train_set) if a.devices else None
+    reps = Replicas(a, train_set, **trainer_kw(a)) if a.devices else None
     if reps:
         ctx, trainer = None, reps.trainers[0]
     else:
         ctx = api.Context(api.default_params(C), device=device)
-        trainer = api.Trainer(ctx, max_batch=a.batch)
+        trainer = api.Trainer(ctx, max_batch=a.batch, **trainer_kw(a))
     try:
-        trainer.set_state(api.init_state(C, a.seed))
+        trainer.set_state(api.init_state(C, a.seed, shape=a.net))
         if reps:
             reps.group.broadcast(0)
             print("training on %d images of %d channels over %d replicas%s" % (sum(reps.shards), C, len(reps.shards), ", testing on %d" % reps.n_test if reps.n_test else ""))
@@ -365,13 +407,7 @@ def main(argv=None):
         else:
             trainer.close()
             ctx.close()
-    try:
-        import torch
-    except ImportError:
-        torch = None
-    if torch is not None:
-        torch.save({k: torch.from_numpy(v.copy()) for k, v in state.items()}, os.path.join(a.out, "model.pwf"))
-        names.append("model.pwf")
+    names += save_pwf(state, a.out)
     print("wrote %s: %s" % (a.out, " ".join(names)))
     return 0
 

@@ -884,6 +884,45 @@ const char *gpd_hip_train_kernel_name_of(const gpd_hip_trainer *t, int i);
 int gpd_hip_train_get_solver_state(gpd_hip_trainer *t, float *const m[8], float *const v[8], long long *count);
 int gpd_hip_train_set_solver_state(gpd_hip_trainer *t, const float *const m[8], const float *const v[8], long long count);
 
+/* ---- trainers of any network of the family (train.hip) ------------------------------------------------------
+ * Everything above trains the stock widths (C, 20, 50, 500, 0).  gpd_hip_train_create_net trains any gpd_lenet_shape that
+ * gpd_hip_lenet_shape_check accepts — pytorch/network.py::Net of other widths, and ::NetCCFFF with its third dense layer
+ * (fc2_out = H2 > 0) — under either network variant (with or without the conv ReLUs) and either solver.  Data pools, steps,
+ * eval, append_view, step_timed and the group take such a trainer as they take the stock one.
+ *
+ * The state of a trainer with H2 == 0 is the eight tensors above with sizes following its shape (F1 = conv1_out, F2 =
+ * conv2_out, H1 = fc1_out): conv1.weight [F1][C][5][5], conv1.bias [F1], conv2.weight [F2][F1][5][5], conv2.bias [F2],
+ * fc1.weight [H1][F2 * 144], fc1.bias [H1], fc2.weight [2][H1], fc2.bias [2]; the entries with tables of 8 serve it.  With
+ * H2 > 0 there are ten: fc2.weight [H2][H1], fc2.bias [H2], fc3.weight [2][H2], fc3.bias [2]; the entries with tables of 8 then
+ * return GPD_ERR_STATE and change nothing.  The gpd_hip_train_net_ entries take tables of 10 in the order of
+ * gpd_hip_lenet_net_from_torch's input and serve every trainer; slots [8] and [9] are not read when H2 == 0 and may be NULL.
+ *
+ * Summation order (the stock shape's is unchanged): fc1 forward sums K = 144 F2 in 16 ranges of 9 F2; conv2's weight gradient
+ * one partial per image, conv1's four per image, joined as before; the third dense layer is one chain per output forward
+ * (K = H1), K = B for its weight gradient, K = H2 for the gradient it hands back, its bias and fc1's summed over the batch in
+ * eight interleaved chains.  gpd_hip_train_step_timed lists four more launches for H2 > 0 (gpd_hip_train_kernel_name_of).
+ *
+ * gpd_hip_train_create_net: recipe may be NULL (gpd_hip_train_create's).  GPD_ERR_INVALID before anything is allocated, beyond
+ * gpd_hip_train_create_recipe's: a NULL shape, a shape gpd_hip_lenet_shape_check refuses, shape->channels != params->channels,
+ * H2 > 0 with any lr_mult or decay_mult other than 1 (the recipe has eight multiplier slots).  The stock shape through this
+ * entry is gpd_hip_train_create_recipe byte for byte. */
+int gpd_hip_train_create_net(gpd_hip_ctx *ctx, const gpd_train_params *params, const gpd_train_recipe *recipe, const gpd_lenet_shape *shape,
+                             gpd_hip_trainer **out);
+int gpd_hip_train_shape(const gpd_hip_trainer *t, gpd_lenet_shape *out);
+int gpd_hip_train_net_set_state(gpd_hip_trainer *t, const float *const tensors[10]);
+int gpd_hip_train_net_get_state(gpd_hip_trainer *t, float *const tensors[10]);
+int gpd_hip_train_net_gradients(gpd_hip_trainer *t, const int32_t *indices, int batch, float *const grads[10], float *loss);
+int gpd_hip_train_net_apply(gpd_hip_trainer *t, const float *const grads[10]);
+int gpd_hip_train_net_get_solver_state(gpd_hip_trainer *t, float *const m[10], float *const v[10], long long *count);
+int gpd_hip_train_net_set_solver_state(gpd_hip_trainer *t, const float *const m[10], const float *const v[10], long long count);
+/* Host only.  sizes: the element counts of the ten tensors (n[8] = n[9] = 0 when H2 == 0).  init_state / init_xavier:
+ * gpd_hip_train_init_state / gpd_hip_train_init_xavier for the shape — the same stream, the tensors in order, fan_in 25 C,
+ * 25 F1, 144 F2, H1, H2 — and their bytes at the stock shape.  GPD_ERR_INVALID, nothing written: a NULL argument, a NULL among
+ * the used tensors, a shape outside the limits. */
+int gpd_hip_train_net_sizes(const gpd_lenet_shape *shape, size_t n[10]);
+int gpd_hip_train_net_init_state(const gpd_lenet_shape *shape, uint32_t seed, float *const tensors[10]);
+int gpd_hip_train_net_init_xavier(const gpd_lenet_shape *shape, uint32_t seed, float *const tensors[10]);
+
 /* ---- training on several replicas (train_group.hip, group_model.h) ---------------------------------------------
  * What pytorch/train_net3.py:97-99 gets from nn.DataParallel: G trainers ("replicas"), each on a context of its own — on G
  * devices, or several on one device — run forward and backward on a batch each, and every replica's solver applies the MEAN
@@ -913,7 +952,8 @@ int gpd_hip_train_group_schedule(int G, int num_steps, void *ops, int capacity, 
 typedef struct gpd_hip_train_group gpd_hip_train_group;
 /* 1 <= num <= 16 trainers.  The group takes no ownership: it is destroyed before its trainers, and a trainer may still be
  * stepped alone (gpd_hip_train_group_verify then tells).  GPD_ERR_INVALID before anything is allocated: a null or repeated
- * trainer, two trainers on one context, channel counts, gpd_train_params (apart from max_batch) or recipes that differ.
+ * trainer, two trainers on one context, channel counts, network widths, gpd_train_params (apart from max_batch) or recipes that
+ * differ.
  * Allocates per replica a gather block of G - 1 slices and three events; never enables peer access. */
 int gpd_hip_train_group_create(gpd_hip_trainer *const *trainers, int num, gpd_hip_train_group **out);
 void gpd_hip_train_group_destroy(gpd_hip_train_group *g);
