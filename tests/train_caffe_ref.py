@@ -123,14 +123,16 @@ def logits_yardstick(state, img, input_scale=1.0 / 256):
     return z64, max(float(np.abs(z - z64).max()) for z in runs), max(float(np.abs((z[:, 1] - z[:, 0]) - d64).max()) for z in runs)
 
 
-def sgd_trajectory(state, img, lab, rows, dtype, hyper=None, lr_mult=None, decay_mult=None, reverse=False, threads=None):
-    """The network under Caffe's SGD rule, one step per row of `rows`, the update arithmetic in `dtype` with the rate rounded to
-    float32 first (what the solver hands to its update) -> (every step's loss f64 [len(rows)], the final state {key: numpy})"""
+def caffe_sgd_trajectory(state, keys, loss_of, rows, dtype, hyper=None, lr_mult=None, decay_mult=None, reverse=False, threads=None):
+    """Caffe's SGD rule over the tensors `keys` of `state`, one step per row of `rows`: loss_of(tensors, row, h) is the batch's
+    loss under the tensors {key: torch tensor of dtype} and the solver settings h.  The update arithmetic is in `dtype` with the
+    rate rounded to float32 first (what the solver hands to its update): d = g + (wd * decay_mult) w, hist = m * hist +
+    (lr * lr_mult) * d, w = w - hist -> (every step's loss f64 [len(rows)], the final state {key: numpy})"""
     import torch
     h = dict(SOLVER, **(hyper or {}))
-    lm = dict.fromkeys(api.TORCH_KEYS, 1.0)
+    lm = dict.fromkeys(keys, 1.0)
     lm.update(lr_mult or {})
-    dm = dict.fromkeys(api.TORCH_KEYS, 1.0)
+    dm = dict.fromkeys(keys, 1.0)
     dm.update(decay_mult or {})
     f32 = dtype == torch.float32
 
@@ -138,25 +140,33 @@ def sgd_trajectory(state, img, lab, rows, dtype, hyper=None, lr_mult=None, decay
         return float(np.float32(x)) if f32 else float(x)
 
     with _Threads(threads):
-        t = {k: torch.from_numpy(np.array(state[k])).to(dtype).requires_grad_(True) for k in api.TORCH_KEYS}
-        hist = {k: torch.zeros_like(t[k]) for k in api.TORCH_KEYS}
+        t = {k: torch.from_numpy(np.array(state[k])).to(dtype).requires_grad_(True) for k in keys}
+        hist = {k: torch.zeros_like(t[k]) for k in keys}
         losses = []
         for it, row in enumerate(np.asarray(rows)):
             order = row[::-1].copy() if reverse else row
-            for k in api.TORCH_KEYS:
+            for k in keys:
                 t[k].grad = None
-            loss = _loss(t, np.asarray(img)[order], np.asarray(lab)[order], dtype, h["input_scale"])
+            loss = loss_of(t, order, h)
             loss.backward()
             lr = float(np.float32(learning_rate64(h["lr_policy"], h["lr"], it, h["gamma"], h["power"], h["stepsize"])))
             with torch.no_grad():
-                for k in api.TORCH_KEYS:
+                for k in keys:
                     rate = num(np.float32(lr) * np.float32(lm[k])) if f32 else lr * lm[k]
                     decay = num(np.float32(h["weight_decay"]) * np.float32(dm[k])) if f32 else num(h["weight_decay"]) * dm[k]
                     d = t[k].grad + decay * t[k]
                     hist[k] = num(h["momentum"]) * hist[k] + rate * d
                     t[k] -= hist[k]
             losses.append(float(loss.item()))
-        return np.array(losses, np.float64), {k: t[k].detach().numpy().copy() for k in api.TORCH_KEYS}
+        return np.array(losses, np.float64), {k: t[k].detach().numpy().copy() for k in keys}
+
+
+def sgd_trajectory(state, img, lab, rows, dtype, hyper=None, lr_mult=None, decay_mult=None, reverse=False, threads=None):
+    """The stock network (no conv ReLUs) under caffe_sgd_trajectory's rule -> (every step's loss f64 [len(rows)], the final state)"""
+    def loss_of(t, order, h):
+        return _loss(t, np.asarray(img)[order], np.asarray(lab)[order], dtype, h["input_scale"])
+
+    return caffe_sgd_trajectory(state, api.TORCH_KEYS, loss_of, rows, dtype, hyper, lr_mult, decay_mult, reverse, threads)
 
 
 def sgd_trajectory_yardstick(state, img, lab, rows, hyper=None, lr_mult=None, decay_mult=None):
