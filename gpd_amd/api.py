@@ -109,6 +109,7 @@ class GpdHipError(RuntimeError):
 
 # gpd_hip_set_lenet_mode (include/gpd_hip.h)
 LENET_SPLIT, LENET_F32_CHAIN = 0, 1
+LENET_NET_CHAIN, LENET_NET_SPLIT = 0, 1  # gpd_hip_set_lenet_net_mode: the arithmetic of the shape-general route
 
 
 def sample_positions(n, num_draws, seed=0, with_repetition=False):
@@ -309,6 +310,16 @@ def _pointer_table(arrs):
     return t
 
 
+def bf16_split3(x):
+    """gpd_hip_bf16_split3: the three bf16 pieces (uint16 bit patterns h, m, l, shaped like x) of float32 values, as the split
+    kernels and their weight tables make them.  Host only."""
+    x = np.ascontiguousarray(x, np.float32)
+    h, m, l = (np.zeros(x.shape, np.uint16) for _ in range(3))
+    if lib().gpd_hip_bf16_split3(_ptr(x), x.size, _ptr(h), _ptr(m), _ptr(l)) != 0:
+        raise GpdHipError(lib().gpd_hip_last_error().decode())
+    return h, m, l
+
+
 def lenet_net_from_torch(state, input_scale=1.0 / 256):
     """gpd_hip_lenet_net_from_torch: a state dict of Net / NetCCFFF (see torch_net_arrays) -> (LenetShape, the 8 or 10 tensors
     in the layouts gpd_hip_set_lenet_net takes).  Host only."""
@@ -337,7 +348,7 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals", "gpd_hip_sample_positions",
            "gpd_hip_set_lenet_conv_relu", "gpd_hip_lenet_from_torch",
            "gpd_hip_lenet_shape_check", "gpd_hip_lenet_net_from_torch", "gpd_hip_set_lenet_net", "gpd_hip_lenet_net_debug",
-           "gpd_hip_lenet_net_info",
+           "gpd_hip_lenet_net_info", "gpd_hip_set_lenet_net_mode", "gpd_hip_bf16_split3",
            "gpd_hip_upload_ground_truth", "gpd_hip_label_view", "gpd_hip_balance_view", "gpd_hip_sizeof_label_view_job",
            "gpd_hip_shuffle_orders", "gpd_hip_sis_proposals", "gpd_hip_sis_select", "gpd_hip_detect_sis", "gpd_hip_sizeof_sis_job",
            "gpd_hip_image_model", "gpd_hip_given_check", "gpd_hip_images_given", "gpd_hip_score_given",
@@ -420,6 +431,8 @@ def lib():
         L.gpd_hip_set_lenet_net.argtypes = [C.c_void_p, C.POINTER(LenetShape), C.c_void_p]
         L.gpd_hip_lenet_net_debug.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.gpd_hip_lenet_net_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.gpd_hip_set_lenet_net_mode.argtypes = [C.c_void_p, C.c_int]
+        L.gpd_hip_bf16_split3.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gpd_hip_replay_times.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
         L.gpd_hip_upload_ground_truth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.gpd_hip_label_view.argtypes = [C.c_void_p, C.POINTER(LabelViewJob)]
@@ -564,15 +577,24 @@ class Context:
         self.set_lenet_weights(lenet_from_torch(state, self.params.image_num_channels, input_scale))
         self.set_lenet_conv_relu(True)
 
-    def set_lenet_net(self, state, input_scale=1.0 / 256, conv_relu=True):
+    def set_lenet_net(self, state, input_scale=1.0 / 256, conv_relu=True, net_mode=None):
         """A state dict of pytorch/network.py::Net or ::NetCCFFF of any widths within the limits (LenetShape) as the context's
-        scoring network, on the shape-general route (exact f32 chains; set_lenet_mode is ignored by it).  set_lenet_weights /
-        set_lenet_torch return the context to the stock route.  -> the LenetShape"""
+        scoring network, on the shape-general route (exact f32 chains by default; set_lenet_mode is ignored by it,
+        set_lenet_net_mode chooses its arithmetic — net_mode: that call as a convenience, None leaves the context's mode alone).
+        set_lenet_weights / set_lenet_torch return the context to the stock route.  -> the LenetShape"""
         shape, arrs = lenet_net_from_torch(state, input_scale)
         self._lenet_shape = shape
+        if net_mode is not None:
+            self.set_lenet_net_mode(net_mode)
         self._check(lib().gpd_hip_set_lenet_net(self._h, C.byref(shape), _pointer_table(arrs)))
         self.set_lenet_conv_relu(conv_relu)
         return shape
+
+    def set_lenet_net_mode(self, mode):
+        """gpd_hip_set_lenet_net_mode: LENET_NET_CHAIN (default: the f32 chains, the bit-for-bit checker) or LENET_NET_SPLIT (the
+        bf16 matrix pipe on exactly split operands, for throughput) for the shape-general route.  Context state: legal before or
+        after set_lenet_net, kept across installs.  A change frees the route's scratch: install, set the mode, then reserve."""
+        self._check(lib().gpd_hip_set_lenet_net_mode(self._h, int(mode)))
 
     def lenet_net_debug(self, which, n):
         """gpd_hip_lenet_net_debug: pool1 [n,F1,28,28] (0), pool2 [n,F2,12,12] (1), fc1 [n,H1] (2), fc2 [n,H2] (3) or the logits
@@ -1355,11 +1377,14 @@ class Trainer:
         self._check(lib().gpd_hip_train_step_timed(self._h, _ptr(idx), len(idx), _ptr(ms), len(ms), C.byref(k)))
         return [(lib().gpd_hip_train_kernel_name_of(self._h, i).decode(), float(ms[i])) for i in range(k.value)]
 
-    def install(self, ctx=None, input_scale=None):
+    def install(self, ctx=None, input_scale=None, net_mode=None):
         """get_state followed by Context.set_lenet_torch: the trained network becomes `ctx`'s (default: the trainer's own) scoring
         network, with the conv ReLUs on for Net and off for the Caffe network.  A network of other widths than the stock ones
-        goes through Context.set_lenet_net onto the general route."""
+        goes through Context.set_lenet_net onto the general route.  net_mode: Context.set_lenet_net_mode on `ctx` first (None
+        leaves the context's mode alone; context state, so it is set whichever route the network takes)."""
         ctx = self._ctx if ctx is None else ctx
+        if net_mode is not None:
+            ctx.set_lenet_net_mode(net_mode)
         if self.shape.as_tuple()[1:] != (20, 50, 500, 0):
             ctx.set_lenet_net(self.get_state(), float(self.params.input_scale) if input_scale is None else input_scale,
                               conv_relu=not self.caffe_network)

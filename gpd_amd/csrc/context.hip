@@ -124,7 +124,7 @@ int reserve_selection(Lane &L, int k, int n) {
 // its image, the LeNet scratch of both scoring modes (pool1, the f32 and the three-plane bf16 flatten, ip1 and its four K
 // quarters), score and records; per (hand set, camera) a shadow voxel bitset of the 86^3-bit default window (wider image
 // volumes take more: images_reserve grows them on demand).  With a network of the general route installed (`net`) a candidate
-// costs that network's scratch (LeNetNet::scratch_per_image) and its score instead of the stock scratch, which lane_reserve
+// costs that network's scratch (LeNetNet::scratch_per_image, of the mode in force: gpd_hip_set_lenet_net_mode) and its score instead of the stock scratch, which lane_reserve
 // then sizes for one image.
 int candidate_bound(const gpd_params &p, int samples, int cams, size_t budget, const LeNetNet *net) {
   const long long upper = (long long)samples * p.num_hand_axes * p.num_orientations;

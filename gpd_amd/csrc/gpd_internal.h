@@ -56,6 +56,13 @@ struct LeNetNet {
   long long scratch_per_image = 0;   // bytes
   long long macs_per_image = 0;
   int chunk = 0;                     // images per pass
+  // GPD_LENET_NET_SPLIT (lenet_net_split.hip).  `mode` is the arithmetic in force: scratch_per_image, chunk and lds_max above are
+  // its values (lenet_net_apply_mode); the chain's tables stay as they are, the pieces below exist in split mode only.
+  int mode = 0;
+  uint4 *s_c1 = nullptr, *s_c2 = nullptr;  // conv weights as B fragments [chunk of 8 channels][filter tile of 16][7 k-steps][3 pieces][64 lanes] x 8 bf16
+  uint4 *s_f1 = nullptr, *s_f2 = nullptr;  // dense weights as B fragments [unit tile of 16][k-steps][3 pieces][64 lanes] x 8 bf16
+  int s_ft1 = 0, s_ft2 = 0;                // filter tiles the conv tables hold per chunk (an even count)
+  int s_k1 = 0, s_k2 = 0;                  // fc1's and fc2's K, padded to whole k-steps of 32 (row length of the bf16 planes)
 };
 struct LeNetNetScratch {
   int capacity = 0;  // images
@@ -64,6 +71,12 @@ struct LeNetNetScratch {
   float *pool2 = nullptr;  // [cap][144][F2]: pixel-major, fc1's k order
   float *h1 = nullptr, *h2 = nullptr;  // [cap][ld]: ld = the units rounded up to a multiple of 4 (16-byte row reads)
   float *logits = nullptr;             // [cap][2]
+  // GPD_LENET_NET_SPLIT: activations as three bf16 planes, in the layout the consuming loader takes (lenet_net_split.hip).
+  // h1 / h2 above hold the LAST hidden layer as f32 for the logit chains; pool1 and pool2 stay null.
+  int mode = 0;                        // the mode the buffers were sized for
+  unsigned short *p1s = nullptr;       // [cap][F1 / 8 chunks][3][784][8]
+  unsigned short *xs = nullptr;        // [cap][3][K1pad], k = pixel * round_up(F2, 8) + channel
+  unsigned short *h1s = nullptr;       // [cap][3][K2pad] (networks with fc2; the padding zeroed at allocation)
 };
 void lenet_net_free(LeNetNet &net);
 void lenet_net_scratch_free(LeNetNetScratch &s);
@@ -71,11 +84,28 @@ void lenet_net_scratch_free(LeNetNetScratch &s);
 // lenet_net_forward calls it per pass, lane_reserve ahead of the first cloud.  gpd_hip_set_lenet_net frees the scratch of every
 // lane when it installs a network: a reservation made before the install does not outlive it.
 hipError_t lenet_net_scratch_reserve(const LeNetNet &net, LeNetNetScratch &s, int n);
+// gpd_hip_set_lenet_net_mode met gpd_hip_set_lenet_net (whichever came second): builds or frees the weight piece tables and sets
+// net.mode, scratch_per_image, chunk and lds_max to the values of `mode`.  The caller has freed the lanes' general-route scratch.
+int lenet_net_apply_mode(LeNetNet &net, int mode);
+// lenet_net_split.hip
+struct LeNetWeights;
+struct LeNetScratch;
+void lenet_net_split_free(LeNetNet &net);
+int lenet_net_split_prepare(LeNetNet &net);  // the piece tables from the chain's device tables
+long long lenet_net_split_scratch_per_image(const gpd_lenet_shape &sh);
+int lenet_net_split_lds();
+hipError_t lenet_net_split_scratch_alloc(const LeNetNet &net, LeNetNetScratch &s, size_t cap);
+hipError_t lenet_net_split_forward(const LeNetWeights &w, LeNetNetScratch &t, const uint8_t *img, int m, float *d_scores, hipStream_t stream,
+                                   hipEvent_t *kernel_events);
+int lenet_net_split_debug(const LeNetNet &net, const LeNetNetScratch &t, int which, int n, float *out);  // the stream is idle
+// the two logits and the score of m images from the last hidden layer (lenet_net.hip: one kernel for both modes)
+void lenet_net_logits(const LeNetNet &net, const float *hid, int ldh, int K, float *logits, float *d_scores, int m, hipStream_t stream);
 
 struct LeNetWeights {
   int channels = 0;
   int mode = GPD_LENET_SPLIT;  // gpd_hip_set_lenet_mode
   bool conv_relu = false;      // gpd_hip_set_lenet_conv_relu: ReLU on pool1 and pool2 (the network of the reference's PyTorch scripts)
+  int net_mode = GPD_LENET_NET_CHAIN;  // gpd_hip_set_lenet_net_mode: outlives installs and gpd_hip_set_lenet_weights (net.mode: what is in force)
   LeNetNet net;                // gpd_hip_set_lenet_net
   LeNetFast fast;
   float *c1w = nullptr, *c1b = nullptr, *c2w = nullptr, *c2b = nullptr;

@@ -20,6 +20,8 @@
 //   net_dense_kernel       out[n][U] = ReLU(X[n][K] W[K][U] + b): M = 128 units x N = 32 NB images per workgroup, K in LDS
 //                          stages of 32
 //   net_logits_kernel      the two logits of an image as two VALU fmaf chains, and the score y1 - y0
+// That is GPD_LENET_NET_CHAIN, the default.  gpd_hip_set_lenet_net_mode (below) chooses the route's other arithmetic,
+// GPD_LENET_NET_SPLIT: the kernels of lenet_net_split.hip on the bf16 matrix pipe, with the logits kernel of this file.
 #include <algorithm>
 #include <cstring>
 
@@ -284,13 +286,18 @@ void dense(const float *X, int ldx, const float *W, int upad, const float *bias,
 
 }  // namespace
 
+void lenet_net_logits(const LeNetNet &net, const float *hid, int ldh, int K, float *logits, float *d_scores, int m, hipStream_t stream) {
+  net_logits_kernel<<<(m + NL_THREADS - 1) / NL_THREADS, NL_THREADS, 0, stream>>>(hid, ldh, net.lw, net.lb, logits, d_scores, m, K);
+}
+
 void lenet_net_free(LeNetNet &net) {
+  lenet_net_split_free(net);
   device_release(net.c1wt, net.c1b, net.c2wt, net.c2b, net.f1w, net.f1b, net.f2w, net.f2b, net.lw, net.lb);
   net = LeNetNet();
 }
 
 void lenet_net_scratch_free(LeNetNetScratch &s) {
-  device_release(s.pool1, s.pool2, s.h1, s.h2, s.logits);
+  device_release(s.pool1, s.pool2, s.h1, s.h2, s.logits, s.p1s, s.xs, s.h1s);
   s = LeNetNetScratch();
 }
 
@@ -301,6 +308,12 @@ hipError_t lenet_net_scratch_reserve(const LeNetNet &net, LeNetNetScratch &s, in
   const gpd_lenet_shape &sh = net.shape;
   const size_t cap = (size_t)std::min(net.chunk, slack_cap(n, 4));
   hipError_t e;
+  if (net.mode == GPD_LENET_NET_SPLIT) {
+    if ((e = lenet_net_split_scratch_alloc(net, s, cap)) != hipSuccess) return e;
+    s.capacity = (int)cap;
+    s.mode = net.mode;
+    return hipSuccess;
+  }
   if ((e = device_alloc(s.pool1, cap * sh.conv1_out * 784)) != hipSuccess) return e;
   if ((e = device_alloc(s.pool2, cap * sh.conv2_out * 144)) != hipSuccess) return e;
   if ((e = device_alloc(s.h1, cap * round_up(sh.fc1_out, 4))) != hipSuccess) return e;
@@ -327,6 +340,10 @@ hipError_t lenet_net_forward(const LeNetWeights &w, LeNetScratch &s, const uint8
     const int m = std::min(chunk, n - off);
     const bool ev = kernel_events && off == 0;
     const uint8_t *img = d_images + (size_t)off * kPix * C;
+    if (net.mode == GPD_LENET_NET_SPLIT) {
+      if ((e = lenet_net_split_forward(w, t, img, m, d_scores + off, stream, ev ? kernel_events : nullptr)) != hipSuccess) return e;
+      continue;
+    }
     net_conv_pool_kernel<uint8_t, 60><<<dim3(m, net.f1pad / 32, (25 + kConv1Waves - 1) / kConv1Waves), kConv1Waves * 64, net.lds1, stream>>>(
         img, net.c1wt, net.c1b, t.pool1, C, net.cb1, net.aoff1, F1, net.f1pad, relu, 784, 1);
     if (ev) (void)hipEventRecord(kernel_events[0], stream);
@@ -421,6 +438,22 @@ int gpd_hip_lenet_net_from_torch(const gpd_lenet_shape *shape, double input_scal
 }
 
 namespace {
+// scratch bytes per image, images per pass and the largest LDS of `mode`'s kernels (lds1 / lds2: the chain's conv launches)
+void net_costs(LeNetNet &net, int mode) {
+  const gpd_lenet_shape &sh = net.shape;
+  const int lds_dense = (ND_BK * ND_BU + ND_BK * (32 * 4 + 2)) * (int)sizeof(float), lds_logits = 2 * NL_MAXK * (int)sizeof(float);
+  if (mode == GPD_LENET_NET_SPLIT) {
+    net.scratch_per_image = lenet_net_split_scratch_per_image(sh);
+    net.lds_max = std::max(lenet_net_split_lds(), lds_logits);
+  } else {
+    net.scratch_per_image = ((long long)sh.conv1_out * 784 + (long long)sh.conv2_out * 144 + round_up(sh.fc1_out, 4) + round_up(sh.fc2_out, 4) + 2) *
+                            (long long)sizeof(float);
+    net.lds_max = std::max(std::max(net.lds1, net.lds2), std::max(lds_dense, lds_logits));
+  }
+  // chunked like lenet_forward: at most 65536 images and at most 6 GiB of scratch per pass
+  net.chunk = (int)std::max(1ll, std::min((long long)kLeNetChunk, (6ll << 30) / net.scratch_per_image));
+}
+
 // [rows][cols] -> device [rows_pad][cols_pad] (zeros in the padding); transpose: the source is [cols][rows]
 int upload_padded(float *&dst, const float *src, int rows, int cols, int rows_pad, int cols_pad, bool transpose) {
   std::vector<float> h((size_t)rows_pad * cols_pad, 0.f);
@@ -472,16 +505,12 @@ int gpd_hip_set_lenet_net(gpd_hip_ctx *ctx, const gpd_lenet_shape *shape, const 
   net.aoff2 = conv_a_off(net.cb2, 28, 4, kConv2Waves);
   net.lds1 = conv_lds(net.cb1, 60, 1, kConv1Waves);
   net.lds2 = conv_lds(net.cb2, 28, 4, kConv2Waves);
-  const int lds_dense = (ND_BK * ND_BU + ND_BK * (32 * 4 + 2)) * (int)sizeof(float);
-  net.lds_max = std::max(std::max(net.lds1, net.lds2), std::max(lds_dense, 2 * NL_MAXK * (int)sizeof(float)));
+  net_costs(net, GPD_LENET_NET_CHAIN);
   if (net.lds_max > kLdsLimit) {
     set_error("gpd_hip_set_lenet_net: the shape needs %d bytes of LDS (limit %d)", net.lds_max, kLdsLimit);
     return GPD_ERR_INVALID;
   }
-  net.scratch_per_image = ((long long)F1 * 784 + (long long)F2 * 144 + round_up(H1, 4) + round_up(H2, 4) + 2) * (long long)sizeof(float);
   net.macs_per_image = (long long)F1 * 3136 * C * 25 + (long long)F2 * 576 * F1 * 25 + (long long)F2 * 144 * H1 + (long long)H1 * (H2 ? H2 : 2) + (long long)H2 * 2;
-  // chunked like lenet_forward: at most 65536 images and at most 6 GiB of scratch per pass
-  net.chunk = (int)std::max(1ll, std::min((long long)kLeNetChunk, (6ll << 30) / net.scratch_per_image));
   HIP_RET(hipSetDevice(ctx->device));
   for (auto &L : ctx->lane)
     if (L.stream) HIP_RET(hipStreamSynchronize(L.stream));  // no kernel still reads the old network
@@ -518,6 +547,8 @@ int gpd_hip_set_lenet_net(gpd_hip_ctx *ctx, const gpd_lenet_shape *shape, const 
     plain(net.lw, t[6], (size_t)H1 * 2);
     plain(net.lb, t[7], 2);
   }
+  // the mode met the network: the piece tables, and the scratch, chunk and LDS of the mode in force
+  if (rc == GPD_OK) rc = lenet_net_apply_mode(net, ctx->lenet.net_mode);
   if (rc != GPD_OK) {
     lenet_net_free(net);
     return rc;
@@ -525,6 +556,40 @@ int gpd_hip_set_lenet_net(gpd_hip_ctx *ctx, const gpd_lenet_shape *shape, const 
   net.active = true;
   ctx->lenet.net = net;
   ctx->lenet.channels = C;
+  return GPD_OK;
+}
+
+namespace gpd {
+int lenet_net_apply_mode(LeNetNet &net, int mode) {
+  if (mode == GPD_LENET_NET_SPLIT) {
+    if (lenet_net_split_lds() > kLdsLimit) {
+      set_error("gpd_hip_set_lenet_net_mode: the split kernels need %d bytes of LDS (limit %d)", lenet_net_split_lds(), kLdsLimit);
+      return GPD_ERR_INVALID;
+    }
+    if (int rc = lenet_net_split_prepare(net)) return rc;
+  } else {
+    lenet_net_split_free(net);
+  }
+  net.mode = mode;
+  net_costs(net, mode);
+  return GPD_OK;
+}
+}  // namespace gpd
+
+// Context state like gpd_hip_set_lenet_conv_relu: kept across installs and gpd_hip_set_lenet_weights.  With a network installed
+// the mode meets it here: the piece tables are built (or freed), and — the two modes' scratch differs — the general-route
+// scratch of every lane is freed, as an install frees it.
+int gpd_hip_set_lenet_net_mode(gpd_hip_ctx *ctx, int mode) {
+  if (int rc = refuse("gpd_hip_set_lenet_net_mode", ctx, mode == GPD_LENET_NET_CHAIN || mode == GPD_LENET_NET_SPLIT)) return rc;
+  LeNetNet &net = ctx->lenet.net;
+  if (net.active && net.mode != mode) {
+    HIP_RET(hipSetDevice(ctx->device));
+    for (auto &L : ctx->lane)
+      if (L.stream) HIP_RET(hipStreamSynchronize(L.stream));  // no kernel still reads the tables or the scratch
+    for (auto &L : ctx->lane) lenet_net_scratch_free(L.lenet_scratch.net);
+    if (int rc = lenet_net_apply_mode(net, mode)) return rc;  // (a failure leaves the mode and the network as they were, without piece tables)
+  }
+  ctx->lenet.net_mode = mode;
   return GPD_OK;
 }
 
@@ -568,6 +633,7 @@ int gpd_hip_lenet_net_debug(gpd_hip_ctx *ctx, int which, int n, float *out) {
   }
   HIP_RET(hipSetDevice(ctx->device));
   HIP_RET(hipStreamSynchronize(L.stream));
+  if (net.mode == GPD_LENET_NET_SPLIT && (which <= 1 || (which == 2 && sh.fc2_out > 0))) return lenet_net_split_debug(net, t, which, n, out);
   if (which == 0) {
     HIP_RET(hipMemcpy(out, t.pool1, (size_t)n * sh.conv1_out * 784 * sizeof(float), hipMemcpyDeviceToHost));
   } else if (which == 1) {  // the device keeps pool2 pixel-major (fc1's k order)

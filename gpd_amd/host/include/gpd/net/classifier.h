@@ -51,6 +51,9 @@ class HipClassifier : public Classifier {
   // pipes (default: within 1e-4 of EigenClassifier's plain-float result, closer to float64 than it), 1 = the f32 chain
   // in the reference's own operation order.  GraspDetector sets it from the cfg key `hip_lenet_mode`.
   bool setScoringMode(int mode);
+  // Arithmetic of the shape-general route (gpd_hip_set_lenet_net_mode): 0 = the f32 chains (default), 1 = split operands on
+  // the bf16 matrix pipe.  GraspDetector sets it from the cfg key `hip_lenet_net_mode`.
+  bool setNetMode(int mode);
   // raw float32 parameter file -> vector (EigenClassifier::readBinaryFileIntoVector, :185-204)
   static std::vector<float> readBinaryFileIntoVector(const std::string &location);
   // The parameters as read from the files (conv1 w, b, conv2 w, b, ip1 w, b, ip2 w, b): GraspDetector loads the

@@ -700,6 +700,15 @@ bool HipClassifier::setScoringMode(int mode) {
   return true;
 }
 
+bool HipClassifier::setNetMode(int mode) {
+  if (!ok()) return false;
+  if (gpd_hip_set_lenet_net_mode(ctx_, mode) != GPD_OK) {
+    printf("ERROR: %s\n", gpd_hip_last_error());
+    return false;
+  }
+  return true;
+}
+
 std::vector<float> HipClassifier::classifyImages(const std::vector<std::unique_ptr<Image>> &image_list) {
   std::vector<float> out(image_list.size(), 0.f);
   if (!ok()) return out;
@@ -873,6 +882,21 @@ GraspDetector::GraspDetector(const std::string &config_filename) {
     } else {
       printf("ERROR: %s\n", gpd_hip_last_error());
       classifier_.reset();
+    }
+    // hip_lenet_net_mode (not a reference key): the arithmetic of the shape-general route (gpd_hip_set_lenet_net_mode), 0 = the
+    // f32 chains (default), 1 = split operands on the bf16 matrix pipe; context state, so it is legal whichever route the
+    // directory's network takes, and both the fused path's context and the plugin's own take it
+    const int net_mode = config_file.getValueOfKey<int>("hip_lenet_net_mode", 0);
+    if (fused_classifier_ && net_mode != 0) {
+      bool set = gpd_hip_set_lenet_net_mode(ctx_, net_mode) == GPD_OK;
+      if (!set) printf("ERROR: hip_lenet_net_mode = %d: %s\n", net_mode, gpd_hip_last_error());
+      set = set && hc->setNetMode(net_mode);
+      if (!set) {
+        has_classifier_ = fused_classifier_ = false;
+        classifier_.reset();
+      } else {
+        printf("hip_lenet_net_mode: %d\n", net_mode);
+      }
     }
     plugin_route_ = config_file.getValueOfKey<int>("classifier_plugin_route", 0) != 0;
   }

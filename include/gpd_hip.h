@@ -195,21 +195,57 @@ int gpd_hip_lenet_net_from_torch(const gpd_lenet_shape *shape, double input_scal
  * the context — gpd_hip_score, gpd_hip_detect*, gpd_hip_detect_batch[_multi], gpd_hip_detect_sharded (each context its own),
  * gpd_hip_detect_sis, gpd_hip_score_given, gpd_hip_replay — takes the general route, until gpd_hip_set_lenet_weights
  * returns the context to the stock one.  gpd_hip_set_lenet_conv_relu is honoured as on the stock route;
- * gpd_hip_set_lenet_mode is accepted and IGNORED: this route is always the exact f32 chain.  shape->channels must equal the
+ * gpd_hip_set_lenet_mode is accepted and IGNORED: this route computes the chain by default; gpd_hip_set_lenet_net_mode
+ * (below) chooses its other arithmetic.  shape->channels must equal the
  * context's image_num_channels; every weight and bias must be finite (subnormal ones are kept and computed with: the
  * route does not flush); the LDS the shape needs is checked here, not at launch (GPD_ERR_INVALID each).
  * Order: install, THEN gpd_hip_reserve.  The route's scratch depends on the shape, so an install frees the scratch of every
  * lane; a reservation made before it is void for the scoring buffers, which then grow (booked) in the first pass of each lane. */
 int gpd_hip_set_lenet_net(gpd_hip_ctx *ctx, const gpd_lenet_shape *shape, const float *const tensors[10]);
 
+/* The arithmetic of the general route, per context:
+ *  GPD_LENET_NET_CHAIN  (default) the f32 chains above, bit for bit the CPU checker's.
+ *  GPD_LENET_NET_SPLIT  v_mfma_f32_16x16x32_bf16 (16 times the matrix rate of the f32-input instruction) on exactly split
+ *                       operands, f32 accumulation:
+ *    pieces   a = h + m + l with h = bf16(a), m = bf16(a - h), l = bf16(a - h - m), round to nearest even, the residuals
+ *             exact in f32 (gpd_hip_bf16_split3 is the definition); the sum is exact for an f32 whose pieces stay normal.
+ *    conv1    the u8 inputs are ONE exact piece (255 has 8 significant bits), the weights (input scale folded in) three:
+ *             three exact products per term, nothing dropped.
+ *    conv2, fc1, fc2   both operands three pieces; the six products h*h, h*m, m*h, h*l, l*h, m*m accumulate in f32; m*l, l*m
+ *             and l*l are dropped (below 2^-24 of the term).  Then, as in the chain: the max over the 2x2 window on the
+ *             accumulators, + bias, the optional ReLU.
+ *    last     the two logits stay the chain's two fmaf chains: given the last hidden tensor they are the chain bit for bit.
+ *    order    no split-K, no atomics; which k a step of 32 holds and the order of the products inside it are fixed by the
+ *             shape alone (convolutions: chunks of 8 input channels, inside a chunk k = tap * 8 + channel; fc1: k = pixel *
+ *             round_up(conv2_out, 8) + channel; fc2: the hidden index).  A score depends neither on the batch an image is in
+ *             nor on its position nor on the chunk, and two runs give the same bits.
+ *    domain   bf16 has f32's exponent range (scalings such as 2^+-100 are fine).  The accuracy statement covers operands that
+ *             are zero or at least 2^-100 in magnitude: below 2^-110 the lower pieces fall into bf16's subnormal range, where
+ *             the matrix pipe's behaviour is unmeasured.  Smaller operands are computed with unspecified accuracy and are NOT
+ *             refused (activations cannot be policed).
+ *  Context state like gpd_hip_set_lenet_conv_relu: legal before or after gpd_hip_set_lenet_net; neither an install nor
+ *  gpd_hip_set_lenet_weights resets it.  The weight piece tables are built when network and mode meet, whichever call comes
+ *  second (the LDS of the split kernels is checked there too), and freed with the network.  The two modes' scratch differs, so
+ *  a mode change with a network installed frees the general-route scratch of every lane, as an install does: install, set the
+ *  mode, THEN gpd_hip_reserve.  gpd_hip_reserve and gpd_hip_lenet_net_info price the mode in force; the mode never falls back.
+ *  Any other value, or a null context: GPD_ERR_INVALID, "gpd_hip_set_lenet_net_mode: bad argument". */
+#define GPD_LENET_NET_CHAIN 0
+#define GPD_LENET_NET_SPLIT 1
+int gpd_hip_set_lenet_net_mode(gpd_hip_ctx *ctx, int mode);
+
+/* The three bf16 pieces (bit patterns) of n floats, as the split kernels and their weight tables make them.  Host only, no
+ * context.  GPD_ERR_INVALID: n < 0, or a null pointer with n > 0. */
+int gpd_hip_bf16_split3(const float *x, long long n, uint16_t *h, uint16_t *m, uint16_t *l);
+
 /* Activations of the last scoring call that took the general route (lane 0; n images, at most the first chunk), plain
  * row-major f32: which = 0: pool1 [n][F1][28][28], 1: pool2 [n][F2][12][12], 2: fc1 [n][H1], 3: fc2 [n][H2] (H2 > 0 only),
- * 4: logits [n][2] — pool tensors after the ReLU when it is on.  GPD_ERR_INVALID when the last scoring call did not take
+ * 4: logits [n][2] — pool tensors after the ReLU when it is on.  In GPD_LENET_NET_SPLIT a tensor the device holds as bf16
+ * pieces is returned as the exact sum of its pieces.  GPD_ERR_INVALID when the last scoring call did not take
  * the general route (how a caller learns which route ran). */
 int gpd_hip_lenet_net_debug(gpd_hip_ctx *ctx, int which, int n, float *out);
 
 /* info[0] images per chunk, [1] scratch bytes per image, [2] the largest static + dynamic LDS of the route's kernels
- * (bytes), [3] multiply-adds per image.  GPD_ERR_STATE without an installed network. */
+ * (bytes) — each of the mode in force — [3] multiply-adds per image (the algorithmic count, either mode).  GPD_ERR_STATE without an installed network. */
 int gpd_hip_lenet_net_info(gpd_hip_ctx *ctx, long long info[4]);
 
 /* Replaces Classifier::classifyImages (net/classifier.h:70-71,
