@@ -52,6 +52,8 @@ class DetectJob(C.Structure):
         ("samples_out", C.c_void_p),
         ("refine_passes", C.c_int32), ("refine_num_nan", C.c_int32), ("plane_num_above", C.c_int32), ("plane_iterations", C.c_int32),
         ("preprocess_ms", C.c_float * 4),
+        ("outlier_mean_k", C.c_int32), ("num_outliers", C.c_int32), ("outlier_stddev_mult", C.c_double), ("outlier_ms", C.c_float),
+        ("reserved2_", C.c_int32),
     ]
 
 
@@ -346,6 +348,7 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_detect_select", "gpd_hip_detect_batch", "gpd_hip_detect_batch_multi", "gpd_hip_conv1_stats", "gpd_hip_last_fallbacks", "gpd_hip_preprocess_cloud", "gpd_hip_find_clusters", "gpd_hip_reserve", "gpd_hip_bind_host_thread",
            "gpd_hip_set_lenet_mode", "gpd_hip_lenet_debug", "gpd_hip_lenet_fast_tables", "gpd_hip_detect_sharded",
            "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals", "gpd_hip_sample_positions",
+           "gpd_hip_remove_statistical_outliers",
            "gpd_hip_set_lenet_conv_relu", "gpd_hip_lenet_from_torch",
            "gpd_hip_lenet_shape_check", "gpd_hip_lenet_net_from_torch", "gpd_hip_set_lenet_net", "gpd_hip_lenet_net_debug",
            "gpd_hip_lenet_net_info", "gpd_hip_set_lenet_net_mode", "gpd_hip_bf16_split3",
@@ -412,6 +415,8 @@ def lib():
                                                  C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.gpd_hip_refine_normals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
                                              C.POINTER(C.c_int), C.c_void_p]
+        L.gpd_hip_remove_statistical_outliers.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
+                                                          C.c_void_p, C.c_void_p]
         L.gpd_hip_sample_positions.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
         L.gpd_hip_find_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_int)]
@@ -826,12 +831,14 @@ class Context:
         return jobs, keep
 
     def raw_batch(self, scans, samples_xyz, workspace=None, voxel_size=0.003, normals_radius=0.03, num_selected=0,
-                  refine_normals_k=0, sample_above_plane=False, num_draws=0, sample_seed=0):
+                  refine_normals_k=0, sample_above_plane=False, num_draws=0, sample_seed=0, outlier_mean_k=0, outlier_stddev_mult=1.0):
         """The job array of gpd_hip_detect_batch for RAW scans (dicts with xyz, cam_source, view_points): preprocessPointCloud
         (workspace cut, voxeliser, normals, refineNormals when refine_normals_k > 0) on the device, search at the given sample
         coordinates (one f64 [S, 3] array per scan).  samples_xyz[i] is None: the index route — sampleAbovePlane when asked for,
         then Cloud::subsample(num_draws) on the stream seeded with sample_seed; the sample indices searched arrive in keep[i][7].
-        refine_normals_k, sample_above_plane, num_draws and sample_seed take one value for all scans or a sequence with one per scan."""
+        outlier_mean_k > 0: removeStatisticalOutliers(outlier_mean_k, outlier_stddev_mult) after the voxeliser, before the normals.
+        refine_normals_k, sample_above_plane, num_draws, sample_seed, outlier_mean_k and outlier_stddev_mult take one value for all
+        scans or a sequence with one per scan."""
         jobs = (DetectJob * len(scans))()
         keep = []
         ws = None if workspace is None else np.ascontiguousarray(workspace, np.float64)
@@ -861,6 +868,7 @@ class Context:
             j.refine_normals_k, j.sample_above_plane = int(per_scan(refine_normals_k, i)), int(bool(per_scan(sample_above_plane, i)))
             j.num_draws, j.sample_seed = draws, int(per_scan(sample_seed, i)) & 0xFFFFFFFF
             j.samples_out = _ptr(drawn)
+            j.outlier_mean_k, j.outlier_stddev_mult = int(per_scan(outlier_mean_k, i)), float(per_scan(outlier_stddev_mult, i))
         return jobs, keep
 
     def batch(self, clouds, samples, num_selected=0):
@@ -1039,6 +1047,23 @@ class Context:
                                                  _ptr(ddots), C.byref(nan), _ptr(ms)))
         self.last_refine_ms = tuple(float(v) for v in ms)
         return out, int(its.value), ddots[: its.value].copy(), int(nan.value)
+
+    def remove_statistical_outliers(self, mean_k=50, stddev_mult=1.0):
+        """Cloud::removeStatisticalOutliers on the uploaded cloud (pcl::StatisticalOutlierRemoval, DESIGN §7): the kept points
+        replace the cloud on the device, their normals and camera rows with them, so an estimate_normals / detect that follows
+        runs on the kept cloud -> (kept input indices i32 ascending, stats f64 [3]: mean, stddev, threshold, mean neighbour
+        distance of every input point f32 [N]).  self.last_outlier_ms: distance kernel, compaction, the whole call (ms)."""
+        P = getattr(self, "_num_points", 0)  # (no upload yet: the call refuses)
+        kept = np.zeros(max(P, 1), np.int32)
+        stats = np.zeros(3, np.float64)
+        dist = np.zeros(max(P, 1), np.float32)
+        ms = np.zeros(3, np.float32)
+        n = C.c_int(0)
+        self._check(lib().gpd_hip_remove_statistical_outliers(self._h, int(mean_k), float(stddev_mult), _ptr(kept), C.byref(n), _ptr(stats),
+                                                              _ptr(dist), _ptr(ms)))
+        self.last_outlier_ms = tuple(float(v) for v in ms)
+        self._num_points = int(n.value)
+        return kept[: n.value].copy(), stats, dist[:P].copy()
 
 
 def torch_state_shapes(channels):

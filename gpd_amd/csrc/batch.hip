@@ -14,6 +14,7 @@
 #include <sched.h>
 
 #include "context.h"
+#include "outlier_model.h"
 #include "sample_model.h"
 
 using namespace gpd;
@@ -73,6 +74,7 @@ struct BatchRun {
   int presize() {
     int maxP = 0, maxC = 0, maxS = 0, maxSel = 0, maxDraws = 0;
     int planeP = 0, refineP = 0, refineK = 0;  // raw jobs that carry on past the normals: their largest cloud (before the cut) and k
+    int outlierP = 0;                          // raw jobs that remove outliers ahead of the normals
     bool all_selected = n > 0;
     for (int i = 0; i < n; i++) {
       maxP = std::max(maxP, jobs[i].num_points);
@@ -88,6 +90,7 @@ struct BatchRun {
         refineP = std::max(refineP, jobs[i].num_points);
         refineK = std::max(refineK, jobs[i].refine_normals_k);
       }
+      if (jobs[i].raw && jobs[i].outlier_mean_k > 0) outlierP = std::max(outlierP, jobs[i].num_points);
       maxSel = std::max(maxSel, jobs[i].num_selected);
       all_selected = all_selected && jobs[i].num_selected > 0;
     }
@@ -126,6 +129,7 @@ struct BatchRun {
       // the lane's fit / refinement states for the raw scans as they come in (the voxeliser only makes them smaller)
       if (!rc && planeP > 0) rc = plane_reserve(L.plane, planeP);
       if (!rc && refineP > 0) rc = refine_reserve(L.refine, refineP, std::min(refineK, refineP));
+      if (!rc && outlierP > 0) rc = outlier_reserve(L.outliers, outlierP, maxC);
       if (rc == GPD_ERR_HIP) {
         (void)hipGetLastError();  // out of memory: clear it, the jobs size their buffers themselves
         break;
@@ -174,6 +178,8 @@ struct BatchRun {
     j.num_samples_processed = 0;
     j.refine_passes = j.refine_num_nan = j.plane_num_above = j.plane_iterations = 0;
     for (float &t : j.preprocess_ms) t = 0.f;
+    j.num_outliers = 0;
+    j.outlier_ms = 0.f;
     const double t_begin = now_ms();
     int rc = check_samples("gpd_hip_detect_batch", nullptr, j.sample_xyz, j.num_samples, j.num_points);
     if (!rc && (j.refine_normals_k < 0 || j.num_draws < 0 || (j.num_draws != 0 && j.sample_xyz))) {
@@ -186,6 +192,14 @@ struct BatchRun {
     if (!rc && j.refine_normals_k > kRefineKCap) {
       set_error("gpd_hip_detect_batch: cloud %d: refine_normals_k = %d, the capacity is %d", i, j.refine_normals_k, kRefineKCap);
       rc = GPD_ERR_CAPACITY;
+    }
+    if (!rc && j.outlier_mean_k != 0) {
+      const int why = outlier::refusal(j.outlier_mean_k + 1, j.outlier_mean_k, j.outlier_stddev_mult);  // (the cloud's size: once it is voxelised)
+      if (why) {
+        set_error("gpd_hip_detect_batch: cloud %d: outlier_mean_k = %d, outlier_stddev_mult = %g: %s", i, j.outlier_mean_k, j.outlier_stddev_mult,
+                  why == 2 ? "the capacity is 255" : "mean_k must be positive and the multiplier finite");
+        rc = why == 2 ? GPD_ERR_CAPACITY : GPD_ERR_INVALID;
+      }
     }
     if (!rc && j.workspace) {
       // strict double comparisons on both sides, sample by sample, order kept (cloud.cpp:229-233): a sample outside the cut would
@@ -222,6 +236,22 @@ struct BatchRun {
     }
     if (!rc) rc = cloud_from_device(L.cloud, L.pre.d_out_xyz, L.pre.d_out_cam, L.pre.M, j.num_cams, j.view_points, L.stream);
     j.preprocess_ms[0] += (float)(now_ms() - t0);
+    // removeStatisticalOutliers, where the cloud has a grid and nothing has read it yet: the kept points replace the lane's cloud
+    if (!rc && j.outlier_mean_k > 0) {
+      t0 = now_ms();
+      if (L.cloud.num_points < j.outlier_mean_k + 1) {
+        set_error("gpd_hip_detect_batch: cloud %d: outlier_mean_k = %d needs %d points, %d are left after the voxeliser", i, j.outlier_mean_k,
+                  j.outlier_mean_k + 1, L.cloud.num_points);
+        rc = GPD_ERR_INVALID;
+      } else {
+        int kept = 0;
+        double stats[3];
+        rc = outlier_run(L.outliers, L.cloud, j.outlier_mean_k, j.outlier_stddev_mult, /*carry_normals=*/false, nullptr, &kept, stats, nullptr,
+                         nullptr, L.stream);
+        if (!rc) j.num_outliers = L.pre.M - kept;
+      }
+      j.outlier_ms = (float)(now_ms() - t0);
+    }
     t0 = now_ms();
     if (!rc) rc = normals_run(L.cloud, j.normals_radius, nullptr, L.stream);
     j.preprocess_ms[1] = (float)(now_ms() - t0);
@@ -243,7 +273,7 @@ struct BatchRun {
       j.allocs += allocs_now() - allocs0;
       return fail(i, rc);
     }
-    j.num_points_processed = L.pre.M;
+    j.num_points_processed = L.cloud.num_points;
     J[i].sample_idx = nullptr;
     j.num_samples_processed = J[i].S;
     fill_job(J[i], j);
@@ -268,7 +298,7 @@ struct BatchRun {
     gpd_detect_job &j = jobs[i];
     Lane &L = lane(i);
     int rc = GPD_OK;
-    const int M = L.pre.M;
+    const int M = L.cloud.num_points;  // (the voxelised cloud, less the outliers when they were removed)
     int above = 0;
     if (j.sample_above_plane) {
       const double t0 = now_ms();

@@ -52,6 +52,7 @@ struct Lane {
   // lane's stream while this lane's search still gathers from plane.d_idx
   PlaneState plane;
   RefineState refine;
+  OutlierState outliers;
   int32_t *d_pos = nullptr;  // [draw_cap] the draw positions of Cloud::subsample (sample_model.h), computed on the host
   int32_t *h_pos = nullptr;  // pinned: [draw_cap] their way up, then [2][draw_cap] the sample indices searched on their way
   int draw_cap = 0;          //   down (samples_out), one half per job of the lane in flight
@@ -90,6 +91,7 @@ struct gpd_hip_ctx {
   gpd::ClusterState cluster;
   gpd::PlaneState plane;  // gpd_hip_sample_above_plane
   gpd::RefineState refine;  // gpd_hip_refine_normals
+  gpd::OutlierState outliers;  // gpd_hip_remove_statistical_outliers
   gpd::LabelState label;    // gpd_hip_upload_ground_truth / gpd_hip_label_view: the ground-truth slot and a view's accumulator
   gpd::SisState sis;        // gpd_hip_detect_sis: the draw's buffers and the accumulators of the rounds
   std::vector<hipEvent_t> replay_events;  // 6 per gpd_hip_replay call: start, images done, conv1, conv2, fc1, end

@@ -15,6 +15,7 @@
 #include "context.h"
 #include "buffers.h"
 #include "balance_model.h"
+#include "outlier_model.h"
 #include "sample_model.h"
 #include "sis_model.h"
 
@@ -77,6 +78,7 @@ static void lane_free(Lane &L) {
   images_free(L.images);
   plane_free(L.plane);
   refine_free(L.refine);
+  outlier_free(L.outliers);
   pinned_release(L.h_pos);
   device_release(L.d_scores, L.d_out, L.d_sel, L.d_all, L.d_img_in, L.d_img_planar, L.d_pos);
   pinned_release(L.h_out, L.h_flags);
@@ -388,6 +390,7 @@ void gpd_hip_destroy(gpd_hip_ctx *ctx) {
   cluster_free(ctx->cluster);
   plane_free(ctx->plane);
   refine_free(ctx->refine);
+  outlier_free(ctx->outliers);
   label_free(ctx->label);
   sis_free(ctx->sis);
   for (auto &e : ctx->pre.ev)
@@ -431,7 +434,7 @@ int gpd_hip_reserve(gpd_hip_ctx *ctx, int max_points, int max_cams, int max_samp
     if (!rc && max_selected > 0) rc = lane_reserve(ctx, L, max_points, max_cams, max_samples, cand, max_selected);
     if (rc) return rc;
   }
-  return GPD_OK;
+  return outlier_reserve(ctx->outliers, max_points, max_cams);  // gpd_hip_remove_statistical_outliers on clouds within these sizes
 }
 
 int gpd_hip_set_lenet_weights(gpd_hip_ctx *ctx, int channels, const float *conv1_w, const float *conv1_b, const float *conv2_w,
@@ -838,6 +841,28 @@ int gpd_hip_refine_normals(gpd_hip_ctx *ctx, int k, int max_iterations, float co
   HIP_RET(hipSetDevice(ctx->device));
   return refine_run(ctx->refine, L.cloud, k, max_iterations, convergence_threshold, normals_out, iterations_out, ddot_out, num_nan_out, kernel_ms,
                     L.stream);
+}
+
+int gpd_hip_remove_statistical_outliers(gpd_hip_ctx *ctx, int mean_k, double stddev_mult, int32_t *kept_out, int *num_kept, double stats[3],
+                                        float *dist_out, float kernel_ms[3]) {
+  if (int rc = refuse("gpd_hip_remove_statistical_outliers", ctx, kept_out && num_kept && stats && mean_k >= 1 && std::isfinite(stddev_mult)))
+    return rc;
+  if (mean_k > outlier::kMeanKCap) {
+    set_error("gpd_hip_remove_statistical_outliers: mean_k = %d, the capacity is %d", mean_k, outlier::kMeanKCap);
+    return GPD_ERR_CAPACITY;
+  }
+  Lane &L = ctx->lane[0];
+  if (!L.cloud.num_points) {
+    set_error("gpd_hip_remove_statistical_outliers: bad argument: no cloud uploaded");
+    return GPD_ERR_INVALID;
+  }
+  if (L.cloud.num_points < mean_k + 1) {
+    set_error("gpd_hip_remove_statistical_outliers: bad argument: mean_k = %d needs %d points, the cloud has %d", mean_k, mean_k + 1,
+              L.cloud.num_points);
+    return GPD_ERR_INVALID;
+  }
+  HIP_RET(hipSetDevice(ctx->device));
+  return outlier_run(ctx->outliers, L.cloud, mean_k, stddev_mult, /*carry_normals=*/true, kept_out, num_kept, stats, dist_out, kernel_ms, L.stream);
 }
 
 // samples by index (sample_xyz == nullptr) or by coordinates (sample_indices == nullptr)

@@ -160,7 +160,7 @@ void ctx_device_stream(gpd_hip_ctx *ctx, int *device, hipStream_t *stream);
 // reports the count per cloud (gpd_detect_job::allocs) so that a pass that was supposed to run on pre-sized lanes can be
 // seen to have done so.  The rule of a growth has one text, buffers.h; its helpers book on the `who` they are handed, and
 // a group site books once itself.  BOOKED: everything a lane, a cloud, a search, a plan, the image and LeNet buffers, the
-// normals, plane, refine, label and SIS states grow by size.  NOT booked (as found; the helpers take a null `who`, these
+// normals, plane, refine, outlier, label and SIS states grow by size.  NOT booked (as found; the helpers take a null `who`, these
 // sites use the typed allocate / release alone): gpd_hip_score's staging pair (d_img_in, d_img_planar), the HWC copy of a
 // download (d_images_hwc), plan_build's given-set tables, cluster_reserve, the LeNet weight tables, everything of a
 // trainer and a trainer group (their pools included), the replay pipe's second buffer, and the fixed-size words a state
@@ -693,5 +693,28 @@ int refine_reserve(RefineState &s, int n, int k);  // the buffers for clouds of 
 // non-finite ones are counted on the device; only the per-pass dots of the stop rule and that count cross PCIe
 int refine_run(RefineState &s, Cloud &c, int k, int max_iterations, float threshold, float *normals_out, int *iterations_out, float *ddot_out,
                int *num_nan_out, float *kernel_ms, hipStream_t stream);
+
+// ---- Cloud::removeStatisticalOutliers on the device (outliers.hip; the definition: outlier_model.h) ----------
+struct OutlierState {
+  int cap_points = 0, cap_cams = 0;
+  float *d_dist = nullptr;           // [P] the mean neighbour distance of every point, by original index
+  float *h_dist = nullptr;           // pinned: its way down for the two sequential sums of the threshold
+  int32_t *d_block_count = nullptr, *d_block_off = nullptr;  // the compaction's per-workgroup counts and their scan
+  int32_t *d_kept = nullptr;         // [P] the kept input indices, ascending
+  float *d_xyz = nullptr, *d_nrm = nullptr;  // [P][3] the kept points and their normals
+  int32_t *d_cam = nullptr;          // [cams][kept] their camera-source rows
+  int32_t *d_total = nullptr;        // the number of kept points ...
+  int32_t *h_total = nullptr;        // ... and its pinned host side
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // distance kernel start / end, compaction start / end
+};
+void outlier_free(OutlierState &s);
+int outlier_reserve(OutlierState &s, int n, int num_cams);  // the buffers for clouds of up to n points / num_cams cameras
+// On the uploaded cloud c, inside the domain of outlier::refusal (the caller has checked it): the kept points, with their
+// normals (carry_normals; zeros otherwise) and camera-source rows, become c — grid rebuilt, generation bumped.
+// kept_out (may be null, else room for the old num_points): the kept input indices, ascending; *num_kept their number;
+// stats: mean, stddev, threshold; dist_out (may be null): the old num_points mean distances; kernel_ms (may be null):
+// distance kernel, compaction, the whole call.  GPD_ERR_INVALID and c untouched when no point would be kept.
+int outlier_run(OutlierState &s, Cloud &c, int mean_k, double mult, bool carry_normals, int32_t *kept_out, int *num_kept, double stats[3],
+                float *dist_out, float *kernel_ms, hipStream_t stream);
 
 }  // namespace gpd

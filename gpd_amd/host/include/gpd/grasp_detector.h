@@ -68,6 +68,13 @@ class GraspDetector {
   // refine_normals_k = k: preprocessPointCloud with num_samples = 0, this, then cloud.subsample(num_samples).  False when
   // the device call fails or the cloud has no normals.
   bool refineNormals(util::Cloud &cloud, int k, int max_iterations = 15, float convergence_threshold = 1e-5f);
+  // Cloud::removeStatisticalOutliers (cloud.cpp:166-174) on the device (gpd_hip_remove_statistical_outliers, after uploading
+  // the cloud): the cloud becomes the kept points with their normals, camera columns and remapped sample indices, as
+  // util::Cloud::removeStatisticalOutliers leaves it, and the context holds the same kept cloud.  The reference reads cfg
+  // remove_outliers and never calls the method; here the method is the API (the cfg key stays refused): call it after
+  // preprocessPointCloud with num_samples = 0, then cloud.subsample(num_samples).  False when the device call failed or
+  // the arguments are outside the domain; the cloud is untouched then.
+  bool removeStatisticalOutliers(util::Cloud &cloud, int mean_k = 50, double stddev_mult = 1.0);
   std::vector<std::unique_ptr<candidate::HandSet>> generateGraspCandidates(const util::Cloud &cloud);
   std::vector<std::unique_ptr<candidate::HandSet>> filterGraspsWorkspace(
       std::vector<std::unique_ptr<candidate::HandSet>> &hand_set_list, const std::vector<double> &workspace) const;

@@ -76,6 +76,23 @@ class Cloud {
   NormalRefinement refineNormals(int k, int max_iterations = 15, float convergence_threshold = 1e-5f);
   // what refineNormals does with refined normals: the reference's messages, then the normals replaced
   void applyRefinedNormals(const std::vector<float> &refined);
+  // Cloud::removeStatisticalOutliers (cloud.cpp:166-174): pcl::StatisticalOutlierRemoval with setMeanK(mean_k) and
+  // setStddevMulThresh(stddev_mult) — the definition is DESIGN §7.  Unlike the reference's sor.filter(*cloud_processed_),
+  // which leaves camera_source_, normals_ and the sample indices misaligned, the camera-source columns and the normals
+  // follow their points, and the sample indices are remapped to the kept cloud (those of removed points are dropped, the
+  // order stays).  This is the single-core host model; GraspDetector::removeStatisticalOutliers runs the same filter on
+  // the device.  Outside the domain (mean_k < 1 or > 255, a non-finite multiplier, fewer than mean_k + 1 points) the cloud
+  // is left as it is and `ok` is false.
+  struct OutlierRemoval {
+    bool ok = false;
+    std::vector<int> kept;                  // the kept input indices, ascending
+    double mean = 0, stddev = 0, threshold = 0;
+    std::vector<float> dist;                // the mean neighbour distance of every input point
+  };
+  OutlierRemoval removeStatisticalOutliers(int mean_k = 50, double stddev_mult = 1.0);
+  // what removeStatisticalOutliers does with the kept indices (ascending): points, normals, camera columns gathered, the
+  // sample indices remapped, then the reference's message
+  void applyOutlierRemoval(const std::vector<int> &kept);
 
  private:
   std::vector<float> xyz_, normals_;

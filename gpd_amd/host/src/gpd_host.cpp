@@ -20,6 +20,7 @@
 #include "gpd/util/config_file.h"
 #include "../../csrc/plane_model.h"
 #include "../../csrc/refine_model.h"
+#include "../../csrc/outlier_model.h"
 #include "../../csrc/sample_model.h"
 
 namespace gpd {
@@ -471,6 +472,42 @@ void Cloud::applyRefinedNormals(const std::vector<float> &refined) {
   normals_ = refined;
 }
 
+Cloud::OutlierRemoval Cloud::removeStatisticalOutliers(int mean_k, double stddev_mult) {
+  OutlierRemoval out;
+  if (outlier::refusal((int)size(), mean_k, stddev_mult)) return out;
+  const outlier::Result r = outlier::filter(xyz_.data(), (int)size(), mean_k, stddev_mult);
+  out.ok = true;
+  out.kept.assign(r.kept.begin(), r.kept.end());
+  out.mean = r.stats.mean;
+  out.stddev = r.stats.stddev;
+  out.threshold = r.stats.threshold;
+  out.dist = r.dist;
+  applyOutlierRemoval(out.kept);
+  return out;
+}
+
+void Cloud::applyOutlierRemoval(const std::vector<int> &kept) {
+  const size_t n = size(), m = kept.size();
+  const int cams = numCameras();
+  const bool with_normals = hasNormals();
+  std::vector<float> xyz(m * 3), normals(with_normals ? m * 3 : 0);
+  std::vector<int> cam((size_t)cams * m), new_index(n, -1);
+  for (size_t k = 0; k < m; k++) {
+    new_index[kept[k]] = (int)k;
+    for (int r = 0; r < 3; r++) {
+      xyz[3 * k + r] = xyz_[3 * (size_t)kept[k] + r];
+      if (with_normals) normals[3 * k + r] = normals_[3 * (size_t)kept[k] + r];
+    }
+    for (int c = 0; c < cams; c++) cam[(size_t)c * m + k] = camera_source_[(size_t)c * n + kept[k]];
+  }
+  std::vector<int> samples;
+  for (int i : sample_indices_)
+    if (i >= 0 && (size_t)i < n && new_index[i] >= 0) samples.push_back(new_index[i]);
+  setProcessed(xyz, cam, normals);
+  sample_indices_ = samples;
+  printf("Cloud after removing statistical outliers: %zu\n", size());
+}
+
 void Cloud::subsample(int num_samples, unsigned seed) {
   if (num_samples <= 0) return;
   std::vector<int32_t> pos;  // the draws: ../../csrc/sample_model.h, shared with libgpd_hip.so
@@ -818,7 +855,9 @@ GraspDetector::GraspDetector(const std::string &config_filename) {
   // GraspDetector::sampleAbovePlane (call it between preprocessPointCloud with num_samples = 0 and subsample).
   const struct {
     const char *key, *what;
-  } unsupported[] = {{"remove_outliers", "pcl::StatisticalOutlierRemoval (cloud.cpp:166-174)"},
+  } unsupported[] = {{"remove_outliers",
+                      "pcl::StatisticalOutlierRemoval (cloud.cpp:166-174; the reference reads the key and never runs the filter — here it is "
+                      "GraspDetector::removeStatisticalOutliers, called between preprocessPointCloud and subsample)"},
                      {"sample_above_plane", "a RANSAC plane fit, pcl::SACSegmentation (cloud.cpp:407-436)"},
                      {"refine_normals_k", "pcl::NormalRefinement (cloud.cpp:176-204)"},
                      {"remove_plane_before_image_calculation",
@@ -1043,6 +1082,24 @@ bool GraspDetector::refineNormals(util::Cloud &cloud, int k, int max_iterations,
   }
   last_num_sets_ = 0;
   cloud.applyRefinedNormals(refined);
+  return true;
+}
+
+bool GraspDetector::removeStatisticalOutliers(util::Cloud &cloud, int mean_k, double stddev_mult) {
+  if (!ctx_ || cloud.size() == 0) return false;
+  const std::vector<float> zeros(cloud.hasNormals() ? 0 : cloud.size() * 3, 0.f);
+  std::vector<int> kept(cloud.size());
+  int num = 0;
+  double stats[3];
+  if (gpd_hip_upload_cloud(ctx_, cloud.getCloudProcessed().data(), cloud.hasNormals() ? cloud.getNormals().data() : zeros.data(),
+                           (int)cloud.size(), cloud.getCameraSource().data(), cloud.numCameras(), cloud.getViewPoints().data()) != GPD_OK ||
+      gpd_hip_remove_statistical_outliers(ctx_, mean_k, stddev_mult, kept.data(), &num, stats, nullptr, nullptr) != GPD_OK) {
+    printf("ERROR: %s\n", gpd_hip_last_error());
+    return false;
+  }
+  last_num_sets_ = 0;
+  kept.resize(num);
+  cloud.applyOutlierRemoval(kept);
   return true;
 }
 
@@ -1821,6 +1878,41 @@ extern "C" int gpd_host_refine_normals(const float *xyz, const float *normals, i
   return r.iterations;
 }
 
+// Flat entry for tests / ctypes: the host model of removeStatisticalOutliers on xyz [n][3]; kept and dist hold n entries,
+// stats 3.  Returns the number of kept points, -1 outside the domain (invalid), -2 beyond the capacity.
+extern "C" int gpd_host_remove_statistical_outliers(const float *xyz, int n, int mean_k, double stddev_mult, int32_t *kept, double *stats,
+                                                    float *dist) {
+  if (const int why = gpd::outlier::refusal(n, mean_k, stddev_mult)) return -why;
+  const gpd::outlier::Result r = gpd::outlier::filter(xyz, n, mean_k, stddev_mult);
+  std::copy(r.kept.begin(), r.kept.end(), kept);
+  std::copy(r.dist.begin(), r.dist.end(), dist);
+  stats[0] = r.stats.mean;
+  stats[1] = r.stats.stddev;
+  stats[2] = r.stats.threshold;
+  return (int)r.kept.size();
+}
+
+// Flat entry for tests / ctypes: util::Cloud::removeStatisticalOutliers on a cloud of `cams` cameras that carries normals
+// (may be null), camera-source rows [cams][n] and sample indices: what the cloud holds afterwards.  xyz_out / normals_out
+// [n][3], cam_out [cams][kept], samples_out [num_samples].  Returns the kept points (-1: refused), *num_samples_out the
+// sample indices left.
+extern "C" int gpd_host_cloud_remove_statistical_outliers(const float *xyz, const float *normals, const int *cam, int n, int cams,
+                                                          const int *samples, int num_samples, int mean_k, double stddev_mult, float *xyz_out,
+                                                          float *normals_out, int *cam_out, int *samples_out, int *num_samples_out) {
+  gpd::util::Cloud cloud(std::vector<float>(xyz, xyz + 3 * (size_t)n),
+                         normals ? std::vector<float>(normals, normals + 3 * (size_t)n) : std::vector<float>(),
+                         std::vector<int>(cam, cam + (size_t)cams * n), std::vector<double>(3 * (size_t)cams, 0.0));
+  cloud.setSampleIndices(std::vector<int>(samples, samples + num_samples));
+  if (!cloud.removeStatisticalOutliers(mean_k, stddev_mult).ok) return -1;
+  fflush(stdout);
+  std::copy(cloud.getCloudProcessed().begin(), cloud.getCloudProcessed().end(), xyz_out);
+  if (normals) std::copy(cloud.getNormals().begin(), cloud.getNormals().end(), normals_out);
+  std::copy(cloud.getCameraSource().begin(), cloud.getCameraSource().end(), cam_out);
+  std::copy(cloud.getSampleIndices().begin(), cloud.getSampleIndices().end(), samples_out);
+  *num_samples_out = (int)cloud.getSampleIndices().size();
+  return (int)cloud.size();
+}
+
 // Flat entry for tests / ctypes: util::Cloud::subsample on a cloud of num_points points that carries the sample indices
 // `list` (num_list of them; 0: none).  out holds max(num_list, num_samples, 0) entries; returns how many sample indices
 // the cloud carries afterwards.
@@ -1865,6 +1957,39 @@ extern "C" int gpd_host_detector_refine_normals(const float *xyz, const float *n
   if (!detector.refineNormals(cloud, k)) return -1;
   std::copy(cloud.getNormals().begin(), cloud.getNormals().end(), normals_out);
   return 0;
+}
+
+// Flat entry for tests / ctypes: GraspDetector::removeStatisticalOutliers on a cloud of one camera at the origin that carries
+// normals and sample indices, through a detector as above.  xyz_out / normals_out [n][3], samples_out [num_samples]; returns
+// the kept points (-1: the device call failed), *num_samples_out the sample indices left.
+extern "C" int gpd_host_detector_remove_statistical_outliers(const float *xyz, const float *normals, int n, const int *samples, int num_samples,
+                                                             int mean_k, double stddev_mult, float *xyz_out, float *normals_out,
+                                                             int *samples_out, int *num_samples_out) {
+  gpd_params p;
+  gpd_hip_default_params(&p);
+  gpd::candidate::HandSearch::Parameters hs;
+  hs.nn_radius_frames_ = p.nn_radius_frames;
+  hs.num_threads_ = 1;
+  hs.num_samples_ = 0;
+  hs.num_orientations_ = p.num_orientations;
+  hs.num_finger_placements_ = p.num_finger_placements;
+  hs.hand_axes_.assign(p.hand_axes, p.hand_axes + p.num_hand_axes);
+  hs.deepen_hand_ = p.deepen_hand != 0;
+  hs.friction_coeff_ = p.friction_coeff;
+  hs.min_viable_ = p.min_viable;
+  hs.hand_geometry_ = {p.finger_width, p.hand_outer_diameter, p.hand_depth, p.hand_height, p.init_bite};
+  const gpd::descriptor::ImageGeometry ig = {p.volume_width, p.volume_depth, p.volume_height, p.image_size, p.image_num_channels};
+  gpd::GraspDetector detector(hs, ig, 0);
+  gpd::util::Cloud cloud(std::vector<float>(xyz, xyz + 3 * (size_t)n), std::vector<float>(normals, normals + 3 * (size_t)n),
+                         std::vector<int>((size_t)n, 1), std::vector<double>(3, 0.0));
+  cloud.setSampleIndices(std::vector<int>(samples, samples + num_samples));
+  if (!detector.removeStatisticalOutliers(cloud, mean_k, stddev_mult)) return -1;
+  fflush(stdout);
+  std::copy(cloud.getCloudProcessed().begin(), cloud.getCloudProcessed().end(), xyz_out);
+  std::copy(cloud.getNormals().begin(), cloud.getNormals().end(), normals_out);
+  std::copy(cloud.getSampleIndices().begin(), cloud.getSampleIndices().end(), samples_out);
+  *num_samples_out = (int)cloud.getSampleIndices().size();
+  return (int)cloud.size();
 }
 
 // Flat entry for tests / ctypes: loads a PCD like util::Cloud does; returns the number of points

@@ -72,6 +72,50 @@ def refine_normals(xyz, normals, k, max_iterations=15, convergence_threshold=1e-
     return out[:n].copy(), int(its), ddots[:its].copy(), int(nan.value)
 
 
+def remove_statistical_outliers(xyz, mean_k=50, stddev_mult=1.0):
+    """util::Cloud::removeStatisticalOutliers' filter on one core (the host model, DESIGN §7) ->
+    (kept input indices i32 ascending, stats f64 [3]: mean, stddev, threshold, mean neighbour distance of every point f32 [n]).
+    ValueError outside the domain (mean_k < 1, a non-finite multiplier, fewer than mean_k + 1 points), OverflowError beyond the
+    capacity (mean_k > 255)."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    n = len(xyz)
+    kept = np.zeros(max(n, 1), np.int32)
+    stats = np.zeros(3, np.float64)
+    dist = np.zeros(max(n, 1), np.float32)
+    L = lib()
+    L.gpd_host_remove_statistical_outliers.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    k = L.gpd_host_remove_statistical_outliers(xyz.ctypes.data_as(C.c_void_p), n, int(mean_k), float(stddev_mult), kept.ctypes.data_as(C.c_void_p),
+                                               stats.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p))
+    if k == -2:
+        raise OverflowError("remove_statistical_outliers: mean_k = %d, the capacity is 255" % mean_k)
+    if k < 0:
+        raise ValueError("remove_statistical_outliers: mean_k = %d, stddev_mult = %r on %d points is outside the domain" % (mean_k, stddev_mult, n))
+    return kept[:k].copy(), stats, dist[:n].copy()
+
+
+def cloud_remove_statistical_outliers(xyz, normals, cam_source, sample_indices, mean_k=50, stddev_mult=1.0):
+    """util::Cloud::removeStatisticalOutliers (the C++ mirror's host method) on a cloud with normals (or None), camera-source rows
+    [cams, n] and sample indices -> (xyz, normals or None, cam_source [cams, kept], sample indices) as the cloud holds them after."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    n = len(xyz)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    cam = np.ascontiguousarray(cam_source, np.int32).reshape(-1, n)
+    si = np.ascontiguousarray(sample_indices, np.int32).reshape(-1)
+    xo, no = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    co, so = np.zeros(cam.size, np.int32), np.zeros(max(len(si), 1), np.int32)
+    ns = C.c_int(0)
+    L = lib()
+    L.gpd_host_cloud_remove_statistical_outliers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                             C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    m = L.gpd_host_cloud_remove_statistical_outliers(xyz.ctypes.data_as(C.c_void_p), None if nrm is None else nrm.ctypes.data_as(C.c_void_p),
+                                                     cam.ctypes.data_as(C.c_void_p), n, cam.shape[0], si.ctypes.data_as(C.c_void_p), len(si),
+                                                     int(mean_k), float(stddev_mult), xo.ctypes.data_as(C.c_void_p), no.ctypes.data_as(C.c_void_p),
+                                                     co.ctypes.data_as(C.c_void_p), so.ctypes.data_as(C.c_void_p), C.byref(ns))
+    if m < 0:
+        raise ValueError("Cloud::removeStatisticalOutliers refused the arguments")
+    return xo[:m].copy(), (None if nrm is None else no[:m].copy()), co[: cam.shape[0] * m].reshape(cam.shape[0], m).copy(), so[: ns.value].copy()
+
+
 def subsample_indices(num_points, num_samples, seed=0, sample_indices=None):
     """util::Cloud::subsample on a cloud of num_points points that carries `sample_indices` (None: none) ->
     the sample indices it carries afterwards, i32."""
@@ -108,6 +152,26 @@ def detector_refine_normals(xyz, normals, k):
     if rc != 0:
         raise RuntimeError("GraspDetector::refineNormals failed")
     return out
+
+
+def detector_remove_statistical_outliers(xyz, normals, sample_indices, mean_k=50, stddev_mult=1.0):
+    """GraspDetector::removeStatisticalOutliers (the device path through the C++ mirror) on a one-camera cloud ->
+    (xyz f32 [m,3], normals f32 [m,3], sample indices i32) as the cloud holds them afterwards."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    si = np.ascontiguousarray(sample_indices, np.int32).reshape(-1)
+    xo, no, so = np.zeros_like(xyz), np.zeros_like(xyz), np.zeros(max(len(si), 1), np.int32)
+    ns = C.c_int(0)
+    L = lib()
+    L.gpd_host_detector_remove_statistical_outliers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    m = L.gpd_host_detector_remove_statistical_outliers(xyz.ctypes.data_as(C.c_void_p), normals.ctypes.data_as(C.c_void_p), len(xyz),
+                                                        si.ctypes.data_as(C.c_void_p), len(si), int(mean_k), float(stddev_mult),
+                                                        xo.ctypes.data_as(C.c_void_p), no.ctypes.data_as(C.c_void_p),
+                                                        so.ctypes.data_as(C.c_void_p), C.byref(ns))
+    if m < 0:
+        raise RuntimeError("GraspDetector::removeStatisticalOutliers failed")
+    return xo[:m].copy(), no[:m].copy(), so[: ns.value].copy()
 
 
 def load_pcd(path, cap=1 << 22):

@@ -325,6 +325,24 @@ int gpd_hip_sample_above_plane(gpd_hip_ctx *ctx, double threshold, int max_itera
 int gpd_hip_refine_normals(gpd_hip_ctx *ctx, int k, int max_iterations, float convergence_threshold, float *normals_out, int *iterations_out,
                            float *ddot_out, int *num_nan_out, float kernel_ms[3]);
 
+/* Replaces Cloud::removeStatisticalOutliers (util/cloud.cpp:166-174, which the reference declares and never calls):
+ * pcl::StatisticalOutlierRemoval with setMeanK(mean_k) and setStddevMulThresh(stddev_mult) — the reference's values are 50
+ * and 1.0; the definition is DESIGN §7.  Every point's mean distance to its mean_k nearest neighbours (FLANN's float d2,
+ * correctly rounded float sqrt, summed in double in rank order), the mean and standard deviation of those over the cloud
+ * (two sequential double sums in index order), and a point is removed iff (double)dist > mean + stddev_mult * stddev; a NaN
+ * threshold (equal distances whose variance rounding made negative) removes nothing.
+ * Acts on the cloud uploaded last and REPLACES it on the device with the kept points in input order: their normals and
+ * camera-source rows follow them (unlike the reference's sor.filter(*cloud_processed_), which leaves both misaligned), the
+ * grid is rebuilt, and a following gpd_hip_estimate_normals / gpd_hip_detect uses the kept cloud without an upload — sample
+ * indices then count in the kept cloud.  kept_out (room for num_points entries): the kept input indices, ascending, *num_kept
+ * of them; stats: mean, stddev, threshold; dist_out (may be NULL, else num_points floats): the mean distances; kernel_ms (may be
+ * NULL): the distance kernel, the compaction, the whole call, in ms.
+ * GPD_ERR_INVALID (the cloud stays as it was): a NULL argument, mean_k < 1, a non-finite stddev_mult, no cloud, fewer than
+ * mean_k + 1 points (PCL reads past the lists its search returned there), or a threshold below every distance (no point would
+ * be left).  Capacity (GPD_ERR_CAPACITY beyond it): mean_k <= 255. */
+int gpd_hip_remove_statistical_outliers(gpd_hip_ctx *ctx, int mean_k, double stddev_mult, int32_t *kept_out, int *num_kept, double stats[3],
+                                        float *dist_out, float kernel_ms[3]);
+
 /* Replaces CandidatesGenerator::generateGraspCandidateSets ->
  * HandSearch::searchHands (candidates_generator.cpp:62-69, hand_search.cpp:24-64)
  * for samples given by index (Cloud::getSampleIndices).  Writes
@@ -597,7 +615,7 @@ int gpd_hip_reserve(gpd_hip_ctx *ctx, int max_points, int max_cams, int max_samp
 
 /* One independent cloud of a batch: the arguments of gpd_hip_upload_cloud + gpd_hip_detect_select.
  * ZERO the struct (memset / `gpd_detect_job j = {0}`) before filling it: fields added in later rounds (lcg_base, raw, voxel_size,
- * workspace, normals_radius, sample_xyz, refine_normals_k, sample_above_plane, num_draws, sample_seed, samples_out) are INPUTS,
+ * workspace, normals_radius, sample_xyz, refine_normals_k, sample_above_plane, num_draws, sample_seed, samples_out, outlier_mean_k, outlier_stddev_mult) are INPUTS,
  * and an uninitialised `raw` or `lcg_base` selects the raw-scan route or offsets the cloud's shadow stream — wrong images, not an
  * error; an uninitialised `num_draws` or `samples_out` of a raw job draws samples nobody asked for or writes through a wild pointer. */
 typedef struct gpd_detect_job {
@@ -678,6 +696,17 @@ typedef struct gpd_detect_job {
   int32_t plane_num_above;   /* out: points off the support plane; 0: the fit failed or was not run */
   int32_t plane_iterations;  /* out: hypotheses RANSAC evaluated */
   float preprocess_ms[4];    /* out: host wall time of this job's cut + voxeliser, normals, refinement, plane fit */
+  /* Cloud::removeStatisticalOutliers for a RAW scan (read only when raw != 0; zero: off, as above): outlier_mean_k (in) > 0 runs
+   * gpd_hip_remove_statistical_outliers(outlier_mean_k, outlier_stddev_mult) AFTER the voxeliser and BEFORE calculateNormals — the
+   * reference gives the method no position (it never calls it); this is the one place where the cloud that the normals, the
+   * search and the images see has a grid.  num_points_processed then counts the kept points, the index route draws from them,
+   * and the kept cloud never leaves the device.  outlier_mean_k < 0, a non-finite outlier_stddev_mult or fewer than
+   * outlier_mean_k + 1 points after the voxeliser: GPD_ERR_INVALID; outlier_mean_k > 255: GPD_ERR_CAPACITY — for this job alone. */
+  int32_t outlier_mean_k;
+  int32_t num_outliers;      /* out: points the step removed (0: not asked for) */
+  double outlier_stddev_mult;
+  float outlier_ms;          /* out: host wall time of the step */
+  int32_t reserved2_;
 } gpd_detect_job;
 
 /* The positions Cloud::subsample draws from a candidate list of n entries on the seeded stream described at
