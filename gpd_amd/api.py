@@ -193,16 +193,32 @@ class ImageModel(C.Structure):
                 ("thr", (C.c_double * 61) * 3)]
 
 
-def image_model(params):
+def image_model(params, shadow_jitter=None):
     """gpd_hip_image_model: what the image stage derives from the geometry in `params` (host only) -> dict: window_class,
-    set_sd, set_sr, num_shadow, stride_a, stride_c, true_div and thr f64 [3, 61]."""
+    set_sd, set_sr, num_shadow, stride_a, stride_c, true_div and thr f64 [3, 61].  With `shadow_jitter` (0 or 1)
+    gpd_hip_image_model_jitter: the windows of that setting of Context.set_shadow_jitter."""
     m = ImageModel()
-    rc = lib().gpd_hip_image_model(C.byref(params), C.byref(m))
+    if shadow_jitter is None:
+        rc = lib().gpd_hip_image_model(C.byref(params), C.byref(m))
+    else:
+        rc = lib().gpd_hip_image_model_jitter(C.byref(params), int(shadow_jitter), C.byref(m))
     if rc != 0:
         raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
     out = {k: int(getattr(m, k)) for k in ("window_class", "set_sd", "set_sr", "num_shadow", "stride_a", "stride_c", "true_div")}
     out["thr"] = np.array(m.thr, np.float64).reshape(3, 61)
     return out
+
+
+def shadow_jitter_model(seed, voxels):
+    """gpd_hip_shadow_jitter_model: the draw g of every voxel in `voxels` (int32 [n, 3]) under `seed` (host only) -> f64 [n]."""
+    v = np.ascontiguousarray(voxels, np.int32)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError("voxels must be [n, 3]")
+    g = np.empty(v.shape[0], np.float64)
+    rc = lib().gpd_hip_shadow_jitter_model(int(seed) & 0xFFFFFFFFFFFFFFFF, v.ctypes.data, v.shape[0], g.ctypes.data)
+    if rc != 0:
+        raise GpdHipError("libgpd_hip error %d: %s" % (rc, lib().gpd_hip_last_error().decode()))
+    return g
 
 
 TORCH_KEYS = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
@@ -354,7 +370,8 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_lenet_net_info", "gpd_hip_set_lenet_net_mode", "gpd_hip_bf16_split3",
            "gpd_hip_upload_ground_truth", "gpd_hip_label_view", "gpd_hip_balance_view", "gpd_hip_sizeof_label_view_job",
            "gpd_hip_shuffle_orders", "gpd_hip_sis_proposals", "gpd_hip_sis_select", "gpd_hip_detect_sis", "gpd_hip_sizeof_sis_job",
-           "gpd_hip_image_model", "gpd_hip_given_check", "gpd_hip_images_given", "gpd_hip_score_given",
+           "gpd_hip_image_model", "gpd_hip_image_model_jitter", "gpd_hip_set_shadow_jitter", "gpd_hip_shadow_jitter_model",
+           "gpd_hip_given_check", "gpd_hip_images_given", "gpd_hip_score_given",
            "gpd_hip_train_default_params", "gpd_hip_train_create", "gpd_hip_train_destroy", "gpd_hip_train_init_state",
            "gpd_hip_train_set_state", "gpd_hip_train_get_state", "gpd_hip_train_set_data", "gpd_hip_train_steps",
            "gpd_hip_train_gradients", "gpd_hip_train_apply", "gpd_hip_train_eval", "gpd_hip_train_step_timed",
@@ -448,6 +465,9 @@ def lib():
                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.gpd_hip_detect_sis.argtypes = [C.c_void_p, C.POINTER(SisJob)]
         L.gpd_hip_image_model.argtypes = [C.POINTER(Params), C.POINTER(ImageModel)]
+        L.gpd_hip_image_model_jitter.argtypes = [C.POINTER(Params), C.c_int, C.POINTER(ImageModel)]
+        L.gpd_hip_set_shadow_jitter.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
+        L.gpd_hip_shadow_jitter_model.argtypes = [C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]
         L.gpd_hip_given_check.argtypes = [C.POINTER(Params), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.gpd_hip_images_given.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                            C.POINTER(C.c_uint64)]
@@ -571,6 +591,12 @@ class Context:
         """LENET_SPLIT (default: int8 / bf16 matrix pipes on exactly split operands) or LENET_F32_CHAIN (the oracle's
         k-ascending fmaf chains, bit-identical, 1/16 of the matrix rate)."""
         self._check(lib().gpd_hip_set_lenet_mode(self._h, int(mode)))
+
+    def set_shadow_jitter(self, on, seed=0):
+        """gpd_hip_set_shadow_jitter: the shadow points of every later image-making call leave the 3 mm lattice by a draw that is a
+        pure function of (seed, voxel) — the reference's magnitude and arithmetic (hand_set.cpp:187-204), not its unseeded
+        stream.  Off by default; without a shadow channel (1, 3, 12 channels) it changes nothing."""
+        self._check(lib().gpd_hip_set_shadow_jitter(self._h, int(bool(on)), int(seed) & 0xFFFFFFFFFFFFFFFF))
 
     def set_lenet_conv_relu(self, on):
         """gpd_hip_set_lenet_conv_relu: a ReLU after conv1 and conv2 (the reference's PyTorch network) for every later scoring

@@ -527,6 +527,30 @@ int gpd_hip_set_lenet_conv_relu(gpd_hip_ctx *ctx, int on) {
   return GPD_OK;
 }
 
+// The seeded per-voxel jitter of the shadow points (jitter_model.h; hand_set.cpp:187-204 draws it from an unseeded generator).
+// Context state like the ReLU above: every entry that makes images goes through images_run / images_launch with the lane's
+// ImageState, which holds the setting.  A switch can change the window class (image_model.h), so nothing may be in flight, and a
+// resident candidate list gets the buffers and the constant block of the new setting here: gpd_hip_replay re-launches under it.
+int gpd_hip_set_shadow_jitter(gpd_hip_ctx *ctx, int on, uint64_t seed) {
+  if (int rc = refuse("gpd_hip_set_shadow_jitter", ctx, on == 0 || on == 1, {Need::NoBatch})) return rc;
+  HIP_RET(hipSetDevice(ctx->device));
+  for (auto &L : ctx->lane)
+    if (L.stream) HIP_RET(hipStreamSynchronize(L.stream));
+  for (auto &L : ctx->lane) {
+    ImageState &im = L.images;
+    im.jitter = on;
+    im.jitter_seed = on ? (unsigned long long)seed : 0ull;
+    if (im.num_candidates > 0 && !im.consts.empty()) {
+      const int rc = images_prepare(ctx->params, im);
+      if (rc) {
+        im.num_candidates = 0;  // no list this setting can re-launch
+        return rc;
+      }
+    }
+  }
+  return GPD_OK;
+}
+
 // pytorch/network.py::Net's tensors -> the layouts gpd_hip_set_lenet_weights takes (host only).  conv2 and all biases need no
 // conversion: [50][20][5][5] row-major is the reference's [50][500], and a bias is a bias.
 //   conv1  [20][C][5][5] is the reference's row-major [20][C*25]; the input scale of the training data (hdf5_dataset.py:17:

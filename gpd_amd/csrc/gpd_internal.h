@@ -585,6 +585,8 @@ struct ImageState {
   bool huge = false;                  // ... or beyond those: the general shadow kernel, a set region of run-time size
   int set_sd = 0, set_sr = 0;         // edge / radius (voxels) of the region shadow_set_kernel fills around a sample
   size_t cap_setwords = 0;            // words per row of d_set_bits
+  int jitter = 0;                     // gpd_hip_set_shadow_jitter (15 channels): the windows above and the constant block follow it,
+  unsigned long long jitter_seed = 0; // so a switch is a new geometry to this state
   int32_t *d_overflow2 = nullptr;     // [capacity]: candidates the large shadow instantiation could not list (count: d_status[2])
   char *d_huge_scratch = nullptr;     // list rows of the general shadow kernel
   int channels = 0;
@@ -603,6 +605,8 @@ struct ImageState {
   bool side_stream = true;  // off inside gpd_hip_detect_batch: the other cloud's kernels already fill the gaps (measured)
 };
 int images_reserve(const gpd_params &p, ImageState &im, int n, int shadow_sets);
+// images_reserve for the state's own list and its constant block, under the state's present settings (the lane is idle)
+int images_prepare(const gpd_params &p, ImageState &im);
 // Sizes the image buffers for the plan's candidate list (summary already on the host) and launches the image kernels.
 int images_run(const gpd_params &p, const Cloud &c, const SearchState &s, const Plan &pl, ImageState &im, hipStream_t stream);
 // Re-launches them on the resident list.  Nothing waits for the device: capacity flags accumulate in im.d_status.

@@ -13,6 +13,7 @@
 #include <mutex>
 
 #include "../../include/gpd_hip.h"
+#include "jitter_model.h"
 
 namespace gpd {
 
@@ -61,6 +62,8 @@ struct ImgConsts {
   int true_div;                 // 1: the host self-check of div_len failed for these extents, divide for real
   int set_sd, set_sr;           // edge / radius of the voxel region shadow_set_kernel fills around a sample: 86 / 43, 128 / 64 (WIDE) or,
                                 // for image volumes beyond those windows, whatever the geometry needs (image::window_class)
+  int jitter;                   // gpd_hip_set_shadow_jitter: 1 = the shadow points are moved off the lattice (jitter_model.h) ...
+  unsigned long long jitter_seed;  // ... by the draws of this seed
 };
 
 namespace image {
@@ -88,6 +91,10 @@ constexpr LcgMap lcg_affine(unsigned long long n) {
 // image box (+ 3 voxels of margins), the region of a set every box of the set.  A box spans x in [bottom, bottom + depth]
 // with init_bite - hand_depth <= bottom <= 0, y in center -+ width / 2 with |center| <= (outer_diameter - finger_width) / 2,
 // |z| <= height (finger_hand.cpp:155-168, image_strategy.cpp:53-70).
+// With the shadow jitter on, a voxel's point lies up to jitter::kShiftBound (under two voxels) from its lattice position: a
+// candidate's window must hold every voxel whose MOVED point can lie in the box, a set's region likewise — two more voxels on
+// each side of the window, two more of reach.  (The default window has one voxel to spare at the stock geometry: jitter
+// there means the wide windows.)
 struct Window {
   bool wide = false;           // the wide windows, or ...
   bool huge = false;           // ... beyond those: the general shadow kernel, a set region of the size this geometry needs
@@ -95,13 +102,14 @@ struct Window {
   int cls() const { return huge ? 2 : (wide ? 1 : 0); }
 };
 // GPD_OK, or GPD_ERR_CAPACITY with its text in msg
-inline int window_class(const gpd_params &p, Window &w, char *msg, size_t msg_len) {
+inline int window_class(const gpd_params &p, int jitter, Window &w, char *msg, size_t msg_len) {
   const double vox = 0.003;
   const double diag = std::sqrt(p.volume_depth * p.volume_depth + p.volume_width * p.volume_width + 4.0 * p.volume_height * p.volume_height);
   const double rx = std::fmax(p.hand_depth - p.init_bite, p.volume_depth);
   const double ry = 0.5 * (p.hand_outer_diameter - p.finger_width) + 0.5 * p.volume_width;
   const double reach = std::sqrt(rx * rx + ry * ry + p.volume_height * p.volume_height);
-  const double need_win = std::ceil(diag / vox) + 3.0, need_reach = std::ceil(reach / vox) + 1.0;
+  const double more = jitter ? (double)jitter::kShiftVoxels : 0.0;
+  const double need_win = std::ceil(diag / vox) + 3.0 + 2.0 * more, need_reach = std::ceil(reach / vox) + 1.0 + more;
   w.wide = need_win > (double)Vox<false>::VD || need_reach > (double)(Vox<false>::SR - 1);
   // beyond the wide windows as well: the general shadow kernel with a set region of the size this geometry needs
   // (the reference has no limit, hand_set.cpp:138; what is left of ours: 256 voxels = 0.77 m of window edge, 65535 voxels in a box)
@@ -174,8 +182,9 @@ inline void axis_model(double len, Axis &ac) {
   }
 }
 
-// The constant block of the geometry in p with the windows w (every byte defined: the block is compared bytewise).
-inline void fill_consts(const gpd_params &p, const Window &w, ImgConsts &k) {
+// The constant block of the geometry in p with the windows w (every byte defined: the block is compared bytewise).  The shadow
+// jitter and its seed matter to 15 channels alone: without a shadow channel the block is the one of jitter off.
+inline void fill_consts(const gpd_params &p, const Window &w, int jitter, unsigned long long jitter_seed, ImgConsts &k) {
   const int C = p.image_num_channels;
   std::memset(&k, 0, sizeof(k));
   k.vol_depth = p.volume_depth;
@@ -198,6 +207,8 @@ inline void fill_consts(const gpd_params &p, const Window &w, ImgConsts &k) {
   k.true_div = 0;
   k.set_sd = w.set_sd;
   k.set_sr = w.set_sr;
+  k.jitter = (jitter && C == 15) ? 1 : 0;
+  k.jitter_seed = k.jitter ? jitter_seed : 0ull;
   {
     // thresholds and the div_len() self-check depend on the box extents only: computed once per
     // geometry (the self-check alone is ~2 ms of host time)

@@ -44,7 +44,8 @@ int images_reserve(const gpd_params &p, ImageState &im, int n, int shadow_sets) 
     // which voxel windows the shadow kernels need
     image::Window w;
     char msg[160];
-    const int rc = image::window_class(p, w, msg, sizeof(msg));
+    // (the shadow jitter widens them; it is a setting of the shadow channel, so of 15 channels alone)
+    const int rc = image::window_class(p, im.jitter && C == 15, w, msg, sizeof(msg));
     im.wide = w.wide;
     im.huge = w.huge;
     if (rc) {
@@ -78,6 +79,28 @@ int images_reserve(const gpd_params &p, ImageState &im, int n, int shadow_sets) 
   return GPD_OK;
 }
 
+// The buffers and the constant block of the list in `im` (num_candidates, num_shadow_sets) under the state's present settings:
+// what images_run does ahead of its launch, and what a switch of the shadow jitter does to a resident list, so that a
+// re-launch (gpd_hip_replay) never reads buffers or a block of the other setting.  The caller has waited for the lane.
+int images_prepare(const gpd_params &p, ImageState &im) {
+  {
+    const int rc = images_reserve(p, im, im.num_candidates, im.num_shadow_sets);
+    if (rc) return rc;
+  }
+  ImgConsts k;
+  {
+    image::Window w;
+    w.wide = im.wide;
+    w.huge = im.huge;
+    w.set_sd = im.set_sd;
+    w.set_sr = im.set_sr;
+    image::fill_consts(p, w, im.jitter, im.jitter_seed, k);
+  }
+  const unsigned char *kb = reinterpret_cast<const unsigned char *>(&k);
+  if (im.consts.size() != sizeof(k) || std::memcmp(im.consts.data(), kb, sizeof(k)) != 0) im.consts.assign(kb, kb + sizeof(k));
+  return GPD_OK;
+}
+
 // The candidate list itself (which hands, in which order, where each hand set starts in the LCG stream) is
 // built on the device by plan_kernel; its sizes are in pl.h_summary by now.  This sizes the image buffers,
 // prepares the constant block of the image geometry and launches the kernels.
@@ -94,22 +117,11 @@ int images_run(const gpd_params &p, const Cloud &c, const SearchState &s, const 
   im.num_shadow_sets = sm.num_shadow_sets;
   std::memcpy(im.view_points, c.view_points, sizeof(im.view_points));
   {
-    const int rc = images_reserve(p, im, n, im.num_shadow_sets);
+    const int rc = images_prepare(p, im);
     if (rc) return rc;
   }
   HIP_RET(hipMemsetAsync(im.d_status, 0, 4 * sizeof(int32_t), stream));  // the flags and the overflow counters of this launch
   if (n == 0) return GPD_OK;
-  ImgConsts k;
-  {
-    image::Window w;
-    w.wide = im.wide;
-    w.huge = im.huge;
-    w.set_sd = im.set_sd;
-    w.set_sr = im.set_sr;
-    image::fill_consts(p, w, k);
-  }
-  const unsigned char *kb = reinterpret_cast<const unsigned char *>(&k);
-  if (im.consts.size() != sizeof(k) || std::memcmp(im.consts.data(), kb, sizeof(k)) != 0) im.consts.assign(kb, kb + sizeof(k));
   return images_launch(s, pl, im, stream, /*counters_clean=*/true);
 }
 
@@ -162,21 +174,21 @@ int images_routes(const ImageState &im, int32_t *route, long long info[8]) {
 }  // namespace gpd
 
 // The image model of a geometry, host only (include/gpd_hip.h)
-extern "C" int gpd_hip_image_model(const gpd_params *params, gpd_image_model *out) {
+static int image_model_of(const char *who, const gpd_params *params, int shadow_jitter, gpd_image_model *out) {
   using namespace gpd;
-  if (!params || !out) {
-    set_error("gpd_hip_image_model: bad argument");
+  if (!params || !out || (shadow_jitter != 0 && shadow_jitter != 1)) {
+    set_error("%s: bad argument", who);
     return GPD_ERR_INVALID;
   }
   image::Window w;
   char msg[160];
-  const int rc = image::window_class(*params, w, msg, sizeof(msg));
+  const int rc = image::window_class(*params, shadow_jitter, w, msg, sizeof(msg));
   if (rc) {
     set_error("%s", msg);
     return rc;
   }
   ImgConsts k;
-  image::fill_consts(*params, w, k);
+  image::fill_consts(*params, w, shadow_jitter, 0ull, k);
   static_assert(sizeof(out->thr) == sizeof(k.thr), "gpd_image_model");
   out->window_class = w.cls();
   out->set_sd = k.set_sd;
@@ -187,5 +199,23 @@ extern "C" int gpd_hip_image_model(const gpd_params *params, gpd_image_model *ou
   out->true_div = k.true_div;
   out->reserved_ = 0;
   std::memcpy(out->thr, k.thr, sizeof(k.thr));
+  return GPD_OK;
+}
+extern "C" int gpd_hip_image_model(const gpd_params *params, gpd_image_model *out) {
+  return image_model_of("gpd_hip_image_model", params, 0, out);
+}
+// ... with the windows of the given shadow-jitter setting (the geometry's own, whatever its channel count)
+extern "C" int gpd_hip_image_model_jitter(const gpd_params *params, int shadow_jitter, gpd_image_model *out) {
+  return image_model_of("gpd_hip_image_model_jitter", params, shadow_jitter, out);
+}
+
+// g of jitter_model.h for n voxels [n][3], host only
+extern "C" int gpd_hip_shadow_jitter_model(uint64_t seed, const int32_t *voxels, int n, double *g) {
+  using namespace gpd;
+  if (!voxels || !g || n < 0) {
+    set_error("gpd_hip_shadow_jitter_model: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  for (int i = 0; i < n; i++) g[i] = jitter::draw(seed, voxels[3 * (size_t)i], voxels[3 * (size_t)i + 1], voxels[3 * (size_t)i + 2]);
   return GPD_OK;
 }

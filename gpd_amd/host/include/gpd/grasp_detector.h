@@ -111,6 +111,9 @@ class GraspDetector {
   const std::vector<double> &getWorkspaceGrasps() const { return workspace_grasps_; }
   bool ok() const { return ctx_ != nullptr; }
   gpd_hip_ctx *context() const { return ctx_; }  // for the objects that run on the same device context (Clustering)
+  // cfg hip_shadow_jitter / hip_shadow_jitter_seed (gpd_hip_set_shadow_jitter): what the context was set to
+  int shadowJitter() const { return shadow_jitter_; }
+  unsigned long long shadowJitterSeed() const { return shadow_jitter_seed_; }
   // stage runtimes of the last detectGrasps, seconds: candidates, images, classification, total
   const double *lastRuntimes() const { return runtimes_; }
 
@@ -122,6 +125,8 @@ class GraspDetector {
   std::vector<gpd_hand> flatten(const std::vector<std::unique_ptr<candidate::HandSet>> &sets) const;
   gpd_params params_;
   gpd_hip_ctx *ctx_ = nullptr;
+  int shadow_jitter_ = 0;
+  unsigned long long shadow_jitter_seed_ = 0;
   std::shared_ptr<net::Classifier> classifier_;  // grasp_detector.h: classifier_, made by net::Classifier::create
   bool has_classifier_ = false;
   bool fused_classifier_ = false;  // the classifier is the HIP back-end and its parameters are loaded in ctx_

@@ -168,6 +168,13 @@ bool DataGenerator::labelView(int object, int view, util::Cloud &cloud, SetData 
     printf("ERROR: %s\n", gpd_hip_last_error());
     return false;
   }
+  // hip_shadow_jitter (the detector read it): every view its own pattern, seed + the view's ordinal in the data set — with one
+  // seed all views would move the voxel at a given lattice position alike
+  if (detector_->shadowJitter() != 0 &&
+      gpd_hip_set_shadow_jitter(ctx, 1, detector_->shadowJitterSeed() + (unsigned long long)(object * num_views_per_object_ + view)) != GPD_OK) {
+    printf("ERROR: %s\n", gpd_hip_last_error());
+    return false;
+  }
   // the draws of every round that may run (Cloud::subsampleUniformly is time-seeded in the reference; these are seeded)
   const int per = std::max(std::min(num_samples_, m), 0), rounds = std::max(max_rounds_per_view_, 0);
   std::vector<int32_t> samples((size_t)per * rounds + 1);

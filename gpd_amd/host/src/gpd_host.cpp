@@ -878,6 +878,24 @@ GraspDetector::GraspDetector(const std::string &config_filename) {
     return;
   }
   if (ctx_) clustering_->setContext(ctx_);
+  // hip_shadow_jitter / hip_shadow_jitter_seed (not reference keys): 1 = the shadow points of the 15-channel images leave the
+  // 3 mm lattice by a seeded per-voxel draw of the reference's magnitude and arithmetic (gpd_hip_set_shadow_jitter; the
+  // reference's own draw is unseeded, hand_set.cpp:187-204).  Default 0: the lattice.  Context state: detectGrasps, the
+  // importance sampler and the data generator on this detector's context all image with it.
+  shadow_jitter_ = config_file.getValueOfKey<int>("hip_shadow_jitter", 0);
+  shadow_jitter_seed_ = config_file.getValueOfKey<unsigned long long>("hip_shadow_jitter_seed", 0ull);
+  if (shadow_jitter_ != 0) {  // (printed like hip_lenet_mode: only when it is not the default)
+    if (gpd_hip_set_shadow_jitter(ctx_, shadow_jitter_, shadow_jitter_seed_) != GPD_OK) {
+      printf("ERROR: hip_shadow_jitter = %d: %s\n", shadow_jitter_, gpd_hip_last_error());
+      gpd_hip_destroy(ctx_);
+      ctx_ = nullptr;  // ok() is false: a detector that images differently from its cfg file is not handed out
+      return;
+    }
+    printf("============ IMAGES ==========================\n");
+    printf("volume_width: %.3f\nvolume_depth: %.3f\nvolume_height: %.3f\nimage_num_channels: %d\nhip_shadow_jitter: %d\nhip_shadow_jitter_seed: %llu\n",
+           params_.volume_width, params_.volume_depth, params_.volume_height, params_.image_num_channels, shadow_jitter_, shadow_jitter_seed_);
+    printf("==============================================\n");
+  }
   // classifier (grasp_detector.cpp:129-145): created through the plugin factory, as the reference does.  For the
   // Eigen-layout parameters weights_file is the parameter directory.
   std::string model_file = config_file.getValueOfKeyAsString("model_file", "");

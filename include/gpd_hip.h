@@ -449,6 +449,42 @@ typedef struct gpd_image_model {
   double thr[3][61];
 } gpd_image_model;
 int gpd_hip_image_model(const gpd_params *params, gpd_image_model *out);
+/* ... with the windows of a shadow-jitter setting (gpd_hip_set_shadow_jitter below; 0 or 1, anything else GPD_ERR_INVALID).
+ * gpd_hip_image_model is the case 0.  With 1 a candidate's window holds every voxel whose moved point can lie in its box and a
+ * set's region likewise — two more voxels on each side of the window, two more of reach — so the stock geometry takes the wide
+ * windows (window_class 1) and a wide geometry may take the general kernel; thresholds, num_shadow and the LCG stride do not
+ * depend on the setting. */
+int gpd_hip_image_model_jitter(const gpd_params *params, int shadow_jitter, gpd_image_model *out);
+
+/* ---- shadow points off the lattice: an opt-in, seeded, per-voxel jitter -------------------------------------------------
+ * HandSet::shadowVoxelsToPoints (hand_set.cpp:187-204) moves every shadow voxel's point by ONE N(0,1) draw times 0.3 voxels,
+ * the same draw on all three coordinates, from a generator seeded by std::random_device: no two runs of the reference draw
+ * alike.  By default this library puts the points on the 3 mm lattice (zero jitter, the policy its oracle is built with).
+ * The mode below has the reference's magnitude and arithmetic with a draw that is a pure function of (seed, voxel) — so it
+ * does not depend on how a cloud is batched, sharded or resumed.  It is NOT the reference's own, unreproducible stream.
+ *
+ * The definition (gpd_amd/csrc/jitter_model.h), all integer arithmetic and exact double operations.  mix(z), on 64-bit words:
+ *   z += 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *   return z ^ (z >> 31).
+ * Voxel (x, y, z), int32 read as uint32 and zero-extended:  k0 = mix(seed ^ (x | y << 32)), k1 = mix(k0 ^ z), k2 = mix(k1),
+ * k3 = mix(k2);  S = the sum of the twelve 16-bit fields of k1, k2, k3;  g = (double)(S - 393210) * (1.0 / 65536.0): Irwin-Hall
+ * with twelve terms, mean 0, variance 1 - 2^-32, |g| < 6.  The voxel's point, unfused and in the reference's operand order:
+ *   p_a = (double)v_a * 0.003 + (g * 0.003) * 0.3,  a = 0, 1, 2  (|shift| < 5.4 mm per world axis).
+ * The box test, the cell lookup and the depth that enters a pixel's mean take the moved point; the order in which points enter
+ * a pixel's mean stays lexicographic in the VOXEL; the voxel sets and their intersection over cameras stay on voxels.
+ *
+ * gpd_hip_set_shadow_jitter: context state like gpd_hip_set_lenet_conv_relu.  on = 0 (default) or 1, anything else is
+ * GPD_ERR_INVALID and changes nothing; GPD_ERR_STATE while gpd_hip_detect_batch drives the lanes.  It holds for every later
+ * call of the context that makes images: gpd_hip_images, _images_given, _score_given, _detect, _detect_select,
+ * _detect_samples, _detect_batch, _detect_batch_multi, _detect_sis, _label_view, _train_append_view, _replay (a resident
+ * candidate list is re-launched under the setting in force) and _detect_sharded, where each context applies its OWN setting:
+ * the caller sets them alike.  With 1, 3 or 12 channels there is no shadow channel: accepted, changes nothing.  The call waits
+ * for the context's streams.  It may change the window class (above), so buffers sized before it can grow at the next call;
+ * gpd_hip_reserve after the switch sizes for the setting in force.  The shadow draws a hand set consumes (lcg_draws) do not
+ * depend on it. */
+int gpd_hip_set_shadow_jitter(gpd_hip_ctx *ctx, int on, uint64_t seed);
+/* g of the definition above for n voxels [n][3].  Host only, no context.  GPD_ERR_INVALID: a NULL pointer or n < 0. */
+int gpd_hip_shadow_jitter_model(uint64_t seed, const int32_t *voxels, int n, double *g);
 
 /* The draws of SequentialImportanceSampling::detectGrasps (sequential_importance_sampling.cpp:189-270) — host only, no context;
  * the definition (gpd_amd/csrc/sis_model.h) the device draw of gpd_hip_detect_sis equals.  The reference draws from
