@@ -22,8 +22,10 @@
  * reference leaves open are fixed here and are part of the oracle's definition:
  *   - every fp expression is evaluated left to right, unfused (-ffp-contract=off);
  *   - M = N*N^T and other reductions are sequential sums in neighbour order;
- *   - shadow voxels are visited in lexicographic (x,y,z) order, no jitter
- *     (hand_set.cpp:191-199 draws from std::random_device: irreproducible);
+ *   - shadow voxels are visited in lexicographic (x,y,z) order; by default no jitter
+ *     (hand_set.cpp:191-199 draws from std::random_device: irreproducible), and with
+ *     gpd_oracle_set_shadow_jitter on the seeded per-voxel draw that include/gpd_hip.h
+ *     defines (gpd_hip_set_shadow_jitter), restated here, with the reference's arithmetic;
  *   - the shadow LCG (hand_set.cpp:263-266) starts at seed 0 for every cloud;
  *   - LeNet dot products are fmaf chains in ascending k, bias added last.
  *
@@ -657,6 +659,24 @@ static double nnRadiusImages(const gpd_params &P) {  // image_generator.cpp:43-4
 // Shadow — hand_set.cpp:118-283 (15 channels only).
 // ---------------------------------------------------------------------------
 static uint64_t g_lcg_base = 0, g_lcg_draws = 0;  // gpd_oracle_set_lcg_base / gpd_oracle_last_lcg_draws (below)
+static int g_jitter_on = 0;                        // gpd_oracle_set_shadow_jitter (below): off by default
+static uint64_t g_jitter_seed = 0;
+// The seeded draw of a shadow voxel, restated from its definition in include/gpd_hip.h (gpd_hip_set_shadow_jitter): the
+// splitmix64 step, the voxel's int32 coordinates read as uint32 and zero-extended, the twelve 16-bit fields of k1, k2, k3.
+static uint64_t jitterMix(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+static double jitterDraw(uint64_t seed, const int *v) {
+  const uint64_t x = (uint32_t)v[0], y = (uint32_t)v[1], z = (uint32_t)v[2];
+  uint64_t k = jitterMix(jitterMix(seed ^ (x | (y << 32))) ^ z);
+  int64_t S = 0;
+  for (int i = 0; i < 3; i++, k = jitterMix(k))
+    for (int f = 0; f < 64; f += 16) S += (int64_t)((k >> f) & 0xFFFFu);
+  return (double)(S - 393210) * (1.0 / 65536.0);
+}
 struct Lcg {  // hand_set.cpp:263-266 ("fastrand"); jump() = n steps at once
   uint32_t s;
   int next() {
@@ -902,7 +922,9 @@ static void createImage(const gpd_params &P, const gpd_hand &H, const float *xyz
   if (C == 15)
     toUnitImage(P, H, (int)shadow.size(),
                 [&](int i, double *w, double *) {
-                  for (int r = 0; r < 3; r++) w[r] = (double)shadow[i].v[r] * 0.003;
+                  // hand_set.cpp:197-199 with the seeded draw: one g per voxel, the same on all three axes
+                  const double off = g_jitter_on ? (jitterDraw(g_jitter_seed, shadow[i].v) * 0.003) * 0.3 : 0.0;
+                  for (int r = 0; r < 3; r++) w[r] = g_jitter_on ? (double)shadow[i].v[r] * 0.003 + off : (double)shadow[i].v[r] * 0.003;
                 },
                 false, sh);
   const int np = (int)pts.u.size() / 3, ns = (int)sh.u.size() / 3;
@@ -1470,6 +1492,22 @@ int gpd_oracle_num_threads() {
 // set, and the draws its hand sets consumed (tests/test_multi_gpu_gloo.py: two ranks, a host-side scan of the totals)
 void gpd_oracle_set_lcg_base(uint64_t base) { g_lcg_base = base; }
 uint64_t gpd_oracle_last_lcg_draws(void) { return g_lcg_draws; }
+// The seeded shadow jitter of include/gpd_hip.h (gpd_hip_set_shadow_jitter), global like the base above and off by default:
+// createImage moves every shadow voxel's point by its draw; the voxel sets, their order and the LCG stream do not change.
+void gpd_oracle_set_shadow_jitter(int on, uint64_t seed) {
+  g_jitter_on = on ? 1 : 0;
+  g_jitter_seed = seed;
+}
+int gpd_oracle_get_shadow_jitter(uint64_t *seed) {
+  if (seed) *seed = g_jitter_seed;
+  return g_jitter_on;
+}
+void gpd_oracle_shadow_jitter_draws(uint64_t seed, const int32_t *voxels, int n, double *g) {
+  for (int i = 0; i < n; i++) {
+    const int v[3] = {voxels[3 * i], voxels[3 * i + 1], voxels[3 * i + 2]};
+    g[i] = jitterDraw(seed, v);
+  }
+}
 
 void gpd_oracle_set_num_threads(int n) {
 #ifdef _OPENMP

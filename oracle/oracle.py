@@ -1,4 +1,5 @@
 """ctypes binding of oracle/libgpd_oracle.so (TEST INFRASTRUCTURE ONLY)."""
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -145,6 +146,45 @@ def last_lcg_draws():
     L = lib()
     L.gpd_oracle_last_lcg_draws.restype = C.c_uint64
     return int(L.gpd_oracle_last_lcg_draws())
+
+
+def set_shadow_jitter(on, seed=0):
+    """The seeded per-voxel shadow jitter of include/gpd_hip.h (gpd_hip_set_shadow_jitter) for every later images() / detect():
+    global, off by default, stays set until changed — prefer shadow_jitter() below, which switches it off again."""
+    L = lib()
+    L.gpd_oracle_set_shadow_jitter.argtypes = [C.c_int, C.c_uint64]
+    L.gpd_oracle_set_shadow_jitter.restype = None
+    L.gpd_oracle_set_shadow_jitter(int(bool(on)), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def shadow_jitter_state():
+    """The seed in force, or None with the setting off (read back from the library)."""
+    seed = C.c_uint64(0)
+    on = lib().gpd_oracle_get_shadow_jitter(C.byref(seed))
+    return int(seed.value) if on else None
+
+
+@contextlib.contextmanager
+def shadow_jitter(seed):
+    """with oracle.shadow_jitter(seed): the setting on inside, off after it whatever happens (seed None: off inside too)."""
+    if shadow_jitter_state() is not None:
+        raise RuntimeError("oracle.shadow_jitter does not nest")
+    set_shadow_jitter(seed is not None, seed or 0)
+    try:
+        yield
+    finally:
+        set_shadow_jitter(False)
+
+
+def shadow_jitter_draws(seed, voxels):
+    """g of the definition in include/gpd_hip.h for voxels int32 [n, 3], in the oracle's own statement of it -> f64 [n]."""
+    v = np.ascontiguousarray(voxels, np.int32).reshape(-1, 3)
+    g = np.zeros(len(v), np.float64)
+    L = lib()
+    L.gpd_oracle_shadow_jitter_draws.argtypes = [C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]
+    L.gpd_oracle_shadow_jitter_draws.restype = None
+    L.gpd_oracle_shadow_jitter_draws(int(seed) & 0xFFFFFFFFFFFFFFFF, _p(v), len(v), _p(g))
+    return g
 
 
 def images(params, xyz, normals, cam_source, view_points, hands, want_images=True):

@@ -1,7 +1,9 @@
 """What every composed entry of the library must return on a variant of tests/ref_cases.py, composed from the oracle alone and
 computed once per variant: detect / detect_select, detect_samples, the batch entries (three jobs), images_given / score_given,
 detect_sis and label_view.  tests/test_entry_cases.py proves on the CPU that none of these expectations is empty;
-tests/test_gpu_entries_by_variant.py runs the library against them.  Nothing here is modified after it is built."""
+tests/test_gpu_entries_by_variant.py runs the library against them.  Inside `with jitter(om, seed):` the same functions give
+the expectations of gpd_hip_set_shadow_jitter(on, seed), from the oracle's own statement of that policy
+(tests/test_gpu_entries_by_variant_jitter.py).  Nothing here is modified after it is built."""
 import numpy as np
 
 import label_view_cases as lvc
@@ -16,12 +18,20 @@ LCG_BASES = (0, 12345678901)
 SIS = dict(seed=7, method=0, rounds=2, per=24, min_score=-300.0, min_inliers=0)
 GT_SEED, ROUNDS_SEED, VIEW_ROUNDS, SAMPLES_PER_ROUND = 7, 7, 4, 16
 MIN_POSITIVES, MAX_GRASPS_PER_VIEW = 10 ** 6, 500  # no round stops the view early
+# the shadow jitter (gpd_hip_set_shadow_jitter): the seed, and the variants every entry also runs on with the setting on — the
+# window-class transitions of image::window_class (stock 0 -> 1, one voxel to spare, 1 -> 1, wide -> general, general -> general),
+# a channel count without a shadow, 24 slots, a 12-way set intersection with a blind camera, off-lattice input with two cameras
+JITTER_SEED = 0x5EED5EED5EED
+JITTER_VARIANTS = ("default_c15", "default_c12", "other_image_volume", "wide_image_volume", "huge_image_volume", "deep_hand",
+                   "three_axes", "twelve_cameras", "offlattice_two_cameras")
 
 _cache = {}
 
 
-def _once(kind, name, make):
-    key = (kind, name)
+def _once(om, kind, name, make):
+    """One expectation per (kind, variant, shadow-jitter seed of the oracle or None): what was composed with the setting off is
+    never returned with it on, nor the reverse.  The seed is read back from the oracle itself (entry_cases.jitter below)."""
+    key = (kind, name, om.shadow_jitter_state())
     if key not in _cache:
         _cache[key] = make()
     return _cache[key]
@@ -37,6 +47,12 @@ def _freeze(x):
         for v in x:
             _freeze(v)
     return x
+
+
+def jitter(om, seed):
+    """with jitter(om, seed): every expectation built or fetched inside is the one of gpd_hip_set_shadow_jitter(on, seed); seed
+    None: off, as outside.  The oracle is switched off again on the way out."""
+    return om.shadow_jitter(seed)
 
 
 def slots(p):
@@ -75,7 +91,7 @@ def detect(om, name):
     def make():
         p, cl, si, w = inputs(name, om.default_params)
         return _freeze(_detect(om, p, cl, si, w))
-    return _once("detect", name, make)
+    return _once(om, "detect", name, make)
 
 
 def sample_points(name):
@@ -103,7 +119,7 @@ def detect_samples(om, name):
         sets = om.search_xyz(p, cl["xyz"], cl["normals"], sample_points(name))
         hands, img, cand, scores = _score_sets(om, p, cl, sets, w)
         return _freeze(dict(hands=hands, n_cand=len(cand), cand=cand, scores=scores))
-    return _once("detect_samples", name, make)
+    return _once(om, "detect_samples", name, make)
 
 
 def batch_jobs(name, default_params):
@@ -124,7 +140,7 @@ def batch(om, name):
         clouds, samples = batch_jobs(name, om.default_params)
         out = [detect(om, name)] + [_detect(om, p, cl, s, w) for cl, s in zip(clouds[1:], samples[1:])]
         return _freeze(out)
-    return _once("batch", name, make)
+    return _once(om, "batch", name, make)
 
 
 def given_sets(om, name):
@@ -137,7 +153,7 @@ def given_sets(om, name):
         flat = b.reshape(-1)
         flat["valid"][np.flatnonzero(flat["valid"])[::3]] = 0
         return _freeze(dict(a=a, b=b))
-    return _once("given_sets", name, make)
+    return _once(om, "given_sets", name, make)
 
 
 def given(om, name, which, lcg_base):
@@ -151,7 +167,7 @@ def given(om, name, which, lcg_base):
         finally:
             om.set_lcg_base(0)
         return _freeze(dict(images=img, cand=cand, draws=draws, scores=om.lenet(img, w) if len(cand) else np.zeros(0, np.float32)))
-    return _once("given_%s_%d" % (which, lcg_base), name, make)
+    return _once(om, "given_%s_%d" % (which, lcg_base), name, make)
 
 
 def shard_draws(om, name, cut):
@@ -164,7 +180,7 @@ def shard_draws(om, name, cut):
         om.images(p, cl["xyz"], cl["normals"], cl["cam_source"], cl["view_points"], a[:cut], want_images=False)
         head = om.last_lcg_draws()
         return head, given(om, name, "a", 0)["draws"] - head
-    return _once("shard_draws_%d" % cut, name, make)
+    return _once(om, "shard_draws_%d" % cut, name, make)
 
 
 def nonempty(images):
@@ -175,7 +191,7 @@ def sis_predict(om, name):
     def make():
         p, cl, si, w = inputs(name, om.default_params)
         return _freeze(sc.predict(om, p, cl, cl["cam_source"], cl["view_points"], si, w, **SIS))
-    return _once("sis", name, make)
+    return _once(om, "sis", name, make)
 
 
 def sis_replay(om, name, samples):
@@ -204,4 +220,4 @@ def view(om, name):
         gt, gn = ground_truth(name)
         return _freeze(lvc.expected_view(om, p, cl["xyz"], cl["normals"], cl["cam_source"], cl["view_points"], gt, gn, view_rounds(name),
                                          MIN_POSITIVES, MAX_GRASPS_PER_VIEW))
-    return _once("view", name, make)
+    return _once(om, "view", name, make)

@@ -48,7 +48,38 @@ def test_the_table_names_every_variant():
 
 @pytest.mark.parametrize("name", sorted(rcs.VARIANTS))
 def test_no_expectation_is_empty(oracle_mod, name):
+    _proofs(oracle_mod, name)
+
+
+@pytest.mark.parametrize("name", ec.JITTER_VARIANTS)
+def test_no_expectation_is_empty_with_the_shadow_jitter_on(oracle_mod, name):
+    """The same proofs on the expectations of gpd_hip_set_shadow_jitter(on, JITTER_SEED): the counts are those of the setting
+    off, since no candidate, label or draw depends on it and detect_sis keeps every hand at this min_score."""
+    with ec.jitter(oracle_mod, ec.JITTER_SEED):
+        _proofs(oracle_mod, name)
+
+
+@pytest.mark.parametrize("name", ec.JITTER_VARIANTS)
+def test_the_shadow_jitter_decides_the_scores(oracle_mod, name):
+    """What tests/test_gpu_entries_by_variant_jitter.py compares is not what the walk with the setting off compares: with 15
+    channels at least half of the candidates' detect scores differ; without a shadow channel none does."""
     om = oracle_mod
+    off = ec.detect(om, name)
+    with ec.jitter(om, ec.JITTER_SEED):
+        on = ec.detect(om, name)
+    assert on is not off and on["n_cand"] == off["n_cand"] > 0
+    a, b = on["cands"].copy(), off["cands"].copy()
+    differ = int((a["score"] != b["score"]).sum())
+    print(name, "detect scores that differ with the jitter on: %d of %d" % (differ, len(a)))
+    a["score"] = b["score"] = 0
+    assert a.tobytes() == b.tobytes()  # the records are the same but for the score
+    if ec.inputs(name, om.default_params)[0].image_num_channels == 15:
+        assert 2 * differ >= len(a), (name, differ, len(a))
+    else:
+        assert name == "default_c12" and differ == 0 and on["hands"].tobytes() == off["hands"].tobytes()
+
+
+def _proofs(om, name):
     n_cand, live, n_sis, (v_cand, v_pos, v_out) = COUNTS[name]
     p = ec.inputs(name, om.default_params)[0]
     slots = ec.slots(p)

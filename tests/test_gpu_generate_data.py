@@ -46,8 +46,9 @@ def _cylinder(rng, r, h, n):
     return np.stack([rr * np.cos(th), rr * np.sin(th), z], 1)
 
 
-def _data_set(tmp):
-    """Per object a complete surface as the mesh and three views of it (seeded subsets, a little noise).  The objects stand on the
+def _data_set(tmp, channels=CHANNELS, extra=""):
+    """(`channels`: image_num_channels of the cfg file; `extra`: further cfg lines.)
+    Per object a complete surface as the mesh and three views of it (seeded subsets, a little noise).  The objects stand on the
     camera axis, half a metre from the view point (0, 0, 0): normals flipped towards it point INTO such an object on every side,
     which is why the reference's cfg reverses them — and only then do opposite faces carry opposite normals, i.e. positives."""
     clouds = {}
@@ -73,15 +74,17 @@ def _data_set(tmp):
                    "num_views_per_object = %d\nmin_grasps_per_view = %d\nmax_grasps_per_view = %d\ntest_views = %s\n"
                    "num_samples = %d\nremove_nans = 1\nvoxel_size_views = %g\nnormals_radius = %g\nreverse_mesh_normals = 1\n"
                    "reverse_view_normals = 1\nsample_seed = %d\nshuffle_seed = %d\nmax_rounds_per_view = %d\n"
-                   "image_num_channels = %d\nnum_orientations = 8\nhand_axes = 2\nworkspace_grasps = -1 1 -1 1 -1 1\n"
+                   "image_num_channels = %d\nnum_orientations = 8\nhand_axes = 2\nworkspace_grasps = -1 1 -1 1 -1 1\n%s"
                    % (tmp, tmp, out, VIEWS, MIN_GRASPS, MAX_GRASPS, " ".join(map(str, TEST_VIEWS)), NUM_SAMPLES, VOXEL, RADIUS,
-                      SAMPLE_SEED, SHUFFLE_SEED, MAX_ROUNDS, CHANNELS))
+                      SAMPLE_SEED, SHUFFLE_SEED, MAX_ROUNDS, channels, extra))
     return cfg, out, clouds
 
 
-def _composed(clouds):
-    """The same data set through gpd_amd.api -> (train images, train labels, test images, test labels)."""
-    ctx = api.Context(api.default_params(CHANNELS))
+def _composed(clouds, channels=CHANNELS, jitter_seed=None, per_view=True):
+    """The same data set through gpd_amd.api -> (train images, train labels, test images, test labels).  With `jitter_seed` S
+    every view is labelled under set_shadow_jitter(True, S + the view's ordinal in the data set), as DataGenerator::labelView
+    sets it (`per_view` False: under S itself, which the generator does NOT do)."""
+    ctx = api.Context(api.default_params(channels))
     sets = {"train": ([], []), "test": ([], [])}
     sizes, stored = [], []
     try:
@@ -96,6 +99,8 @@ def _composed(clouds):
                 ctx.upload_cloud(xyz, -ctx.estimate_normals(RADIUS), cam, np.zeros((1, 3)))
                 seed = (SAMPLE_SEED + 1000003 * (o * VIEWS + j)) & 0xFFFFFFFF
                 rounds = np.stack([api.sample_positions(len(xyz), NUM_SAMPLES, (seed + r) & 0xFFFFFFFF) for r in range(MAX_ROUNDS)])
+                if jitter_seed is not None:
+                    ctx.set_shadow_jitter(True, jitter_seed + (o * VIEWS + j if per_view else 0))
                 got = ctx.label_view(rounds, MIN_GRASPS, MAX_GRASPS)
                 which = per_object["test" if j in TEST_VIEWS else "train"]
                 which[0].append(got["images"])
@@ -134,3 +139,33 @@ def test_generate_data_cli_equals_the_composed_sequence(tmp_path):
     assert "Generated %d training and test %d instances" % (n_train, n_test) in out.stdout
     assert out.stdout.count("positives, negatives found for this view:") == len(OBJECTS) * VIEWS
     assert out.stdout.count("test view, # test data:") == len(OBJECTS) * len(TEST_VIEWS)
+
+
+JITTER_SEED = 0x5EED5EED5EED
+
+
+def test_generate_data_cli_at_15_channels_with_a_shadow_jitter_seed_per_view(tmp_path):
+    """hip_shadow_jitter = 1 in the cfg file, 15 channels: DataGenerator gives every view the seed S + object *
+    num_views_per_object + view (data_generator.cpp, labelView).  The files equal the sequence composed with those seeds byte for
+    byte, and not the one composed with S for every view, nor the one with the setting off."""
+    cfg, out_dir, clouds = _data_set(tmp_path, 15, "hip_shadow_jitter = 1\nhip_shadow_jitter_seed = %d\n" % JITTER_SEED)
+    out = subprocess.run([CLI, str(cfg)], capture_output=True, text=True, cwd=str(tmp_path), timeout=300)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
+    assert "hip_shadow_jitter: 1" in out.stdout and ("hip_shadow_jitter_seed: %d" % JITTER_SEED) in out.stdout
+    want = _composed(clouds, 15, JITTER_SEED)
+    names = ("train_images", "train_labels", "test_images", "test_labels")
+    got = [np.load(str(out_dir / (n + ".npy"))) for n in names]
+    for n, g, w in zip(names, got, want):
+        shape = (len(w), 60, 60, 15) if n.endswith("images") else (len(w), 1)
+        assert g.dtype == np.uint8 and g.shape == shape, (n, g.dtype, g.shape, shape)
+        assert g.tobytes() == w.tobytes(), n
+    n_train, n_test = len(want[1]), len(want[3])
+    assert n_train > 0 and n_test > 0 and 0 < int(want[1].sum()) < n_train
+    shadow = [4, 9, 14]
+    assert all((want[0][..., c] > 0).any() for c in shadow)
+    # the labels and the twelve other channels do not depend on the seeds; the shadow channels of the training views do
+    for other in (_composed(clouds, 15, JITTER_SEED, per_view=False), _composed(clouds, 15)):
+        assert other[0].shape == want[0].shape and np.array_equal(other[1], want[1])
+        rest = [c for c in range(15) if c not in shadow]
+        assert other[0][..., rest].tobytes() == want[0][..., rest].tobytes()
+        assert other[0][..., shadow].tobytes() != want[0][..., shadow].tobytes()

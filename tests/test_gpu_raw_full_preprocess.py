@@ -299,3 +299,33 @@ def test_batch_multi_over_two_contexts(ctx, weights, full_specs, full_want):
             check_job(j, k, w, "multi %d" % i)
     finally:
         other.close()
+
+
+def test_a_raw_job_images_with_the_shadow_jitter_of_its_context(weights):
+    """gpd_hip_set_shadow_jitter holds for a raw job of gpd_hip_detect_batch as for the single calls: with the setting on the
+    job returns the records of preprocess_cloud + upload_cloud + detect_samples on the same context byte for byte, and their
+    scores are not those of the setting off; off again, the job returns the first records again."""
+    scan, sm = synth_scan(780, 16000, base=8000)
+    s = spec(scan, WS, sm[:24])
+    c = api.Context(api.default_params(15))
+    try:
+        c.set_lenet_weights(weights)
+        off = stepwise(c, s)
+        c.set_shadow_jitter(True, 0x5EED5EED5EED)
+        on = stepwise(c, s)
+        assert on["n_cand"] == off["n_cand"] >= 20 and on["M"] == off["M"]
+        a, b = on["records"].copy(), off["records"].copy()
+        differ = int((a["score"] != b["score"]).sum())
+        print("raw job: %d of %d scores differ with the jitter on" % (differ, len(a)))
+        assert differ >= 1
+        a["score"] = b["score"] = 0
+        assert a.tobytes() == b.tobytes()
+        jobs, keeps = build(c, [s])
+        run(c, jobs)
+        check_job(jobs[0], keeps[0], on, "jitter on")
+        assert records(jobs[0], keeps[0])["score"].tobytes() != off["records"]["score"].tobytes()
+        c.set_shadow_jitter(False)
+        run(c, jobs)
+        check_job(jobs[0], keeps[0], off, "jitter off again")
+    finally:
+        c.close()

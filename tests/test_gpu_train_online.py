@@ -395,3 +395,47 @@ def test_refusals_before_any_work():
     finally:
         ctx.close()
         three.close()
+
+
+# ---- 10. the shadow jitter of the labelling context ---------------------------------------------------------------------------
+def test_append_view_images_with_the_shadow_jitter_of_the_labelling_context():
+    """gpd_hip_set_shadow_jitter is state of the context that labels: a view appended from a context with the setting on lands
+    in the pool with the images label_view returns on that context, one appended from a context with it off with the others —
+    whichever context the trainer itself was made on.  One view of default_c15 (tests/entry_cases.py: its four rounds)."""
+    import entry_cases as ec
+    name, seed = "default_c15", ec.JITTER_SEED
+    p, cl, _, _ = ec.inputs(name, api.default_params)
+    gt, gn = ec.ground_truth(name)
+    rounds = ec.view_rounds(name)
+    shadow = [4, 9, 14]
+    rest = [c for c in range(15) if c not in shadow]
+    ctxs = []
+    try:
+        for on in (True, False):
+            c = api.Context(p)
+            ctxs.append(c)
+            c.upload_ground_truth(gt, gn)
+            c.upload_cloud(cl["xyz"], cl["normals"], cl["cam_source"], cl["view_points"])
+            if on:
+                c.set_shadow_jitter(True, seed)
+        on_ctx, off_ctx = ctxs
+        want_on = on_ctx.label_view(rounds, ec.MIN_POSITIVES, ec.MAX_GRASPS_PER_VIEW, want_all_labels=True)
+        want_off = off_ctx.label_view(rounds, ec.MIN_POSITIVES, ec.MAX_GRASPS_PER_VIEW, want_all_labels=True)
+        assert want_on["num_out"] == want_off["num_out"] == 6 and want_on["labels"].tobytes() == want_off["labels"].tobytes()
+        assert want_on["images"][..., rest].tobytes() == want_off["images"][..., rest].tobytes()
+        assert want_on["images"][..., shadow].tobytes() != want_off["images"][..., shadow].tobytes()
+        for home in (on_ctx, off_ctx):
+            t = api.Trainer(home)
+            try:
+                got = t.append_view(on_ctx, rounds, ec.MIN_POSITIVES, ec.MAX_GRASPS_PER_VIEW, want_all_labels=True)
+                _assert_appended(got, want_on, t, 0)
+                got = t.append_view(off_ctx, rounds, ec.MIN_POSITIVES, ec.MAX_GRASPS_PER_VIEW, want_all_labels=True)
+                assert got["first"] == want_on["num_out"]
+                _assert_appended(got, want_off, t, 0)
+                img, _ = t.get_data(0, 2 * want_on["num_out"])
+                assert img[:6].tobytes() == want_on["images"].tobytes() != img[6:].tobytes()
+            finally:
+                t.close()
+    finally:
+        for c in ctxs:
+            c.close()

@@ -92,6 +92,58 @@ def test_detect_grasps_cli_matches_oracle(tmp_path, oracle_mod, lenet15_real):
     assert [int(g[6]) for g in got] == want["finger_placement_index"].tolist()
 
 
+JITTER_SEED = 104240208772845  # 0x5ECE509D7EED: above 2^32, and its low 32 bits are another seed
+
+
+@pytest.mark.gpu
+def test_detect_grasps_cli_reads_the_shadow_jitter_keys(tmp_path, oracle_mod, lenet15_real):
+    """The case above with hip_shadow_jitter = 1 and a seed above 2^32 in the cfg file (gpd_host.cpp: not reference keys):
+    the 20 grasps are those of the oracle with its statement of the policy on at that seed — and neither those of the policy
+    off (a parser that drops the key) nor those of the seed's low 32 bits (one that truncates it)."""
+    om = oracle_mod
+    assert JITTER_SEED > 2 ** 32 and JITTER_SEED & 0xFFFFFFFF != JITTER_SEED
+    cl = synth.make_cloud(99, 12000)
+    cfg, pcd = _write_case(tmp_path, cl, lenet15_real, 150, 20,
+                           extra="hip_shadow_jitter = 1\nhip_shadow_jitter_seed = %d\n" % JITTER_SEED)
+    out = subprocess.run([CLI, str(cfg), str(pcd)], capture_output=True, text=True, cwd=str(tmp_path), timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = out.stdout.splitlines()
+    assert "hip_shadow_jitter: 1" in lines and ("hip_shadow_jitter_seed: %d" % JITTER_SEED) in lines, out.stdout[:3000]
+    got = [l.split() for l in lines if l.startswith("GRASP ")]
+    assert len(got) == 20
+    si = _subsample_indices(len(cl["xyz"]), 150)
+    p = om.default_params(15)
+    hands = om.filter_workspace(p, om.search(p, cl["xyz"], cl["normals"], si))
+
+    def top20(seed):
+        with om.shadow_jitter(seed):
+            img, cand = om.images(p, cl["xyz"], cl["normals"], cl["cam_source"], cl["view_points"], hands)
+        sc = om.lenet(img, lenet15_real)
+        order = np.argsort(-sc, kind="stable")[:20]
+        return hands.reshape(-1)[cand][order], sc[order]
+
+    want, wsc = top20(JITTER_SEED)
+    gs = np.array([float(g[1]) for g in got])
+    err = float(np.abs(gs - wsc).max())
+    miss = {what: float(np.abs(gs - top20(seed)[1]).max()) for what, seed in (("off", None), ("low 32 bits", JITTER_SEED & 0xFFFFFFFF))}
+    print("detect_grasps with the jitter keys: max |score - oracle| = %.3g; against the oracle with the policy %s" % (err, miss))
+    assert err <= 1e-4
+    assert np.all(np.diff(gs) <= 0)
+    gp = np.array([[float(x) for x in g[2:5]] for g in got])
+    assert np.allclose(gp, want["position"], rtol=1e-12, atol=1e-15)
+    assert [int(g[6]) for g in got] == want["finger_placement_index"].tolist()
+    assert all(m > 1e-3 for m in miss.values()), miss
+
+
+@pytest.mark.gpu
+def test_detect_grasps_cli_refuses_an_unknown_shadow_jitter_mode(tmp_path):
+    cl = synth.make_cloud(5, 2000)
+    cfg, pcd = _write_case(tmp_path, cl, synth.lenet_weights(15), 10, 5, extra="hip_shadow_jitter = 2\nhip_shadow_jitter_seed = 1\n")
+    out = subprocess.run([CLI, str(cfg), str(pcd)], capture_output=True, text=True, cwd=str(tmp_path), timeout=300)
+    assert out.returncode != 0 and "ERROR: hip_shadow_jitter" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+    assert not [l for l in out.stdout.splitlines() if l.startswith("GRASP ")]
+
+
 @pytest.mark.gpu
 def test_cli_direction_filter_and_clustering(tmp_path, oracle_mod, lenet15_real):
     """detectGrasps with filter_approach_direction = 1 and min_inliers = 1 (grasp_detector.cpp:247-255,
