@@ -31,7 +31,7 @@ static int round_plan(gpd_hip_ctx *ctx, Lane &L, Job &J, PlanSummary &sm, long l
   return GPD_OK;
 }
 
-// gpd_hip_label_view, and gpd_hip_train_append_view through a sink (train.hip): the rounds and the selection are one code
+// gpd_hip_label_view, and gpd_hip_train_append_view through a sink (train_sets.hip): the rounds and the selection are one code
 int label_view_run(gpd_hip_ctx *ctx, gpd_label_view_job *job, const char *who, const LabelSink *sink) {
   StageRange range_("gpd:label_view");
   int rc = refuse(who, ctx, job);

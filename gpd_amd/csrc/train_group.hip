@@ -143,9 +143,7 @@ hipError_t enqueue_op(gpd_hip_train_group *g, const group::Op &op, int batch, st
   switch (op.kind) {
     case group::kBackward: {
       const int s = step[(size_t)r]++;
-      const int *idx = t->d_idx + (size_t)s * batch;
-      enqueue_forward(t, 0, idx, batch, true, t->d_loss + s, false, k);
-      enqueue_backward(t, idx, batch, false, k);
+      enqueue_gradients(t, t->d_idx + (size_t)s * batch, batch, t->d_loss + s, false, k);
       return hipGetLastError();
     }
     case group::kWait: return hipStreamWaitEvent(t->stream, g->ev[(size_t)op.event], 0);
@@ -241,8 +239,8 @@ int gpd_hip_train_group_create(gpd_hip_trainer *const *trainers, int num, gpd_hi
         return GPD_ERR_INVALID;
       }
     }
-    if (trainers[r]->C != trainers[0]->C) {
-      set_error("gpd_hip_train_group_create: trainer %d has %d channels, trainer 0 has %d", r, trainers[r]->C, trainers[0]->C);
+    if (trainers[r]->p.channels != trainers[0]->p.channels) {
+      set_error("gpd_hip_train_group_create: trainer %d has %d channels, trainer 0 has %d", r, trainers[r]->p.channels, trainers[0]->p.channels);
       return GPD_ERR_INVALID;
     }
     const gpd_lenet_shape &sr = trainers[r]->shape, &s0 = trainers[0]->shape;
@@ -336,8 +334,8 @@ int gpd_hip_train_group_steps(gpd_hip_train_group *g, const int32_t *const *indi
       set_error("gpd_hip_train_group_steps: replica %d has no index list", r);
       return GPD_ERR_INVALID;
     }
-    if (batch < 1 || batch > t->maxb) {
-      set_error("gpd_hip_train_group_steps: batch %d is outside 1 .. max_batch = %d of replica %d", batch, t->maxb, r);
+    if (batch < 1 || batch > t->p.max_batch) {
+      set_error("gpd_hip_train_group_steps: batch %d is outside 1 .. max_batch = %d of replica %d", batch, t->p.max_batch, r);
       return GPD_ERR_INVALID;
     }
     if (t->n[0] < 1) {
