@@ -50,12 +50,33 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // (float) max(S_i) == max((float) S_i), bit for bit (tests/test_conv1_pool_model.py).  Until this form the pool ran in f64, in
 // every lane for all five row tiles, and the correction was an f64 add behind it: 89 vector instructions per tile, now 59.
 // Stores: image and tile parts of the address are wave-uniform (scalar arithmetic), the lane adds a constant 32-bit offset.
-// (The bias and shift loads of the kernel's head are first waited for inside the tile loop, a vmcnt(0) in every epilogue.  Moving
-//  that wait in front of the loop LOST 0.027 ms of 0.40: profiles/NOTES.md §O.  It stays.)
-// Persistent workgroups, one per CU: the next image streams into a raw LDS region one 16-byte piece per thread and tile,
-// and is turned pixel-major between two barriers.
+// (One group per CU: the bias and shift loads of the kernel's head are first waited for inside the tile loop, a vmcnt(0) in every
+//  epilogue.  Moving that wait in front of the loop LOST 0.027 ms of 0.40 when sixteen-byte pixels ran in that frame:
+//  profiles/NOTES.md §O.  It stays there.  With two groups the first turn's waits cover those loads.)
+//
+// Persistent workgroups.  A workgroup takes image blockIdx.x first and then whatever the launch's counter hands out (`queue`, zero
+// at launch: ticket = gridDim.x + atomicAdd), until a ticket is past the end.  Two frames, chosen per geometry by f1_two_groups()
+// from the size of the pixel-major image alone:
+//   TWO GROUPS per CU (sixteen-byte pixels: 69 120 B, narrow images: 65 280 B; 2 x that + the ticket words < 160 KB).  256 threads,
+//     four waves, wave w takes tiles w, w + 4, ...: 49 each.  LDS holds the pixel-major image and the ticket, nothing else.  Per
+//     image: ticket (one lane; its round trip runs under the loads), the image straight from global memory into pixel-major LDS
+//     (a task = four consecutive pixels of a row: one 4-byte read per plane, consecutive lanes read consecutive words; the reads
+//     of two task rounds are in flight before the first is turned — the tile loop's registers are dead there, the weight
+//     fragments are not: 238 VGPRs, no scratch), barrier, tiles, barrier (which is also what makes the image free to overwrite).
+//     Nothing inside a workgroup is pipelined by hand: while one workgroup loads and turns, no MFMA of its own is issued — and the
+//     CU's other workgroup, whose waves share the four SIMDs with it one to one, has the matrix pipes to itself.  The tile loop
+//     holds no global load, no LDS store and no vmcnt wait any more.
+//   ONE GROUP per CU (twelve channels: two 44 160 B copies — twice that does not fit).  512 threads, eight waves, as before: the
+//     next image streams into a raw LDS region (C x 3600 B) one 16-byte piece per thread and tile, and is turned pixel-major
+//     between two barriers; waves w and w + 4 share a SIMD and the lower one runs at s_setprio(2).
+// Who owns the matrix pipe with two groups: a SIMD's two waves belong to different workgroups.  Measured, two builds alternating
+// on one box, six counted rounds each, conv1 per 5000 images as a share of conv2's time in the same run (the boxes' clocks wander
+// by 3 % inside a session, together for all kernels), in two sessions: (a) no priorities 0.587 / 0.590 — kept: equal to the
+// others and nothing to guess about placement —, (b) s_setprio(2) for the workgroups with blockIdx.x < gridDim.x / 2:
+// 0.586 / 0.589, (c) s_setprio(2) by the parity of the wave's hardware slot (s_getreg_b32 HW_ID, wave_id): 0.585 / 0.590; the
+// one-group frame that sixteen-byte pixels ran in before: 0.613 / 0.616 (profiles/NOTES.md §P, which also has a start delay for
+// half of the workgroups: no gain, and scalar plane bases for the turn's loads: a loss).
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int F1_THREADS = 512, F1_WAVES = 8;
 constexpr int F1_PITCH = 72;                  // pixels per LDS row
 constexpr int F1_ROWB = F1_PITCH * 16;        // 1152 bytes
 constexpr int F1_HWC = kImg * F1_ROWB;        // 69120 bytes
@@ -90,6 +111,12 @@ __host__ __device__ constexpr int f1n_slot(int ks, int g) {
   const int sl = 4 * ks + g;
   return sl < 5 ? 2 * sl : sl < 10 ? 2 * (sl - 5) + 1 : -1;
 }
+// ---- The frame: two 256-thread workgroups per CU where two pixel-major images fit its LDS, one of 512 threads with a raw copy of
+// the next image where they do not (see the head of the section)
+constexpr int F1_LDS_CU = 160 * 1024;
+__host__ __device__ constexpr int f1_hwc_bytes(int C) { return C <= 4 ? 4 * F1N_COPY : C == 12 ? 2 * F1P_COPY : F1_HWC; }
+__host__ __device__ constexpr bool f1_two_groups(int C) { return 2 * (f1_hwc_bytes(C) + 64) <= F1_LDS_CU; }  // (+ the ticket word, rounded up)
+__host__ __device__ constexpr int f1_threads(int C) { return f1_two_groups(C) ? 256 : 512; }
 
 // max over the four lanes of a quad, for the five row tiles of a conv1 tile at once: two v_max_f32 per value whose first operand
 // comes through DPP (quad_perm [1,0,3,2], then [2,3,0,1]).  In asm: fmaxf() on a DPP move does not fold (v_mov_b32_dpp + a
@@ -119,18 +146,23 @@ __device__ __forceinline__ void conv1_i8_body(const uint8_t *__restrict__ images
   constexpr bool NARROW = C <= 4;                       // four-byte pixels, four shifted copies (see f1n_slot)
   constexpr bool PACK12 = C == 12;                      // twelve-byte pixels, two shifted copies, a kernel row per k-step
   constexpr int KS = NARROW ? F1N_KS : PACK12 ? F1P_KS : F1_KS;
-  __shared__ __attribute__((aligned(16))) uint8_t s_hwc[NARROW ? 4 * F1N_COPY : PACK12 ? 2 * F1P_COPY : F1_HWC];
-  __shared__ __attribute__((aligned(16))) uint8_t s_raw[RAW];
+  constexpr bool TWO = f1_two_groups(C);                // the frame: two workgroups per CU and no raw copy, or one with it
+  constexpr int THREADS = f1_threads(C), WAVES = THREADS / 64;
+  constexpr int TASKS = kImg * (kImg / 4);              // of the turn: four consecutive pixels of a row
+  __shared__ __attribute__((aligned(16))) uint8_t s_hwc[f1_hwc_bytes(C)];
+  __shared__ __attribute__((aligned(16))) uint8_t s_raw[TWO ? 16 : RAW];  // (two groups: never touched, and not allocated)
   __shared__ int s_nxt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, q = lane >> 4;
   int img = blockIdx.x;
   if (img >= n) return;
-  // waves w and w + 4 share a SIMD (MI355X_MICROARCH.md: a workgroup's waves go to the SIMDs cyclically): the first keeps a
-  // higher priority for the whole launch, so its MFMA run always has the matrix pipe and the other wave's run falls into ITS
-  // epilogue — complementary phases instead of lockstep
-  if (wave < F1_WAVES / 2) __builtin_amdgcn_s_setprio(2);
+  // one group: waves w and w + 4 share a SIMD (MI355X_MICROARCH.md: a workgroup's waves go to the SIMDs cyclically): the first
+  // keeps a higher priority for the whole launch, so its MFMA run always has the matrix pipe and the other wave's run falls into
+  // ITS epilogue — complementary phases instead of lockstep.  Two groups: a SIMD's two waves come from two workgroups that are
+  // not in step to begin with; no priorities (head of the section)
+  if constexpr (!TWO)
+    if (wave < WAVES / 2) __builtin_amdgcn_s_setprio(2);
   // the weight fragments: resident for the whole launch
   i32x4 A[KS][F1_MT];
 #pragma unroll
@@ -140,95 +172,96 @@ __device__ __forceinline__ void conv1_i8_body(const uint8_t *__restrict__ images
       const uint4 v = atab[(ks * F1_MT + mt) * 64 + lane];
       A[ks][mt] = i32x4{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
     }
-  {  // the first image, by everybody
+  if constexpr (!TWO) {  // the first image, by everybody
     const uint4 *src = reinterpret_cast<const uint4 *>(images + (size_t)img * RAW);
     uint4 *dst = reinterpret_cast<uint4 *>(s_raw);
-    for (int i = tid; i < NV; i += F1_THREADS) dst[i] = src[i];
+    for (int i = tid; i < NV; i += THREADS) dst[i] = src[i];
+    __syncthreads();
   }
-  __syncthreads();
-  // raw planar [C][60][60] -> pixel-major [60][72][16] with x ^ 0x80 (u8 -> s8 of x - 128): a task is four consecutive pixels
-  auto transpose = [&]() {
+  // The turn, planar [C][60][60] -> pixel-major with x ^ 0x80 (u8 -> s8 of x - 128).  A task is four consecutive pixels of a row:
+  // one 4-byte read per plane at byte 4 task of the plane (60 = 4 x 15: consecutive lanes read consecutive words) ...
+  auto task_load = [&](const uint8_t *src, int task, uint32_t (&r)[16]) {
+    const uint32_t off = 4u * (uint32_t)task;
+#pragma unroll
+    for (int c = 0; c < 16; c++)  // (a padding channel's weight is zero)
+      r[c] = c < C ? *reinterpret_cast<const uint32_t *>(src + c * kPix + off) : NARROW ? 0x80808080u : 0u;
+  };
+  // ... a 4 x 4 byte transpose per four channels (v_perm) and the stores of the geometry
+  auto task_store = [&](int task, const uint32_t (&r)[16]) {
+    const int y = task / (kImg / 4), x0 = 4 * (task - y * (kImg / 4));
     if constexpr (NARROW) {
-      // raw planar [C][60][60] -> four copies of [60][68] four-byte pixels (x ^ 0x80; the padding byte's weight is zero), copy s
-      // shifted by s pixels; a task is four consecutive pixels: one 16-byte store into copy 0, four 4-byte stores into the others
-      for (int task = tid; task < kImg * (kImg / 4); task += F1_THREADS) {
-        const int y = task / (kImg / 4), x0 = 4 * (task - y * (kImg / 4));
-        uint32_t r[4];
+      // four copies of [60][68] four-byte pixels, copy s shifted by s pixels: one 16-byte store into copy 0, four 4-byte stores
+      // into each of the others
+      const uint32_t t0 = __builtin_amdgcn_perm(r[1], r[0], 0x05010400u), t1 = __builtin_amdgcn_perm(r[1], r[0], 0x07030602u);
+      const uint32_t t2 = __builtin_amdgcn_perm(r[3], r[2], 0x05010400u), t3 = __builtin_amdgcn_perm(r[3], r[2], 0x07030602u);
+      const uint32_t o0 = __builtin_amdgcn_perm(t2, t0, 0x05040100u) ^ 0x80808080u, o1 = __builtin_amdgcn_perm(t2, t0, 0x07060302u) ^ 0x80808080u;
+      const uint32_t o2 = __builtin_amdgcn_perm(t3, t1, 0x05040100u) ^ 0x80808080u, o3 = __builtin_amdgcn_perm(t3, t1, 0x07060302u) ^ 0x80808080u;
+      uint8_t *d = s_hwc + (y * F1N_PITCH + x0) * 4;
+      *reinterpret_cast<uint4 *>(d) = make_uint4(o0, o1, o2, o3);
 #pragma unroll
-        for (int c = 0; c < 4; c++) r[c] = c < C ? *reinterpret_cast<const uint32_t *>(s_raw + c * kPix + y * kImg + x0) : 0x80808080u;
-        const uint32_t t0 = __builtin_amdgcn_perm(r[1], r[0], 0x05010400u), t1 = __builtin_amdgcn_perm(r[1], r[0], 0x07030602u);
-        const uint32_t t2 = __builtin_amdgcn_perm(r[3], r[2], 0x05010400u), t3 = __builtin_amdgcn_perm(r[3], r[2], 0x07030602u);
-        const uint32_t o0 = __builtin_amdgcn_perm(t2, t0, 0x05040100u) ^ 0x80808080u, o1 = __builtin_amdgcn_perm(t2, t0, 0x07060302u) ^ 0x80808080u;
-        const uint32_t o2 = __builtin_amdgcn_perm(t3, t1, 0x05040100u) ^ 0x80808080u, o3 = __builtin_amdgcn_perm(t3, t1, 0x07060302u) ^ 0x80808080u;
-        uint8_t *d = s_hwc + (y * F1N_PITCH + x0) * 4;
-        *reinterpret_cast<uint4 *>(d) = make_uint4(o0, o1, o2, o3);
-#pragma unroll
-        for (int sh = 1; sh < 4; sh++) {
-          uint32_t *e = reinterpret_cast<uint32_t *>(d + sh * F1N_COPY + sh * 4);
-          e[0] = o0;
-          e[1] = o1;
-          e[2] = o2;
-          e[3] = o3;
-        }
+      for (int sh = 1; sh < 4; sh++) {
+        uint32_t *e = reinterpret_cast<uint32_t *>(d + sh * F1N_COPY + sh * 4);
+        e[0] = o0;
+        e[1] = o1;
+        e[2] = o2;
+        e[3] = o3;
       }
       return;
+    }
+    uint32_t o[4][4];  // [pixel][channel group]
+#pragma unroll
+    for (int cg = 0; cg < (PACK12 ? 3 : 4); cg++) {
+      // 4 x 4 byte transpose: (channel, pixel) -> (pixel, channel)
+      const uint32_t t0 = __builtin_amdgcn_perm(r[4 * cg + 1], r[4 * cg], 0x05010400u);      // c0.p0 c1.p0 c0.p1 c1.p1
+      const uint32_t t1 = __builtin_amdgcn_perm(r[4 * cg + 1], r[4 * cg], 0x07030602u);      // c0.p2 c1.p2 c0.p3 c1.p3
+      const uint32_t t2 = __builtin_amdgcn_perm(r[4 * cg + 3], r[4 * cg + 2], 0x05010400u);  // c2.p0 c3.p0 c2.p1 c3.p1
+      const uint32_t t3 = __builtin_amdgcn_perm(r[4 * cg + 3], r[4 * cg + 2], 0x07030602u);
+      o[0][cg] = __builtin_amdgcn_perm(t2, t0, 0x05040100u) ^ 0x80808080u;
+      o[1][cg] = __builtin_amdgcn_perm(t2, t0, 0x07060302u) ^ 0x80808080u;
+      o[2][cg] = __builtin_amdgcn_perm(t3, t1, 0x05040100u) ^ 0x80808080u;
+      o[3][cg] = __builtin_amdgcn_perm(t3, t1, 0x07060302u) ^ 0x80808080u;
     }
     if constexpr (PACK12) {
-      // raw planar [12][60][60] -> two copies of [60][736 B] twelve-byte pixels (x ^ 0x80), copy 1 shifted by 4 bytes; a task is four
-      // consecutive pixels = 48 contiguous bytes: three 16-byte stores into copy 0 (48 x0 / 4 is a multiple of 16), twelve 4-byte
-      // stores into copy 1
-      for (int task = tid; task < kImg * (kImg / 4); task += F1_THREADS) {
-        const int y = task / (kImg / 4), x0 = 4 * (task - y * (kImg / 4));
-        uint32_t o[4][3];  // [pixel][channel group]
+      // two copies of [60][736 B] twelve-byte pixels, copy 1 shifted by 4 bytes; four consecutive pixels are 48 contiguous bytes:
+      // three 16-byte stores into copy 0 (48 x0 / 4 is a multiple of 16), twelve 4-byte stores into copy 1
+      uint8_t *d = s_hwc + y * F1P_ROWB + 12 * x0;
+      uint4 *d4 = reinterpret_cast<uint4 *>(d);
+      d4[0] = make_uint4(o[0][0], o[0][1], o[0][2], o[1][0]);
+      d4[1] = make_uint4(o[1][1], o[1][2], o[2][0], o[2][1]);
+      d4[2] = make_uint4(o[2][2], o[3][0], o[3][1], o[3][2]);
+      uint32_t *e = reinterpret_cast<uint32_t *>(d + F1P_COPY + 4);
 #pragma unroll
-        for (int cg = 0; cg < 3; cg++) {
-          uint32_t r[4];
+      for (int px = 0; px < 4; px++)
 #pragma unroll
-          for (int c = 0; c < 4; c++) r[c] = *reinterpret_cast<const uint32_t *>(s_raw + (4 * cg + c) * kPix + y * kImg + x0);
-          const uint32_t t0 = __builtin_amdgcn_perm(r[1], r[0], 0x05010400u), t1 = __builtin_amdgcn_perm(r[1], r[0], 0x07030602u);
-          const uint32_t t2 = __builtin_amdgcn_perm(r[3], r[2], 0x05010400u), t3 = __builtin_amdgcn_perm(r[3], r[2], 0x07030602u);
-          o[0][cg] = __builtin_amdgcn_perm(t2, t0, 0x05040100u) ^ 0x80808080u;
-          o[1][cg] = __builtin_amdgcn_perm(t2, t0, 0x07060302u) ^ 0x80808080u;
-          o[2][cg] = __builtin_amdgcn_perm(t3, t1, 0x05040100u) ^ 0x80808080u;
-          o[3][cg] = __builtin_amdgcn_perm(t3, t1, 0x07060302u) ^ 0x80808080u;
-        }
-        uint8_t *d = s_hwc + y * F1P_ROWB + 12 * x0;
-        uint4 *d4 = reinterpret_cast<uint4 *>(d);
-        d4[0] = make_uint4(o[0][0], o[0][1], o[0][2], o[1][0]);
-        d4[1] = make_uint4(o[1][1], o[1][2], o[2][0], o[2][1]);
-        d4[2] = make_uint4(o[2][2], o[3][0], o[3][1], o[3][2]);
-        uint32_t *e = reinterpret_cast<uint32_t *>(d + F1P_COPY + 4);
-#pragma unroll
-        for (int px = 0; px < 4; px++)
-#pragma unroll
-          for (int cg = 0; cg < 3; cg++) e[3 * px + cg] = o[px][cg];
-      }
+        for (int cg = 0; cg < 3; cg++) e[3 * px + cg] = o[px][cg];
       return;
     }
-    for (int task = tid; task < kImg * (kImg / 4); task += F1_THREADS) {
-      const int y = task / (kImg / 4), x0 = 4 * (task - y * (kImg / 4));
-      uint32_t r[16];
+    // [60][72] sixteen-byte pixels
 #pragma unroll
-      for (int c = 0; c < 16; c++) r[c] = c < C ? *reinterpret_cast<const uint32_t *>(s_raw + c * kPix + y * kImg + x0) : 0u;
-      uint32_t o[4][4];  // [pixel][channel group]
+    for (int e = 0; e < 4; e++)
+      *reinterpret_cast<uint4 *>(s_hwc + (y * F1_PITCH + x0 + e) * 16) = make_uint4(o[e][0], o[e][1], o[e][2], o[e][3]);
+  };
+  // One group: out of the raw copy in LDS.  Two groups: straight out of the planar image in global memory (per plane a wave reads
+  // 256 contiguous bytes), the reads of two task rounds in flight before the first is turned — the tile loop's registers are dead
+  // here, the weight fragments are not.
+  auto turn = [&](const uint8_t *src) {
+    if constexpr (TWO) {
+      constexpr int ROUNDS = (TASKS + THREADS - 1) / THREADS;
+      uint32_t r[ROUNDS][16];
 #pragma unroll
-      for (int cg = 0; cg < 4; cg++) {
-        // 4 x 4 byte transpose: (channel, pixel) -> (pixel, channel)
-        const uint32_t t0 = __builtin_amdgcn_perm(r[4 * cg + 1], r[4 * cg], 0x05010400u);      // c0.p0 c1.p0 c0.p1 c1.p1
-        const uint32_t t1 = __builtin_amdgcn_perm(r[4 * cg + 1], r[4 * cg], 0x07030602u);      // c0.p2 c1.p2 c0.p3 c1.p3
-        const uint32_t t2 = __builtin_amdgcn_perm(r[4 * cg + 3], r[4 * cg + 2], 0x05010400u);  // c2.p0 c3.p0 c2.p1 c3.p1
-        const uint32_t t3 = __builtin_amdgcn_perm(r[4 * cg + 3], r[4 * cg + 2], 0x07030602u);
-        o[0][cg] = __builtin_amdgcn_perm(t2, t0, 0x05040100u) ^ 0x80808080u;
-        o[1][cg] = __builtin_amdgcn_perm(t2, t0, 0x07060302u) ^ 0x80808080u;
-        o[2][cg] = __builtin_amdgcn_perm(t3, t1, 0x05040100u) ^ 0x80808080u;
-        o[3][cg] = __builtin_amdgcn_perm(t3, t1, 0x07060302u) ^ 0x80808080u;
+      for (int k = 0; k < ROUNDS + 2; k++) {
+        if (k >= 2 && (THREADS * (k - 1) <= TASKS || tid + THREADS * (k - 2) < TASKS)) task_store(tid + THREADS * (k - 2), r[k - 2]);
+        if (k < ROUNDS && (THREADS * (k + 1) <= TASKS || tid + THREADS * k < TASKS)) task_load(src, tid + THREADS * k, r[k]);
       }
-#pragma unroll
-      for (int e = 0; e < 4; e++)
-        *reinterpret_cast<uint4 *>(s_hwc + (y * F1_PITCH + x0 + e) * 16) = make_uint4(o[e][0], o[e][1], o[e][2], o[e][3]);
+    } else {
+      for (int task = tid; task < TASKS; task += THREADS) {
+        uint32_t r[16];
+        task_load(src, task, r);
+        task_store(task, r);
+      }
     }
   };
-  transpose();
+  if constexpr (!TWO) turn(s_raw);
   // the lane's pixel inside a tile and its tap rows
   const int m_row = (j >> 1) & 1, m_x = 2 * (j >> 2) + (j & 1);
   const int kyg = q == 0 ? 0 : q == 1 ? 2 : q == 2 ? 1 : 3;
@@ -259,19 +292,26 @@ __device__ __forceinline__ void conv1_i8_body(const uint8_t *__restrict__ images
   const int k_shift_own = shift[4 * p + q], k_shift_4 = shift[16 + q];  // the filter's fixed-point position s: value = integer * 2^-s
   const float k_bias_own = bias[4 * p + q], k_bias_4 = bias[16 + q];
   for (;;) {
-    if (tid == 0) s_nxt = (int)gridDim.x + atomicAdd(queue, 1);
-    __syncthreads();  // the pixel-major image is complete, the raw region is free, s_nxt is visible
+    if constexpr (TWO) {  // the ticket's round trip runs under the image's load; its value goes to LDS behind the turn
+      int ticket = 0;
+      if (tid == 0) ticket = atomicAdd(queue, 1);
+      turn(images + (size_t)__builtin_amdgcn_readfirstlane(img) * RAW);
+      if (tid == 0) s_nxt = (int)gridDim.x + ticket;
+    } else {
+      if (tid == 0) s_nxt = (int)gridDim.x + atomicAdd(queue, 1);
+    }
+    __syncthreads();  // the pixel-major image is complete, the raw region (one group) is free, s_nxt is visible
     const int nxt = __builtin_amdgcn_readfirstlane(s_nxt);  // (wave-uniform, and known to be: image addresses stay on the scalar unit)
-    const uint4 *nsrc = reinterpret_cast<const uint4 *>(images + (size_t)(nxt < n ? nxt : img) * RAW);
+    const uint4 *nsrc = reinterpret_cast<const uint4 *>(images + (size_t)(nxt < n ? nxt : img) * RAW);  // (one group)
     // pool1 goes past 4 GB, so the image's part of a store address is 64-bit — and wave-uniform, like the tile's: both are scalar
     // arithmetic, once per image and once per tile; the lane adds its constant 32-bit byte offset (global_store_dword v, v, s[..])
     const uint64_t pool_img = (uint64_t)__builtin_amdgcn_readfirstlane(img) * (784 * 20 * 4);  // byte offset of the image's pooled planes
-    // A wave's tiles are wave, wave + 8, ...  Per tile: 35 MFMAs back to back (a VALU instruction of the SAME wave between two
+    // A wave's tiles are wave, wave + WAVES, ...  Per tile: 35 MFMAs back to back (a VALU instruction of the SAME wave between two
     // MFMAs costs matrix-pipe time — interleaving this wave's epilogue with its own MFMAs by sched_group_barrier measured
     // 0.48 ms against 0.40 — an instruction of the SIMD's OTHER wave costs nothing), then the requests for the next tile's pixel
-    // fragments (their registers are free now; the data arrives during the epilogue), then the epilogue.  The two waves of a SIMD
-    // run at different priorities (see kernel head): with equal priorities they fall into lockstep — both in their MFMA runs,
-    // sharing the pipe, then both in their epilogues with the pipe idle.
+    // fragments (their registers are free now; the data arrives during the epilogue), then the epilogue.  One group: the two waves
+    // of a SIMD run at different priorities (see kernel head): with equal priorities they fall into lockstep — both in their MFMA
+    // runs, sharing the pipe, then both in their epilogues with the pipe idle.
     auto tile_addr = [&](int t, const uint8_t *&pa, const uint8_t *&pb, const uint8_t *&pc) {
       const int tc = t < F1_TILES ? t : F1_TILES - 1;  // past the end: any valid address (the fragments are not used)
       const int trow = tc / 7, tcol = tc - 7 * trow;
@@ -303,12 +343,13 @@ __device__ __forceinline__ void conv1_i8_body(const uint8_t *__restrict__ images
       for (int ks = 0; ks < KS; ks++) B[ks] = frag_b(ks, pa, pb, pc);
     }
     int it = 0;
-    for (int t = wave; t < F1_TILES; t += F1_WAVES, it++) {
-      // one 16-byte piece of the next image per thread and tile: requested now, stored after the tile
-      const int piece = it * F1_THREADS + tid;
-      const bool has_piece = nxt < n && piece < NV;
+    for (int t = wave; t < F1_TILES; t += WAVES, it++) {
+      // one group: one 16-byte piece of the next image per thread and tile, requested now, stored after the tile
+      const int piece = it * THREADS + tid;
+      const bool has_piece = !TWO && nxt < n && piece < NV;
       uint4 stage = make_uint4(0, 0, 0, 0);
-      if (has_piece) stage = nsrc[piece];
+      if constexpr (!TWO)
+        if (has_piece) stage = nsrc[piece];
       i32x4 acc[F1_MT];
 #pragma unroll
       for (int mt = 0; mt < F1_MT; mt++) acc[mt] = k_start[mt];
@@ -320,7 +361,7 @@ __device__ __forceinline__ void conv1_i8_body(const uint8_t *__restrict__ images
       __builtin_amdgcn_sched_barrier(0);
       {
         const uint8_t *pa, *pb, *pc;
-        tile_addr(t + F1_WAVES, pa, pb, pc);
+        tile_addr(t + WAVES, pa, pb, pc);
 #pragma unroll
         for (int ks = 0; ks < KS; ks++) B[ks] = frag_b(ks, pa, pb, pc);
       }
@@ -352,24 +393,25 @@ __device__ __forceinline__ void conv1_i8_body(const uint8_t *__restrict__ images
       // immediate, and builds a 64-bit vector address for this one.  It does not count this store on vmcnt: its own waits come
       // out one store more careful than they had to be; nothing in the kernel reads pool1)
       if (p == 0) asm volatile("global_store_dword %0, %1, %2 offset:64" ::"v"(voff), "v"(v_4), "s"(dst) : "memory");
-      if (has_piece) reinterpret_cast<uint4 *>(s_raw)[piece] = stage;
+      if constexpr (!TWO)
+        if (has_piece) reinterpret_cast<uint4 *>(s_raw)[piece] = stage;
     }
-    __syncthreads();  // every tile of the image is done, the next image's raw bytes are in LDS
+    __syncthreads();  // every tile of the image is done: s_hwc is free; one group: the next image's raw bytes are in LDS
     if (nxt >= n) break;
-    transpose();
+    if constexpr (!TWO) turn(s_raw);
     img = nxt;
   }
 }
 
 template <int C>
-__global__ __launch_bounds__(F1_THREADS) void conv1_i8_kernel(const uint8_t *__restrict__ images,
+__global__ __launch_bounds__(f1_threads(C), 2) void conv1_i8_kernel(const uint8_t *__restrict__ images,
                                                               const uint4 *__restrict__ atab, const double *__restrict__ corr,
                                                               const int *__restrict__ shift, const float *__restrict__ bias,
                                                               float *__restrict__ pool1, int n, int *__restrict__ queue) {
   conv1_i8_body<C, false>(images, atab, corr, shift, bias, pool1, n, queue);
 }
 template <int C>
-__global__ __launch_bounds__(F1_THREADS) void conv1_i8_relu_kernel(const uint8_t *__restrict__ images,
+__global__ __launch_bounds__(f1_threads(C), 2) void conv1_i8_relu_kernel(const uint8_t *__restrict__ images,
                                                                    const uint4 *__restrict__ atab,
                                                                    const double *__restrict__ corr,
                                                                    const int *__restrict__ shift,
@@ -1055,8 +1097,10 @@ hipError_t lenet_forward_fast(const LeNetWeights &w, LeNetScratch &s, const uint
                               hipEvent_t *kernel_events, int *queue) {
   const int num_cus = s.num_cus;
   const int grid = m < num_cus ? m : num_cus;
+  // conv1: persistent workgroups, two per CU where the geometry's frame has them (f1_two_groups)
+  auto f1_grid = [&](int channels) { const int g = (f1_two_groups(channels) ? 2 : 1) * num_cus; return m < g ? m : g; };
   // conv_relu (gpd_hip_set_lenet_conv_relu) picks the instantiations whose epilogues clamp the pooled values at zero
-#define F1_LAUNCH(KERNEL, CH) KERNEL<CH><<<grid, F1_THREADS, 0, stream>>>(img, w.fast.c1a, w.fast.c1corr, w.fast.c1shift, w.c1b, s.pool1, m, queue)
+#define F1_LAUNCH(KERNEL, CH) KERNEL<CH><<<f1_grid(CH), f1_threads(CH), 0, stream>>>(img, w.fast.c1a, w.fast.c1corr, w.fast.c1shift, w.c1b, s.pool1, m, queue)
   if (w.conv_relu) {
     switch (w.channels) {
       case 15: F1_LAUNCH(conv1_i8_relu_kernel, 15); break;
