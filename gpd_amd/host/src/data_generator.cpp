@@ -9,6 +9,7 @@
 #include <sstream>
 
 #include "gpd/util/config_file.h"
+#include "host_internal.h"
 #include "../../csrc/balance_model.h"
 
 namespace gpd {
@@ -153,28 +154,20 @@ bool DataGenerator::labelView(int object, int view, util::Cloud &cloud, SetData 
   std::vector<float> xyz((size_t)n * 3);
   std::vector<int> cam((size_t)n * cams), src(n);
   int m = 0;
-  if (gpd_hip_preprocess_cloud(ctx, cloud.getCloudProcessed().data(), cloud.getCameraSource().data(), n, cams, nullptr, (float)voxel_size_views_,
-                               xyz.data(), cam.data(), src.data(), &m, nullptr) != GPD_OK) {
-    printf("ERROR: %s\n", gpd_hip_last_error());
+  if (hip_failed(gpd_hip_preprocess_cloud(ctx, cloud.getCloudProcessed().data(), cloud.getCameraSource().data(), n, cams, nullptr,
+                                          (float)voxel_size_views_, xyz.data(), cam.data(), src.data(), &m, nullptr)))
     return false;
-  }
   xyz.resize((size_t)m * 3);
   cam.resize((size_t)m * cams);
   cloud.setProcessed(xyz, cam, std::vector<float>());
   printf("Voxelized cloud: %zu\n", cloud.size());
   if (!estimateNormals(cloud, reverse_view_normals_)) return false;
-  if (gpd_hip_upload_cloud(ctx, cloud.getCloudProcessed().data(), cloud.getNormals().data(), m, cloud.getCameraSource().data(), cams,
-                           cloud.getViewPoints().data()) != GPD_OK) {
-    printf("ERROR: %s\n", gpd_hip_last_error());
-    return false;
-  }
+  if (hip_failed(upload_cloud(ctx, cloud))) return false;
   // hip_shadow_jitter (the detector read it): every view its own pattern, seed + the view's ordinal in the data set — with one
   // seed all views would move the voxel at a given lattice position alike
   if (detector_->shadowJitter() != 0 &&
-      gpd_hip_set_shadow_jitter(ctx, 1, detector_->shadowJitterSeed() + (unsigned long long)(object * num_views_per_object_ + view)) != GPD_OK) {
-    printf("ERROR: %s\n", gpd_hip_last_error());
+      hip_failed(gpd_hip_set_shadow_jitter(ctx, 1, detector_->shadowJitterSeed() + (unsigned long long)(object * num_views_per_object_ + view))))
     return false;
-  }
   // the draws of every round that may run (Cloud::subsampleUniformly is time-seeded in the reference; these are seeded)
   const int per = std::max(std::min(num_samples_, m), 0), rounds = std::max(max_rounds_per_view_, 0);
   std::vector<int32_t> samples((size_t)per * rounds + 1);
@@ -201,10 +194,7 @@ bool DataGenerator::labelView(int object, int view, util::Cloud &cloud, SetData 
     job.labels = labels.data();
     job.capacity = capacity;
   }
-  if ((sink ? gpd_hip_train_append_view(sink, which, ctx, &job) : gpd_hip_label_view(ctx, &job)) != GPD_OK) {
-    printf("ERROR: %s\n", gpd_hip_last_error());
-    return false;
-  }
+  if (hip_failed(sink ? gpd_hip_train_append_view(sink, which, ctx, &job) : gpd_hip_label_view(ctx, &job))) return false;
   printf("rounds: %d, #grasps: %d\n", job.rounds_run, job.num_candidates);
   printf("positives, negatives found for this view: %d, %d\n", job.num_positives, job.num_candidates - job.num_positives);
   printf("#positives: %d, #negatives: %d\n", job.num_positives_out, job.num_out - job.num_positives_out);
@@ -240,16 +230,11 @@ bool DataGenerator::generateData(gpd_hip_trainer *sink) {
     }
     printf("Loaded mesh with %d points.\n", (int)mesh.size());
     if (!estimateNormals(mesh, reverse_mesh_normals_)) return false;
-    if (gpd_hip_upload_ground_truth(ctx, mesh.getCloudProcessed().data(), mesh.getNormals().data(), (int)mesh.size()) != GPD_OK) {
-      printf("ERROR: %s\n", gpd_hip_last_error());
-      return false;
-    }
+    if (hip_failed(gpd_hip_upload_ground_truth(ctx, mesh.getCloudProcessed().data(), mesh.getNormals().data(), (int)mesh.size()))) return false;
     SetData train_data, test_data;
     int first[2] = {0, 0};  // under a sink: where this object's range of each resident set begins
-    if (sink && (gpd_hip_train_count(sink, 0, &first[0], nullptr) != GPD_OK || gpd_hip_train_count(sink, 1, &first[1], nullptr) != GPD_OK)) {
-      printf("ERROR: %s\n", gpd_hip_last_error());
+    if (sink && (hip_failed(gpd_hip_train_count(sink, 0, &first[0], nullptr)) || hip_failed(gpd_hip_train_count(sink, 1, &first[1], nullptr))))
       return false;
-    }
     for (int j = 0; j < num_views_per_object_; j++) {
       printf("===> Processing view %d/%d\n", j + 1, num_views_per_object_);
       util::Cloud cloud(prefix + "_" + std::to_string(j + 1) + ".pcd", {0.0, 0.0, 0.0});
@@ -272,8 +257,7 @@ bool DataGenerator::generateData(gpd_hip_trainer *sink) {
       balance::shuffle_order(data[w]->count, shuffle, order);
       if (!sink) {
         if (!appendSet(*sets[w], *data[w], order)) return false;
-      } else if (gpd_hip_train_reorder(sink, w, first[w], data[w]->count, order.data()) != GPD_OK) {
-        printf("ERROR: %s\n", gpd_hip_last_error());
+      } else if (hip_failed(gpd_hip_train_reorder(sink, w, first[w], data[w]->count, order.data()))) {
         return false;
       } else {
         sets[w]->count += data[w]->count;

@@ -8,9 +8,27 @@ import os
 
 import numpy as np
 
-from .api import HAND_DTYPE
+from .api import HAND_DTYPE, _ptr
 
 _LIB = None
+
+_P, _I, _D = C.c_void_p, C.c_int, C.c_double
+_IP = C.POINTER(C.c_int)
+# every entry of gpd_amd/host/src/flat_entries.cpp: its argument types (all return int)
+_ARGTYPES = {
+    "gpd_host_find_clusters": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "gpd_host_sample_above_plane": [_P, _I, _D, _I, _D, _I, _P, _P, _IP, _IP],
+    "gpd_host_refine_normals": [_P, _P, _I, _I, _I, C.c_float, _P, _P, _IP],
+    "gpd_host_remove_statistical_outliers": [_P, _I, _I, _D, _P, _P, _P],
+    "gpd_host_cloud_remove_statistical_outliers": [_P, _P, _P, _I, _I, _P, _I, _I, _D, _P, _P, _P, _P, _IP],
+    "gpd_host_subsample_indices": [_I, _P, _I, _I, C.c_uint, _P],
+    "gpd_host_knn": [_P, _I, _I, _P],
+    "gpd_host_detector_refine_normals": [_P, _P, _I, _I, _P],
+    "gpd_host_detector_remove_statistical_outliers": [_P, _P, _I, _P, _I, _I, _D, _P, _P, _P, _IP],
+    "gpd_host_load_pcd": [C.c_char_p, _P, _P, _I, _IP],
+    "gpd_host_load_normals_csv": [C.c_char_p, C.c_char_p, _P, _I],
+    "gpd_host_generate_data": [C.c_char_p, _P, _IP, _IP],
+}
 
 
 def lib():
@@ -19,8 +37,11 @@ def lib():
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host", "libgpd_host.so")
         if not os.path.exists(path):
             raise OSError("libgpd_host.so is not built (run `make -C gpd_amd/host` or __graft_entry__.build())")
-        _LIB = C.CDLL(path)
-        _LIB.gpd_host_find_clusters.restype = C.c_int
+        L = C.CDLL(path)
+        for name, argtypes in _ARGTYPES.items():
+            getattr(L, name).argtypes = argtypes
+            getattr(L, name).restype = C.c_int
+        _LIB = L
     return _LIB
 
 
@@ -33,9 +54,7 @@ def find_clusters(hands, scores, min_inliers=1, remove_inliers=False):
     out = np.zeros(max(n, 1), HAND_DTYPE)
     osc = np.zeros(max(n, 1), np.float64)
     src = np.zeros(max(n, 1), np.int32)
-    k = lib().gpd_host_find_clusters(hands.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p), n, int(min_inliers),
-                                     int(bool(remove_inliers)), out.ctypes.data_as(C.c_void_p), osc.ctypes.data_as(C.c_void_p),
-                                     src.ctypes.data_as(C.c_void_p))
+    k = lib().gpd_host_find_clusters(_ptr(hands), _ptr(scores), n, int(min_inliers), int(bool(remove_inliers)), _ptr(out), _ptr(osc), _ptr(src))
     return out[:k].copy(), osc[:k].copy(), src[:k].copy()
 
 
@@ -47,12 +66,8 @@ def sample_above_plane(xyz, threshold=0.01, max_iterations=50, probability=0.99,
     above = np.zeros(max(n, 1), np.int32)
     coeffs = np.zeros(4, np.float32)
     inl, its = C.c_int(0), C.c_int(0)
-    L = lib()
-    L.gpd_host_sample_above_plane.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
-                                              C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    k = L.gpd_host_sample_above_plane(xyz.ctypes.data_as(C.c_void_p), n, float(threshold), int(max_iterations), float(probability),
-                                      int(bool(optimize)), above.ctypes.data_as(C.c_void_p), coeffs.ctypes.data_as(C.c_void_p), C.byref(inl),
-                                      C.byref(its))
+    k = lib().gpd_host_sample_above_plane(_ptr(xyz), n, float(threshold), int(max_iterations), float(probability), int(bool(optimize)),
+                                          _ptr(above), _ptr(coeffs), C.byref(inl), C.byref(its))
     return above[:k].copy(), coeffs, int(inl.value), int(its.value)
 
 
@@ -65,10 +80,8 @@ def refine_normals(xyz, normals, k, max_iterations=15, convergence_threshold=1e-
     out = np.zeros((max(n, 1), 3), np.float32)
     ddots = np.zeros(max(int(max_iterations), 1), np.float32)
     nan = C.c_int(0)
-    L = lib()
-    L.gpd_host_refine_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-    its = L.gpd_host_refine_normals(xyz.ctypes.data_as(C.c_void_p), normals.ctypes.data_as(C.c_void_p), n, int(k), int(max_iterations),
-                                    float(convergence_threshold), out.ctypes.data_as(C.c_void_p), ddots.ctypes.data_as(C.c_void_p), C.byref(nan))
+    its = lib().gpd_host_refine_normals(_ptr(xyz), _ptr(normals), n, int(k), int(max_iterations), float(convergence_threshold), _ptr(out),
+                                        _ptr(ddots), C.byref(nan))
     return out[:n].copy(), int(its), ddots[:its].copy(), int(nan.value)
 
 
@@ -82,10 +95,7 @@ def remove_statistical_outliers(xyz, mean_k=50, stddev_mult=1.0):
     kept = np.zeros(max(n, 1), np.int32)
     stats = np.zeros(3, np.float64)
     dist = np.zeros(max(n, 1), np.float32)
-    L = lib()
-    L.gpd_host_remove_statistical_outliers.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-    k = L.gpd_host_remove_statistical_outliers(xyz.ctypes.data_as(C.c_void_p), n, int(mean_k), float(stddev_mult), kept.ctypes.data_as(C.c_void_p),
-                                               stats.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p))
+    k = lib().gpd_host_remove_statistical_outliers(_ptr(xyz), n, int(mean_k), float(stddev_mult), _ptr(kept), _ptr(stats), _ptr(dist))
     if k == -2:
         raise OverflowError("remove_statistical_outliers: mean_k = %d, the capacity is 255" % mean_k)
     if k < 0:
@@ -104,13 +114,8 @@ def cloud_remove_statistical_outliers(xyz, normals, cam_source, sample_indices, 
     xo, no = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
     co, so = np.zeros(cam.size, np.int32), np.zeros(max(len(si), 1), np.int32)
     ns = C.c_int(0)
-    L = lib()
-    L.gpd_host_cloud_remove_statistical_outliers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                             C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-    m = L.gpd_host_cloud_remove_statistical_outliers(xyz.ctypes.data_as(C.c_void_p), None if nrm is None else nrm.ctypes.data_as(C.c_void_p),
-                                                     cam.ctypes.data_as(C.c_void_p), n, cam.shape[0], si.ctypes.data_as(C.c_void_p), len(si),
-                                                     int(mean_k), float(stddev_mult), xo.ctypes.data_as(C.c_void_p), no.ctypes.data_as(C.c_void_p),
-                                                     co.ctypes.data_as(C.c_void_p), so.ctypes.data_as(C.c_void_p), C.byref(ns))
+    m = lib().gpd_host_cloud_remove_statistical_outliers(_ptr(xyz), _ptr(nrm), _ptr(cam), n, cam.shape[0], _ptr(si), len(si), int(mean_k),
+                                                         float(stddev_mult), _ptr(xo), _ptr(no), _ptr(co), _ptr(so), C.byref(ns))
     if m < 0:
         raise ValueError("Cloud::removeStatisticalOutliers refused the arguments")
     return xo[:m].copy(), (None if nrm is None else no[:m].copy()), co[: cam.shape[0] * m].reshape(cam.shape[0], m).copy(), so[: ns.value].copy()
@@ -121,10 +126,7 @@ def subsample_indices(num_points, num_samples, seed=0, sample_indices=None):
     the sample indices it carries afterwards, i32."""
     lst = np.zeros(0, np.int32) if sample_indices is None else np.ascontiguousarray(sample_indices, np.int32).reshape(-1)
     out = np.zeros(max(len(lst), int(num_samples), 1), np.int32)
-    L = lib()
-    L.gpd_host_subsample_indices.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_void_p]
-    k = L.gpd_host_subsample_indices(int(num_points), lst.ctypes.data_as(C.c_void_p), len(lst), int(num_samples), int(seed) & 0xFFFFFFFF,
-                                     out.ctypes.data_as(C.c_void_p))
+    k = lib().gpd_host_subsample_indices(int(num_points), _ptr(lst), len(lst), int(num_samples), int(seed) & 0xFFFFFFFF, _ptr(out))
     return out[:k].copy()
 
 
@@ -134,9 +136,7 @@ def knn(xyz, k):
     n = len(xyz)
     kk = min(int(k), n)
     out = np.zeros((max(n, 1), max(kk, 1)), np.int32)
-    L = lib()
-    L.gpd_host_knn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.gpd_host_knn(xyz.ctypes.data_as(C.c_void_p), n, int(k), out.ctypes.data_as(C.c_void_p))
+    lib().gpd_host_knn(_ptr(xyz), n, int(k), _ptr(out))
     return out[:n, :kk].copy()
 
 
@@ -145,11 +145,7 @@ def detector_refine_normals(xyz, normals, k):
     xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
     normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
     out = np.zeros_like(xyz)
-    L = lib()
-    L.gpd_host_detector_refine_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    rc = L.gpd_host_detector_refine_normals(xyz.ctypes.data_as(C.c_void_p), normals.ctypes.data_as(C.c_void_p), len(xyz), int(k),
-                                            out.ctypes.data_as(C.c_void_p))
-    if rc != 0:
+    if lib().gpd_host_detector_refine_normals(_ptr(xyz), _ptr(normals), len(xyz), int(k), _ptr(out)) != 0:
         raise RuntimeError("GraspDetector::refineNormals failed")
     return out
 
@@ -162,13 +158,8 @@ def detector_remove_statistical_outliers(xyz, normals, sample_indices, mean_k=50
     si = np.ascontiguousarray(sample_indices, np.int32).reshape(-1)
     xo, no, so = np.zeros_like(xyz), np.zeros_like(xyz), np.zeros(max(len(si), 1), np.int32)
     ns = C.c_int(0)
-    L = lib()
-    L.gpd_host_detector_remove_statistical_outliers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
-                                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-    m = L.gpd_host_detector_remove_statistical_outliers(xyz.ctypes.data_as(C.c_void_p), normals.ctypes.data_as(C.c_void_p), len(xyz),
-                                                        si.ctypes.data_as(C.c_void_p), len(si), int(mean_k), float(stddev_mult),
-                                                        xo.ctypes.data_as(C.c_void_p), no.ctypes.data_as(C.c_void_p),
-                                                        so.ctypes.data_as(C.c_void_p), C.byref(ns))
+    m = lib().gpd_host_detector_remove_statistical_outliers(_ptr(xyz), _ptr(normals), len(xyz), _ptr(si), len(si), int(mean_k), float(stddev_mult),
+                                                            _ptr(xo), _ptr(no), _ptr(so), C.byref(ns))
     if m < 0:
         raise RuntimeError("GraspDetector::removeStatisticalOutliers failed")
     return xo[:m].copy(), no[:m].copy(), so[: ns.value].copy()
@@ -179,9 +170,7 @@ def load_pcd(path, cap=1 << 22):
     xyz = np.zeros((cap, 3), np.float32)
     nrm = np.zeros((cap, 3), np.float32)
     has = C.c_int(0)
-    L = lib()
-    L.gpd_host_load_pcd.restype = C.c_int
-    n = L.gpd_host_load_pcd(str(path).encode(), xyz.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p), cap, C.byref(has))
+    n = lib().gpd_host_load_pcd(str(path).encode(), _ptr(xyz), _ptr(nrm), cap, C.byref(has))
     n = min(n, cap)
     return xyz[:n].copy(), (nrm[:n].copy() if has.value else None)
 
@@ -190,10 +179,7 @@ def generate_data(config, trainer):
     """DataGenerator::generateData(sink) of the config file into the resident sets of `trainer` (api.Trainer): every view is one
     gpd_hip_train_append_view, every object's ranges are shuffled on the device, no .npy file is written -> (n_train, n_test)
     generated."""
-    L = lib()
-    L.gpd_host_generate_data.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.gpd_host_generate_data.restype = C.c_int
     n_train, n_test = C.c_int(0), C.c_int(0)
-    if L.gpd_host_generate_data(str(config).encode(), trainer._h, C.byref(n_train), C.byref(n_test)) != 0:
+    if lib().gpd_host_generate_data(str(config).encode(), trainer._h, C.byref(n_train), C.byref(n_test)) != 0:
         raise RuntimeError("generate_data into the trainer failed (the C++ side printed why)")
     return int(n_train.value), int(n_test.value)

@@ -97,7 +97,7 @@ JITTER_SEED = 104240208772845  # 0x5ECE509D7EED: above 2^32, and its low 32 bits
 
 @pytest.mark.gpu
 def test_detect_grasps_cli_reads_the_shadow_jitter_keys(tmp_path, oracle_mod, lenet15_real):
-    """The case above with hip_shadow_jitter = 1 and a seed above 2^32 in the cfg file (gpd_host.cpp: not reference keys):
+    """The case above with hip_shadow_jitter = 1 and a seed above 2^32 in the cfg file (grasp_detector.cpp: not reference keys):
     the 20 grasps are those of the oracle with its statement of the policy on at that seed — and neither those of the policy
     off (a parser that drops the key) nor those of the seed's low 32 bits (one that truncates it)."""
     om = oracle_mod

@@ -32,7 +32,7 @@ def test_scoring_mode_key_is_documented():
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     assert "hip_lenet_mode" in open(os.path.join(root, "INTEGRATION.md")).read()
-    assert "hip_lenet_mode" in open(os.path.join(root, "gpd_amd", "host", "src", "gpd_host.cpp")).read()
+    assert "hip_lenet_mode" in open(os.path.join(root, "gpd_amd", "host", "src", "grasp_detector.cpp")).read()
 
 
 @pytest.mark.gpu
