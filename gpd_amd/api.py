@@ -363,7 +363,7 @@ EXPORTS = ["gpd_hip_default_params", "gpd_hip_create", "gpd_hip_destroy", "gpd_h
            "gpd_hip_search_samples", "gpd_hip_detect_samples", "gpd_hip_reevaluate", "gpd_hip_replay_kernel_ms", "gpd_hip_last_centre_chains",
            "gpd_hip_detect_select", "gpd_hip_detect_batch", "gpd_hip_detect_batch_multi", "gpd_hip_conv1_stats", "gpd_hip_last_fallbacks", "gpd_hip_preprocess_cloud", "gpd_hip_find_clusters", "gpd_hip_reserve", "gpd_hip_bind_host_thread",
            "gpd_hip_set_lenet_mode", "gpd_hip_lenet_debug", "gpd_hip_lenet_fast_tables", "gpd_hip_detect_sharded",
-           "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_refine_normals", "gpd_hip_sample_positions",
+           "gpd_hip_sample_above_plane", "gpd_hip_last_image_routes", "gpd_hip_last_normals_routes", "gpd_hip_refine_normals", "gpd_hip_sample_positions",
            "gpd_hip_remove_statistical_outliers",
            "gpd_hip_set_lenet_conv_relu", "gpd_hip_lenet_from_torch",
            "gpd_hip_lenet_shape_check", "gpd_hip_lenet_net_from_torch", "gpd_hip_set_lenet_net", "gpd_hip_lenet_net_debug",
@@ -424,6 +424,7 @@ def lib():
         L.gpd_hip_detect_sharded.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(DetectJob)]
         L.gpd_hip_last_fallbacks.argtypes = [C.c_void_p, C.c_void_p]
         L.gpd_hip_last_image_routes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.gpd_hip_last_normals_routes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.gpd_hip_last_centre_chains.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
         L.gpd_hip_last_stage_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.gpd_hip_replay.argtypes = [C.c_void_p, C.c_int]
@@ -1001,6 +1002,18 @@ class Context:
         keys = ("candidates", "window_class", "set_mode", "status", "pt_cap", "pt_cap_big", "sh_cap", "sh_cap_big")
         info = {k: int(v) for k, v in zip(keys, info)}
         return route[: info["candidates"]].copy(), info
+
+    def normals_routes(self):
+        """Which route every point took through the last estimate_normals (tests only) -> (count int32 [P], info): count =
+        neighbours found per point by original index, self included; info: points, tiles, queued (more than 1024 neighbours),
+        queued_lds / queued_arena (where their keys were sorted), attempts (2: the arena grew and the run was repeated),
+        arena_slots (its capacity after the call, 8-byte slots), centroid_chains (points not queued whose centroid chains were walked)."""
+        count = np.zeros(max(getattr(self, "_num_points", 0), 1), np.int32)  # (no upload yet: the call refuses)
+        info = np.zeros(8, np.int64)
+        self._check(lib().gpd_hip_last_normals_routes(self._h, _ptr(count), len(count), _ptr(info)))
+        keys = ("points", "tiles", "queued", "queued_lds", "queued_arena", "attempts", "arena_slots", "centroid_chains")
+        info = {k: int(v) for k, v in zip(keys, info)}
+        return count[: info["points"]].copy(), info
 
     def centre_chains(self):
         """(sample, coordinate) pairs of the last search whose neighbourhood centre took the serial fp64 chain (the order-free sum

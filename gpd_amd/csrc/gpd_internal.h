@@ -253,6 +253,8 @@ struct NormalsScratch {
   float *d_out = nullptr;
   double *d_cent = nullptr;         // [P][3] centroids certified by the list kernel (NaN: walk the chain)
   int last_queued = 0;             // of the last run: points that went through the large-neighbourhood kernel
+  int last_points = 0, last_tiles = 0, last_attempts = 0;  // of the last run, for normals_routes: its cloud size, its tiles, 2 when the arena grew
+  uint64_t last_generation = 0;    // the cloud's generation the last run left: normals_routes reads the grid of THAT cloud
 };
 void normals_free(NormalsScratch &s);
 struct Cloud {
@@ -305,6 +307,8 @@ int cloud_from_device(Cloud &c, const float *d_xyz, const int32_t *d_cam, int n,
 int cloud_reserve_grid(Cloud &c, int cells);
 void cloud_free(Cloud &c);
 int normals_run(Cloud &c, double radius, float *normals_out, hipStream_t stream);  // normals.hip
+// gpd_hip_last_normals_routes on a cloud whose stream has been waited for (count: room for n_room entries, by original index)
+int normals_routes(const Cloud &c, int32_t *count, int n_room, long long info[8]);
 
 // ---- Candidate search (search.hip) -----------------------------------------------
 struct SearchState {

@@ -526,7 +526,9 @@ int normals_run(Cloud &c, double radius, float *normals_out, hipStream_t stream)
   int32_t queued = 0;
   const int tiles = (P + kNormalsTile - 1) / kNormalsTile;
   std::vector<int32_t> tile_queued((size_t)tiles, 0);
+  int attempts = 0;
   for (int attempt = 0; attempt < 2; attempt++) {
+    attempts = attempt + 1;
     np.arena = s.d_arena;
     np.arena_cap = s.arena_cap;
     HIP_RET(hipMemsetAsync(s.d_out, 0, (size_t)P * 3 * sizeof(float), stream));
@@ -576,7 +578,61 @@ int normals_run(Cloud &c, double radius, float *normals_out, hipStream_t stream)
     s.arena_cap = want;
   }
   s.last_queued = queued;
+  s.last_points = P;
+  s.last_tiles = tiles;
+  s.last_attempts = attempts;
   c.generation++;
+  s.last_generation = c.generation;
+  return GPD_OK;
+}
+
+// gpd_hip_last_normals_routes (tests only): what the last normals_run left on the device, read after the fact — the counts by
+// cell-order position (every tile writes its own range of d_count and d_cent, so both hold the whole cloud), carried to the
+// original index through the grid's point table, and the routes that follow from them by the kernels' own rules.  The stream
+// has been waited for.
+int normals_routes(const Cloud &c, int32_t *count, int n_room, long long info[8]) {
+  const NormalsScratch &s = c.normals;
+  const int P = s.last_points;
+  if (P <= 0 || P != c.num_points || s.last_generation != c.generation) {
+    set_error("gpd_hip_last_normals_routes: no gpd_hip_estimate_normals ran on the cloud the context holds");
+    return GPD_ERR_STATE;
+  }
+  if (n_room < P) {
+    set_error("gpd_hip_last_normals_routes: room for %d points, the last run had %d", n_room, P);
+    return GPD_ERR_INVALID;
+  }
+  std::vector<int32_t> n((size_t)P);
+  std::vector<float4> gp((size_t)P);
+  std::vector<double> cent((size_t)P * 3);
+  HIP_RET(hipMemcpy(n.data(), s.d_count, n.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_RET(hipMemcpy(gp.data(), c.g_p, gp.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_RET(hipMemcpy(cent.data(), s.d_cent, cent.size() * sizeof(double), hipMemcpyDeviceToHost));
+  long long in_lds = 0, in_arena = 0, chains = 0;
+  for (int w = 0; w < P; w++) {
+    int32_t pi;
+    std::memcpy(&pi, &gp[(size_t)w].w, sizeof(pi));
+    if (pi < 0 || pi >= P) {
+      set_error("gpd_hip_last_normals_routes: cell-order position %d holds the index %d (points: %d)", w, pi, P);
+      return GPD_ERR_STATE;
+    }
+    count[pi] = n[(size_t)w];
+    if (n[(size_t)w] > NL_CAP) {  // normals_list_big_kernel's choice of sort space
+      long long m = 1;
+      while (m < n[(size_t)w]) m <<= 1;
+      (m <= NL_BIG_LDS ? in_lds : in_arena)++;
+    } else {
+      const double *k = &cent[3 * (size_t)w];
+      chains += k[0] != k[0] || k[1] != k[1] || k[2] != k[2];
+    }
+  }
+  info[0] = P;
+  info[1] = s.last_tiles;
+  info[2] = s.last_queued;
+  info[3] = in_lds;
+  info[4] = in_arena;
+  info[5] = s.last_attempts;
+  info[6] = s.arena_cap;
+  info[7] = chains;
   return GPD_OK;
 }
 

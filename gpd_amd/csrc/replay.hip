@@ -188,6 +188,17 @@ int gpd_hip_last_image_routes(gpd_hip_ctx *ctx, int32_t *route, int n, long long
   return images_routes(L.images, route, info);
 }
 
+int gpd_hip_last_normals_routes(gpd_hip_ctx *ctx, int32_t *count, int n, long long info[8]) {
+  if (!ctx || !count || !info || n < 0) {
+    set_error("gpd_hip_last_normals_routes: bad argument");
+    return GPD_ERR_INVALID;
+  }
+  Lane &L = ctx->lane[0];
+  HIP_RET(hipSetDevice(ctx->device));
+  HIP_RET(hipStreamSynchronize(L.stream));
+  return normals_routes(L.cloud, count, n, info);
+}
+
 int gpd_hip_last_centre_chains(gpd_hip_ctx *ctx, long long *out) {
   if (!ctx || !out) return GPD_ERR_INVALID;
   HIP_RET(hipSetDevice(ctx->device));

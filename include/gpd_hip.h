@@ -823,6 +823,20 @@ int gpd_hip_last_fallbacks(gpd_hip_ctx *ctx, long long out[4]);
  * GPD_ERR_INVALID for a null argument or n < info[0]; GPD_ERR_STATE if a list holds an entry that is no candidate. */
 int gpd_hip_last_image_routes(gpd_hip_ctx *ctx, int32_t *route, int n, long long info[8]);
 
+/* Which route every point took through the last gpd_hip_estimate_normals of the context, read back from what its kernels left
+ * on the device (none of it changes a result).  Tests only: the timed path never calls it.  Waits for the context's stream.
+ * count (n entries, n >= info[0]): per point, by ORIGINAL index, the neighbours found within the radius, the point itself
+ * included.  The count decides the route: up to 256 / 512 / 1024 a wave sorts the list in 4 / 8 / 16 registers per lane; beyond
+ * 1024 the point is queued for the workgroup-per-point kernel, which sorts 2^ceil(log2 count) keys in LDS (up to 8192) or in
+ * the point's slice of the arena.
+ * info: [0] points, [1] tiles of 65536 cell-order positions the run took, [2] queued points, [3] of these, sorted in LDS,
+ * [4] sorted in the arena, [5] attempts (2: the arena was too small, grew, and the run was repeated), [6] the arena's
+ * capacity after the call in 8-byte slots, [7] points that were not queued and whose centroid could not be certified
+ * order-free by the list kernel (their three fp64 chains were walked in neighbour order).
+ * GPD_ERR_INVALID for a null argument or n < info[0]; GPD_ERR_STATE when no gpd_hip_estimate_normals ran on the cloud the
+ * context holds (an upload, or another entry that replaces the cloud or its normals, came after it). */
+int gpd_hip_last_normals_routes(gpd_hip_ctx *ctx, int32_t *count, int n, long long info[8]);
+
 /* Of the last search's 3 x num_samples centre coordinates (the mean of a sample's image neighbourhood, hand_set.cpp:131-133):
  * how many took the serial fp64 chain in neighbour order because the order-free sum taken inside the neighbourhood kernel could
  * not be certified exact (a point within micrometres of a coordinate plane among points decimetres away).  Wherever the

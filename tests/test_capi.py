@@ -107,6 +107,23 @@ def test_image_routes_refuses_null_arguments():
     assert b"bad argument" in L.gpd_hip_last_error()
 
 
+def test_normals_routes_refuses_null_arguments():
+    """gpd_hip_last_normals_routes, like its sibling, checks its arguments before it touches a context or the device: a null context,
+    count buffer or info block, or a negative size, is GPD_ERR_INVALID (no GPU needed)."""
+    from gpd_amd import api
+    L = api.lib()
+    count = (ctypes.c_int32 * 4)()
+    info = (ctypes.c_longlong * 8)()
+    not_a_context = ctypes.create_string_buffer(64)  # never dereferenced: the null buffer next to it is refused first
+    assert L.gpd_hip_last_normals_routes(None, count, 4, info) == -1
+    assert L.gpd_hip_last_error() == b"gpd_hip_last_normals_routes: bad argument"
+    assert L.gpd_hip_last_normals_routes(not_a_context, None, 4, info) == -1
+    assert L.gpd_hip_last_normals_routes(not_a_context, count, 4, None) == -1
+    assert L.gpd_hip_last_normals_routes(not_a_context, count, -1, info) == -1
+    assert L.gpd_hip_last_error() == b"gpd_hip_last_normals_routes: bad argument"
+    assert list(count) == [0] * 4 and list(info) == [0] * 8  # nothing was written
+
+
 def test_context_entries_refuse_null_arguments():
     """Every entry of context.hip, detect.hip, rounds.hip and given.hip that takes a context, and gpd_hip_detect_batch, refuses a
     null context, and a null in place of its first required pointer, with GPD_ERR_INVALID and the text "<entry>: bad argument" (gpd_hip_set_lenet_weights has

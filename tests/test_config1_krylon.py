@@ -68,7 +68,7 @@ def test_config1_on_gpu_matches_oracle(oracle_mod, krylon, lenet15_real):
         ctx.set_lenet_weights(lenet15_real)
         ctx.upload_cloud(v, np.zeros_like(v))
         got_n = ctx.estimate_normals(0.03)
-        assert np.array_equal(got_n, want_n), "normals differ in %d of %d components" % ((got_n != want_n).sum(), got_n.size)
+        assert got_n.shape == want_n.shape and got_n.tobytes() == want_n.tobytes(), "normals differ in %d of %d components" % ((got_n != want_n).sum(), got_n.size)
         si = _samples(len(v), 500)
         hands, n_cand = ctx.detect(si)  # uses the normals left on the device
         p = oracle_mod.default_params(15)
@@ -89,7 +89,7 @@ def test_normals_on_synthetic_cloud(oracle_mod, cloud30k):
         ctx.upload_cloud(cloud30k["xyz"], np.zeros_like(cloud30k["xyz"]))
         got = ctx.estimate_normals(0.03)
         want = oracle_mod.estimate_normals(cloud30k["xyz"])
-        assert np.array_equal(got, want)
+        assert got.shape == want.shape and got.tobytes() == want.tobytes()
         # sanity: close to the analytic normals on the table plane
         tab = ~cloud30k["is_object"]
         assert np.abs(np.abs(np.einsum("ij,ij->i", got[tab], cloud30k["normals"][tab])) - 1).mean() < 0.05

@@ -305,7 +305,7 @@ def test_twelve_cameras(oracle_mod):
         ctx.upload_cloud(cl["xyz"], np.zeros_like(cl["xyz"]), cam, vp)
         nrm = ctx.estimate_normals(0.03)
         want_n = oracle_mod.estimate_normals(cl["xyz"], cam, vp, 0.03)
-        assert np.array_equal(nrm, want_n)
+        assert nrm.shape == want_n.shape and nrm.tobytes() == want_n.tobytes()
         assert not np.array_equal(nrm, oracle_mod.estimate_normals(cl["xyz"], cam[:1], vp[:1], 0.03))
         si = synth.sample_indices(cl, 120)
         hands, n_cand = ctx.detect(si)
@@ -600,9 +600,13 @@ def test_normals_of_neighbourhoods_beyond_every_lds_capacity(oracle_mod):
         ctx.upload_cloud(xyz, np.zeros_like(xyz), cam, vp)
         got = ctx.estimate_normals(0.06)
         want = oracle_mod.estimate_normals(xyz, cam, vp, 0.06)
-        assert np.array_equal(got, want)
+        _, info = ctx.normals_routes()
+        assert got.shape == want.shape and got.tobytes() == want.tobytes()
+        # the claims above, from the run's own report: lists beyond the wave sort, some of them beyond the LDS sort, and an
+        # arena that had to grow for them (the run was repeated)
+        assert info["queued"] > 0 and info["queued_arena"] > 0 and info["attempts"] == 2
         got2 = ctx.estimate_normals(0.02)  # same context, smaller lists: the scratch array is reused
-        assert np.array_equal(got2, oracle_mod.estimate_normals(xyz, cam, vp, 0.02))
+        assert got2.tobytes() == oracle_mod.estimate_normals(xyz, cam, vp, 0.02).tobytes()
     finally:
         ctx.close()
 
@@ -660,10 +664,10 @@ def test_normals_of_a_cloud_beyond_one_tile_of_points(oracle_mod):
         ctx.upload_cloud(cl["xyz"], np.zeros_like(cl["xyz"]), cl["cam_source"], cl["view_points"])
         got = ctx.estimate_normals(0.01)
         want = oracle_mod.estimate_normals(cl["xyz"], cl["cam_source"], cl["view_points"], 0.01)
-        assert np.array_equal(got, want)
+        assert got.shape == want.shape and got.tobytes() == want.tobytes()
         small = synth.make_cloud(32, 5000)
         ctx.upload_cloud(small["xyz"], np.zeros_like(small["xyz"]), small["cam_source"], small["view_points"])
-        assert np.array_equal(ctx.estimate_normals(0.03), oracle_mod.estimate_normals(small["xyz"], small["cam_source"], small["view_points"], 0.03))
+        assert ctx.estimate_normals(0.03).tobytes() == oracle_mod.estimate_normals(small["xyz"], small["cam_source"], small["view_points"], 0.03).tobytes()
     finally:
         ctx.close()
 

@@ -28,7 +28,9 @@ def test_unvoxelised_table_mug(oracle_mod, lenet15_real):
         ctx.upload_cloud(xyz, np.zeros_like(xyz), cam, vp)
         nrm = ctx.estimate_normals(0.03)                       # Cloud::calculateNormals on the device (retry with the large lists)
         onrm = oracle_mod.estimate_normals(xyz, cam, vp, 0.03)
-        assert np.array_equal(nrm, onrm)
+        _, info = ctx.normals_routes()
+        assert nrm.shape == onrm.shape and nrm.tobytes() == onrm.tobytes()
+        assert info["queued"] > 0 and info["attempts"] == 2          # the large lists, and the retry: both ran
         hands, n_cand = ctx.detect(si)
         p = oracle_mod.default_params(15)
         ohands, on_cand, _ = oracle_mod.detect(p, xyz, onrm, cam, vp, si, lenet15_real)
